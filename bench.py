@@ -13,7 +13,19 @@ image; at N > 1 each step also all-gathers the depth maps over RCCL (the exchang
 geometric-consistency passes).  Reference images shard one per rank, so per-GPU
 work is fixed as N grows ("scaling": "weak"); value = all ranks' pixels / max-over-ranks time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+  A plain run does only what the headline figure needs: it stages the inputs, runs W warm-up and K
+  timed steps and prints one JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+  the workload and, at N > 1, the exchange share).
+  --dump-outputs DIR  after the timed steps, write what the last timed step computed (the arrays
+      dpe_pm_fetch hands a caller: planes, weak, sel, costs) as DIR/<name>.npy, float32 / float64,
+      every value finite (a NaN cost the pass stores is written as 0 and flagged in
+      costs_nonfinite.npy), at most 64 MB in all.  The inputs depend only on the arguments, so two
+      builds can be compared output for output.
+  --full  adds everything else to the line: the instrumented executes (kernel_ms, work, roofline,
+      gather_roof), the other pass types and pyramid levels, the BASELINE configs[3] / [4] pipeline
+      lines, the end-to-end run, the CPU baseline and the parity check against the oracle (each can
+      be dropped again with its --no-... option).
   N > 1 either under a launcher (WORLD_SIZE must equal N):
       python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
   or directly: `python bench.py --gpus N` starts the N ranks itself as a child torch.distributed.run
@@ -314,6 +326,43 @@ def parity_on_sample(native, local_rank: int, sample) -> dict:
             "bit_exact": bits}
 
 
+DUMP_BUDGET_BYTES = 63 * 1000 * 1000   # --dump-outputs: 64 MB in all, less room for the .npy headers
+DUMP_SAMPLE_SEED = 20251205
+
+
+def dump_outputs(folder: str, out: dict, num_images: int = 32) -> dict:
+    """--dump-outputs: the fetched pass state as DIR/<name>.npy, float32 where that holds every value
+    (planes, costs, the u8 weak map, view masks of up to 24 source views) and float64 for wider
+    selected-view masks.  Every written value is finite: the pass stores a NaN cost (0 / 0, as
+    DPE.cu:1845-1861 does) at a pixel whose final plane has no selected view, so costs.npy holds 0
+    there and costs_nonfinite.npy says what the pass stored (0 finite, 1 NaN, 2 +inf, 3 -inf); planes
+    get the same pair only if a value of theirs is not finite.  A frame whose arrays exceed the
+    budget is written as a fixed, seeded sample of its pixels (the same pixels of every array, in
+    raster order; their flat indices go to DIR/pixels.npy)."""
+    os.makedirs(folder, exist_ok=True)
+    arrs = {"planes": np.ascontiguousarray(out["planes"], np.float32), "weak": out["weak"].astype(np.float32),
+            "sel": out["sel"].astype(np.float32 if num_images - 1 <= 24 else np.float64),
+            "costs": np.ascontiguousarray(out["costs"], np.float32)}
+    for k in ("planes", "costs"):
+        a = arrs[k]
+        code = (np.isnan(a) + 2 * np.isposinf(a) + 3 * np.isneginf(a)).astype(np.float32)
+        if k == "costs" or code.any():
+            arrs[k] = np.where(code == 0, a, np.float32(0))
+            arrs[k + "_nonfinite"] = code
+    L = arrs["costs"].size
+    per_px = sum(a.nbytes for a in arrs.values()) // L
+    keep = DUMP_BUDGET_BYTES // (per_px + 8)
+    sampled = L > DUMP_BUDGET_BYTES // per_px
+    if sampled:
+        pix = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(L, size=keep, replace=False)).astype(np.int64)
+        arrs = {k: a.reshape(L, -1)[pix].squeeze() for k, a in arrs.items()}
+        arrs["pixels"] = pix.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(folder, k + ".npy"), a)
+    return {"dir": folder, "arrays": {k: list(a.shape) for k, a in arrs.items()}, "sampled": sampled,
+            "bytes": int(sum(a.nbytes for a in arrs.values()))}
+
+
 def spawn_ranks(n: int) -> int:
     """`--gpus N` (N > 1) without a launcher: one rank per GPU through a CHILD torch.distributed.run
     on 127.0.0.1 (never an exec; nothing has initialised the GPU in this process), its stdout (rank
@@ -351,6 +400,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0's at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure (instrumented executes, other pass types "
+                         "and levels, pipeline configs, end-to-end, CPU baseline, parity); the --no-... options "
+                         "below drop parts of it again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-instrument", action="store_true", help="skip the hipEvent / work-counter runs (PMC profiling)")
     ap.add_argument("--no-pass-types", action="store_true", help="skip the FIRST_INIT / REFINE_INIT passes (kernel traces)")
@@ -365,6 +420,8 @@ def main():
 
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus {args.gpus}: need at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit(f"bench.py: --steps {args.steps} --warmup {args.warmup}: need at least 1 timed step and no negative warm-up")
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -470,13 +527,40 @@ def main():
                              "events on the pass stream); execute_ms = the pass",
                     "measured_on_hardware": dist.get_backend() == "nccl"}
 
-    if args.no_instrument:
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the state the last timed step left, as a caller fetches it
+        dumped = dump_outputs(args.dump_outputs, ctx.fetch(), NV_)
+    result = {
+        "metric": METRIC,
+        "value": round(value, 4),
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (DPE_MVS.synthetic pinhole scene, ground-truth-derived priors; no datasets reachable)",
+        "config": {"workload": f"DTU-like {Wd}x{Hd}, 9 src views, full-res REFINE_ITER pass + geometric consistency "
+                               "(BASELINE configs[2])",
+                   "width": Wd, "height": Hd, "num_images": NV_, "max_iterations": 3,
+                   "parallelism": f"reference-image sharding x{world}" + (
+                       (" + RCCL depth all-gather" if dist.get_backend() == "nccl" else f" + {dist.get_backend()} depth "
+                        "all-gather (rehearsal)") if world > 1 else "")},
+    }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if not args.full or args.no_instrument:   # the plain run ends here
+        result["stage_ms"] = round(stage_ms, 3)
+        if exchange is not None:
+            result["exchange"] = exchange
         if rank == 0:
-            line = {"metric": METRIC, "value": round(value, 4), "unit": "Mpix/s", "ms_per_step": round(ms_per_step, 3)}
-            if exchange is not None:
-                line["exchange"] = exchange
-            print(json.dumps(line))
+            print(json.dumps(result), flush=True)
         ctx.close()
+        if dist:
+            dist.destroy_process_group()
         return
     # instrumented (untimed) runs: per-class kernel time (hipEvents on the pass stream) and
     # algorithmic work counters (separate run; atomics are never in a timed run)
@@ -530,25 +614,7 @@ def main():
     # algorithmic HBM bytes of the whole pass (~1.5 KB/px/pass compulsory)
     L = Wd * Hd
     pass_bytes = L * (4 * NV_ + 4 * NV_ + 16 * 2 + 4 + 5 + 32 + 32 + 36) * 1.0
-    result = {
-        "metric": METRIC,
-        "value": round(value, 4),
-        "unit": "Mpix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (DPE_MVS.synthetic pinhole scene, ground-truth-derived priors; no datasets reachable)",
-        "config": {"workload": f"DTU-like {Wd}x{Hd}, 9 src views, full-res REFINE_ITER pass + geometric consistency "
-                               "(BASELINE configs[2])",
-                   "width": Wd, "height": Hd, "num_images": NV_, "max_iterations": 3,
-                   "parallelism": f"reference-image sharding x{world}" + (
-                       (" + RCCL depth all-gather" if dist.get_backend() == "nccl" else f" + {dist.get_backend()} depth "
-                        "all-gather (rehearsal)") if world > 1 else "")},
+    result.update({
         "roofline": {
             "bound": "valu",
             "kernel": f"k_{dom}",
@@ -602,7 +668,7 @@ def main():
         "pass_levels": levels,
         "kernel_ms": {k: round(v, 3) for k, v in tim.items()},
         "work": {k: v for k, v in cnt.items() if v["launches"]},
-    }
+    })
     if exchange is not None:
         result["exchange"] = exchange
     if not args.no_pipeline:   # every rank joins (the pipeline all-gathers depth maps between passes)

@@ -76,7 +76,7 @@ def test_gpu_bench_two_ranks_self_launched():
     """The real bench loop through the self-launch path: 2 ranks on the box's one GPU (gloo exchange,
     a rehearsal of the driver's N-GPU run), small frame, no side lines."""
     r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "320", "--height", "240",
-              "--no-pass-types", "--no-pipeline", "--no-e2e", "--no-cpu-baseline"],
+              "--full", "--no-pass-types", "--no-pipeline", "--no-e2e", "--no-cpu-baseline"],
              _env(DPE_BENCH_BACKEND="gloo"), timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     (line,) = _json_lines(r.stdout)

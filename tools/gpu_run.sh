@@ -26,18 +26,18 @@ for step in "$@"; do
     tests)  (cd "$R" && timeout -k 10 1100 $PT tests -m gpu -v --durations=15 > "$log" 2>&1) ;;
     subset) (cd "$R" && timeout -k 10 900 $PT $arg -m gpu -v --durations=10 > "$log" 2>&1) ;;
     smoke)  (cd "$R" && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('SMOKE_OK')" > "$log" 2>&1) ;;
-    bench)  (cd "$R" && timeout -k 10 700 python -u bench.py --steps 20 --warmup 5 > "$log" 2>&1) ;;
-    quick)  (cd "$R" && timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-e2e --no-cpu-baseline \
+    bench)  (cd "$R" && timeout -k 10 700 python -u bench.py --full --steps 20 --warmup 5 > "$log" 2>&1) ;;
+    quick)  (cd "$R" && timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 3 --no-e2e --no-cpu-baseline \
                --no-pass-types --no-pipeline > "$log" 2>&1) ;;
     prof)   (cd /tmp && export TMPDIR=/tmp && DPE_OVERLAP=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats \
                --output-format csv -d "$R/gpurun_out/${tag}_prof" -o run -- python3 "$R/bench.py" --steps 10 --warmup 2 \
-               --no-e2e --no-cpu-baseline --no-pass-types --no-pipeline > "$log" 2>&1) ;;
+               --full --no-e2e --no-cpu-baseline --no-pass-types --no-pipeline > "$log" 2>&1) ;;
     timeline) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv \
                -d "$R/gpurun_out/${tag}_tl" -o run -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-instrument \
                > "$log" 2>&1) ;;
     pmc)    (cd "$R" && bash tools/pmc.sh "$tag" > "$log" 2>&1 && bash tools/pmc_bottleneck.sh "$tag" >> "$log" 2>&1) ;;
     rehearsal) (cd "$R" && DPE_BENCH_BACKEND=gloo timeout -k 10 500 python -u bench.py --gpus 2 --steps 3 --warmup 1 \
-               --no-pass-types --no-config5 > "$log" 2>&1) ;;
+               --full --no-pass-types --no-config5 > "$log" 2>&1) ;;
     ab)     (cd "$R" && AB_ROUNDS=${AB_ROUNDS:-5} timeout -k 10 600 python -u tools/ab_libs.py ${arg//,/ } > "$log" 2>&1) ;;
     phase)  (cd "$R" && timeout -k 10 200 python -u tools/phase_prof.py "$arg" > "$log" 2>&1) ;;
     run)    log=$R/gpurun_out/${tag}_run$((++nrun)).log

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Summarise rocprofv3 output of bench.py into profiles/ (markdown + JSON).
 
-  kernel trace:  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python3 bench.py ...
+  kernel trace:  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python3 bench.py --full ...
   PMC traffic:   tools/pmc.sh TAG  (one rocprofv3 --pmc pass per counter group over one bench step)
 
-Kernel durations: bench.py runs W warmup + K timed executes, then one hipEvent-timed execute and one
+Kernel durations: bench.py --full runs W warmup + K timed executes, then one hipEvent-timed execute and one
 work-counting execute (device atomics).  The counting execute's dispatches are dropped (they are
 slowed by the atomics), so the averages here are the ones bench.py's roofline uses.
 
