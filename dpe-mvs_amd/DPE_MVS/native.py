@@ -23,7 +23,11 @@ EXPORTED = [
     "dpe_pm_stage_resident", "dpe_state_save", "dpe_state_snapshot", "dpe_state_fetch", "dpe_state_export_depth",
     "dpe_state_import_depth", "dpe_state_clear", "dpe_device_buffer", "dpe_device_copy",
     "dpe_resize_linear", "dpe_resize_u8", "dpe_canny", "dpe_roberts_threshold",
+    "dpe_state_render", "dpe_state_render_jpeg_blocks", "dpe_state_render_wait", "dpe_viz_render_arrays",
+    "dpe_jpeg_blocks_device", "dpe_viz_launches",
 ]
+
+VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
 
 CLASSES = ["setup", "init", "strong", "ransac", "weak", "filter", "depth_to_weak", "local_refine"]
 
@@ -73,6 +77,27 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_roberts_threshold.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     for fn in ("dpe_resize_linear", "dpe_resize_u8", "dpe_canny", "dpe_roberts_threshold"):
         getattr(lib, fn).restype = C.c_int
+    lib.dpe_state_save.argtypes = [C.c_void_p, C.c_int]
+    lib.dpe_state_save.restype = C.c_int
+    lib.dpe_state_fetch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]
+    lib.dpe_state_fetch.restype = C.c_int
+    lib.dpe_sync.argtypes = [C.c_void_p]
+    lib.dpe_sync.restype = C.c_int
+    lib.dpe_state_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]
+    lib.dpe_state_render.restype = C.c_int
+    lib.dpe_state_render_jpeg_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p]
+    lib.dpe_state_render_jpeg_blocks.restype = C.c_int
+    lib.dpe_state_render_wait.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dpe_state_render_wait.restype = C.c_int
+    lib.dpe_viz_render_arrays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_float, C.c_float, C.c_void_p]
+    lib.dpe_viz_render_arrays.restype = C.c_int
+    lib.dpe_jpeg_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.dpe_jpeg_blocks_device.restype = C.c_int
+    lib.dpe_viz_launches.argtypes = []
+    lib.dpe_viz_launches.restype = C.c_longlong
     return lib
 
 
@@ -207,11 +232,76 @@ class PatchMatchContext:
                "dpe_fusion_candidates")
         return idx, val
 
+    # HBM-resident state and the viz medium results rendered from it (include/dpe_mvs.h)
+    def state_save(self, image_id: int):
+        _check(_LIB.dpe_state_save(self._ctx, int(image_id)), "dpe_state_save")
+
+    def state_fetch(self, image_id: int) -> dict:
+        """{'depth' f32 [H,W], 'normal' f32 [H,W,3], 'weak' u8 [H,W], 'sel' u32 [H,W]} of a saved state."""
+        w, h = C.c_int(), C.c_int()
+        _check(_LIB.dpe_state_fetch(self._ctx, int(image_id), C.byref(w), C.byref(h), None, None, None, None), "dpe_state_fetch")
+        H, W = h.value, w.value
+        out = {"depth": np.empty((H, W), np.float32), "normal": np.empty((H, W, 3), np.float32),
+               "weak": np.empty((H, W), np.uint8), "sel": np.empty((H, W), np.uint32)}
+        _check(_LIB.dpe_state_fetch(self._ctx, int(image_id), C.byref(w), C.byref(h), out["depth"].ctypes.data,
+                                    out["normal"].ctypes.data, out["weak"].ctypes.data, out["sel"].ctypes.data), "dpe_state_fetch")
+        return out
+
+    def _state_size(self, image_id: int):
+        w, h = C.c_int(), C.c_int()
+        _check(_LIB.dpe_state_fetch(self._ctx, int(image_id), C.byref(w), C.byref(h), None, None, None, None), "dpe_state_fetch")
+        return w.value, h.value
+
+    def state_render(self, image_id: int, kind: int, dmin: float = 0.0, dmax: float = 0.0) -> np.ndarray:
+        """ShowDepthMap / ShowNormalMap / ShowWeakImage of a saved state on the device: uint8 [H, W, 3] BGR."""
+        w, h = self._state_size(image_id)
+        out = np.empty((h, w, 3), np.uint8)
+        _check(_LIB.dpe_state_render(self._ctx, int(image_id), int(kind), float(dmin), float(dmax), out.ctypes.data),
+               "dpe_state_render")
+        return out
+
+    def state_render_jpeg_blocks(self, image_id: int, kind: int, dmin: float = 0.0, dmax: float = 0.0,
+                                 quality: int = 95) -> np.ndarray:
+        """The picture's quantised JPEG blocks (render + front half on the device): int16 [n_blocks, 64]
+        in scan order, natural coefficient order (pipeline.jpeg_blocks of the same picture)."""
+        w, h = self._state_size(image_id)
+        out = np.empty((((w + 15) // 16) * ((h + 15) // 16) * 6, 64), np.int16)
+        _check(_LIB.dpe_state_render_jpeg_blocks(self._ctx, int(image_id), int(kind), float(dmin), float(dmax), int(quality),
+                                                 out.ctypes.data, out.size, None), "dpe_state_render_jpeg_blocks")
+        _check(_LIB.dpe_state_render_wait(self._ctx, out.ctypes.data), "dpe_state_render_wait")
+        return out
+
+    def viz_render_arrays(self, kind: int, depth=None, normal=None, weak=None, dmin: float = 0.0, dmax: float = 0.0) -> np.ndarray:
+        """The render kernel on caller arrays (diagnostic): uint8 [H, W, 3] BGR."""
+        d = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        n = None if normal is None else np.ascontiguousarray(normal, np.float32)
+        k = None if weak is None else np.ascontiguousarray(weak, np.uint8)
+        h, w = (d if d is not None else n if n is not None else k).shape[:2]
+        out = np.empty((h, w, 3), np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        _check(_LIB.dpe_viz_render_arrays(self._ctx, int(kind), w, h, ptr(d), ptr(n), ptr(k), float(dmin), float(dmax),
+                                          out.ctypes.data), "dpe_viz_render_arrays")
+        return out
+
+    def jpeg_blocks(self, bgr: np.ndarray, quality: int = 95) -> np.ndarray:
+        """The JPEG front-half kernel on a caller uint8 [H, W, 3] BGR image (diagnostic): int16 [n_blocks, 64]."""
+        a = np.ascontiguousarray(bgr, np.uint8)
+        h, w = a.shape[:2]
+        out = np.empty((((w + 15) // 16) * ((h + 15) // 16) * 6, 64), np.int16)
+        _check(_LIB.dpe_jpeg_blocks_device(self._ctx, a.ctypes.data, w, h, int(quality), out.ctypes.data, out.size),
+               "dpe_jpeg_blocks_device")
+        return out
+
     def device_planes(self) -> int:
         return int(_LIB.dpe_pm_device_planes(self._ctx) or 0)
 
     def export_depth(self, dev_ptr: int, stream: int | None = None):
         _check(_LIB.dpe_pm_export_depth(self._ctx, C.c_void_p(dev_ptr), C.c_void_p(stream or 0)), "dpe_pm_export_depth")
+
+
+def viz_launches() -> int:
+    """Kernels of the viz medium results launched by this process so far."""
+    return int(_LIB.dpe_viz_launches())
 
 
 def run_pass(pass_input: dict, state: dict, device: int = 0) -> dict:
@@ -230,4 +320,6 @@ def param_struct(**overrides) -> _abi.DpePatchMatchParams:
     return p
 
 
-__all__ = ["PatchMatchContext", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]
+Context = PatchMatchContext
+
+__all__ = ["PatchMatchContext", "Context", "viz_launches", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]

@@ -77,6 +77,14 @@ def lib() -> C.CDLL:
         L.dpe_host_connect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.dpe_host_hough_lines_p.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
                                              C.c_double, C.c_void_p, C.c_int]
+        L.dpe_host_jpeg_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]
+        L.dpe_host_jpeg_write_blocks.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.dpe_host_write_jpeg.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.dpe_host_edge_segment_connect.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.dpe_host_viz_render.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                          C.c_void_p]
         _lib = L
     return _lib
 
@@ -123,6 +131,60 @@ def rescale_to(src: np.ndarray, W: int, H: int) -> np.ndarray:
     return dst
 
 
+# ------------------------------------------------------------------------------ viz pictures and their JPEG encoder (C++)
+VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
+
+
+def _jpeg_image(img: np.ndarray):
+    a = np.ascontiguousarray(img)
+    if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError("expected a uint8 [H, W] grey or [H, W, 3] BGR image")
+    return a, (1 if a.ndim == 2 else 3)
+
+
+def write_jpeg(path: str, img: np.ndarray, quality: int = 95) -> None:
+    """cv::imwrite(path, img) with its defaults: uint8 [H, W, 3] BGR (4:2:0) or [H, W] grey."""
+    a, ch = _jpeg_image(img)
+    if lib().dpe_host_write_jpeg(path.encode(), a.ctypes.data, a.shape[1], a.shape[0], ch, quality) != 0:
+        raise PipelineError(f"cannot write {path}")
+
+
+def jpeg_blocks(img: np.ndarray, quality: int = 95) -> np.ndarray:
+    """The encoder's front half: quantised coefficient blocks int16 [n_blocks, 64], scan (MCU) order,
+    natural coefficient order."""
+    a, ch = _jpeg_image(img)
+    n = C.c_size_t()
+    if lib().dpe_host_jpeg_blocks(a.ctypes.data, a.shape[1], a.shape[0], ch, quality, None, 0, C.byref(n)) != 0:
+        raise PipelineError("jpeg_blocks: bad argument")
+    out = np.empty((n.value, 64), np.int16)
+    if lib().dpe_host_jpeg_blocks(a.ctypes.data, a.shape[1], a.shape[0], ch, quality, out.ctypes.data, out.size, C.byref(n)) != 0:
+        raise PipelineError("jpeg_blocks failed")
+    return out
+
+
+def write_jpeg_blocks(path: str, blocks: np.ndarray, w: int, h: int, channels: int = 3, quality: int = 95) -> None:
+    """The encoder's back half: Huffman-codes `blocks` (jpeg_blocks' layout) of a w x h image into `path`."""
+    b = np.ascontiguousarray(blocks, np.int16)
+    if lib().dpe_host_jpeg_write_blocks(path.encode(), b.ctypes.data, w, h, channels, quality) != 0:
+        raise PipelineError(f"cannot write {path}")
+
+
+def viz_render(kind: int, depth=None, normal=None, weak=None, dmin: float = 0, dmax: float = 0) -> np.ndarray:
+    """ShowDepthMap / ShowNormalMap / ShowWeakImage (DPE.cpp:384-502): uint8 [H, W, 3] BGR."""
+    d = None if depth is None else np.ascontiguousarray(depth, np.float32)
+    n = None if normal is None else np.ascontiguousarray(normal, np.float32)
+    k = None if weak is None else np.ascontiguousarray(weak, np.uint8)
+    src = {VIZ_DEPTH: d, VIZ_NORMAL: n, VIZ_WEAK: k}.get(kind)
+    if src is None:
+        raise ValueError("viz_render: bad kind or missing array")
+    h, w = src.shape[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    if lib().dpe_host_viz_render(kind, w, h, ptr(d), ptr(n), ptr(k), dmin, dmax, out.ctypes.data) != 0:
+        raise PipelineError("viz_render failed")
+    return out
+
+
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)
 def _u8(img: np.ndarray) -> np.ndarray:
     a = np.ascontiguousarray(img)
@@ -142,6 +204,34 @@ def edge_segment(scale: int, img: np.ndarray, mode: int, use_canny: bool, high_r
     if lib().dpe_host_edge_segment(*args, out.ctypes.data, out.nbytes, C.byref(ow), C.byref(oh)) != 0:
         raise PipelineError("EdgeSegment failed")
     return out
+
+
+def connect_color(label: int):
+    """colors[label] of connect_<s>.jpg as (B, G, R): a fixed 32-bit hash of the label, label 0 black."""
+    if label == 0:
+        return (0, 0, 0)
+    x = label & 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & 0xFFFFFFFF
+    x ^= x >> 16
+    return (x & 255, (x >> 8) & 255, (x >> 16) & 255)
+
+
+def edge_segment_connect(scale: int, img: np.ndarray, high_res: bool = True):
+    """EdgeSegment's labels (mode 1) and its img_connect picture (uint8 [h, w, 3] BGR: colors[label] before
+    the small regions become -1) from one segmentation."""
+    a = _u8(img)
+    ow, oh = C.c_int(), C.c_int()
+    args = (scale, a.ctypes.data, a.shape[1], a.shape[0], int(high_res))
+    if lib().dpe_host_edge_segment_connect(*args, None, None, 0, C.byref(ow), C.byref(oh)) != 0:
+        raise PipelineError("EdgeSegment failed")
+    lab = np.empty((oh.value, ow.value), np.int32)
+    bgr = np.empty((oh.value, ow.value, 3), np.uint8)
+    if lib().dpe_host_edge_segment_connect(*args, lab.ctypes.data, bgr.ctypes.data, lab.size, C.byref(ow), C.byref(oh)) != 0:
+        raise PipelineError("EdgeSegment failed")
+    return lab, bgr
 
 
 def canny(img: np.ndarray, low: float, high: float) -> np.ndarray:

@@ -15,7 +15,9 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <atomic>
 #include <map>
+#include <mutex>
 #include <vector>
 
 #include "pass_kernels.h"
@@ -23,6 +25,7 @@
 #include "pass_fusion.h"
 #include "pass_sweep.h"
 #include "pass_edges.h"
+#include "pass_viz.h"
 #include "tap_launch.h"
 
 using namespace dpe;
@@ -167,6 +170,15 @@ struct DpeContext {
   DevArr<int32_t> fz_idx;
   DevArr<float> fz_val;
   int fz_n = 0;
+  // viz medium results (dpe_state_render*): scratch, allocated on first use
+  DevArr<uint8_t> viz_bgr;           // the rendered picture
+  DevArr<int16_t> viz_blocks;        // its quantised JPEG blocks
+  DevArr<uint16_t> viz_q;            // quantisation tables of viz_quality (64 luma + 64 chroma)
+  int viz_quality = 0;
+  DevArr<float4> viz_planes;         // dpe_viz_render_arrays: the caller's arrays
+  DevArr<uint8_t> viz_weak;
+  std::mutex viz_mu;                 // guards viz_ev (dpe_state_render_wait runs on other host threads)
+  std::map<const void*, hipEvent_t> viz_ev;   // per host block buffer: end of the last copy into it
 };
 
 extern "C" {
@@ -284,6 +296,8 @@ void dpe_destroy(DpeContext* c) {
   c->e_rows.release(); c->e_mag.release(); c->e_itab.release(); c->e_dx.release(); c->e_dy.release();
   c->e_ftab.release(); c->e_stab.release();
   c->cnt.release();
+  c->viz_bgr.release(); c->viz_blocks.release(); c->viz_q.release(); c->viz_planes.release(); c->viz_weak.release();
+  for (auto& kv : c->viz_ev) (void)hipEventDestroy(kv.second);
   c->tab_right.release(); c->tab_down.release(); c->gn_ovf.release(); c->gn_tab.release(); c->gn_complex.release();
   c->lists.release(); c->row_counts.release(); c->list_totals.release(); c->part_cnt.release();
   (void)hipStreamSynchronize(c->aux);
@@ -1387,6 +1401,164 @@ extern "C" int dpe_host_pin(void* ptr, size_t bytes) {
 extern "C" int dpe_host_unpin(void* ptr) {
   if (!ptr) return DPE_ERR_ARG;
   return hipHostUnregister(ptr) == hipSuccess ? DPE_OK : DPE_ERR_HIP;
+}
+
+// ---------------------------------------------------------------- viz medium results (pass_viz.h)
+static std::atomic<long long> g_viz_launches{0};
+
+extern "C" long long dpe_viz_launches(void) { return g_viz_launches.load(); }
+
+static size_t viz_block_values(int w, int h) { return (size_t)((w + 15) / 16) * ((h + 15) / 16) * 6 * 64; }
+
+// the picture of (planes, weak) into c->viz_bgr on stream s
+static int viz_enqueue_render(DpeContext* c, int kind, const float4* planes, const uint8_t* weak, int w, int h, float dmin,
+                              float dmax, hipStream_t s) {
+  const size_t L = (size_t)w * h;
+  HIPC(c->viz_bgr.ensure(3 * L));
+  k_viz_render<<<(unsigned)((L + 1023) / 1024), 256, 0, s>>>(kind, planes, weak, dmin, dmax, c->viz_bgr.p, L);
+  HIPC(hipGetLastError());
+  g_viz_launches++;
+  return DPE_OK;
+}
+
+// the JPEG front half of c->viz_bgr (w x h) into c->viz_blocks on stream s
+static int viz_enqueue_front(DpeContext* c, int w, int h, int quality, hipStream_t s) {
+  if (c->viz_quality != quality) {   // first use, or another quality: no kernel may still read the old tables
+    HIPC(hipStreamSynchronize(s));
+    HIPC(hipStreamSynchronize(c->stream));
+    uint16_t q[128];
+    dpe_jpeg::quant_tables(quality, q);
+    HIPC(c->viz_q.ensure(128));
+    HIPC(hipMemcpy(c->viz_q.p, q, sizeof(q), hipMemcpyHostToDevice));
+    c->viz_quality = quality;
+  }
+  HIPC(c->viz_blocks.ensure(viz_block_values(w, h)));
+  k_jpeg_front<<<dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)), 384, 0, s>>>(c->viz_bgr.p, w, h, c->viz_q.p,
+                                                                                        c->viz_blocks.p);
+  HIPC(hipGetLastError());
+  g_viz_launches++;
+  return DPE_OK;
+}
+
+static ResState* viz_state(DpeContext* c, int image_id, int kind, const char* who) {
+  if (kind != DPE_VIZ_DEPTH && kind != DPE_VIZ_NORMAL && kind != DPE_VIZ_WEAK) { g_err = std::string(who) + ": bad kind"; return nullptr; }
+  auto it = c->rstore.find(image_id);
+  if (it == c->rstore.end()) { g_err = std::string(who) + ": no state of image " + std::to_string(image_id); return nullptr; }
+  if (!it->second->full) { g_err = std::string(who) + ": image " + std::to_string(image_id) + " holds a depth map only"; return nullptr; }
+  return it->second;
+}
+
+extern "C" int dpe_state_render(DpeContext* c, int image_id, int kind, float dmin, float dmax, uint8_t* host_bgr) {
+  g_err.clear();
+  if (!c || !host_bgr) { g_err = "dpe_state_render: null argument"; return DPE_ERR_ARG; }
+  ResState* r = viz_state(c, image_id, kind, "dpe_state_render");
+  if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
+  HIPC(hipSetDevice(c->device));
+  if (c->pending) HIPC(hipStreamWaitEvent(c->stream, c->ev_done, 0));
+  const int rc = viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, c->stream);
+  if (rc != DPE_OK) return rc;
+  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, (size_t)r->w * r->h * 3, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  return DPE_OK;
+}
+
+extern "C" int dpe_state_render_jpeg_blocks(DpeContext* c, int image_id, int kind, float dmin, float dmax, int quality,
+                                            int16_t* host_blocks, size_t cap, void* stream_) {
+  g_err.clear();
+  if (!c || !host_blocks) { g_err = "dpe_state_render_jpeg_blocks: null argument"; return DPE_ERR_ARG; }
+  if (quality < 1 || quality > 100) { g_err = "dpe_state_render_jpeg_blocks: bad quality"; return DPE_ERR_ARG; }
+  ResState* r = viz_state(c, image_id, kind, "dpe_state_render_jpeg_blocks");
+  if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
+  const size_t n = viz_block_values(r->w, r->h);
+  if (cap < n) { g_err = "dpe_state_render_jpeg_blocks: block buffer too small"; return DPE_ERR_ARG; }
+  HIPC(hipSetDevice(c->device));
+  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
+  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));   // after the save that wrote the state
+  int rc = viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s);
+  if (rc == DPE_OK) rc = viz_enqueue_front(c, r->w, r->h, quality, s);
+  if (rc != DPE_OK) return rc;
+  HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+  hipEvent_t ev = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->viz_mu);
+    auto it = c->viz_ev.find(host_blocks);
+    if (it == c->viz_ev.end()) {
+      HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      c->viz_ev[host_blocks] = ev;
+    } else {
+      ev = it->second;
+    }
+  }
+  HIPC(hipEventRecord(ev, s));
+  if (s != c->stream) {   // the scratch is reused, and the state rewritten, by later work of the context
+    HIPC(hipEventRecord(c->ev_done, s));
+    c->pending = true;
+  }
+  return DPE_OK;
+}
+
+extern "C" int dpe_state_render_wait(DpeContext* c, const int16_t* host_blocks) {
+  g_err.clear();
+  if (!c || !host_blocks) { g_err = "dpe_state_render_wait: null argument"; return DPE_ERR_ARG; }
+  hipEvent_t ev = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->viz_mu);
+    auto it = c->viz_ev.find(host_blocks);
+    if (it == c->viz_ev.end()) { g_err = "dpe_state_render_wait: no render into this buffer"; return DPE_ERR_ARG; }
+    ev = it->second;
+  }
+  HIPC(hipSetDevice(c->device));
+  HIPC(hipEventSynchronize(ev));
+  return DPE_OK;
+}
+
+extern "C" int dpe_viz_render_arrays(DpeContext* c, int kind, int w, int h, const float* depth, const float* normal,
+                                     const uint8_t* weak, float dmin, float dmax, uint8_t* host_bgr) {
+  g_err.clear();
+  if (!c || !host_bgr || w < 1 || h < 1) { g_err = "dpe_viz_render_arrays: bad argument"; return DPE_ERR_ARG; }
+  if (kind == DPE_VIZ_DEPTH ? !depth : kind == DPE_VIZ_NORMAL ? !normal : kind == DPE_VIZ_WEAK ? !weak : true) {
+    g_err = "dpe_viz_render_arrays: bad kind or missing array";
+    return DPE_ERR_ARG;
+  }
+  HIPC(hipSetDevice(c->device));
+  const size_t L = (size_t)w * h;
+  std::vector<float4> p(L);
+  for (size_t i = 0; i < L; ++i)
+    p[i] = make_float4(normal ? normal[3 * i] : 0.f, normal ? normal[3 * i + 1] : 0.f, normal ? normal[3 * i + 2] : 0.f,
+                       depth ? depth[i] : 0.f);
+  HIPC(wait_pending(c));
+  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(c->viz_planes.ensure(L));
+  HIPC(c->viz_weak.ensure(L));
+  HIPC(hipMemcpy(c->viz_planes.p, p.data(), L * sizeof(float4), hipMemcpyHostToDevice));
+  if (weak) HIPC(hipMemcpy(c->viz_weak.p, weak, L, hipMemcpyHostToDevice));
+  else HIPC(hipMemset(c->viz_weak.p, 0, L));
+  const int rc = viz_enqueue_render(c, kind, c->viz_planes.p, c->viz_weak.p, w, h, dmin, dmax, c->stream);
+  if (rc != DPE_OK) return rc;
+  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, 3 * L, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  return DPE_OK;
+}
+
+extern "C" int dpe_jpeg_blocks_device(DpeContext* c, const uint8_t* host_bgr, int w, int h, int quality, int16_t* host_blocks,
+                                      size_t cap) {
+  g_err.clear();
+  if (!c || !host_bgr || !host_blocks || w < 1 || h < 1 || w > 65535 || h > 65535 || quality < 1 || quality > 100) {
+    g_err = "dpe_jpeg_blocks_device: bad argument";
+    return DPE_ERR_ARG;
+  }
+  const size_t n = viz_block_values(w, h);
+  if (cap < n) { g_err = "dpe_jpeg_blocks_device: block buffer too small"; return DPE_ERR_ARG; }
+  HIPC(hipSetDevice(c->device));
+  HIPC(wait_pending(c));
+  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(c->viz_bgr.ensure((size_t)w * h * 3));
+  HIPC(hipMemcpy(c->viz_bgr.p, host_bgr, (size_t)w * h * 3, hipMemcpyHostToDevice));
+  const int rc = viz_enqueue_front(c, w, h, quality, c->stream);
+  if (rc != DPE_OK) return rc;
+  HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  return DPE_OK;
 }
 
 extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n) {

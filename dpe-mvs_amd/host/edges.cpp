@@ -408,7 +408,7 @@ bool stage_resize_linear(const EdgeDevice* dev, const float* src, int w, int h, 
 // EdgeSegment (DPE.cpp:129-291) for mode 0 (edges: CV_8UC1 0/255) and mode 1 (labels: CV_32SC1,
 // -1 = small region, 0 = boundary, > 0 region).
 bool edge_segment(int scale, const uint8_t* src, int cols, int rows, int mode, bool use_canny, bool high_res, Mat& out,
-                  std::string& err, const EdgeDevice* dev) {
+                  std::string& err, const EdgeDevice* dev, std::vector<uint8_t>* connect_bgr) {
   if (cols < 4 || rows < 4) { err = "EdgeSegment: image too small"; return false; }
   const int robthr = high_res ? 4 : 6;
   const int weak_tex_num = (int)(1.0 * rows * cols / (1024 << scale << scale));
@@ -485,6 +485,10 @@ bool edge_segment(int scale, const uint8_t* src, int cols, int rows, int mode, b
   int* lab = out.ptr<int>();
   std::vector<int> cnt;
   connect(rs.data(), ow, oh, lab, cnt);
+  if (connect_bgr) {   // img_connect (DPE.cpp:267-284): colors[label] before the small regions become -1
+    connect_bgr->resize((size_t)ow * oh * 3);
+    for (size_t i = 0; i < (size_t)ow * oh; ++i) connect_color(lab[i], connect_bgr->data() + 3 * i);
+  }
   for (size_t i = 0; i < (size_t)ow * oh; ++i)
     if (cnt[lab[i]] <= weak_tex_num && lab[i] != 0) lab[i] = -1;
   return true;
@@ -493,7 +497,7 @@ bool edge_segment(int scale, const uint8_t* src, int cols, int rows, int mode, b
 // GetProblemEdges (main.cpp:331-388): edges_<s>.dmb from the scaled image (32-bit float resize,
 // then round to 8 bits), labels_<s>.dmb from the full-resolution image; files that exist are kept.
 bool get_problem_edges(const GrayImage& full, int scale_size, const std::string& result_folder, bool use_edge,
-                       bool use_label, bool high_res, std::string& err, const EdgeDevice* dev) {
+                       bool use_label, bool high_res, std::string& err, const EdgeDevice* dev, bool viz) {
   int scale = 0;
   while ((1 << scale) < scale_size) scale++;
   const fs::path rf(result_folder);
@@ -511,14 +515,20 @@ bool get_problem_edges(const GrayImage& full, int scale_size, const std::string&
       Mat m;
       if (!edge_segment(scale, s.data(), nw, nh, 0, true, high_res, m, err, dev)) return false;
       if (!write_bin_mat(ep.string(), m, err)) return false;
+      if (viz && !write_jpeg((rf / ("rawedge_" + std::to_string(scale) + ".jpg")).string(), m.ptr<uint8_t>(), m.cols, m.rows, 1,
+                             95, err))
+        return false;
     }
   }
   if (use_label) {
     const fs::path lp = rf / ("labels_" + std::to_string(scale) + ".dmb");
     if (!fs::exists(lp)) {
       Mat m;
-      if (!edge_segment(scale, full.px.data(), full.w, full.h, 1, false, high_res, m, err, dev)) return false;
+      std::vector<uint8_t> con;   // the reference runs EdgeSegment(mode -1) again for it (main.cpp:382)
+      if (!edge_segment(scale, full.px.data(), full.w, full.h, 1, false, high_res, m, err, dev, viz ? &con : nullptr)) return false;
       if (!write_bin_mat(lp.string(), m, err)) return false;
+      if (viz && !write_jpeg((rf / ("connect_" + std::to_string(scale) + ".jpg")).string(), con.data(), m.cols, m.rows, 3, 95, err))
+        return false;
     }
   }
   return true;
@@ -567,6 +577,22 @@ int dpe_host_edge_segment(int scale, const uint8_t* src, int w, int h, int mode,
   if (out) {
     if (cap < m.data.size()) return 2;
     std::memcpy(out, m.data.data(), m.data.size());
+  }
+  return 0;
+}
+
+int dpe_host_edge_segment_connect(int scale, const uint8_t* src, int w, int h, int high_res, int32_t* labels,
+                                  uint8_t* connect_bgr, size_t cap_pixels, int* ow, int* oh) {
+  dpe_host::Mat m;
+  std::string err;
+  std::vector<uint8_t> con;
+  if (!src || !dpe_host::edge_segment(scale, src, w, h, 1, false, high_res != 0, m, err, nullptr, &con)) return 1;
+  if (ow) *ow = m.cols;
+  if (oh) *oh = m.rows;
+  if (labels || connect_bgr) {
+    if (cap_pixels < (size_t)m.cols * m.rows) return 2;
+    if (labels) std::memcpy(labels, m.data.data(), m.data.size());
+    if (connect_bgr) std::memcpy(connect_bgr, con.data(), con.size());
   }
   return 0;
 }

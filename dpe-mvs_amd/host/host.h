@@ -65,10 +65,27 @@ struct EdgeDevice {
   DpeContext* ctx = nullptr;
   std::mutex* mu = nullptr;
 };
+// `connect_bgr` (mode 1 only): also returns img_connect (DPE.cpp:267-284), colors[label] of every
+// pixel before the small regions become -1, 8-bit BGR of the labels' size
 bool edge_segment(int scale, const uint8_t* src, int cols, int rows, int mode, bool use_canny, bool high_res, Mat& out,
-                  std::string& err, const EdgeDevice* dev = nullptr);
+                  std::string& err, const EdgeDevice* dev = nullptr, std::vector<uint8_t>* connect_bgr = nullptr);
+// `viz`: also writes rawedge_<s>.jpg / connect_<s>.jpg beside a map it computes (main.cpp:361-364, 380-383)
 bool get_problem_edges(const GrayImage& full, int scale_size, const std::string& result_folder, bool use_edge,
-                       bool use_label, bool high_res, std::string& err, const EdgeDevice* dev = nullptr);
+                       bool use_label, bool high_res, std::string& err, const EdgeDevice* dev = nullptr, bool viz = false);
+
+// jpeg_enc.cpp: baseline JPEG encoder (cv::imwrite's defaults), split into the front half
+// (pixels -> quantised blocks in scan order, natural coefficient order) and the back half
+size_t jpeg_block_count(int w, int h, int channels);
+void jpeg_blocks(const uint8_t* px, int w, int h, int channels, int quality, int16_t* blocks);
+void jpeg_encode_blocks(const int16_t* blocks, int w, int h, int channels, int quality, std::vector<uint8_t>& file);
+bool jpeg_write_blocks(const std::string& path, const int16_t* blocks, int w, int h, int channels, int quality,
+                       std::string& err);
+bool write_jpeg(const std::string& path, const uint8_t* px, int w, int h, int channels, int quality, std::string& err);
+
+// viz.cpp: ShowDepthMap / ShowNormalMap / ShowWeakImage (DPE.cpp:384-502) into 8-bit BGR
+void viz_render(int kind, int w, int h, const float* depth, const float* normal, const uint8_t* weak, float dmin,
+                float dmax, uint8_t* bgr);
+void connect_color(int label, uint8_t* bgr);
 
 // fusion.cpp: RunFusion (DPE.cpp:1220-1370) / ExportPointCloud (DPE.cpp:532-572)
 struct FusionView {

@@ -17,18 +17,28 @@
 // fusion = true runs RunFusion (fusion.cpp) on rank 0 after the outputs: the per-(pixel, view)
 // projection tests on the GPU (dpe_fusion_candidates), the order-dependent rest on the host; with
 // several ranks the final normals and pixel states are all-gathered first.  As in the reference the
-// edges_/labels_ maps are deleted at the end unless keep_intermediate.  Not part of this build: the
-// viz medium results (ignored).
+// edges_/labels_ maps are deleted at the end unless keep_intermediate.
+//
+// viz = true writes the reference's medium results: depth_<it>.jpg / normal_<it>.jpg / weak_<it>.jpg
+// after every pass (main.cpp:448-454; <it> = the 0-based pass index) and rawedge_<s>.jpg /
+// connect_<s>.jpg beside the maps GetProblemEdges computes.  With the default runner the pictures
+// are rendered and taken through the data-parallel half of the JPEG encode on the GPU from the
+// HBM-resident state (dpe_state_render_jpeg_blocks); only the quantised blocks come back, into a
+// few pinned buffers, and a small pool of host threads (VizWriter) Huffman-codes and writes them
+// while the following passes run.  With a runner hook the state is on the host and the same
+// pictures come from viz.cpp / jpeg_enc.cpp, byte for byte the same files.
 #include "host.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
 #include <chrono>
+#include <condition_variable>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <filesystem>
 #include <fstream>
 #include <iostream>
@@ -266,10 +276,108 @@ bool fetch_state(DpeContext* ctx, int id, ImageState& s, std::string& err, bool 
   return true;
 }
 
+int viz_threads() {   // as fusion.cpp's fusion_threads(): at most 16, and OMP_NUM_THREADS
+  unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  if (const char* e = std::getenv("OMP_NUM_THREADS")) { const int v = std::atoi(e); if (v > 0) hw = std::min(hw, (unsigned)v); }
+  return (int)std::min(16u, hw);
+}
+
+const char* const kVizNames[3] = {"depth_", "normal_", "weak_"};   // DPE_VIZ_DEPTH / NORMAL / WEAK
+constexpr int kVizQuality = 95;   // cv::imwrite's default
+
+// The host half of the viz pictures of the resident runner.  submit() enqueues one picture's render,
+// JPEG front half and block copy on the context's stream into one of a fixed set of pinned buffers
+// (sized to the full-resolution level) and returns; it blocks only while every buffer is in
+// flight.  The worker threads wait for a buffer's copy (dpe_state_render_wait), Huffman-code it
+// into the file and hand the buffer back.  finish() joins them and reports the first error.
+class VizWriter {
+ public:
+  VizWriter(DpeContext* ctx, int max_w, int max_h) : ctx_(ctx) {
+    const size_t values = jpeg_block_count(max_w, max_h, 3) * 64;
+    bufs_.resize(kBuffers);
+    for (int i = 0; i < kBuffers; ++i) {
+      bufs_[i].resize(values);
+      pinned_.push_back(dpe_host_pin(bufs_[i].data(), values * sizeof(int16_t)) == 0);   // refused: pageable, still works
+      free_.push_back(i);
+    }
+    const int nt = std::max(1, std::min(viz_threads(), kBuffers));
+    for (int t = 0; t < nt; ++t) pool_.emplace_back([this]() { work(); });
+  }
+  ~VizWriter() { std::string e; finish(e); }
+  VizWriter(const VizWriter&) = delete;
+  VizWriter& operator=(const VizWriter&) = delete;
+
+  bool submit(int image_id, int kind, float dmin, float dmax, int w, int h, const std::string& path, std::string& err) {
+    int b;
+    {
+      std::unique_lock<std::mutex> lk(mu_);
+      cv_free_.wait(lk, [this]() { return !free_.empty(); });
+      b = free_.front(); free_.pop_front();
+    }
+    const int rc = dpe_state_render_jpeg_blocks(ctx_, image_id, kind, dmin, dmax, kVizQuality, bufs_[b].data(), bufs_[b].size(), nullptr);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (rc != 0) {
+      err = std::string("viz render failed: ") + dpe_last_error();
+      free_.push_back(b);
+      return false;
+    }
+    jobs_.push_back(Job{b, path, w, h});
+    cv_job_.notify_one();
+    return true;
+  }
+
+  bool finish(std::string& err) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      stop_ = true;
+    }
+    cv_job_.notify_all();
+    for (auto& th : pool_) th.join();
+    pool_.clear();
+    for (size_t i = 0; i < bufs_.size(); ++i)
+      if (pinned_[i]) { dpe_host_unpin(bufs_[i].data()); pinned_[i] = false; }
+    err = err_;
+    return err_.empty();
+  }
+
+ private:
+  static constexpr int kBuffers = 6;   // two images' three pictures
+  struct Job { int buf; std::string path; int w, h; };
+  void work() {
+    for (;;) {
+      Job j;
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_job_.wait(lk, [this]() { return stop_ || !jobs_.empty(); });
+        if (jobs_.empty()) return;
+        j = std::move(jobs_.front()); jobs_.pop_front();
+      }
+      std::string e;
+      bool ok = dpe_state_render_wait(ctx_, bufs_[j.buf].data()) == 0;
+      if (!ok) e = std::string("viz render failed: ") + dpe_last_error();
+      else ok = jpeg_write_blocks(j.path, bufs_[j.buf].data(), j.w, j.h, 3, kVizQuality, e);
+      std::lock_guard<std::mutex> lk(mu_);
+      if (!ok && err_.empty()) err_ = e.empty() ? "viz write failed" : e;
+      free_.push_back(j.buf);
+      cv_free_.notify_one();
+    }
+  }
+  DpeContext* ctx_;
+  std::vector<std::vector<int16_t>> bufs_;
+  std::vector<bool> pinned_;
+  std::deque<int> free_;
+  std::deque<Job> jobs_;
+  std::mutex mu_;
+  std::condition_variable cv_free_, cv_job_;
+  std::vector<std::thread> pool_;
+  bool stop_ = false;
+  std::string err_;
+};
+
 // InuputInitialization + SupportInitialization (DPE.cpp:733-914, 1025-1052), the pass, the epilogue
 bool process_problem(Problem& p, ImageCache& cache, std::map<int, ImageState>& states,
                      const std::map<int, DepthMap>& depth_src, const DpePipelineOptions& opt, Runner& run,
-                     std::string& err) {
+                     VizWriter* viz, std::string& err) {
   DpePatchMatchParams& P = p.params;
   std::vector<int> ids{p.ref_image_id};
   ids.insert(ids.end(), p.src_image_ids.begin(), p.src_image_ids.end());
@@ -368,6 +476,11 @@ bool process_problem(Problem& p, ImageCache& cache, std::map<int, ImageState>& s
       if (!fetch_state(run.ctx, p.ref_image_id, s, err)) return false;
       if (!write_state_maps(p, s, err)) return false;
     }
+    if (viz)   // main.cpp:448-454, from the saved (post-epilogue) state; the stream orders the next pass after it
+      for (int kind = 0; kind < 3; ++kind)
+        if (!viz->submit(p.ref_image_id, kind, P.depth_min, P.depth_max, W, H,
+                         (fs::path(p.result_folder) / (kVizNames[kind] + std::to_string(p.iteration) + ".jpg")).string(), err))
+          return false;
     return true;
   }
   std::vector<float> costs(L);
@@ -388,6 +501,15 @@ bool process_problem(Problem& p, ImageCache& cache, std::map<int, ImageState>& s
     s.normal[3 * i + 0] = planes[4 * i + 0]; s.normal[3 * i + 1] = planes[4 * i + 1]; s.normal[3 * i + 2] = planes[4 * i + 2];
   }
   if (opt.keep_intermediate && !write_state_maps(p, s, err)) return false;
+  if (opt.viz) {   // main.cpp:448-454 on the host (a runner hook keeps the state here)
+    std::vector<uint8_t> bgr(L * 3);
+    for (int kind = 0; kind < 3; ++kind) {
+      viz_render(kind, W, H, s.depth.data(), s.normal.data(), s.weak.data(), P.depth_min, P.depth_max, bgr.data());
+      if (!write_jpeg((fs::path(p.result_folder) / (kVizNames[kind] + std::to_string(p.iteration) + ".jpg")).string(), bgr.data(),
+                      W, H, 3, kVizQuality, err))
+        return false;
+    }
+  }
   states[p.ref_image_id] = std::move(s);
   return true;
 }
@@ -569,7 +691,7 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
           const Problem& p = problems[blocks[rank][k]];
           for (int i = 0; i < round_num && terr[t].empty(); ++i)
             if (!get_problem_edges(grey[k], (int)std::pow(2, round_num - 1 - i), p.result_folder, p.params.use_edge,
-                                   p.params.use_label, p.params.high_res_img, terr[t], &edev) && terr[t].empty())
+                                   p.params.use_label, p.params.high_res_img, terr[t], &edev, opt.viz) && terr[t].empty())
               terr[t] = "EdgeSegment failed";
         }
       });
@@ -585,6 +707,8 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
   std::map<int, DepthMap> depth_cur;
   int iteration_index = 0;
   const bool resident = runner.ctx != nullptr;
+  std::unique_ptr<VizWriter> viz;   // declared after `runner`: joined before the context goes
+  if (opt.viz && resident) viz.reset(new VizWriter(runner.ctx, w0, h0));
   double t_pass = 0.0, t_xchg = 0.0;   // g_times[6] / [5]
   for (int i = 0; i < round_num; ++i) {
     for (int j = -1; j < 3; ++j) {
@@ -609,7 +733,7 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
         const std::string rname = "ProcessProblem round " + std::to_string(i) + " pass " + std::to_string(j + 1) +
                                   " image " + std::to_string(p.ref_image_id);
         roctxRangePushA(rname.c_str());
-        const bool ok = process_problem(p, cache, states, depth_src, opt, runner, perr);
+        const bool ok = process_problem(p, cache, states, depth_src, opt, runner, viz.get(), perr);
         roctxRangePop();
         if (!ok) { fail(perr); break; }
         if (!resident) {
@@ -697,6 +821,10 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
   g_times[5] = t_xchg;
   g_times[6] = t_pass;
   t_mark = now_s();
+  if (viz) {   // the pictures still being coded or written; their errors
+    std::string verr;
+    if (!viz->finish(verr)) fail(verr);
+  }
   if (resident && !failed)   // the final states come back from HBM once
     for (int pi : blocks[rank]) {
       std::string ferr;

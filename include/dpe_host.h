@@ -20,6 +20,11 @@
  *                                                tests on the GPU (dpe_fusion_candidates), serial rest
  *   cv::imread(IMREAD_COLOR)  DPE.cpp:1253       dpe_host_read_bgr
  *   cv::HoughLinesP           DPE.cpp:186        dpe_host_hough_lines_p
+ *   ShowDepthMap              DPE.cpp:384-448    dpe_host_viz_render(DPE_VIZ_DEPTH)  (viz = true: on the
+ *   ShowNormalMap             DPE.cpp:450-473    dpe_host_viz_render(DPE_VIZ_NORMAL)  GPU from the resident
+ *   ShowWeakImage             DPE.cpp:475-502    dpe_host_viz_render(DPE_VIZ_WEAK)    state, dpe_state_render*)
+ *   cv::imwrite(".jpg")       DPE.cpp:446, main.cpp:363  dpe_host_write_jpeg (libjpeg's defaults: quality 95,
+ *                                                baseline, 4:2:0 / grey, Annex K Huffman tables)
  *
  * Additions for the one-process-per-GPU deployment: a pass runner hook (default: the HIP library
  * on `gpu_index`) and an all-gather hook for the depth maps (RCCL in the CLI, torch.distributed
@@ -111,6 +116,13 @@ void dpe_host_rescale_nearest(const void* src, int w, int h, void* dst, int nw, 
  * *ow, *oh).  0 on success. */
 int dpe_host_edge_segment(int scale, const uint8_t* src, int w, int h, int mode, int use_canny, int high_res, void* out,
                           size_t cap, int* ow, int* oh);
+/* EdgeSegment's labels (mode 1, use_canny = 0) together with its img_connect picture (DPE.cpp:256-290,
+ * connect_<s>.jpg of the viz medium results), from one segmentation: 8-bit BGR colors[label] of every
+ * pixel taken BEFORE the small regions become -1.  The colour is a fixed 32-bit hash of the label
+ * (label 0 black), where the reference draws from an unseeded rand().  labels / connect_bgr hold
+ * cap_pixels pixels (both NULL: size query).  0 on success. */
+int dpe_host_edge_segment_connect(int scale, const uint8_t* src, int w, int h, int high_res, int32_t* labels,
+                                  uint8_t* connect_bgr, size_t cap_pixels, int* ow, int* oh);
 /* cv::Canny(src, dst, low, high, 3, L2gradient = true): dst uint8 0/255.  0 on success. */
 int dpe_host_canny(const uint8_t* src, int w, int h, double low, double high, uint8_t* dst);
 /* cv::resize(INTER_LINEAR) of a CV_8UC1 image (exact 1/2: INTER_AREA fast path).  0 on success. */
@@ -121,6 +133,30 @@ int dpe_host_connect(const uint8_t* img, int w, int h, int* label, int* cnt, int
 /* cv::HoughLinesP: writes up to `cap` segments (x0, y0, x1, y1) into `lines`; returns the count or -1. */
 int dpe_host_hough_lines_p(const uint8_t* img, int w, int h, double rho, double theta, int threshold, double min_len,
                            double max_gap, int* lines, int cap);
+
+/*
+ * Baseline JPEG encoder: what cv::imwrite(path, mat) writes with its defaults (libjpeg, baseline
+ * sequential, Annex K Huffman tables, JFIF APP0; channels = 3: 8-bit BGR as Y/Cb/Cr 4:2:0,
+ * channels = 1: one component).  Integer arithmetic; split where the GPU takes over:
+ *   dpe_host_jpeg_blocks        front half: pixels -> quantised coefficient blocks in scan (MCU) order.
+ *                               Colour: 16x16 MCUs in raster order, blocks Y00 Y01 Y10 Y11 Cb Cr; grey:
+ *                               one block per 8x8 MCU.  64 int16 per block in NATURAL (row-major) order,
+ *                               not zigzag.  Writes up to `cap` int16 values (blocks = NULL: size query);
+ *                               *n_blocks receives the block count.  dpe_state_render_jpeg_blocks
+ *                               (dpe_mvs.h) computes the same blocks on the device.
+ *   dpe_host_jpeg_write_blocks  back half: DC prediction, Huffman coding, byte stuffing, headers, file.
+ *   dpe_host_write_jpeg         the two chained.
+ * 0 on success.
+ */
+int dpe_host_jpeg_blocks(const uint8_t* pixels, int w, int h, int channels, int quality, int16_t* blocks, size_t cap,
+                         size_t* n_blocks);
+int dpe_host_jpeg_write_blocks(const char* path, const int16_t* blocks, int w, int h, int channels, int quality);
+int dpe_host_write_jpeg(const char* path, const uint8_t* pixels, int w, int h, int channels, int quality);
+/* ShowDepthMap / ShowNormalMap / ShowWeakImage (DPE.cpp:384-502) of a w x h state into 8-bit BGR
+ * [h][w][3]: `kind` = DPE_VIZ_DEPTH (reads depth f32 [h][w], depth_min, depth_max), DPE_VIZ_NORMAL
+ * (normal f32 [h][w][3]) or DPE_VIZ_WEAK (weak u8 [h][w]); the other inputs may be NULL.  0 on success. */
+int dpe_host_viz_render(int kind, int w, int h, const float* depth, const float* normal, const uint8_t* weak,
+                        float depth_min, float depth_max, uint8_t* bgr);
 
 #ifdef __cplusplus
 }

@@ -317,6 +317,40 @@ int dpe_fusion_candidates(DpeContext* ctx, int ref, const int* src, int ns, int3
 int dpe_host_pin(void* ptr, size_t bytes);
 int dpe_host_unpin(void* ptr);
 
+/*
+ * The viz medium results (ShowDepthMap / ShowNormalMap / ShowWeakImage, DPE.cpp:384-502, and the
+ * data-parallel half of cv::imwrite's JPEG encode) from an HBM-resident state, after dpe_state_save.
+ * The pictures are bit-identical to dpe_host_viz_render and the blocks to dpe_host_jpeg_blocks
+ * (include/dpe_host.h, which also documents the block layout); no float image crosses PCIe.
+ *
+ * dpe_state_render:  image_id's state as 8-bit BGR [h][w][3] into a HOST buffer.  Synchronous.
+ * dpe_state_render_jpeg_blocks: renders, runs the JPEG front half (BGR -> YCbCr 4:2:0, edge
+ *                    replication, forward DCT, quantisation at `quality`) and copies the
+ *                    ceil(w/16) * ceil(h/16) * 6 * 64 int16 values into host_blocks (`cap` in int16;
+ *                    pin it with dpe_host_pin for an asynchronous copy).  Enqueued on `stream`
+ *                    (NULL = the context's); complete at dpe_sync, or when dpe_state_render_wait
+ *                    (ctx, host_blocks), which any host thread may call, returns.
+ * Both are ordered by the stream only: a later pass of the same image runs after them.
+ * DPE_ERR_STATE for an unknown id or a depth-only (imported) state, DPE_ERR_ARG for a bad kind or a
+ * cap that is too small.
+ *
+ * Diagnostic entries (tests) through the same kernels: dpe_viz_render_arrays renders caller HOST
+ * arrays (depth f32 [h][w], normal f32 [h][w][3], weak u8 [h][w]; those the kind does not read may
+ * be NULL), dpe_jpeg_blocks_device runs the front half on a caller HOST BGR image; both synchronous.
+ * dpe_viz_launches: kernels of this section launched by the process so far (a run with viz = false
+ * launches none).
+ */
+enum { DPE_VIZ_DEPTH = 0, DPE_VIZ_NORMAL = 1, DPE_VIZ_WEAK = 2 };
+int dpe_state_render(DpeContext* ctx, int image_id, int kind, float depth_min, float depth_max, uint8_t* host_bgr);
+int dpe_state_render_jpeg_blocks(DpeContext* ctx, int image_id, int kind, float depth_min, float depth_max, int quality,
+                                 int16_t* host_blocks, size_t cap, void* stream);
+int dpe_state_render_wait(DpeContext* ctx, const int16_t* host_blocks);
+int dpe_viz_render_arrays(DpeContext* ctx, int kind, int w, int h, const float* depth, const float* normal,
+                          const uint8_t* weak, float depth_min, float depth_max, uint8_t* host_bgr);
+int dpe_jpeg_blocks_device(DpeContext* ctx, const uint8_t* host_bgr, int w, int h, int quality, int16_t* host_blocks,
+                           size_t cap);
+long long dpe_viz_launches(void);
+
 #ifdef __cplusplus
 }
 #endif
