@@ -24,7 +24,7 @@ EXPORTED = [
     "dpe_state_import_depth", "dpe_state_clear", "dpe_device_buffer", "dpe_device_copy",
     "dpe_resize_linear", "dpe_resize_u8", "dpe_canny", "dpe_roberts_threshold",
     "dpe_state_render", "dpe_state_render_jpeg_blocks", "dpe_state_render_wait", "dpe_viz_render_arrays",
-    "dpe_jpeg_blocks_device", "dpe_viz_launches",
+    "dpe_jpeg_blocks_device", "dpe_viz_launches", "dpe_live_device_bytes",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -98,6 +98,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_jpeg_blocks_device.restype = C.c_int
     lib.dpe_viz_launches.argtypes = []
     lib.dpe_viz_launches.restype = C.c_longlong
+    for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
+        getattr(lib, fn).argtypes = [C.c_void_p]
+        getattr(lib, fn).restype = None
+    lib.dpe_live_device_bytes.argtypes = []
+    lib.dpe_live_device_bytes.restype = C.c_longlong
     return lib
 
 
@@ -236,6 +241,12 @@ class PatchMatchContext:
     def state_save(self, image_id: int):
         _check(_LIB.dpe_state_save(self._ctx, int(image_id)), "dpe_state_save")
 
+    def state_clear(self):
+        _LIB.dpe_state_clear(self._ctx)
+
+    def image_cache_clear(self):
+        _LIB.dpe_image_cache_clear(self._ctx)
+
     def state_fetch(self, image_id: int) -> dict:
         """{'depth' f32 [H,W], 'normal' f32 [H,W,3], 'weak' u8 [H,W], 'sel' u32 [H,W]} of a saved state."""
         w, h = C.c_int(), C.c_int()
@@ -304,6 +315,11 @@ def viz_launches() -> int:
     return int(_LIB.dpe_viz_launches())
 
 
+def live_device_bytes() -> int:
+    """Device bytes the library's contexts in this process hold at the moment."""
+    return int(_LIB.dpe_live_device_bytes())
+
+
 def run_pass(pass_input: dict, state: dict, device: int = 0) -> dict:
     ctx = PatchMatchContext(device)
     try:
@@ -322,4 +338,4 @@ def param_struct(**overrides) -> _abi.DpePatchMatchParams:
 
 Context = PatchMatchContext
 
-__all__ = ["PatchMatchContext", "Context", "viz_launches", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]
+__all__ = ["PatchMatchContext", "Context", "viz_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]

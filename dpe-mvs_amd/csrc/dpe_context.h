@@ -1,0 +1,186 @@
+// dpe_context.h -- what a DpeContext (include/dpe_mvs.h) holds: device arrays, streams and events that
+// own their HIP resources, the cached images, the resident states and the context itself.  Internal
+// to csrc/dpe_mvs.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <cstdint>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "pass_common.h"
+#include "pass_fusion.h"
+
+namespace {
+
+std::atomic<long long> g_live_bytes{0};   // dpe_live_device_bytes: what every DevArr of the process holds
+
+// A device array that owns its allocation (move-only; freed with its owner).  ensure() only grows,
+// and keeps 256 bytes behind the last element.
+template <class T>
+struct DevArr {
+  T* p = nullptr;
+  size_t n = 0;
+  DevArr() = default;
+  DevArr(DevArr&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevArr& operator=(DevArr&& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
+  DevArr(const DevArr&) = delete;
+  DevArr& operator=(const DevArr&) = delete;
+  ~DevArr() { reset(); }
+  hipError_t ensure(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    reset();
+    hipError_t e = hipMalloc((void**)&p, count * sizeof(T) + 256);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    n = count;
+    g_live_bytes += (long long)bytes();
+    return e;
+  }
+  size_t bytes() const { return p ? n * sizeof(T) + 256 : 0; }
+
+ private:
+  void reset() {
+    if (p) { g_live_bytes -= (long long)bytes(); (void)hipFree(p); }
+    p = nullptr; n = 0;
+  }
+};
+
+// a stream / an event of the context: created after construction (create() returns the error),
+// destroyed with its owner
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e, flags); }
+  operator hipEvent_t() const { return e; }
+};
+
+}  // namespace
+
+// An image kept in HBM across passes (DpePassInput.image_ids): its f32 grey levels and the gather
+// layouts built from them.
+struct CachedImage {
+  int id = 0, W = 0, H = 0;
+  int cls = dpe::IMG_F32;   // ImgClass of the grey levels
+  DevArr<float> plain;
+  DevArr<uint32_t> q8;      // TEX_U8 quad texels (8-bit images)
+  DevArr<uint2> q16;        // TEX_F16 quad texels (8-bit images)
+  DevArr<uint32_t> qp;      // TEX_P16 column pairs (8-bit images)
+  DevArr<float4> qf;        // f32 quad texels (built on demand)
+  uint64_t last_use = 0;
+  size_t bytes() const { return plain.n * 4 + q8.n * 4 + q16.n * 8 + qp.n * 4 + qf.n * 16; }
+};
+
+// Per-image pipeline state kept in HBM between passes (the reference's depths.dmb / normals.dmb /
+// weak.bin / selected_views.bin round trip, main.cpp:439-446 -> DPE.cpp:826-911).
+struct ResState {
+  int w = 0, h = 0;
+  bool full = false;          // planes / weak / sel of a pass of this image; false: depth only (imported)
+  DevArr<float4> planes;      // (world normal xyz, depth) after the ProcessProblem epilogue
+  DevArr<uint8_t> weak;
+  DevArr<uint32_t> sel;
+  DevArr<float> snap;         // depth snapshot for the Jacobi schedule (dpe_state_snapshot)
+  int snap_w = 0, snap_h = 0;
+  bool has_snap = false;
+};
+
+// Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
+// reverse order: the streams and events are declared first and so outlive every buffer.
+struct DpeContext {
+  int device = 0;
+  Stream stream;
+  Stream aux;                        // GenNeighbours beside the first strong half-sweep
+  Event ev_fork, ev_join, ev_ei;
+  Event ev_done;                     // end of the last dpe_pm_execute's work on its stream
+  Event ev_start;                    // timing: start of the pass
+  std::vector<Event> ev;             // timing: (start, end) per launch class slot
+  std::mutex viz_mu;                 // guards viz_ev (dpe_state_render_wait runs on other host threads)
+  std::map<const void*, Event> viz_ev;   // per host block buffer: end of the last copy into it
+  std::map<int, ResState> rstore;    // node addresses are stable: StageSrc points into it
+  DevArr<float> xbuf[2];             // dpe_device_buffer: exchange buffers of the multi-rank schedule
+  // EdgeSegment stages (dpe_canny / dpe_resize_* / dpe_roberts_threshold): scratch
+  DevArr<uint8_t> e_a, e_b, e_map;
+  DevArr<float> e_fa, e_fb;
+  DevArr<int> e_rows, e_mag, e_itab;
+  DevArr<int16_t> e_dx, e_dy;
+  DevArr<float> e_ftab;
+  DevArr<short> e_stab;
+  bool snap_mode = false;            // stage_resident reads source depths from the Jacobi snapshots
+  std::vector<std::unique_ptr<CachedImage>> icache;
+  uint64_t icache_clock = 0;
+  bool pending = false;              // ev_done recorded and not yet waited for
+  bool staged = false;
+#if DPE_GN_ONCE
+  bool gn_done_for_stage = false;    // GenNeighbours' outputs of this staged state are kept
+  DevArr<float> gn_complex;          //   and complex_ after GenNeighbours
+#endif
+  bool timing = false;
+  bool counting = false;
+  int gn_slots = 0;                  // DPE_OPT_GN_SLOTS (0 = by rotate_time)
+  float timings[DPE_NUM_CLASSES + 1] = {0};
+  int launches[DPE_NUM_CLASSES + 1] = {0};
+  unsigned long long counts[DPE_NUM_CLASSES * 4] = {0};
+  DevArr<unsigned long long> cnt;
+  DevArr<unsigned long long> phase;  // DPE_PHASE_PROF builds: per-phase cycle sums
+  dpe::PassConst hc;                 // host copy of the pass constants
+  DevArr<dpe::PassConst> dc;
+  // inputs
+  DevArr<float> img_plain[DPE_MAX_IMAGES];  // plain f32 images (ref used directly)
+  DevArr<float4> imgq[DPE_MAX_IMAGES];
+  DevArr<uint32_t> imgq8_all;        // all 8-bit quad images, TEX_U8 layout, one allocation
+  DevArr<uint2> imgq16_all;          //   and TEX_F16 layout (32-bit tap offsets)
+  DevArr<uint32_t> imgqp_all;        //   and TEX_P16 column pairs
+  int img_cls = dpe::IMG_F32;        // ImgClass of the pass (the narrowest class of its views)
+  DevArr<float> depth[DPE_MAX_IMAGES];
+  DevArr<uint8_t> edge, edge_low;
+  DevArr<int> label;
+  // staged initial state
+  DevArr<float4> planes0;
+  DevArr<uint8_t> weak0;
+  DevArr<uint32_t> sel0;
+  // working state
+  DevArr<float4> planes, planes_snap, fit_plane;
+  DevArr<float> costs, costs_snap, complex_;
+  DevArr<uint32_t> sel, sel_snap;
+  DevArr<uint8_t> weak, weak_rel, vw;
+  DevArr<short2> nb, nearest, edge_neigh, lab_bound;
+  DevArr<int> radius;
+  DevArr<int> tab_right, tab_down;   // FindNearestStrongPoint tables
+  DevArr<int> gn_ovf;                // GenNeighbours pixels left to the scratch kernel (k_gen_neighbours_lds)
+  DevArr<float> gn_tab;              // normalised image coordinates per column / row (k_gn_tables)
+  DevArr<int> lists, row_counts, list_totals;   // per-colour pixel lists for the sweeps
+  DevArr<int> part_cnt;                          // per colour: chunk counts / offsets of the weak-list partition
+  dpe::DevBufs bufs;
+  // fusion (dpe_fusion_stage / dpe_fusion_candidates)
+  std::vector<DevArr<float>> fz_depth, fz_normal;
+  std::vector<dpe::FusionViewDev> fz_host;
+  DevArr<dpe::FusionViewDev> fz_views;
+  DevArr<DpeCamera> fz_cams;
+  DevArr<int> fz_src;
+  DevArr<int32_t> fz_idx;
+  DevArr<float> fz_val;
+  int fz_n = 0;
+  // viz medium results (dpe_state_render*): scratch, allocated on first use
+  DevArr<uint8_t> viz_bgr;           // the rendered picture
+  DevArr<int16_t> viz_blocks;        // its quantised JPEG blocks
+  DevArr<uint16_t> viz_q;            // quantisation tables of viz_quality (64 luma + 64 chroma)
+  int viz_quality = 0;
+  DevArr<float4> viz_planes;         // dpe_viz_render_arrays: the caller's arrays
+  DevArr<uint8_t> viz_weak;
+};

@@ -17,7 +17,9 @@
 #include <string>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "pass_kernels.h"
@@ -27,6 +29,7 @@
 #include "pass_edges.h"
 #include "pass_viz.h"
 #include "tap_launch.h"
+#include "dpe_context.h"
 
 using namespace dpe;
 
@@ -55,131 +58,13 @@ struct Range {
     }                                                                               \
   } while (0)
 
-template <class T>
-struct DevArr {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t e = hipMalloc((void**)&p, count * sizeof(T) + 256);
-    if (e == hipSuccess) n = count;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
+// a step of a longer sequence: its DPE_* code ends the caller unless it is DPE_OK
+#define TRY(expr)                                                                   \
+  do {                                                                              \
+    if (const int rc_ = (expr); rc_ != DPE_OK) return rc_;                          \
+  } while (0)
 
 }  // namespace
-
-// An image kept in HBM across passes (DpePassInput.image_ids): its f32 grey levels and the gather
-// layouts built from them.
-struct CachedImage {
-  int id = 0, W = 0, H = 0;
-  int cls = IMG_F32;          // ImgClass of the grey levels
-  DevArr<float> plain;
-  DevArr<uint32_t> q8;      // TEX_U8 quad texels (8-bit images)
-  DevArr<uint2> q16;        // TEX_F16 quad texels (8-bit images)
-  DevArr<uint32_t> qp;      // TEX_P16 column pairs (8-bit images)
-  DevArr<float4> qf;        // f32 quad texels (built on demand)
-  uint64_t last_use = 0;
-  size_t bytes() const { return plain.n * 4 + q8.n * 4 + q16.n * 8 + qp.n * 4 + qf.n * 16; }
-  void release() { plain.release(); q8.release(); q16.release(); qp.release(); qf.release(); }
-};
-
-// Per-image pipeline state kept in HBM between passes (the reference's depths.dmb / normals.dmb /
-// weak.bin / selected_views.bin round trip, main.cpp:439-446 -> DPE.cpp:826-911).
-struct ResState {
-  int w = 0, h = 0;
-  bool full = false;          // planes / weak / sel of a pass of this image; false: depth only (imported)
-  DevArr<float4> planes;      // (world normal xyz, depth) after the ProcessProblem epilogue
-  DevArr<uint8_t> weak;
-  DevArr<uint32_t> sel;
-  DevArr<float> snap;         // depth snapshot for the Jacobi schedule (dpe_state_snapshot)
-  int snap_w = 0, snap_h = 0;
-  bool has_snap = false;
-  void release() { planes.release(); weak.release(); sel.release(); snap.release(); }
-};
-
-struct DpeContext {
-  int device = 0;
-  std::map<int, ResState*> rstore;
-  DevArr<float> xbuf[2];             // dpe_device_buffer: exchange buffers of the multi-rank schedule
-  // EdgeSegment stages (dpe_canny / dpe_resize_* / dpe_roberts_threshold): scratch
-  DevArr<uint8_t> e_a, e_b, e_map;
-  DevArr<float> e_fa, e_fb;
-  DevArr<int> e_rows, e_mag, e_itab;
-  DevArr<int16_t> e_dx, e_dy;
-  DevArr<float> e_ftab;
-  DevArr<short> e_stab;
-  bool snap_mode = false;            // stage_resident reads source depths from the Jacobi snapshots
-  std::vector<CachedImage*> icache;
-  uint64_t icache_clock = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t aux = nullptr;         // GenNeighbours beside the first strong half-sweep
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_ei = nullptr;
-  hipEvent_t ev_done = nullptr;      // end of the last dpe_pm_execute's work on its stream
-  bool pending = false;              // ev_done recorded and not yet waited for
-  bool staged = false;
-  bool gn_done_for_stage = false;    // DPE_DBG_GN_ONCE (timing experiments): GenNeighbours' outputs kept
-  bool timing = false;
-  bool counting = false;
-  int gn_slots = 0;                  // DPE_OPT_GN_SLOTS (0 = by rotate_time)
-  float timings[DPE_NUM_CLASSES + 1] = {0};
-  int launches[DPE_NUM_CLASSES + 1] = {0};
-  unsigned long long counts[DPE_NUM_CLASSES * 4] = {0};
-  std::vector<hipEvent_t> ev;        // timing: (start, end) per launch class slot
-  hipEvent_t ev_start = nullptr;     // timing: start of the pass
-  DevArr<unsigned long long> cnt;
-  DevArr<unsigned long long> phase;  // DPE_PHASE_PROF builds: per-phase cycle sums
-  PassConst hc;                  // host copy of the pass constants
-  DevArr<PassConst> dc;
-  // inputs
-  DevArr<float> img_plain[DPE_MAX_IMAGES];  // plain f32 images (ref used directly)
-  DevArr<float4> imgq[DPE_MAX_IMAGES];
-  DevArr<uint32_t> imgq8_all;        // all 8-bit quad images, TEX_U8 layout, one allocation
-  DevArr<uint2> imgq16_all;          //   and TEX_F16 layout (32-bit tap offsets)
-  DevArr<uint32_t> imgqp_all;        //   and TEX_P16 column pairs
-  int img_cls = IMG_F32;             // ImgClass of the pass (the widest class of its views)
-  DevArr<float> depth[DPE_MAX_IMAGES];
-  DevArr<uint8_t> edge, edge_low;
-  DevArr<int> label;
-  // staged initial state
-  DevArr<float4> planes0;
-  DevArr<uint8_t> weak0;
-  DevArr<uint32_t> sel0;
-  // working state
-  DevArr<float4> planes, planes_snap, fit_plane;
-  DevArr<float> costs, costs_snap, complex_;
-  DevArr<uint32_t> sel, sel_snap;
-  DevArr<uint8_t> weak, weak_rel, vw;
-  DevArr<short2> nb, nearest, edge_neigh, lab_bound;
-  DevArr<int> radius;
-  DevArr<int> tab_right, tab_down;   // FindNearestStrongPoint tables
-  DevArr<int> gn_ovf;                // GenNeighbours pixels left to the scratch kernel (k_gen_neighbours_lds)
-  DevArr<float> gn_complex;          // DPE_DBG_GN_ONCE: complex_ after GenNeighbours
-  DevArr<float> gn_tab;              // normalised image coordinates per column / row (k_gn_tables)
-  DevArr<int> lists, row_counts, list_totals;   // per-colour pixel lists for the sweeps
-  DevArr<int> part_cnt;                          // per colour: chunk counts / offsets of the weak-list partition
-  DevBufs bufs;
-  // fusion (dpe_fusion_stage / dpe_fusion_candidates)
-  std::vector<DevArr<float>> fz_depth, fz_normal;
-  std::vector<FusionViewDev> fz_host;
-  DevArr<FusionViewDev> fz_views;
-  DevArr<DpeCamera> fz_cams;
-  DevArr<int> fz_src;
-  DevArr<int32_t> fz_idx;
-  DevArr<float> fz_val;
-  int fz_n = 0;
-  // viz medium results (dpe_state_render*): scratch, allocated on first use
-  DevArr<uint8_t> viz_bgr;           // the rendered picture
-  DevArr<int16_t> viz_blocks;        // its quantised JPEG blocks
-  DevArr<uint16_t> viz_q;            // quantisation tables of viz_quality (64 luma + 64 chroma)
-  int viz_quality = 0;
-  DevArr<float4> viz_planes;         // dpe_viz_render_arrays: the caller's arrays
-  DevArr<uint8_t> viz_weak;
-  std::mutex viz_mu;                 // guards viz_ev (dpe_state_render_wait runs on other host threads)
-  std::map<const void*, hipEvent_t> viz_ev;   // per host block buffer: end of the last copy into it
-};
 
 extern "C" {
 
@@ -221,30 +106,38 @@ DpeContext* dpe_create(int device) {
     return nullptr;
   }
   if (hipSetDevice(device) != hipSuccess) { g_err = "dpe_create: hipSetDevice failed"; return nullptr; }
-  DpeContext* c = new DpeContext();
+  std::unique_ptr<DpeContext> c(new DpeContext());
   c->device = device;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    g_err = "dpe_create: stream"; delete c; return nullptr;
-  }
-  if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_ei, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&c->ev_start) != hipSuccess) {
+  if (c->stream.create() != hipSuccess) { g_err = "dpe_create: stream"; return nullptr; }
+  if (c->aux.create() != hipSuccess || c->ev_fork.create() != hipSuccess || c->ev_join.create() != hipSuccess ||
+      c->ev_ei.create() != hipSuccess || c->ev_done.create() != hipSuccess ||
+      c->ev_start.create(hipEventDefault) != hipSuccess) {
     g_err = "dpe_create: aux stream";
-    if (c->ev_start) (void)hipEventDestroy(c->ev_start);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_ei) (void)hipEventDestroy(c->ev_ei);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->aux) (void)hipStreamDestroy(c->aux);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
     return nullptr;
   }
-  return c;
+  return c.release();
 }
+
+}  // extern "C"
+
+// The concurrency contract of the entry points.  Work of the context runs on its own stream, or on
+// the stream a caller passes; `ev_done` marks the end of the last work that may be on another stream
+// than the context's, and `pending` says that nobody has waited for it yet.
+//   * Entry points that read results on the host, overwrite or free buffers HOST-WAIT with
+//     host_wait(): dpe_pm_fetch, dpe_state_fetch, dpe_state_clear, dpe_image_cache_clear, dpe_destroy,
+//     dpe_sync, dpe_device_copy, dpe_device_buffer (when it grows), dpe_viz_render_arrays and
+//     dpe_jpeg_blocks_device.  dpe_pm_stage / dpe_pm_stage_resident wait for ev_done only
+//     (wait_pending): what they enqueue goes on the context's stream behind its earlier work, and they
+//     synchronise it before they return.  dpe_pm_last_stat waits for ev_done and the aux stream.
+//   * Entry points that only enqueue STREAM-WAIT with enqueue_stream(): dpe_pm_execute,
+//     dpe_pm_export_depth, dpe_state_export_depth, dpe_state_import_depth and
+//     dpe_state_render_jpeg_blocks on the caller's stream; dpe_state_save, dpe_state_snapshot and
+//     dpe_state_render on the context's.  Those whose work later calls must wait for record ev_done
+//     again: dpe_pm_execute, dpe_state_save and dpe_state_snapshot always (mark_pending), the import
+//     and the JPEG blocks when they ran on a caller's stream (publish_foreign); the two exports only
+//     read, and dpe_state_render synchronises its stream itself.
+//   * The EdgeSegment stages and the fusion calls use the context's stream and scratch of their own,
+//     and synchronise the stream before they return.
 
 // Host-waits for the work of the last dpe_pm_execute, which may have been enqueued on a caller
 // stream: staging, fetching and freeing must not overwrite or release buffers that pass still uses.
@@ -254,58 +147,58 @@ static hipError_t wait_pending(DpeContext* c) {
   return e;
 }
 
+// Host-waits until the context is quiet: the pending work, then everything on its own stream.
+static hipError_t host_wait(DpeContext* c) {
+  const hipError_t e = wait_pending(c);
+  return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+}
+
+// The stream an entry point enqueues on (the caller's, or the context's for nullptr), after making it
+// wait for the pending work.
+static hipError_t enqueue_stream(DpeContext* c, void* caller_stream, hipStream_t* s) {
+  *s = caller_stream ? (hipStream_t)caller_stream : (hipStream_t)c->stream;
+  return c->pending ? hipStreamWaitEvent(*s, c->ev_done, 0) : hipSuccess;
+}
+
+// Makes the work enqueued on `s` so far the pending work that later calls wait for.
+static hipError_t mark_pending(DpeContext* c, hipStream_t s) {
+  const hipError_t e = hipEventRecord(c->ev_done, s);
+  if (e == hipSuccess) c->pending = true;
+  return e;
+}
+
+// The same for work that went on a caller's stream; the context's own stream orders its work itself.
+static hipError_t publish_foreign(DpeContext* c, hipStream_t s) {
+  return s == (hipStream_t)c->stream ? hipSuccess : mark_pending(c, s);
+}
+
+// The prologue of an entry point: clears the thread's error, refuses a null context or bad arguments
+// with DPE_ERR_ARG and `bad_args`, and selects the context's device.
+static int enter(DpeContext* c, bool args_ok, const char* bad_args) {
+  g_err.clear();
+  if (!c || !args_ok) { g_err = bad_args; return DPE_ERR_ARG; }
+  HIPC(hipSetDevice(c->device));
+  return DPE_OK;
+}
+
+extern "C" {
+
 void dpe_image_cache_clear(DpeContext* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)wait_pending(c);
-  (void)hipStreamSynchronize(c->stream);
-  for (CachedImage* e : c->icache) { e->release(); delete e; }
+  (void)host_wait(c);
   c->icache.clear();
 }
 
 void dpe_destroy(DpeContext* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)wait_pending(c);
-  (void)hipStreamSynchronize(c->stream);
+  (void)host_wait(c);
   (void)hipStreamSynchronize(c->aux);
-  dpe_image_cache_clear(c);
-  for (auto& a : c->fz_depth) a.release();
-  for (auto& a : c->fz_normal) a.release();
-  c->fz_views.release(); c->fz_cams.release(); c->fz_src.release(); c->fz_idx.release(); c->fz_val.release();
-  for (auto& e : c->ev) (void)hipEventDestroy(e);
-  (void)hipEventDestroy(c->ev_start);
-  (void)hipEventDestroy(c->ev_done);
-  c->dc.release();
-  for (int i = 0; i < DPE_MAX_IMAGES; ++i) { c->img_plain[i].release(); c->imgq[i].release(); c->depth[i].release(); }
-  c->imgq8_all.release();
-  c->imgq16_all.release();
-  c->imgqp_all.release();
-  c->edge.release(); c->edge_low.release(); c->label.release();
-  c->planes0.release(); c->weak0.release(); c->sel0.release();
-  c->planes.release(); c->planes_snap.release(); c->fit_plane.release();
-  c->costs.release(); c->costs_snap.release(); c->complex_.release();
-  c->sel.release(); c->sel_snap.release();
-  c->weak.release(); c->weak_rel.release(); c->vw.release();
-  c->nb.release(); c->nearest.release(); c->edge_neigh.release(); c->lab_bound.release();
-  c->radius.release();
-  for (auto& kv : c->rstore) { kv.second->release(); delete kv.second; }
-  c->rstore.clear();
-  c->xbuf[0].release(); c->xbuf[1].release();
-  c->e_a.release(); c->e_b.release(); c->e_map.release(); c->e_fa.release(); c->e_fb.release();
-  c->e_rows.release(); c->e_mag.release(); c->e_itab.release(); c->e_dx.release(); c->e_dy.release();
-  c->e_ftab.release(); c->e_stab.release();
-  c->cnt.release();
-  c->viz_bgr.release(); c->viz_blocks.release(); c->viz_q.release(); c->viz_planes.release(); c->viz_weak.release();
-  for (auto& kv : c->viz_ev) (void)hipEventDestroy(kv.second);
-  c->tab_right.release(); c->tab_down.release(); c->gn_ovf.release(); c->gn_tab.release(); c->gn_complex.release();
-  c->lists.release(); c->row_counts.release(); c->list_totals.release(); c->part_cnt.release();
-  (void)hipStreamSynchronize(c->aux);
-  (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join); (void)hipEventDestroy(c->ev_ei);
-  (void)hipStreamDestroy(c->aux);
-  (void)hipStreamDestroy(c->stream);
   delete c;
 }
+
+long long dpe_live_device_bytes(void) { return g_live_bytes.load(); }
 
 void dpe_set_timing(DpeContext* c, int enable) { if (c) c->timing = enable != 0; }
 
@@ -361,16 +254,6 @@ static void compute_pass_constants(PassConst& pc) {
   pc.weak_nn = pc.P.weak_radius >= 0 && pc.P.weak_increment > 0 ? (2 * pc.P.weak_radius) / pc.P.weak_increment + 1 : 0;
 }
 
-// where a stage takes the initial state and the source depths from: host buffers (dpe_pm_stage) or
-// the resident store (dpe_pm_stage_resident)
-struct StageSrc {
-  const DpePassState* st = nullptr;   // host initial state
-  const ResState* prior = nullptr;    // resident initial state (nullptr: none, FIRST_INIT)
-  const ResState* dep[DPE_MAX_IMAGES] = {};   // resident source depths (index 1..N-1)
-  bool dep_snap = false;              // read the depths' Jacobi snapshots
-};
-static int stage_impl(DpeContext* c, const DpePassInput* in, const StageSrc& src);
-
 #if DPE_POOL_STATS
 extern "C" void dpe_dbg_pool_stats_main(unsigned long long out[24], int reset) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_pool), sizeof(dpe::g_pool));
@@ -398,20 +281,6 @@ extern "C" void dpe_dbg_weak_stats(unsigned long long out[24], int reset) {
 }
 #endif
 
-extern "C" int dpe_pm_stage(DpeContext* c, const DpePassInput* in, const DpePassState* st) {
-  g_err.clear();
-  if (!c || !in || !st || !in->images || !in->cams || !st->planes || !st->weak_info || !st->selected_views) {
-    g_err = "dpe_pm_stage: null argument"; return DPE_ERR_ARG;
-  }
-  if (in->params.geom_consistency) {
-    if (!in->depths) { g_err = "dpe_pm_stage: geom_consistency needs depths"; return DPE_ERR_ARG; }
-    for (int i = 1; i < in->num_images; ++i) if (!in->depths[i]) { g_err = "dpe_pm_stage: missing source depth"; return DPE_ERR_ARG; }
-  }
-  StageSrc src;
-  src.st = st;
-  return stage_impl(c, in, src);
-}
-
 template <class T>
 __global__ void k_rescale_nearest(const T* __restrict__ src, int w, int h, T* __restrict__ dst, int nw, int nh, T zero) {
   // RescaleMatToTargetSize (DPE.cpp:1146-1165) with its swapped factors, as host rescale_nearest
@@ -427,253 +296,6 @@ __global__ void k_rescale_depth(const float4* __restrict__ src, int w, int h, fl
   const float scale_x = nw / (float)w, scale_y = nh / (float)h;
   const int o_r = (int)(r / scale_x), o_c = (int)(c / scale_y);
   dst[(size_t)r * nw + c] = (o_r < 0 || o_c < 0 || o_r >= h || o_c >= w) ? 0.0f : src[(size_t)o_r * w + o_c].w;
-}
-
-extern "C" int dpe_pm_stage_resident(DpeContext* c, const DpePassInput* in, int prior_id) {
-  g_err.clear();
-  if (!c || !in || !in->images || !in->cams) { g_err = "dpe_pm_stage_resident: null argument"; return DPE_ERR_ARG; }
-  const DpePatchMatchParams& P = in->params;
-  StageSrc src;
-  auto find = [&](int id) -> ResState* { auto it = c->rstore.find(id); return it == c->rstore.end() ? nullptr : it->second; };
-  if (P.state != DPE_FIRST_INIT || P.use_APD) {
-    src.prior = find(prior_id);
-    if (!src.prior || !src.prior->full) {
-      g_err = "dpe_pm_stage_resident: no resident state of image " + std::to_string(prior_id); return DPE_ERR_STATE;
-    }
-  }
-  if (P.geom_consistency) {
-    if (!in->image_ids) { g_err = "dpe_pm_stage_resident: geom_consistency needs image_ids"; return DPE_ERR_ARG; }
-    for (int i = 1; i < in->num_images && i < DPE_MAX_IMAGES; ++i) {
-      src.dep[i] = find(in->image_ids[i]);
-      if (!src.dep[i]) { g_err = "no depth map of source image " + std::to_string(in->image_ids[i]); return DPE_ERR_STATE; }
-    }
-    src.dep_snap = c->snap_mode;
-    if (src.dep_snap)
-      for (int i = 1; i < in->num_images && i < DPE_MAX_IMAGES; ++i)
-        if (!src.dep[i]->has_snap) { g_err = "no depth snapshot of source image " + std::to_string(in->image_ids[i]); return DPE_ERR_STATE; }
-  }
-  return stage_impl(c, in, src);
-}
-
-static int stage_impl(DpeContext* c, const DpePassInput* in, const StageSrc& src) {
-  g_err.clear();
-  Range range_(src.st ? "dpe_pm_stage" : "dpe_pm_stage_resident");
-  const DpePassState* st = src.st;
-  if (in->num_images > DPE_MAX_IMAGES) { g_err = "dpe_pm_stage: num_images > 32 (DPE.cpp:762)"; return DPE_ERR_TOO_MANY; }
-  if (in->num_images < 2 || in->width <= 0 || in->height <= 0) { g_err = "dpe_pm_stage: bad shape"; return DPE_ERR_ARG; }
-  if (in->width > 32000 || in->height > 32000) { g_err = "dpe_pm_stage: image too large for short2 coordinates"; return DPE_ERR_ARG; }
-  // tap coordinates on the unit grid of [2^23, 2^24) (pass_common.h kTexMagic): 256 (lim + 1) < 2^22
-  if (in->width > 16000 || in->height > 16000) { g_err = "dpe_pm_stage: image wider or taller than 16000 px"; return DPE_ERR_ARG; }
-  const DpePatchMatchParams& P = in->params;
-  if (P.rotate_time < 1 || P.rotate_time > 4) { g_err = "dpe_pm_stage: rotate_time must be in [1,4]"; return DPE_ERR_ARG; }
-  if (P.strong_increment <= 0 || P.weak_increment <= 0) { g_err = "dpe_pm_stage: increments must be > 0"; return DPE_ERR_ARG; }
-  for (int i = 0; i < in->num_images; ++i) if (!in->images[i]) { g_err = "dpe_pm_stage: missing image"; return DPE_ERR_ARG; }
-  if ((P.use_edge || P.use_limit) && (!in->edge || !in->edge_low_res || in->low_width <= 0 || in->low_height <= 0)) {
-    g_err = "dpe_pm_stage: use_edge/use_limit need edge and edge_low_res"; return DPE_ERR_ARG;
-  }
-  if (P.use_label && !in->label) { g_err = "dpe_pm_stage: use_label needs label"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  HIPC(wait_pending(c));   // an earlier execute on a caller stream may still read what is overwritten here
-  const int W = in->width, H = in->height, N = in->num_images;
-  const size_t L = (size_t)W * H;
-  PassConst& pc = c->hc;
-  std::memset(&pc, 0, sizeof(pc));
-  pc.W = W; pc.H = H; pc.N = N;
-  pc.P = P; pc.P.num_images = N;
-  pc.seed32 = (uint32_t)in->seed ^ (uint32_t)(in->seed >> 32);
-  pc.salt = in->pass_salt;
-  for (int i = 0; i < N; ++i) pc.cams[i] = in->cams[i];
-  compute_pass_constants(pc);
-  HIPC(c->dc.ensure(1));
-  HIPC(hipMemcpyAsync(c->dc.p, &pc, sizeof(PassConst), hipMemcpyHostToDevice, c->stream));
-
-  DevBufs& B = c->bufs;
-  std::memset(&B, 0, sizeof(B));
-  const dim3 qb(16, 16), qg((W + 2 + 15) / 16, (H + 2 + 15) / 16);
-  // The half-precision layouts hold every grey level exactly when it is a multiple of 1/4 in
-  // [0, 255] (IMG_Q: the exact 1/2 and 1/4 INTER_LINEAR downscales of an 8-bit image, the coarse
-  // pyramid levels of every BASELINE config; the differences b - a of the F16 / P16 texels are then
-  // exact too); the u8 layout needs integers (IMG_U8: images decoded from 8-bit files).  Identical
-  // sample values in every layout; the smaller ones gather fewer bytes.
-  auto image_class = [&](const float* im) -> int {
-    bool integer = true;
-    for (size_t k = 0; k < L; ++k) {
-      const float v = im[k];
-      if (!(v >= 0.0f && v <= 255.0f)) return IMG_F32;
-      const float v4 = v * 4.0f;   // exact (power of two)
-      if (v4 != (float)(int)v4) return IMG_F32;
-      integer = integer && v == (float)(int)v;
-    }
-    return integer ? IMG_U8 : IMG_Q;
-  };
-  const size_t plane = (size_t)(W + 2) * (H + 2);
-  const size_t pplane = (size_t)(W + 3) * (H + 2);        // TEX_P16
-  const dim3 pg((W + 3 + 15) / 16, (H + 2 + 15) / 16);
-  if (in->image_ids) {   // device-resident images: upload and build layouts once per (id, size)
-    CachedImage* ent[DPE_MAX_IMAGES];
-    const uint64_t call_clock = c->icache_clock;   // entries used by this call have last_use > call_clock
-    for (int i = 0; i < N; ++i) {
-      CachedImage* e = nullptr;
-      for (CachedImage* q : c->icache)
-        if (q->id == in->image_ids[i] && q->W == W && q->H == H) { e = q; break; }
-      if (!e) {
-        size_t total = 0;   // keep the cache under 64 GiB: evict least recently used entries, never one
-        for (CachedImage* q : c->icache) total += q->bytes();   // this call already placed in ent[]
-        while (total > (64ull << 30)) {
-          auto lru = c->icache.end();
-          for (auto it = c->icache.begin(); it != c->icache.end(); ++it)
-            if ((*it)->last_use <= call_clock && (lru == c->icache.end() || (*it)->last_use < (*lru)->last_use)) lru = it;
-          if (lru == c->icache.end()) break;   // only this pass's own views are cached: keep them
-          HIPC(hipStreamSynchronize(c->stream));
-          total -= (*lru)->bytes();
-          (*lru)->release(); delete *lru; c->icache.erase(lru);
-        }
-        e = new CachedImage();
-        e->id = in->image_ids[i]; e->W = W; e->H = H;
-        e->cls = image_class(in->images[i]);
-        c->icache.push_back(e);
-        HIPC(e->plain.ensure(L));
-        HIPC(hipMemcpyAsync(e->plain.p, in->images[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (e->cls != IMG_F32) {
-          if (e->cls == IMG_U8) HIPC(e->q8.ensure(plane));
-          HIPC(e->q16.ensure(plane)); HIPC(e->qp.ensure(pplane));
-          k_build_quad8<<<qg, qb, 0, c->stream>>>(e->plain.p, e->cls == IMG_U8 ? e->q8.p : nullptr, e->q16.p, W, H);
-          k_build_pair16<<<pg, qb, 0, c->stream>>>(e->plain.p, e->qp.p, W, H);
-          HIPC(hipGetLastError());
-        }
-      }
-      e->last_use = ++c->icache_clock;
-      ent[i] = e;
-    }
-    int cls = (size_t)(W + 2) * (H + 2) * 8 * N < (1ull << 32) ? IMG_U8 : IMG_F32;   // 32-bit tap offsets
-    for (int i = 0; i < N; ++i) cls = std::min(cls, ent[i]->cls);
-    c->img_cls = cls;
-    if (cls != IMG_F32) {
-      if (cls == IMG_U8) HIPC(c->imgq8_all.ensure(plane * N));
-      HIPC(c->imgq16_all.ensure(plane * N));
-      HIPC(c->imgqp_all.ensure(pplane * N));
-      for (int i = 0; i < N; ++i) {   // the per-pass views in one allocation (32-bit tap offsets)
-        if (cls == IMG_U8)
-          HIPC(hipMemcpyAsync(c->imgq8_all.p + plane * i, ent[i]->q8.p, plane * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->imgq16_all.p + plane * i, ent[i]->q16.p, plane * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPC(hipMemcpyAsync(c->imgqp_all.p + pplane * i, ent[i]->qp.p, pplane * 4, hipMemcpyDeviceToDevice, c->stream));
-      }
-      if (cls == IMG_U8) { B.img8 = (const uint8_t*)c->imgq8_all.p; B.img8_view = (uint32_t)(plane * 4); }
-      B.img16 = (const uint8_t*)c->imgq16_all.p; B.img16_view = (uint32_t)(plane * 8);
-      B.imgp = (const uint8_t*)c->imgqp_all.p; B.imgp_view = (uint32_t)(pplane * 4);
-    } else {
-      for (int i = 0; i < N; ++i) {
-        if (!ent[i]->qf.p) {
-          HIPC(ent[i]->qf.ensure(plane));
-          k_build_quad<<<qg, qb, 0, c->stream>>>(ent[i]->plain.p, ent[i]->qf.p, W, H);
-          HIPC(hipGetLastError());
-        }
-        B.imgq[i] = ent[i]->qf.p;
-      }
-    }
-    B.ref = ent[0]->plain.p;
-  }
-  int cls = IMG_U8;
-  for (int i = 0; i < N && cls != IMG_F32 && !in->image_ids; ++i) cls = std::min(cls, image_class(in->images[i]));
-  if ((size_t)(W + 2) * (H + 2) * 8 * N >= (1ull << 32)) cls = IMG_F32;   // 32-bit tap offsets
-  if (!in->image_ids) c->img_cls = cls;
-  for (int i = 0; i < N && !in->image_ids; ++i) {
-    HIPC(c->img_plain[i].ensure(L));
-    HIPC(hipMemcpyAsync(c->img_plain[i].p, in->images[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (cls != IMG_F32) {
-      if (cls == IMG_U8) HIPC(c->imgq8_all.ensure(plane * N));
-      HIPC(c->imgq16_all.ensure(plane * N));
-      HIPC(c->imgqp_all.ensure(pplane * N));
-      k_build_quad8<<<qg, qb, 0, c->stream>>>(c->img_plain[i].p, cls == IMG_U8 ? c->imgq8_all.p + plane * i : nullptr,
-                                              c->imgq16_all.p + plane * i, W, H);
-      k_build_pair16<<<pg, qb, 0, c->stream>>>(c->img_plain[i].p, c->imgqp_all.p + pplane * i, W, H);
-      if (cls == IMG_U8) {
-        B.img8 = (const uint8_t*)c->imgq8_all.p;
-        B.img8_view = (uint32_t)(plane * 4);
-      }
-      B.img16 = (const uint8_t*)c->imgq16_all.p;
-      B.img16_view = (uint32_t)(plane * 8);
-      B.imgp = (const uint8_t*)c->imgqp_all.p;
-      B.imgp_view = (uint32_t)(pplane * 4);
-    } else {
-      HIPC(c->imgq[i].ensure((size_t)(W + 2) * (H + 2)));
-      k_build_quad<<<qg, qb, 0, c->stream>>>(c->img_plain[i].p, c->imgq[i].p, W, H);
-      B.imgq[i] = c->imgq[i].p;
-    }
-    HIPC(hipGetLastError());
-  }
-  if (!in->image_ids) B.ref = c->img_plain[0].p;
-  const dim3 rb2(32, 8), rg2((W + 31) / 32, (H + 7) / 8);
-  if (P.geom_consistency) {
-    for (int i = 1; i < N; ++i) {
-      HIPC(c->depth[i].ensure(L));
-      if (st) {
-        HIPC(hipMemcpyAsync(c->depth[i].p, in->depths[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
-      } else {
-        const ResState* r = src.dep[i];
-        if (src.dep_snap)
-          k_rescale_nearest<float><<<rg2, rb2, 0, c->stream>>>(r->snap.p, r->snap_w, r->snap_h, c->depth[i].p, W, H, 0.0f);
-        else
-          k_rescale_depth<<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->depth[i].p, W, H);
-        HIPC(hipGetLastError());
-      }
-      B.depth[i] = c->depth[i].p;
-    }
-  }
-  if (P.use_edge || P.use_limit) {
-    pc.LW = in->low_width; pc.LH = in->low_height;
-    HIPC(c->edge.ensure(L));
-    HIPC(c->edge_low.ensure((size_t)pc.LW * pc.LH));
-    HIPC(hipMemcpyAsync(c->edge.p, in->edge, L, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->edge_low.p, in->edge_low_res, (size_t)pc.LW * pc.LH, hipMemcpyHostToDevice, c->stream));
-    B.edge = c->edge.p; B.edge_low = c->edge_low.p;
-    HIPC(hipMemcpyAsync(c->dc.p, &pc, sizeof(PassConst), hipMemcpyHostToDevice, c->stream));
-  }
-  if (P.use_label) {
-    HIPC(c->label.ensure(L));
-    HIPC(hipMemcpyAsync(c->label.p, in->label, L * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    B.label = c->label.p;
-  }
-  HIPC(c->planes0.ensure(L)); HIPC(c->weak0.ensure(L)); HIPC(c->sel0.ensure(L));
-  if (st) {
-    HIPC(hipMemcpyAsync(c->planes0.p, st->planes, L * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    if (P.use_APD) HIPC(hipMemcpyAsync(c->weak0.p, st->weak_info, L, hipMemcpyHostToDevice, c->stream));
-    else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));   // DPE.cpp:873-881
-    HIPC(hipMemcpyAsync(c->sel0.p, st->selected_views, L * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  } else {   // InuputInitialization's prior (DPE.cpp:845-911) from the resident state, rescaled on device
-    const ResState* r = src.prior;
-    if (P.state != DPE_FIRST_INIT) {
-      k_rescale_nearest<float4><<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->planes0.p, W, H, make_float4(0, 0, 0, 0));
-      k_rescale_nearest<uint32_t><<<rg2, rb2, 0, c->stream>>>(r->sel.p, r->w, r->h, c->sel0.p, W, H, 0u);
-    } else {
-      HIPC(hipMemsetAsync(c->planes0.p, 0, L * sizeof(float4), c->stream));
-      HIPC(hipMemsetAsync(c->sel0.p, 0, L * sizeof(uint32_t), c->stream));
-    }
-    if (P.use_APD) k_rescale_nearest<uint8_t><<<rg2, rb2, 0, c->stream>>>(r->weak.p, r->w, r->h, c->weak0.p, W, H, (uint8_t)0);
-    else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));
-    HIPC(hipGetLastError());
-  }
-  HIPC(c->planes.ensure(L)); HIPC(c->planes_snap.ensure(L)); HIPC(c->fit_plane.ensure(L));
-  HIPC(c->costs.ensure(L)); HIPC(c->costs_snap.ensure(L)); HIPC(c->complex_.ensure(L));
-  HIPC(c->sel.ensure(L)); HIPC(c->sel_snap.ensure(L));
-  HIPC(c->weak.ensure(L)); HIPC(c->weak_rel.ensure(L)); HIPC(c->vw.ensure(L * DPE_MAX_IMAGES));
-  HIPC(c->nb.ensure(L * 9)); HIPC(c->nearest.ensure(L)); HIPC(c->edge_neigh.ensure(L * 8)); HIPC(c->lab_bound.ensure(L * 8));
-  HIPC(c->radius.ensure(L));
-  HIPC(c->tab_right.ensure(L)); HIPC(c->tab_down.ensure(L));
-  HIPC(c->gn_ovf.ensure(L + 64)); HIPC(c->gn_tab.ensure((size_t)W + H));
-  HIPC(c->lists.ensure(6 * (L / 2 + 64) + 3 * (L + 64))); HIPC(c->row_counts.ensure(4 * (size_t)H + 4)); HIPC(c->list_totals.ensure(16));
-  HIPC(c->part_cnt.ensure(2 * ((L / 2 + 1) / kPartChunk + 2)));
-  B.planes = c->planes.p; B.planes_snap = c->planes_snap.p; B.fit_plane = c->fit_plane.p;
-  B.planes0 = c->planes0.p;
-  B.costs = c->costs.p; B.costs_snap = c->costs_snap.p; B.complex_ = c->complex_.p;
-  B.sel = c->sel.p; B.sel_snap = c->sel_snap.p;
-  B.weak = c->weak.p; B.weak_rel = c->weak_rel.p; B.vw = c->vw.p;
-  B.nb = c->nb.p; B.nearest = c->nearest.p; B.edge_neigh = c->edge_neigh.p; B.lab_bound = c->lab_bound.p;
-  B.radius = c->radius.p;
-  HIPC(hipStreamSynchronize(c->stream));
-  c->staged = true;
-  c->gn_done_for_stage = false;
-  return DPE_OK;
 }
 
 // the pass's initial state in one launch: planes, weak_info and selected views from the staged
@@ -706,15 +328,369 @@ __global__ void __launch_bounds__(256) k_snapshot(const uint4* __restrict__ plan
   sel_s[i] = sel[i];
 }
 
-extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
+// where a stage takes the initial state and the source depths from: host buffers (dpe_pm_stage) or
+// the resident store (dpe_pm_stage_resident)
+struct StageSrc {
+  const DpePassState* st = nullptr;   // host initial state
+  const ResState* prior = nullptr;    // resident initial state (nullptr: none, FIRST_INIT)
+  const ResState* dep[DPE_MAX_IMAGES] = {};   // resident source depths (index 1..N-1)
+  bool dep_snap = false;              // read the depths' Jacobi snapshots
+};
+
+// ------------------------------------------------------------------------------ staging
+// stage_impl's steps, in its order.  Each returns a DPE_* code; all enqueue on the context's stream.
+
+static int stage_check_args(const DpePassInput* in) {   // no HIP call
+  if (in->num_images > DPE_MAX_IMAGES) { g_err = "dpe_pm_stage: num_images > 32 (DPE.cpp:762)"; return DPE_ERR_TOO_MANY; }
+  if (in->num_images < 2 || in->width <= 0 || in->height <= 0) { g_err = "dpe_pm_stage: bad shape"; return DPE_ERR_ARG; }
+  if (in->width > 32000 || in->height > 32000) { g_err = "dpe_pm_stage: image too large for short2 coordinates"; return DPE_ERR_ARG; }
+  // tap coordinates on the unit grid of [2^23, 2^24) (pass_common.h kTexMagic): 256 (lim + 1) < 2^22
+  if (in->width > 16000 || in->height > 16000) { g_err = "dpe_pm_stage: image wider or taller than 16000 px"; return DPE_ERR_ARG; }
+  const DpePatchMatchParams& P = in->params;
+  if (P.rotate_time < 1 || P.rotate_time > 4) { g_err = "dpe_pm_stage: rotate_time must be in [1,4]"; return DPE_ERR_ARG; }
+  if (P.strong_increment <= 0 || P.weak_increment <= 0) { g_err = "dpe_pm_stage: increments must be > 0"; return DPE_ERR_ARG; }
+  for (int i = 0; i < in->num_images; ++i) if (!in->images[i]) { g_err = "dpe_pm_stage: missing image"; return DPE_ERR_ARG; }
+  if ((P.use_edge || P.use_limit) && (!in->edge || !in->edge_low_res || in->low_width <= 0 || in->low_height <= 0)) {
+    g_err = "dpe_pm_stage: use_edge/use_limit need edge and edge_low_res"; return DPE_ERR_ARG;
+  }
+  if (P.use_label && !in->label) { g_err = "dpe_pm_stage: use_label needs label"; return DPE_ERR_ARG; }
+  return DPE_OK;
+}
+
+static void set_pass_constants(PassConst& pc, const DpePassInput* in) {
+  std::memset(&pc, 0, sizeof(pc));
+  pc.W = in->width; pc.H = in->height; pc.N = in->num_images;
+  pc.P = in->params; pc.P.num_images = pc.N;
+  pc.seed32 = (uint32_t)in->seed ^ (uint32_t)(in->seed >> 32);
+  pc.salt = in->pass_salt;
+  for (int i = 0; i < pc.N; ++i) pc.cams[i] = in->cams[i];
+  if (pc.P.use_edge || pc.P.use_limit) { pc.LW = in->low_width; pc.LH = in->low_height; }
+  compute_pass_constants(pc);
+}
+
+// The half-precision layouts hold every grey level exactly when it is a multiple of 1/4 in
+// [0, 255] (IMG_Q: the exact 1/2 and 1/4 INTER_LINEAR downscales of an 8-bit image, the coarse
+// pyramid levels of every BASELINE config; the differences b - a of the F16 / P16 texels are then
+// exact too); the u8 layout needs integers (IMG_U8: images decoded from 8-bit files).  Identical
+// sample values in every layout; the smaller ones gather fewer bytes.
+static int image_class(const float* im, size_t L) {
+  bool integer = true;
+  for (size_t k = 0; k < L; ++k) {
+    const float v = im[k];
+    if (!(v >= 0.0f && v <= 255.0f)) return IMG_F32;
+    const float v4 = v * 4.0f;   // exact (power of two)
+    if (v4 != (float)(int)v4) return IMG_F32;
+    integer = integer && v == (float)(int)v;
+  }
+  return integer ? IMG_U8 : IMG_Q;
+}
+
+// The texel class of a pass: the narrowest class of its views (IMG_F32 < IMG_Q < IMG_U8), and f32
+// when the views' packed arrays would not fit the 32-bit tap offsets.
+static int pass_class(int W, int H, int N, const int* view_cls) {
+  int cls = (size_t)(W + 2) * (H + 2) * 8 * N < (1ull << 32) ? IMG_U8 : IMG_F32;
+  for (int i = 0; i < N; ++i) cls = std::min(cls, view_cls[i]);
+  return cls;
+}
+
+static size_t quad_plane(int W, int H) { return (size_t)(W + 2) * (H + 2); }   // padded quad texels of one view
+static size_t pair_plane(int W, int H) { return (size_t)(W + 3) * (H + 2); }   // TEX_P16 column pairs of one view
+
+// The half-precision layouts of one image: TEX_F16 quads into q16, TEX_P16 column pairs into qp and,
+// for an 8-bit image (q8 != nullptr), TEX_U8 quads into q8.
+static int build_packed_layouts(hipStream_t s, const float* plain, int W, int H, uint32_t* q8, uint2* q16, uint32_t* qp) {
+  const dim3 qb(16, 16), qg((W + 2 + 15) / 16, (H + 2 + 15) / 16), pg((W + 3 + 15) / 16, (H + 2 + 15) / 16);
+  k_build_quad8<<<qg, qb, 0, s>>>(plain, q8, q16, W, H);
+  k_build_pair16<<<pg, qb, 0, s>>>(plain, qp, W, H);
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+static int build_f32_quads(hipStream_t s, const float* plain, int W, int H, float4* qf) {
+  k_build_quad<<<dim3((W + 2 + 15) / 16, (H + 2 + 15) / 16), dim3(16, 16), 0, s>>>(plain, qf, W, H);
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+// The packed arrays of a pass of class IMG_U8 / IMG_Q: every view's layout in one allocation (32-bit
+// tap offsets), sized for N views and bound into the pass's DevBufs.
+static int bind_packed_arrays(DpeContext* c, int cls, int W, int H, int N) {
+  const size_t plane = quad_plane(W, H), pplane = pair_plane(W, H);
+  DevBufs& B = c->bufs;
+  if (cls == IMG_U8) {
+    HIPC(c->imgq8_all.ensure(plane * N));
+    B.img8 = (const uint8_t*)c->imgq8_all.p; B.img8_view = (uint32_t)(plane * 4);
+  }
+  HIPC(c->imgq16_all.ensure(plane * N));
+  HIPC(c->imgqp_all.ensure(pplane * N));
+  B.img16 = (const uint8_t*)c->imgq16_all.p; B.img16_view = (uint32_t)(plane * 8);
+  B.imgp = (const uint8_t*)c->imgqp_all.p; B.imgp_view = (uint32_t)(pplane * 4);
+  return DPE_OK;
+}
+
+// The cache entry of (id, W, H): the one kept, or a new one (upload and the layouts of its own
+// class, once).  A new entry first brings the cache under 64 GiB by evicting least recently used
+// entries, never one the current call uses (last_use > call_clock).
+static int cached_image(DpeContext* c, int id, const float* host, int W, int H, uint64_t call_clock, CachedImage** out) {
+  CachedImage* e = nullptr;
+  for (auto& q : c->icache)
+    if (q->id == id && q->W == W && q->H == H) { e = q.get(); break; }
+  if (!e) {
+    size_t total = 0;
+    for (auto& q : c->icache) total += q->bytes();
+    while (total > (64ull << 30)) {
+      auto lru = c->icache.end();
+      for (auto it = c->icache.begin(); it != c->icache.end(); ++it)
+        if ((*it)->last_use <= call_clock && (lru == c->icache.end() || (*it)->last_use < (*lru)->last_use)) lru = it;
+      if (lru == c->icache.end()) break;   // only this pass's own views are cached: keep them
+      HIPC(hipStreamSynchronize(c->stream));   // nothing enqueued may still read the entry
+      total -= (*lru)->bytes();
+      c->icache.erase(lru);
+    }
+    const size_t L = (size_t)W * H;
+    auto fresh = std::make_unique<CachedImage>();
+    fresh->id = id; fresh->W = W; fresh->H = H;
+    fresh->cls = image_class(host, L);
+    HIPC(fresh->plain.ensure(L));
+    HIPC(hipMemcpyAsync(fresh->plain.p, host, L * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (fresh->cls != IMG_F32) {
+      if (fresh->cls == IMG_U8) HIPC(fresh->q8.ensure(quad_plane(W, H)));
+      HIPC(fresh->q16.ensure(quad_plane(W, H))); HIPC(fresh->qp.ensure(pair_plane(W, H)));
+      TRY(build_packed_layouts(c->stream, fresh->plain.p, W, H, fresh->q8.p, fresh->q16.p, fresh->qp.p));
+    }
+    e = fresh.get();
+    c->icache.push_back(std::move(fresh));   // kept only once it is complete
+  }
+  e->last_use = ++c->icache_clock;
+  *out = e;
+  return DPE_OK;
+}
+
+// Device-resident images (image_ids): each view from the cache, then the pass's views gathered
+// device to device into the packed arrays, or (f32 pass) each entry's f32 quads, built on demand.
+static int stage_images_cached(DpeContext* c, const DpePassInput* in) {
+  const int W = in->width, H = in->height, N = in->num_images;
+  const size_t plane = quad_plane(W, H), pplane = pair_plane(W, H);
+  CachedImage* ent[DPE_MAX_IMAGES];
+  int view_cls[DPE_MAX_IMAGES];
+  const uint64_t call_clock = c->icache_clock;   // entries used by this call have last_use > call_clock
+  for (int i = 0; i < N; ++i) {
+    TRY(cached_image(c, in->image_ids[i], in->images[i], W, H, call_clock, &ent[i]));
+    view_cls[i] = ent[i]->cls;
+  }
+  const int cls = c->img_cls = pass_class(W, H, N, view_cls);
+  DevBufs& B = c->bufs;
+  if (cls != IMG_F32) {
+    TRY(bind_packed_arrays(c, cls, W, H, N));
+    for (int i = 0; i < N; ++i) {
+      if (cls == IMG_U8)
+        HIPC(hipMemcpyAsync(c->imgq8_all.p + plane * i, ent[i]->q8.p, plane * 4, hipMemcpyDeviceToDevice, c->stream));
+      HIPC(hipMemcpyAsync(c->imgq16_all.p + plane * i, ent[i]->q16.p, plane * 8, hipMemcpyDeviceToDevice, c->stream));
+      HIPC(hipMemcpyAsync(c->imgqp_all.p + pplane * i, ent[i]->qp.p, pplane * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+  } else {
+    for (int i = 0; i < N; ++i) {
+      if (!ent[i]->qf.p) {
+        HIPC(ent[i]->qf.ensure(plane));
+        TRY(build_f32_quads(c->stream, ent[i]->plain.p, W, H, ent[i]->qf.p));
+      }
+      B.imgq[i] = ent[i]->qf.p;
+    }
+  }
+  B.ref = ent[0]->plain.p;
+  return DPE_OK;
+}
+
+// Images uploaded for this pass only: the layouts of the pass's class built straight into the
+// packed arrays, or (f32 pass) into the context's per-view quads.
+static int stage_images_direct(DpeContext* c, const DpePassInput* in) {
+  const int W = in->width, H = in->height, N = in->num_images;
+  const size_t L = (size_t)W * H, plane = quad_plane(W, H), pplane = pair_plane(W, H);
+  int view_cls[DPE_MAX_IMAGES];
+  for (int i = 0; i < N; ++i)   // one f32 view decides: the rest are not scanned
+    view_cls[i] = i > 0 && view_cls[i - 1] == IMG_F32 ? IMG_F32 : image_class(in->images[i], L);
+  const int cls = c->img_cls = pass_class(W, H, N, view_cls);
+  DevBufs& B = c->bufs;
+  if (cls != IMG_F32) TRY(bind_packed_arrays(c, cls, W, H, N));
+  for (int i = 0; i < N; ++i) {
+    HIPC(c->img_plain[i].ensure(L));
+    HIPC(hipMemcpyAsync(c->img_plain[i].p, in->images[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (cls != IMG_F32) {
+      TRY(build_packed_layouts(c->stream, c->img_plain[i].p, W, H, cls == IMG_U8 ? c->imgq8_all.p + plane * i : nullptr,
+                               c->imgq16_all.p + plane * i, c->imgqp_all.p + pplane * i));
+    } else {
+      HIPC(c->imgq[i].ensure(plane));
+      TRY(build_f32_quads(c->stream, c->img_plain[i].p, W, H, c->imgq[i].p));
+      B.imgq[i] = c->imgq[i].p;
+    }
+  }
+  B.ref = c->img_plain[0].p;
+  return DPE_OK;
+}
+
+// Source depth maps of the geometric term: from the host, or the resident states (or their Jacobi
+// snapshots) rescaled on the device.
+static int stage_source_depths(DpeContext* c, const DpePassInput* in, const StageSrc& src) {
+  const int W = in->width, H = in->height;
+  const size_t L = (size_t)W * H;
+  const dim3 rb2(32, 8), rg2((W + 31) / 32, (H + 7) / 8);
+  for (int i = 1; i < in->num_images; ++i) {
+    HIPC(c->depth[i].ensure(L));
+    if (src.st) {
+      HIPC(hipMemcpyAsync(c->depth[i].p, in->depths[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    } else {
+      const ResState* r = src.dep[i];
+      if (src.dep_snap)
+        k_rescale_nearest<float><<<rg2, rb2, 0, c->stream>>>(r->snap.p, r->snap_w, r->snap_h, c->depth[i].p, W, H, 0.0f);
+      else
+        k_rescale_depth<<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->depth[i].p, W, H);
+      HIPC(hipGetLastError());
+    }
+    c->bufs.depth[i] = c->depth[i].p;
+  }
+  return DPE_OK;
+}
+
+static int stage_edge_label_maps(DpeContext* c, const DpePassInput* in) {
+  const size_t L = (size_t)in->width * in->height, LL = (size_t)in->low_width * in->low_height;
+  DevBufs& B = c->bufs;
+  if (in->params.use_edge || in->params.use_limit) {
+    HIPC(c->edge.ensure(L));
+    HIPC(c->edge_low.ensure(LL));
+    HIPC(hipMemcpyAsync(c->edge.p, in->edge, L, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->edge_low.p, in->edge_low_res, LL, hipMemcpyHostToDevice, c->stream));
+    B.edge = c->edge.p; B.edge_low = c->edge_low.p;
+  }
+  if (in->params.use_label) {
+    HIPC(c->label.ensure(L));
+    HIPC(hipMemcpyAsync(c->label.p, in->label, L * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    B.label = c->label.p;
+  }
+  return DPE_OK;
+}
+
+// The staged initial state (k_pass_init copies it at the start of every execute): from the host, or
+// InuputInitialization's prior (DPE.cpp:845-911) from the resident state, rescaled on the device.
+static int stage_initial_state(DpeContext* c, const DpePassInput* in, const StageSrc& src) {
+  const DpePatchMatchParams& P = in->params;
+  const int W = in->width, H = in->height;
+  const size_t L = (size_t)W * H;
+  HIPC(c->planes0.ensure(L)); HIPC(c->weak0.ensure(L)); HIPC(c->sel0.ensure(L));
+  if (const DpePassState* st = src.st) {
+    HIPC(hipMemcpyAsync(c->planes0.p, st->planes, L * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (P.use_APD) HIPC(hipMemcpyAsync(c->weak0.p, st->weak_info, L, hipMemcpyHostToDevice, c->stream));
+    else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));   // DPE.cpp:873-881
+    HIPC(hipMemcpyAsync(c->sel0.p, st->selected_views, L * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    return DPE_OK;
+  }
+  const ResState* r = src.prior;
+  const dim3 rb2(32, 8), rg2((W + 31) / 32, (H + 7) / 8);
+  if (P.state != DPE_FIRST_INIT) {
+    k_rescale_nearest<float4><<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->planes0.p, W, H, make_float4(0, 0, 0, 0));
+    k_rescale_nearest<uint32_t><<<rg2, rb2, 0, c->stream>>>(r->sel.p, r->w, r->h, c->sel0.p, W, H, 0u);
+  } else {
+    HIPC(hipMemsetAsync(c->planes0.p, 0, L * sizeof(float4), c->stream));
+    HIPC(hipMemsetAsync(c->sel0.p, 0, L * sizeof(uint32_t), c->stream));
+  }
+  if (P.use_APD) k_rescale_nearest<uint8_t><<<rg2, rb2, 0, c->stream>>>(r->weak.p, r->w, r->h, c->weak0.p, W, H, (uint8_t)0);
+  else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+// The buffers a pass works in, sized for W x H and bound into the pass's DevBufs.
+static int ensure_working_set(DpeContext* c, int W, int H) {
+  const size_t L = (size_t)W * H;
+  HIPC(c->planes.ensure(L)); HIPC(c->planes_snap.ensure(L)); HIPC(c->fit_plane.ensure(L));
+  HIPC(c->costs.ensure(L)); HIPC(c->costs_snap.ensure(L)); HIPC(c->complex_.ensure(L));
+  HIPC(c->sel.ensure(L)); HIPC(c->sel_snap.ensure(L));
+  HIPC(c->weak.ensure(L)); HIPC(c->weak_rel.ensure(L)); HIPC(c->vw.ensure(L * DPE_MAX_IMAGES));
+  HIPC(c->nb.ensure(L * 9)); HIPC(c->nearest.ensure(L)); HIPC(c->edge_neigh.ensure(L * 8)); HIPC(c->lab_bound.ensure(L * 8));
+  HIPC(c->radius.ensure(L));
+  HIPC(c->tab_right.ensure(L)); HIPC(c->tab_down.ensure(L));
+  HIPC(c->gn_ovf.ensure(L + 64)); HIPC(c->gn_tab.ensure((size_t)W + H));
+  HIPC(c->lists.ensure(6 * (L / 2 + 64) + 3 * (L + 64))); HIPC(c->row_counts.ensure(4 * (size_t)H + 4)); HIPC(c->list_totals.ensure(16));
+  HIPC(c->part_cnt.ensure(2 * ((L / 2 + 1) / kPartChunk + 2)));
+  DevBufs& B = c->bufs;
+  B.planes = c->planes.p; B.planes_snap = c->planes_snap.p; B.fit_plane = c->fit_plane.p;
+  B.planes0 = c->planes0.p;
+  B.costs = c->costs.p; B.costs_snap = c->costs_snap.p; B.complex_ = c->complex_.p;
+  B.sel = c->sel.p; B.sel_snap = c->sel_snap.p;
+  B.weak = c->weak.p; B.weak_rel = c->weak_rel.p; B.vw = c->vw.p;
+  B.nb = c->nb.p; B.nearest = c->nearest.p; B.edge_neigh = c->edge_neigh.p; B.lab_bound = c->lab_bound.p;
+  B.radius = c->radius.p;
+  return DPE_OK;
+}
+
+static int stage_impl(DpeContext* c, const DpePassInput* in, const StageSrc& src) {
+  Range range_(src.st ? "dpe_pm_stage" : "dpe_pm_stage_resident");
+  TRY(stage_check_args(in));
+  HIPC(hipSetDevice(c->device));
+  HIPC(wait_pending(c));   // an earlier execute on a caller stream may still read what is overwritten here
+  set_pass_constants(c->hc, in);
+  HIPC(c->dc.ensure(1));
+  HIPC(hipMemcpyAsync(c->dc.p, &c->hc, sizeof(PassConst), hipMemcpyHostToDevice, c->stream));
+  std::memset(&c->bufs, 0, sizeof(c->bufs));
+  TRY(in->image_ids ? stage_images_cached(c, in) : stage_images_direct(c, in));
+  if (in->params.geom_consistency) TRY(stage_source_depths(c, in, src));
+  TRY(stage_edge_label_maps(c, in));
+  TRY(stage_initial_state(c, in, src));
+  TRY(ensure_working_set(c, in->width, in->height));
+  HIPC(hipStreamSynchronize(c->stream));
+  c->staged = true;
+#if DPE_GN_ONCE
+  c->gn_done_for_stage = false;
+#endif
+  return DPE_OK;
+}
+
+extern "C" int dpe_pm_stage(DpeContext* c, const DpePassInput* in, const DpePassState* st) {
   g_err.clear();
-  if (!c) { g_err = "dpe_pm_execute: null context"; return DPE_ERR_ARG; }
+  if (!c || !in || !st || !in->images || !in->cams || !st->planes || !st->weak_info || !st->selected_views) {
+    g_err = "dpe_pm_stage: null argument"; return DPE_ERR_ARG;
+  }
+  if (in->params.geom_consistency) {
+    if (!in->depths) { g_err = "dpe_pm_stage: geom_consistency needs depths"; return DPE_ERR_ARG; }
+    for (int i = 1; i < in->num_images; ++i) if (!in->depths[i]) { g_err = "dpe_pm_stage: missing source depth"; return DPE_ERR_ARG; }
+  }
+  StageSrc src;
+  src.st = st;
+  return stage_impl(c, in, src);
+}
+
+extern "C" int dpe_pm_stage_resident(DpeContext* c, const DpePassInput* in, int prior_id) {
+  g_err.clear();
+  if (!c || !in || !in->images || !in->cams) { g_err = "dpe_pm_stage_resident: null argument"; return DPE_ERR_ARG; }
+  const DpePatchMatchParams& P = in->params;
+  StageSrc src;
+  auto find = [&](int id) -> const ResState* { auto it = c->rstore.find(id); return it == c->rstore.end() ? nullptr : &it->second; };
+  if (P.state != DPE_FIRST_INIT || P.use_APD) {
+    src.prior = find(prior_id);
+    if (!src.prior || !src.prior->full) {
+      g_err = "dpe_pm_stage_resident: no resident state of image " + std::to_string(prior_id); return DPE_ERR_STATE;
+    }
+  }
+  if (P.geom_consistency) {
+    if (!in->image_ids) { g_err = "dpe_pm_stage_resident: geom_consistency needs image_ids"; return DPE_ERR_ARG; }
+    for (int i = 1; i < in->num_images && i < DPE_MAX_IMAGES; ++i) {
+      src.dep[i] = find(in->image_ids[i]);
+      if (!src.dep[i]) { g_err = "no depth map of source image " + std::to_string(in->image_ids[i]); return DPE_ERR_STATE; }
+    }
+    src.dep_snap = c->snap_mode;
+    if (src.dep_snap)
+      for (int i = 1; i < in->num_images && i < DPE_MAX_IMAGES; ++i)
+        if (!src.dep[i]->has_snap) { g_err = "no depth snapshot of source image " + std::to_string(in->image_ids[i]); return DPE_ERR_STATE; }
+  }
+  return stage_impl(c, in, src);
+}
+
+extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
+  TRY(enter(c, true, "dpe_pm_execute: null context"));
   if (!c->staged) { g_err = "dpe_pm_execute: call dpe_pm_stage first"; return DPE_ERR_STATE; }
   Range range_("dpe_pm_execute");
-  HIPC(hipSetDevice(c->device));
-  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
+  hipStream_t s;
   // a previous execute, possibly on another stream, still uses the working buffers this one resets
-  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));
+  HIPC(enqueue_stream(c, stream_, &s));
   const PassConst& pc = c->hc;
   const PassConst* dpc = c->dc.p;
   const int W = pc.W, H = pc.H, nv = pc.N - 1;
@@ -738,10 +714,10 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   // launch sequence (setup, init, 5 per iteration, filter, DepthToWeak, LocalRefine)
   const bool timing = c->timing;
   const int max_slots = 5 + 5 * std::max(0, pc.P.max_iterations);
-  if (timing && (int)c->ev.size() < 2 * max_slots) {
-    const size_t have = c->ev.size();
-    c->ev.resize(2 * max_slots, nullptr);
-    for (size_t k = have; k < c->ev.size(); ++k) HIPC(hipEventCreate(&c->ev[k]));
+  while (timing && (int)c->ev.size() < 2 * max_slots) {
+    Event e;
+    HIPC(e.create(hipEventDefault));
+    c->ev.push_back(std::move(e));
   }
   int nev = 0;
   bool slot_overflow = false;   // more timed sections than slots: fail the timed execute loudly
@@ -764,12 +740,21 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   };
 
   if (timing) (void)hipEventRecord(c->ev_start, s);
-  // DPE_DBG_GN_ONCE=1 (timing experiments only): GenNeighbours runs in the first execute after a stage
-  // and its outputs (nb, weak_rel and complex_, which GenEdgeInform rewrites: restored after it) are kept for the next executes of the same staged state,
-  // which then skip it -- the same results (GenNeighbours depends only on the staged state), and the
-  // pass time without GenNeighbours on the critical path
-  static const bool gn_once = [] { const char* e = getenv("DPE_DBG_GN_ONCE"); return e && atoi(e) == 1; }();
-  const bool gn_skip = gn_once && c->gn_done_for_stage;
+#if DPE_GN_ONCE
+  // Timing builds only (pass_common.h): GenNeighbours runs in the first execute after a stage and its
+  // outputs (nb, weak_rel, and complex_, which GenEdgeInform rewrites: restored after it) are kept
+  // for the next executes of the same staged state, which then skip it -- the same results
+  // (GenNeighbours depends only on the staged state), and the pass time without GenNeighbours on the
+  // critical path.  An execute that fails forgets them.
+  const bool gn_skip = c->gn_done_for_stage;
+  struct GnGuard {
+    DpeContext* c;
+    bool ok = false;
+    ~GnGuard() { if (!ok) c->gn_done_for_stage = false; }
+  } gn_guard{c};
+#else
+  constexpr bool gn_skip = false;   // GenNeighbours runs in every execute
+#endif
   // initial state (the reference uploads it in CudaSpaceInitialization, DPE.cpp:964-1015)
   k_pass_init<<<(unsigned)((L + 255) / 256), 256, 0, s>>>((const uint4*)c->planes0.p, c->weak0.p, c->sel0.p, (uint4*)B.planes,
                                                           B.weak, B.sel, (uint32_t*)B.costs, (uint4*)B.vw, L);
@@ -828,7 +813,9 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   if (const int rc = clear_setup_state(a); rc != DPE_OK) return rc;
   k_gen_edge_inform<<<fg, fb, 0, a>>>(dpc, Bc);
   if (pc.P.use_edge) k_edge_rays<<<(unsigned)(3 * (W + H) - 2), 64, 0, a>>>(dpc, Bc);
+#if DPE_GN_ONCE
   if (gn_skip) HIPC(hipMemcpyAsync(B.complex_, c->gn_complex.p, L * sizeof(float), hipMemcpyDeviceToDevice, a));
+#endif
   if (overlap) HIPC(hipEventRecord(c->ev_ei, a));
   k_strong_tables_scan<<<(unsigned)(W + H), 64, 0, a>>>(dpc, Bc, c->tab_right.p, c->tab_down.p);
   k_find_nearest_strong<<<fg, fb, 0, a>>>(dpc, Bc, c->tab_right.p, c->tab_down.p);
@@ -855,11 +842,13 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   } else {
     k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(dpc, Bc, weak_list, c->list_totals.p + 4);
   }
-  if (gn_once && !gn_skip) {
+#if DPE_GN_ONCE
+  if (!gn_skip) {
     HIPC(c->gn_complex.ensure(L));
     HIPC(hipMemcpyAsync(c->gn_complex.p, B.complex_, L * sizeof(float), hipMemcpyDeviceToDevice, a));
     c->gn_done_for_stage = true;
   }
+#endif
   k_neighbour_update<<<fg, fb, 0, a>>>(dpc, Bc);
   if (overlap) {
     k_list_count<2><<<(pc.half_rows + 3) / 4, 256, 0, a>>>(dpc, Bc, c->row_counts.p);
@@ -1008,20 +997,19 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
     HIPC(hipStreamSynchronize(s));
     for (int k = 0; k < DPE_NUM_CLASSES; ++k) c->counts[4 * k + 3] = (unsigned long long)c->launches[k];
   }
-  HIPC(hipEventRecord(c->ev_done, s));
-  c->pending = true;
+  HIPC(mark_pending(c, s));
+#if DPE_GN_ONCE
+  gn_guard.ok = true;
+#endif
   return DPE_OK;
 }
 
 extern "C" int dpe_pm_fetch(DpeContext* c, const DpePassState* st) {
-  g_err.clear();
-  if (!c || !st) { g_err = "dpe_pm_fetch: null argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, st != nullptr, "dpe_pm_fetch: null argument"));
   if (!c->staged) { g_err = "dpe_pm_fetch: nothing staged"; return DPE_ERR_STATE; }
-  HIPC(hipSetDevice(c->device));
   Range range_("dpe_pm_fetch");
   const size_t L = (size_t)c->hc.W * c->hc.H;
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(host_wait(c));
   if (st->planes) HIPC(hipMemcpy(st->planes, c->bufs.planes, L * sizeof(float4), hipMemcpyDeviceToHost));
   if (st->weak_info) HIPC(hipMemcpy(st->weak_info, c->bufs.weak, L, hipMemcpyDeviceToHost));
   if (st->selected_views) HIPC(hipMemcpy(st->selected_views, c->bufs.sel, L * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1045,12 +1033,10 @@ __global__ void k_export_depth(const float4* __restrict__ p, float* __restrict__
 }
 
 extern "C" int dpe_pm_export_depth(DpeContext* c, float* dev_dst, void* stream_) {
-  g_err.clear();
-  if (!c || !dev_dst) { g_err = "dpe_pm_export_depth: null argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, dev_dst != nullptr, "dpe_pm_export_depth: null argument"));
   if (!c->staged) { g_err = "dpe_pm_export_depth: nothing staged"; return DPE_ERR_STATE; }
-  HIPC(hipSetDevice(c->device));
-  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
-  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));   // after the pass that writes the planes
+  hipStream_t s;
+  HIPC(enqueue_stream(c, stream_, &s));   // after the pass that writes the planes
   const size_t L = (size_t)c->hc.W * c->hc.H;
   k_export_depth<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(c->bufs.planes, dev_dst, L);
   HIPC(hipGetLastError());
@@ -1078,47 +1064,34 @@ __global__ void k_depth_into(const float* __restrict__ d, float4* __restrict__ p
   if (i < L) p[i].w = d[i];
 }
 
-static ResState* state_slot(DpeContext* c, int id) {
-  auto it = c->rstore.find(id);
-  if (it != c->rstore.end()) return it->second;
-  ResState* r = new ResState();
-  c->rstore[id] = r;
-  return r;
-}
-
 extern "C" int dpe_state_save(DpeContext* c, int image_id) {
-  g_err.clear();
-  if (!c) { g_err = "dpe_state_save: null context"; return DPE_ERR_ARG; }
+  TRY(enter(c, true, "dpe_state_save: null context"));
   if (!c->staged) { g_err = "dpe_state_save: nothing staged"; return DPE_ERR_STATE; }
-  HIPC(hipSetDevice(c->device));
   Range range_("dpe_state_save");
   const int W = c->hc.W, H = c->hc.H;
   const size_t L = (size_t)W * H;
-  if (c->pending) HIPC(hipStreamWaitEvent(c->stream, c->ev_done, 0));   // after the pass that wrote the outputs
-  ResState* r = state_slot(c, image_id);
+  hipStream_t s;
+  HIPC(enqueue_stream(c, nullptr, &s));   // the context's stream, after the pass that wrote the outputs
+  ResState* r = &c->rstore[image_id];
   HIPC(r->planes.ensure(L)); HIPC(r->weak.ensure(L)); HIPC(r->sel.ensure(L));
   r->w = W; r->h = H; r->full = true;
-  k_state_save<<<(unsigned)((L + 255) / 256), 256, 0, c->stream>>>(c->bufs.planes, c->bufs.weak, c->bufs.sel, c->hc.P.depth_min,
-                                                                  c->hc.P.depth_max, r->planes.p, r->weak.p, r->sel.p, L);
+  k_state_save<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(c->bufs.planes, c->bufs.weak, c->bufs.sel, c->hc.P.depth_min,
+                                                          c->hc.P.depth_max, r->planes.p, r->weak.p, r->sel.p, L);
   HIPC(hipGetLastError());
-  HIPC(hipEventRecord(c->ev_done, c->stream));   // the next execute / stage waits for the save too
-  c->pending = true;
+  HIPC(mark_pending(c, s));   // the next execute / stage waits for the save too
   return DPE_OK;
 }
 
 extern "C" int dpe_state_fetch(DpeContext* c, int image_id, int* w, int* h, float* depth, float* normal, uint8_t* weak,
                                uint32_t* sel) {
-  g_err.clear();
-  if (!c) { g_err = "dpe_state_fetch: null context"; return DPE_ERR_ARG; }
+  TRY(enter(c, true, "dpe_state_fetch: null context"));
   auto it = c->rstore.find(image_id);
   if (it == c->rstore.end()) { g_err = "dpe_state_fetch: no state of image " + std::to_string(image_id); return DPE_ERR_STATE; }
-  ResState* r = it->second;
+  const ResState* r = &it->second;
   if (w) *w = r->w;
   if (h) *h = r->h;
   const size_t L = (size_t)r->w * r->h;
-  HIPC(hipSetDevice(c->device));
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(host_wait(c));
   if (depth || normal) {
     std::vector<float4> p(L);
     HIPC(hipMemcpy(p.data(), r->planes.p, L * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1136,46 +1109,40 @@ extern "C" int dpe_state_fetch(DpeContext* c, int image_id, int* w, int* h, floa
 }
 
 extern "C" int dpe_state_snapshot(DpeContext* c) {
-  g_err.clear();
-  if (!c) { g_err = "dpe_state_snapshot: null context"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  if (c->pending) HIPC(hipStreamWaitEvent(c->stream, c->ev_done, 0));
+  TRY(enter(c, true, "dpe_state_snapshot: null context"));
+  hipStream_t s;
+  HIPC(enqueue_stream(c, nullptr, &s));
   for (auto& kv : c->rstore) {
-    ResState* r = kv.second;
+    ResState* r = &kv.second;
     const size_t L = (size_t)r->w * r->h;
     HIPC(r->snap.ensure(L));
-    k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, c->stream>>>(r->planes.p, r->snap.p, L);
+    k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(r->planes.p, r->snap.p, L);
     r->snap_w = r->w; r->snap_h = r->h;
     r->has_snap = true;
   }
   HIPC(hipGetLastError());
-  HIPC(hipEventRecord(c->ev_done, c->stream));
-  c->pending = true;
+  HIPC(mark_pending(c, s));
   c->snap_mode = true;
   return DPE_OK;
 }
 
 extern "C" int dpe_state_export_depth(DpeContext* c, int image_id, float* dev_dst, void* stream_) {
-  g_err.clear();
-  if (!c || !dev_dst) { g_err = "dpe_state_export_depth: null argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, dev_dst != nullptr, "dpe_state_export_depth: null argument"));
   auto it = c->rstore.find(image_id);
   if (it == c->rstore.end()) { g_err = "dpe_state_export_depth: no state of image " + std::to_string(image_id); return DPE_ERR_STATE; }
-  HIPC(hipSetDevice(c->device));
-  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
-  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));
-  const size_t L = (size_t)it->second->w * it->second->h;
-  k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(it->second->planes.p, dev_dst, L);
+  hipStream_t s;
+  HIPC(enqueue_stream(c, stream_, &s));
+  const size_t L = (size_t)it->second.w * it->second.h;
+  k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(it->second.planes.p, dev_dst, L);
   HIPC(hipGetLastError());
   return DPE_OK;
 }
 
 extern "C" int dpe_state_import_depth(DpeContext* c, int image_id, int w, int h, const float* dev_src, void* stream_) {
-  g_err.clear();
-  if (!c || !dev_src || w <= 0 || h <= 0) { g_err = "dpe_state_import_depth: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
-  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));   // an execute may still read this state's depth
-  ResState* r = state_slot(c, image_id);
+  TRY(enter(c, dev_src && w > 0 && h > 0, "dpe_state_import_depth: bad argument"));
+  hipStream_t s;
+  HIPC(enqueue_stream(c, stream_, &s));   // an execute may still read this state's depth
+  ResState* r = &c->rstore[image_id];
   const size_t L = (size_t)w * h;
   if (r->w != w || r->h != h) {
     HIPC(r->planes.ensure(L));
@@ -1184,10 +1151,7 @@ extern "C" int dpe_state_import_depth(DpeContext* c, int image_id, int w, int h,
   }
   k_depth_into<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(dev_src, r->planes.p, L);
   HIPC(hipGetLastError());
-  if (s != c->stream) {   // later stages on the context stream read it
-    HIPC(hipEventRecord(c->ev_done, s));
-    c->pending = true;
-  }
+  HIPC(publish_foreign(c, s));   // later stages on the context stream read it
   return DPE_OK;
 }
 
@@ -1196,27 +1160,21 @@ extern "C" float* dpe_device_buffer(DpeContext* c, int slot, size_t count) {
   if (!c || slot < 0 || slot > 1) { g_err = "dpe_device_buffer: bad argument"; return nullptr; }
   if (hipSetDevice(c->device) != hipSuccess) { g_err = "dpe_device_buffer: hipSetDevice"; return nullptr; }
   if (c->xbuf[slot].n < count) {
-    if (wait_pending(c) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { g_err = "dpe_device_buffer: sync"; return nullptr; }
+    if (host_wait(c) != hipSuccess) { g_err = "dpe_device_buffer: sync"; return nullptr; }
     if (c->xbuf[slot].ensure(count) != hipSuccess) { g_err = "dpe_device_buffer: hipMalloc"; return nullptr; }
   }
   return c->xbuf[slot].p;
 }
 
 extern "C" int dpe_sync(DpeContext* c) {
-  g_err.clear();
-  if (!c) { g_err = "dpe_sync: null context"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  TRY(enter(c, true, "dpe_sync: null context"));
+  HIPC(host_wait(c));
   return DPE_OK;
 }
 
 extern "C" int dpe_device_copy(DpeContext* c, void* dst, const void* src, size_t bytes, int kind) {
-  g_err.clear();
-  if (!c || !dst || !src || kind < 0 || kind > 2) { g_err = "dpe_device_copy: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  TRY(enter(c, dst && src && kind >= 0 && kind <= 2, "dpe_device_copy: bad argument"));
+  HIPC(host_wait(c));
   const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
   HIPC(hipMemcpy(dst, src, bytes, k));
   return DPE_OK;
@@ -1260,10 +1218,8 @@ int u8_taps(int ssize, int dsize, int* ofs, short* a) {
 }  // namespace
 
 extern "C" int dpe_resize_linear(DpeContext* c, const float* src, int w, int h, float* dst, int nw, int nh) {
-  g_err.clear();
-  if (!c || !src || !dst || w < 1 || h < 1 || nw < 1 || nh < 1) { g_err = "dpe_resize_linear: bad argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, src && dst && w >= 1 && h >= 1 && nw >= 1 && nh >= 1, "dpe_resize_linear: bad argument"));
   if (w == nw && h == nh) { std::memcpy(dst, src, sizeof(float) * (size_t)w * h); return DPE_OK; }
-  HIPC(hipSetDevice(c->device));
   std::vector<int> it(2 * (size_t)(nw + nh));
   std::vector<float> ft(2 * (size_t)(nw + nh));
   f32_taps(w, nw, it.data(), it.data() + nw, ft.data(), ft.data() + nw);
@@ -1318,22 +1274,17 @@ static int resize_u8_dev(DpeContext* c, const uint8_t* dsrc, int w, int h, uint8
 }
 
 extern "C" int dpe_resize_u8(DpeContext* c, const uint8_t* src, int w, int h, uint8_t* dst, int nw, int nh) {
-  g_err.clear();
-  if (!c || !src || !dst || w < 1 || h < 1 || nw < 1 || nh < 1) { g_err = "dpe_resize_u8: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
+  TRY(enter(c, src && dst && w >= 1 && h >= 1 && nw >= 1 && nh >= 1, "dpe_resize_u8: bad argument"));
   HIPC(c->e_a.ensure((size_t)w * h)); HIPC(c->e_b.ensure((size_t)nw * nh));
   HIPC(hipMemcpyAsync(c->e_a.p, src, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
-  const int r = resize_u8_dev(c, c->e_a.p, w, h, c->e_b.p, nw, nh);
-  if (r != DPE_OK) return r;
+  TRY(resize_u8_dev(c, c->e_a.p, w, h, c->e_b.p, nw, nh));
   HIPC(hipMemcpyAsync(dst, c->e_b.p, (size_t)nw * nh, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   return DPE_OK;
 }
 
 extern "C" int dpe_roberts_threshold(DpeContext* c, const uint8_t* src, int w, int h, int thr, uint8_t* dst) {
-  g_err.clear();
-  if (!c || !src || !dst || w < 1 || h < 1) { g_err = "dpe_roberts_threshold: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
+  TRY(enter(c, src && dst && w >= 1 && h >= 1, "dpe_roberts_threshold: bad argument"));
   HIPC(c->e_a.ensure((size_t)w * h)); HIPC(c->e_b.ensure((size_t)w * h));
   HIPC(hipMemcpyAsync(c->e_a.p, src, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
   k_roberts_threshold<<<dim3((w + 31) / 32, (h + 7) / 8), dim3(32, 8), 0, c->stream>>>(c->e_a.p, w, h, thr, c->e_b.p);
@@ -1344,9 +1295,7 @@ extern "C" int dpe_roberts_threshold(DpeContext* c, const uint8_t* src, int w, i
 }
 
 extern "C" int dpe_canny(DpeContext* c, const uint8_t* src, int w, int h, double low_thresh, double high_thresh, uint8_t* dst) {
-  g_err.clear();
-  if (!c || !src || !dst || w < 1 || h < 1) { g_err = "dpe_canny: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
+  TRY(enter(c, src && dst && w >= 1 && h >= 1, "dpe_canny: bad argument"));
   Range range_("dpe_canny");
   if (low_thresh > high_thresh) std::swap(low_thresh, high_thresh);   // canny.cpp threshold handling
   low_thresh = std::min(32767.0, low_thresh);
@@ -1387,11 +1336,12 @@ extern "C" int dpe_canny(DpeContext* c, const uint8_t* src, int w, int h, double
 extern "C" void dpe_state_clear(DpeContext* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)wait_pending(c);
-  (void)hipStreamSynchronize(c->stream);
-  for (auto& kv : c->rstore) { kv.second->release(); delete kv.second; }
+  (void)host_wait(c);
   c->rstore.clear();
   c->snap_mode = false;
+#if DPE_GN_ONCE
+  c->gn_done_for_stage = false;
+#endif
 }
 
 extern "C" int dpe_host_pin(void* ptr, size_t bytes) {
@@ -1440,65 +1390,57 @@ static int viz_enqueue_front(DpeContext* c, int w, int h, int quality, hipStream
   return DPE_OK;
 }
 
-static ResState* viz_state(DpeContext* c, int image_id, int kind, const char* who) {
+static const ResState* viz_state(DpeContext* c, int image_id, int kind, const char* who) {
   if (kind != DPE_VIZ_DEPTH && kind != DPE_VIZ_NORMAL && kind != DPE_VIZ_WEAK) { g_err = std::string(who) + ": bad kind"; return nullptr; }
   auto it = c->rstore.find(image_id);
   if (it == c->rstore.end()) { g_err = std::string(who) + ": no state of image " + std::to_string(image_id); return nullptr; }
-  if (!it->second->full) { g_err = std::string(who) + ": image " + std::to_string(image_id) + " holds a depth map only"; return nullptr; }
-  return it->second;
+  if (!it->second.full) { g_err = std::string(who) + ": image " + std::to_string(image_id) + " holds a depth map only"; return nullptr; }
+  return &it->second;
 }
 
 extern "C" int dpe_state_render(DpeContext* c, int image_id, int kind, float dmin, float dmax, uint8_t* host_bgr) {
-  g_err.clear();
-  if (!c || !host_bgr) { g_err = "dpe_state_render: null argument"; return DPE_ERR_ARG; }
-  ResState* r = viz_state(c, image_id, kind, "dpe_state_render");
+  TRY(enter(c, host_bgr != nullptr, "dpe_state_render: null argument"));
+  const ResState* r = viz_state(c, image_id, kind, "dpe_state_render");
   if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
-  HIPC(hipSetDevice(c->device));
-  if (c->pending) HIPC(hipStreamWaitEvent(c->stream, c->ev_done, 0));
-  const int rc = viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, c->stream);
-  if (rc != DPE_OK) return rc;
-  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, (size_t)r->w * r->h * 3, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
+  hipStream_t s;
+  HIPC(enqueue_stream(c, nullptr, &s));
+  TRY(viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s));
+  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, (size_t)r->w * r->h * 3, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
   return DPE_OK;
 }
 
 extern "C" int dpe_state_render_jpeg_blocks(DpeContext* c, int image_id, int kind, float dmin, float dmax, int quality,
                                             int16_t* host_blocks, size_t cap, void* stream_) {
-  g_err.clear();
-  if (!c || !host_blocks) { g_err = "dpe_state_render_jpeg_blocks: null argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, host_blocks != nullptr, "dpe_state_render_jpeg_blocks: null argument"));
   if (quality < 1 || quality > 100) { g_err = "dpe_state_render_jpeg_blocks: bad quality"; return DPE_ERR_ARG; }
-  ResState* r = viz_state(c, image_id, kind, "dpe_state_render_jpeg_blocks");
+  const ResState* r = viz_state(c, image_id, kind, "dpe_state_render_jpeg_blocks");
   if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
   const size_t n = viz_block_values(r->w, r->h);
   if (cap < n) { g_err = "dpe_state_render_jpeg_blocks: block buffer too small"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  hipStream_t s = stream_ ? (hipStream_t)stream_ : c->stream;
-  if (c->pending) HIPC(hipStreamWaitEvent(s, c->ev_done, 0));   // after the save that wrote the state
-  int rc = viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s);
-  if (rc == DPE_OK) rc = viz_enqueue_front(c, r->w, r->h, quality, s);
-  if (rc != DPE_OK) return rc;
+  hipStream_t s;
+  HIPC(enqueue_stream(c, stream_, &s));   // after the save that wrote the state
+  TRY(viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s));
+  TRY(viz_enqueue_front(c, r->w, r->h, quality, s));
   HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, s));
   hipEvent_t ev = nullptr;
   {
     std::lock_guard<std::mutex> lk(c->viz_mu);
     auto it = c->viz_ev.find(host_blocks);
     if (it == c->viz_ev.end()) {
-      HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      c->viz_ev[host_blocks] = ev;
-    } else {
-      ev = it->second;
+      Event fresh;
+      HIPC(fresh.create());
+      it = c->viz_ev.emplace(host_blocks, std::move(fresh)).first;
     }
+    ev = it->second;
   }
   HIPC(hipEventRecord(ev, s));
-  if (s != c->stream) {   // the scratch is reused, and the state rewritten, by later work of the context
-    HIPC(hipEventRecord(c->ev_done, s));
-    c->pending = true;
-  }
+  HIPC(publish_foreign(c, s));   // the scratch is reused, and the state rewritten, by later work of the context
   return DPE_OK;
 }
 
 extern "C" int dpe_state_render_wait(DpeContext* c, const int16_t* host_blocks) {
-  g_err.clear();
+  g_err.clear();   // (not enter(): the lookup comes before the device is selected, and any host thread may call)
   if (!c || !host_blocks) { g_err = "dpe_state_render_wait: null argument"; return DPE_ERR_ARG; }
   hipEvent_t ev = nullptr;
   {
@@ -1514,27 +1456,23 @@ extern "C" int dpe_state_render_wait(DpeContext* c, const int16_t* host_blocks) 
 
 extern "C" int dpe_viz_render_arrays(DpeContext* c, int kind, int w, int h, const float* depth, const float* normal,
                                      const uint8_t* weak, float dmin, float dmax, uint8_t* host_bgr) {
-  g_err.clear();
-  if (!c || !host_bgr || w < 1 || h < 1) { g_err = "dpe_viz_render_arrays: bad argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, host_bgr && w >= 1 && h >= 1, "dpe_viz_render_arrays: bad argument"));
   if (kind == DPE_VIZ_DEPTH ? !depth : kind == DPE_VIZ_NORMAL ? !normal : kind == DPE_VIZ_WEAK ? !weak : true) {
     g_err = "dpe_viz_render_arrays: bad kind or missing array";
     return DPE_ERR_ARG;
   }
-  HIPC(hipSetDevice(c->device));
   const size_t L = (size_t)w * h;
   std::vector<float4> p(L);
   for (size_t i = 0; i < L; ++i)
     p[i] = make_float4(normal ? normal[3 * i] : 0.f, normal ? normal[3 * i + 1] : 0.f, normal ? normal[3 * i + 2] : 0.f,
                        depth ? depth[i] : 0.f);
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(host_wait(c));
   HIPC(c->viz_planes.ensure(L));
   HIPC(c->viz_weak.ensure(L));
   HIPC(hipMemcpy(c->viz_planes.p, p.data(), L * sizeof(float4), hipMemcpyHostToDevice));
   if (weak) HIPC(hipMemcpy(c->viz_weak.p, weak, L, hipMemcpyHostToDevice));
   else HIPC(hipMemset(c->viz_weak.p, 0, L));
-  const int rc = viz_enqueue_render(c, kind, c->viz_planes.p, c->viz_weak.p, w, h, dmin, dmax, c->stream);
-  if (rc != DPE_OK) return rc;
+  TRY(viz_enqueue_render(c, kind, c->viz_planes.p, c->viz_weak.p, w, h, dmin, dmax, c->stream));
   HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, 3 * L, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   return DPE_OK;
@@ -1542,29 +1480,21 @@ extern "C" int dpe_viz_render_arrays(DpeContext* c, int kind, int w, int h, cons
 
 extern "C" int dpe_jpeg_blocks_device(DpeContext* c, const uint8_t* host_bgr, int w, int h, int quality, int16_t* host_blocks,
                                       size_t cap) {
-  g_err.clear();
-  if (!c || !host_bgr || !host_blocks || w < 1 || h < 1 || w > 65535 || h > 65535 || quality < 1 || quality > 100) {
-    g_err = "dpe_jpeg_blocks_device: bad argument";
-    return DPE_ERR_ARG;
-  }
+  TRY(enter(c, host_bgr && host_blocks && w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && quality >= 1 && quality <= 100,
+            "dpe_jpeg_blocks_device: bad argument"));
   const size_t n = viz_block_values(w, h);
   if (cap < n) { g_err = "dpe_jpeg_blocks_device: block buffer too small"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
-  HIPC(wait_pending(c));
-  HIPC(hipStreamSynchronize(c->stream));
+  HIPC(host_wait(c));
   HIPC(c->viz_bgr.ensure((size_t)w * h * 3));
   HIPC(hipMemcpy(c->viz_bgr.p, host_bgr, (size_t)w * h * 3, hipMemcpyHostToDevice));
-  const int rc = viz_enqueue_front(c, w, h, quality, c->stream);
-  if (rc != DPE_OK) return rc;
+  TRY(viz_enqueue_front(c, w, h, quality, c->stream));
   HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   return DPE_OK;
 }
 
 extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n) {
-  g_err.clear();
-  if (!c || !views || n < 1) { g_err = "dpe_fusion_stage: bad argument"; return DPE_ERR_ARG; }
-  HIPC(hipSetDevice(c->device));
+  TRY(enter(c, views && n >= 1, "dpe_fusion_stage: bad argument"));
   c->fz_depth.resize(n); c->fz_normal.resize(n); c->fz_host.assign(n, FusionViewDev{});
   std::vector<DpeCamera> cams(n);
   for (int i = 0; i < n; ++i) {
@@ -1588,14 +1518,12 @@ extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n
 }
 
 extern "C" int dpe_fusion_candidates(DpeContext* c, int ref, const int* src, int ns, int32_t* idx, float* val) {
-  g_err.clear();
-  if (!c || !src || !idx || !val || ns < 0) { g_err = "dpe_fusion_candidates: bad argument"; return DPE_ERR_ARG; }
+  TRY(enter(c, src && idx && val && ns >= 0, "dpe_fusion_candidates: bad argument"));
   if (c->fz_n < 1) { g_err = "dpe_fusion_candidates: nothing staged"; return DPE_ERR_STATE; }
   if (ref < 0 || ref >= c->fz_n) { g_err = "dpe_fusion_candidates: bad reference view"; return DPE_ERR_ARG; }
   for (int j = 0; j < ns; ++j)
     if (src[j] < 0 || src[j] >= c->fz_n) { g_err = "dpe_fusion_candidates: bad source view"; return DPE_ERR_ARG; }
   if (ns == 0) return DPE_OK;
-  HIPC(hipSetDevice(c->device));
   const size_t L = (size_t)c->fz_host[ref].w * c->fz_host[ref].h;
   HIPC(c->fz_src.ensure(ns));
   HIPC(c->fz_idx.ensure(L * ns));
@@ -1620,7 +1548,7 @@ extern "C" int dpe_pm_last_timings(DpeContext* c, float* out, int n) {
 extern "C" void dpe_set_counting(DpeContext* c, int enable) { if (c) c->counting = enable != 0; }
 
 extern "C" int dpe_set_option(DpeContext* c, int option, int value) {
-  g_err.clear();
+  g_err.clear();   // (touches no device)
   if (!c) { g_err = "dpe_set_option: null context"; return DPE_ERR_ARG; }
   if (option == DPE_OPT_GN_SLOTS && (value == 0 || value == 8 || value == 32 || value == 64)) { c->gn_slots = value; return DPE_OK; }
   g_err = "dpe_set_option: unknown option or value";

@@ -69,6 +69,9 @@ struct DevBufs {
 //  16  job-pool statistics of the cooperative kernels (tools/pool_stats.py)
 //  32  TIMING ONLY, results wrong: the fast taps' texel loads replaced by values made from their
 //      address bits (the gather path's share of a tap kernel, interleaved A/B with AB_NOCHECK=1)
+//  64  TIMING ONLY, host code only: GenNeighbours runs in the first execute after a stage and its
+//      outputs are kept for the later executes of that staged state, which skip it (the pass
+//      without GenNeighbours on its critical path, tools/gn_ceiling.py)
 #ifndef DPE_DIAG
 #define DPE_DIAG 0
 #endif
@@ -82,6 +85,7 @@ struct DevBufs {
 #define DPE_WEAK_STATS (((DPE_DIAG) >> 2) & 1)
 #define DPE_GN_TIMES (((DPE_DIAG) >> 3) & 1)
 #define DPE_FAKE_GATHER (((DPE_DIAG) >> 5) & 1)
+#define DPE_GN_ONCE (((DPE_DIAG) >> 6) & 1)
 // Phase profiling (DPE_DIAG & 1): shader-clock cycles of each phase of a cooperative kernel,
 // summed over waves into B.phase[k].
 #if DPE_PHASE_PROF

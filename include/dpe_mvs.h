@@ -351,6 +351,10 @@ int dpe_jpeg_blocks_device(DpeContext* ctx, const uint8_t* host_bgr, int w, int 
                            size_t cap);
 long long dpe_viz_launches(void);
 
+/* Device bytes held at the moment by every context of the process (their buffers, resident states and
+ * cached images; tests: a destroyed context gives back all it allocated). */
+long long dpe_live_device_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

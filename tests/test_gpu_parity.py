@@ -240,6 +240,130 @@ def test_image_ids_keep_images_resident(ctx):
     assert ref2["planes"].tobytes() == got2["planes"].tobytes()
 
 
+_SCENES = {}
+
+
+def _texel_scene(kind):
+    """One 96x72, 4-view scene with its grey levels in each texel class: "u8" (integers), "quarter"
+    (multiples of 1/4, as test_gpu_quarter_integer_images makes them) and "f32" (neither, as
+    test_gpu_non_integer_images makes them).  Built once; callers do not modify them."""
+    if not _SCENES:
+        from DPE_MVS import pipeline
+        sc = synthetic.make_scene(96, 72, 4)
+        full = synthetic.make_scene(192, 144, 4)
+        quarter = [pipeline.resize_linear(im.astype(np.float32), 96, 72) for im in full["images"]]
+        q = np.concatenate([im.ravel() for im in quarter])
+        assert np.all(q * 4 == np.round(q * 4)) and not np.all(q == np.round(q))
+        f32 = [(im * np.float32(0.73) + np.float32(0.31)).astype(np.float32) for im in sc["images"]]
+        _SCENES.update(u8=sc, quarter=dict(sc, images=quarter), f32=dict(sc, images=f32))
+    return _SCENES[kind]
+
+
+def _ids_case(sc, images=None):
+    """(input, state) of a refine_iter pass with source depths over `sc` (optionally other images)."""
+    inp = synthetic.pass_input(sc if images is None else dict(sc, images=images), _params("refine_iter"),
+                               depths=synthetic.src_depths(sc))
+    return inp, synthetic.gt_state(sc)
+
+
+@pytest.mark.parametrize("kind,cls", [("u8", 2), ("quarter", 1), ("f32", 0)])
+def test_image_ids_each_texel_class(ctx, kind, cls):
+    """The cached image path (image_ids) in each texel class: a pass without ids, the first pass with
+    ids (upload + layouts) and a second one (all from the cache) give the oracle's bits and report
+    the class of the images."""
+    from DPE_MVS import native
+    inp, st = _ids_case(_texel_scene(kind))
+    want = oracle.run_pass(inp, st)
+    plain = ctx.run(inp, st)
+    assert ctx.last_stat(_abi.DPE_STAT_TEX_CLASS) == cls
+    c = native.PatchMatchContext(0)
+    try:
+        inp_ids = dict(inp, image_ids=[1, 2, 3, 4])
+        first = c.run(inp_ids, st)
+        assert c.last_stat(_abi.DPE_STAT_TEX_CLASS) == cls
+        again = c.run(inp_ids, st)
+        assert c.last_stat(_abi.DPE_STAT_TEX_CLASS) == cls
+    finally:
+        c.close()
+    for what, got in (("no ids", plain), ("first pass with ids", first), ("second pass with ids", again)):
+        assert_same(got, want, f"{kind} images, {what}")
+
+
+def test_image_ids_classes_mixed_across_passes(ctx):
+    """One cache, passes of different classes: a pass takes the narrowest class of its views.  Entries
+    1-3 (8-bit) serve a class-2 pass, then a class-1 pass beside a quarter-integer image, then a class-0
+    pass beside a non-quarter image (their f32 quads are built on demand), then the class-2 pass again.
+    Every pass gives the bits of the same input staged without ids."""
+    from DPE_MVS import native
+    u8 = _texel_scene("u8")
+    passes = [("A", [1, 2, 3, 4], u8["images"], 2),
+              ("B", [1, 2, 3, 5], u8["images"][:3] + [_texel_scene("quarter")["images"][3]], 1),
+              ("C", [1, 2, 3, 6], u8["images"][:3] + [_texel_scene("f32")["images"][3]], 0),
+              ("A again", [1, 2, 3, 4], u8["images"], 2)]
+    c = native.PatchMatchContext(0)
+    got = {}
+    try:
+        for name, ids, images, cls in passes:
+            inp, st = _ids_case(u8, images)
+            want = ctx.run(inp, st)
+            assert ctx.last_stat(_abi.DPE_STAT_TEX_CLASS) == cls, name
+            got[name] = c.run(dict(inp, image_ids=ids), st)
+            assert c.last_stat(_abi.DPE_STAT_TEX_CLASS) == cls, name
+            assert_same(got[name], want, f"pass {name} with ids vs without")
+    finally:
+        c.close()
+    assert_same(got["A again"], got["A"], "pass A after B and C")
+
+
+def test_image_ids_one_id_at_two_sizes(ctx):
+    """An id is cached per size: 96x72, then 64x48 with the same ids, then 96x72 again (the packed
+    arrays only grow: a smaller pass and a larger one after it reuse them)."""
+    from DPE_MVS import native
+    big, small = _ids_case(_texel_scene("u8")), _ids_case(synthetic.make_scene(64, 48, 4))
+    c = native.PatchMatchContext(0)
+    try:
+        for what, (inp, st) in (("96x72", big), ("64x48", small), ("96x72 again", big)):
+            want = ctx.run(inp, st)
+            assert_same(c.run(dict(inp, image_ids=[1, 2, 3, 4]), st), want, f"{what} with ids vs without")
+    finally:
+        c.close()
+
+
+def test_contexts_own_their_device_memory():
+    """Every device allocation of a context is returned by dpe_state_clear / dpe_image_cache_clear /
+    dpe_destroy: the library's count of live device bytes drops when states and cached images are
+    cleared, and is back at its starting value once the contexts are closed (other contexts of the
+    process, such as this module's shared one, stay alive: compare with the start, not with 0)."""
+    from DPE_MVS import native
+    before = native.live_device_bytes()
+    inp, st = _ids_case(_texel_scene("u8"))
+    tiny = synthetic.make_scene(32, 24, 2)
+    views = [(np.where(np.isfinite(v["depth"]), v["depth"], 0).astype(np.float32), v["normals"], cam)
+             for v, cam in zip(tiny["views"], tiny["cams"])]
+    img = np.ascontiguousarray(_texel_scene("u8")["images"][0][:48, :64])
+    a, b = native.PatchMatchContext(0), native.PatchMatchContext(0)
+    try:
+        for c in (a, b):
+            c.run(dict(inp, image_ids=[1, 2, 3, 4]), st)
+            c.state_save(1)
+            c.state_render(1, native.VIZ_DEPTH, 1.0, 10.0)
+            c.state_render_jpeg_blocks(1, native.VIZ_NORMAL)
+            c.fusion_candidates(views, 0, [1])
+            c.resize_u8(img.astype(np.uint8), 32, 24)
+            c.resize_linear(img, 32, 24)
+            c.canny(img.astype(np.uint8), 50, 150)
+        live = native.live_device_bytes()
+        assert live > 0 and live > before
+        a.state_clear()
+        a.image_cache_clear()
+        cleared = native.live_device_bytes()
+        assert cleared < live
+    finally:
+        a.close()
+        b.close()
+    assert native.live_device_bytes() == before
+
+
 def test_stage_waits_for_execute_on_a_foreign_stream(ctx):
     """dpe_pm_stage host-waits for the previous execute even when it was enqueued on a caller stream:
     stage(A); execute(A, s); stage(B) must not overwrite inputs pass A is still reading.  The caller

@@ -9,7 +9,7 @@
 #   timeline     overlapped kernel trace (tools/timeline.py) pmc          PMC traffic + bottleneck passes
 #   rehearsal    `bench.py --gpus 2` over gloo on one GPU    ab:<a.so,b.so,...>  interleaved A/B (tools/ab_libs.py)
 #   phase:<so>   phase profile of a DPE_DIAG build
-#   run:<cmd>    any command (quote the step: "run:DPE_DBG_GN_ONCE=1 python -u tools/gn_ceiling.py 10")
+#   run:<cmd>    any command (quote the step: "run:python -u tools/gn_ceiling.py dpe-mvs_amd/lib/variants/gnonce.so 10")
 cd "$GRAFT_REPO_ROOT" || exit 1
 export PYTHONUNBUFFERED=1
 mkdir -p gpurun_out
