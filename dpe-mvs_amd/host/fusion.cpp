@@ -14,6 +14,7 @@
 // order; its host code is built with -ffast-math -march=native, whose contractions are not
 // reproducible, so agreement with the reference binary is unpinned.
 #include "host.h"
+#include "parallel.h"
 
 #include <cmath>
 #include <cstring>
@@ -40,14 +41,6 @@ namespace dpe_host {
 //    same float expressions, into a per-pixel bit set of the candidates that pass and their weights;
 //    the serial walk then visits only those, in ascending view order, and adds the same weights in
 //    the same order (the masks it tests and sets are exactly the reference's).
-namespace {
-int fusion_threads() {
-  unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* e = getenv("OMP_NUM_THREADS")) { const int v = atoi(e); if (v > 0) hw = std::min(hw, (unsigned)v); }
-  return (int)std::min(16u, hw);
-}
-}  // namespace
-
 bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
                 std::string& err) {
   const int n = (int)views.size();
@@ -103,7 +96,7 @@ bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, st
     const int ns = (int)srcs[i].size();
     b->rc = ns > 0 ? fn(user, dv.data(), n, refs[i], srcs[i].data(), ns, b->idx.get(), b->val.get()) : 0;
   };
-  const int nt = fusion_threads();
+  const int nt = host_threads();
   // per image: the candidates whose angle test passes (bit j of pass[p]) and their weights
   struct Terms {
     std::vector<uint32_t> pass;
@@ -121,29 +114,26 @@ bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, st
     const float* cval = b->val.get();
     uint32_t* pass = tm->pass.data();
     float* wgt = tm->wgt.data();
-    std::vector<std::thread> pool;
-    for (int t = 0; t < threads; ++t)
-      pool.emplace_back([&, t]() {
-        const size_t lo = L * t / threads, hi = L * (t + 1) / threads;
-        for (size_t p = lo; p < hi; ++p) {
-          if (!(R.view.depth[p] > 0.0f)) continue;
-          if (!R.block.empty() && R.block[p] < 128) continue;     // skipped by the walk in any case
-          uint32_t m = 0;
-          for (int j = 0; j < ns; ++j) {
-            if (cidx[p * ns + j] < 0) continue;
-            const float* v = cval + (p * ns + j) * 3;
-            float angle = std::acos(v[2]);                 // GetAngle (DPE.cpp:1208-1217)
-            if (angle != angle) angle = 0.0f;
-            if (angle < 0.174533f) {                       // reproj < 2, rel < 0.01 tested by the candidates
-              const float tmp_index = v[0] + 200 * v[1] + angle * 10;
-              wgt[p * ns + j] = std::exp(-tmp_index);
-              m |= 1u << j;
-            }
+    run_on_threads(threads, [&](int t) {
+      const size_t lo = L * t / threads, hi = L * (t + 1) / threads;
+      for (size_t p = lo; p < hi; ++p) {
+        if (!(R.view.depth[p] > 0.0f)) continue;
+        if (!R.block.empty() && R.block[p] < 128) continue;     // skipped by the walk in any case
+        uint32_t m = 0;
+        for (int j = 0; j < ns; ++j) {
+          if (cidx[p * ns + j] < 0) continue;
+          const float* v = cval + (p * ns + j) * 3;
+          float angle = std::acos(v[2]);                 // GetAngle (DPE.cpp:1208-1217)
+          if (angle != angle) angle = 0.0f;
+          if (angle < 0.174533f) {                       // reproj < 2, rel < 0.01 tested by the candidates
+            const float tmp_index = v[0] + 200 * v[1] + angle * 10;
+            wgt[p * ns + j] = std::exp(-tmp_index);
+            m |= 1u << j;
           }
-          pass[p] = m;
         }
-      });
-    for (auto& th : pool) th.join();
+        pass[p] = m;
+      }
+    });
   };
   // the fused pixels of one image in walk order: pixel, depth, the candidates it used (bit j)
   struct Fused {
@@ -218,28 +208,25 @@ bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, st
     const size_t base = cloud.size(), nf = fused.size();
     cloud.resize(base + nf);
     {
-      std::vector<std::thread> pool;
       const int th = (int)std::min<size_t>((size_t)nt, std::max<size_t>(1, nf / 4096));
-      for (int t = 0; t < th; ++t)
-        pool.emplace_back([&, t]() {
-          for (size_t k = nf * t / th; k < nf * (t + 1) / th; ++k) {
-            const Fused& f = fused[k];
-            const size_t p = f.p;
-            float col[3] = {(float)R.bgr[3 * p], (float)R.bgr[3 * p + 1], (float)R.bgr[3 * p + 2]};
-            for (uint32_t m = f.used; m; m &= m - 1) {
-              const int j = __builtin_ctz(m);
-              const size_t sp = (size_t)cidx[p * ns + j];
-              const FusionView& S = views[src[j]];
-              col[0] += S.bgr[3 * sp];
-              col[1] += S.bgr[3 * sp + 1];
-              col[2] += S.bgr[3 * sp + 2];
-            }
-            const int num_consistent = __builtin_popcount(f.used);
-            for (float& x : col) x /= (num_consistent + 1);
-            cloud[base + k] = fusion_point((int)(p % cols), (int)(p / cols), f.depth, R.view.cam, col);
+      run_on_threads(th, [&](int t) {
+        for (size_t k = nf * t / th; k < nf * (t + 1) / th; ++k) {
+          const Fused& f = fused[k];
+          const size_t p = f.p;
+          float col[3] = {(float)R.bgr[3 * p], (float)R.bgr[3 * p + 1], (float)R.bgr[3 * p + 2]};
+          for (uint32_t m = f.used; m; m &= m - 1) {
+            const int j = __builtin_ctz(m);
+            const size_t sp = (size_t)cidx[p * ns + j];
+            const FusionView& S = views[src[j]];
+            col[0] += S.bgr[3 * sp];
+            col[1] += S.bgr[3 * sp + 1];
+            col[2] += S.bgr[3 * sp + 2];
           }
-        });
-      for (auto& th2 : pool) th2.join();
+          const int num_consistent = __builtin_popcount(f.used);
+          for (float& x : col) x /= (num_consistent + 1);
+          cloud[base + k] = fusion_point((int)(p % cols), (int)(p / cols), f.depth, R.view.cam, col);
+        }
+      });
     }
     t_points += now() - t0;
   }

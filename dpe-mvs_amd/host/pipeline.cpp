@@ -27,26 +27,27 @@
 // few pinned buffers, and a small pool of host threads (VizWriter) Huffman-codes and writes them
 // while the following passes run.  With a runner hook the state is on the host and the same
 // pictures come from viz.cpp / jpeg_enc.cpp, byte for byte the same files.
+//
+// run() at the end of the file is the table of contents: the phases of a run in order, each a
+// member of PipelineRun.  The rule every phase keeps with several ranks is in rank_group.h.
 #include "host.h"
+#include "parallel.h"
+#include "rank_group.h"
+#include "viz_writer.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <cmath>
-#include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <filesystem>
 #include <fstream>
 #include <iostream>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <sstream>
-#include <thread>
 
 namespace fs = std::filesystem;
 
@@ -55,10 +56,19 @@ namespace {
 
 thread_local std::string g_err;
 const char* kOutName = "DPE";
-// wall seconds of the last run's phases: total, decode, GetProblemEdges pre-pass, passes (incl. the
-// exchanges), outputs + fusion, then (multi-rank) the depth exchanges alone, the pass work alone and
-// RunFusion alone (rank 0, incl. the normal/weak exchange that feeds it)
-constexpr int kNumTimes = 8;
+// dpe_pipeline_last_timings: wall seconds of the last run's phases
+enum TimeSlot {
+  kTimeTotal = 0,
+  kTimeDecode,     // image decode, up to the first GetProblemEdges
+  kTimeEdges,      // the GetProblemEdges pre-pass
+  kTimePasses,     // the passes, incl. the exchanges
+  kTimeOutputs,    // outputs + fusion
+  kTimeExchange,   // (multi-rank) the depth exchanges alone
+  kTimePassWork,   // the pass work alone
+  kTimeFusion,     // RunFusion alone (rank 0, incl. the normal/weak exchange that feeds it)
+  kNumTimes
+};
+static_assert(kNumTimes == 8, "include/dpe_host.h documents entries [0]..[7]");
 double g_times[kNumTimes] = {0, 0, 0, 0, 0, 0, 0, 0};
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -81,6 +91,11 @@ struct ImageState {   // depths.dmb / normals.dmb / weak.bin / selected_views.bi
 };
 
 int std_round(float v) { return (int)std::round(v); }   // std::round: half away from zero
+
+std::string image_path(const std::string& dense, int id) { return (fs::path(dense) / "images" / (fmt_index(id) + ".jpg")).string(); }
+std::string cam_path(const std::string& dense, int id) { return (fs::path(dense) / "cams" / (fmt_index(id) + "_cam.txt")).string(); }
+// the intrinsics of an image resized by (sx, sy) (DPE.cpp:812-815, 1139-1142)
+void scale_intrinsics(DpeCamera& cam, float sx, float sy) { cam.K[0] *= sx; cam.K[2] *= sx; cam.K[4] *= sy; cam.K[5] *= sy; }
 
 bool generate_sample_list(const std::string& dense, std::vector<Problem>& probs, std::string& err) {   // main.cpp:264-308
   std::ifstream f(fs::path(dense) / "pair.txt");
@@ -121,28 +136,24 @@ class ImageCache {
     auto it = full_.find(idx);
     if (it == full_.end()) {
       GrayImage g;
-      if (!read_gray((fs::path(folder_) / "images" / (fmt_index(idx) + ".jpg")).string(), g, err)) return nullptr;
+      if (!read_gray(image_path(folder_, idx), g, err)) return nullptr;
       Level L{g.w, g.h, std::vector<float>(g.px.begin(), g.px.end())};
       it = full_.emplace(idx, std::move(L)).first;
     }
     w = it->second.w; h = it->second.h;
     return &it->second.px;
   }
-  // decodes the images not cached yet on `nt` host threads (independent files; same pixels as full())
-  bool prefetch(const std::vector<int>& ids, int nt, std::string& err) {
+  // decodes the images not cached yet on host threads (independent files; same pixels as full())
+  bool prefetch(const std::vector<int>& ids, std::string& err) {
     std::vector<int> todo;
     for (int id : ids)
       if (!full_.count(id) && std::find(todo.begin(), todo.end(), id) == todo.end()) todo.push_back(id);
     std::vector<GrayImage> g(todo.size());
     std::vector<std::string> e(todo.size());
-    nt = std::max(1, std::min<int>(nt, (int)todo.size()));
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-      pool.emplace_back([&, t]() {
-        for (size_t k = t; k < todo.size(); k += nt)
-          read_gray((fs::path(folder_) / "images" / (fmt_index(todo[k]) + ".jpg")).string(), g[k], e[k]);
-      });
-    for (auto& th : pool) th.join();
+    const int nt = std::max(1, std::min<int>(host_threads(), (int)todo.size()));
+    run_on_threads(nt, [&](int t) {
+      for (size_t k = t; k < todo.size(); k += nt) read_gray(image_path(folder_, todo[k]), g[k], e[k]);
+    });
     for (size_t k = 0; k < todo.size(); ++k) {
       if (!e[k].empty()) { err = e[k]; return false; }
       full_.emplace(todo[k], Level{g[k].w, g[k].h, std::vector<float>(g[k].px.begin(), g[k].px.end())});
@@ -248,17 +259,15 @@ int native_fusion(void* user, const DpeFusionView* views, int n, int ref, const 
 
 // the per-pass intermediate maps of the reference (main.cpp:439-446)
 bool write_state_maps(const Problem& p, const ImageState& s, std::string& err) {
-  const int W = s.w, H = s.h;
-  const size_t L = (size_t)W * H;
+  const struct { const char* name; int type; const void* data; } maps[4] = {
+      {"depths.dmb", CV_32FC1, s.depth.data()}, {"normals.dmb", CV_32FC3, s.normal.data()},
+      {"weak.bin", CV_8UC1, s.weak.data()}, {"selected_views.bin", CV_32SC1, s.sel.data()}};
   Mat m;
-  m.create(H, W, CV_32FC1); std::memcpy(m.data.data(), s.depth.data(), L * 4);
-  if (!write_bin_mat((fs::path(p.result_folder) / "depths.dmb").string(), m, err)) return false;
-  m.create(H, W, CV_32FC3); std::memcpy(m.data.data(), s.normal.data(), L * 12);
-  if (!write_bin_mat((fs::path(p.result_folder) / "normals.dmb").string(), m, err)) return false;
-  m.create(H, W, CV_8UC1); std::memcpy(m.data.data(), s.weak.data(), L);
-  if (!write_bin_mat((fs::path(p.result_folder) / "weak.bin").string(), m, err)) return false;
-  m.create(H, W, CV_32SC1); std::memcpy(m.data.data(), s.sel.data(), L * 4);
-  if (!write_bin_mat((fs::path(p.result_folder) / "selected_views.bin").string(), m, err)) return false;
+  for (const auto& e : maps) {
+    m.create(s.h, s.w, e.type);
+    std::memcpy(m.data.data(), e.data, m.data.size());
+    if (!write_bin_mat((fs::path(p.result_folder) / e.name).string(), m, err)) return false;
+  }
   return true;
 }
 
@@ -276,241 +285,69 @@ bool fetch_state(DpeContext* ctx, int id, ImageState& s, std::string& err, bool 
   return true;
 }
 
-int viz_threads() {   // as fusion.cpp's fusion_threads(): at most 16, and OMP_NUM_THREADS
-  unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* e = std::getenv("OMP_NUM_THREADS")) { const int v = std::atoi(e); if (v > 0) hw = std::min(hw, (unsigned)v); }
-  return (int)std::min(16u, hw);
+std::string viz_path(const Problem& p, int kind) {   // depth_<it>.jpg / normal_<it>.jpg / weak_<it>.jpg
+  return (fs::path(p.result_folder) / (kVizNames[kind] + std::to_string(p.iteration) + ".jpg")).string();
 }
 
-const char* const kVizNames[3] = {"depth_", "normal_", "weak_"};   // DPE_VIZ_DEPTH / NORMAL / WEAK
-constexpr int kVizQuality = 95;   // cv::imwrite's default
-
-// The host half of the viz pictures of the resident runner.  submit() enqueues one picture's render,
-// JPEG front half and block copy on the context's stream into one of a fixed set of pinned buffers
-// (sized to the full-resolution level) and returns; it blocks only while every buffer is in
-// flight.  The worker threads wait for a buffer's copy (dpe_state_render_wait), Huffman-code it
-// into the file and hand the buffer back.  finish() joins them and reports the first error.
-class VizWriter {
- public:
-  VizWriter(DpeContext* ctx, int max_w, int max_h) : ctx_(ctx) {
-    const size_t values = jpeg_block_count(max_w, max_h, 3) * 64;
-    bufs_.resize(kBuffers);
-    for (int i = 0; i < kBuffers; ++i) {
-      bufs_[i].resize(values);
-      pinned_.push_back(dpe_host_pin(bufs_[i].data(), values * sizeof(int16_t)) == 0);   // refused: pageable, still works
-      free_.push_back(i);
-    }
-    const int nt = std::max(1, std::min(viz_threads(), kBuffers));
-    for (int t = 0; t < nt; ++t) pool_.emplace_back([this]() { work(); });
-  }
-  ~VizWriter() { std::string e; finish(e); }
-  VizWriter(const VizWriter&) = delete;
-  VizWriter& operator=(const VizWriter&) = delete;
-
-  bool submit(int image_id, int kind, float dmin, float dmax, int w, int h, const std::string& path, std::string& err) {
-    int b;
-    {
-      std::unique_lock<std::mutex> lk(mu_);
-      cv_free_.wait(lk, [this]() { return !free_.empty(); });
-      b = free_.front(); free_.pop_front();
-    }
-    const int rc = dpe_state_render_jpeg_blocks(ctx_, image_id, kind, dmin, dmax, kVizQuality, bufs_[b].data(), bufs_[b].size(), nullptr);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (rc != 0) {
-      err = std::string("viz render failed: ") + dpe_last_error();
-      free_.push_back(b);
-      return false;
-    }
-    jobs_.push_back(Job{b, path, w, h});
-    cv_job_.notify_one();
-    return true;
-  }
-
-  bool finish(std::string& err) {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      stop_ = true;
-    }
-    cv_job_.notify_all();
-    for (auto& th : pool_) th.join();
-    pool_.clear();
-    for (size_t i = 0; i < bufs_.size(); ++i)
-      if (pinned_[i]) { dpe_host_unpin(bufs_[i].data()); pinned_[i] = false; }
-    err = err_;
-    return err_.empty();
-  }
-
- private:
-  static constexpr int kBuffers = 6;   // two images' three pictures
-  struct Job { int buf; std::string path; int w, h; };
-  void work() {
-    for (;;) {
-      Job j;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_job_.wait(lk, [this]() { return stop_ || !jobs_.empty(); });
-        if (jobs_.empty()) return;
-        j = std::move(jobs_.front()); jobs_.pop_front();
-      }
-      std::string e;
-      bool ok = dpe_state_render_wait(ctx_, bufs_[j.buf].data()) == 0;
-      if (!ok) e = std::string("viz render failed: ") + dpe_last_error();
-      else ok = jpeg_write_blocks(j.path, bufs_[j.buf].data(), j.w, j.h, 3, kVizQuality, e);
-      std::lock_guard<std::mutex> lk(mu_);
-      if (!ok && err_.empty()) err_ = e.empty() ? "viz write failed" : e;
-      free_.push_back(j.buf);
-      cv_free_.notify_one();
-    }
-  }
-  DpeContext* ctx_;
-  std::vector<std::vector<int16_t>> bufs_;
-  std::vector<bool> pinned_;
-  std::deque<int> free_;
-  std::deque<Job> jobs_;
-  std::mutex mu_;
-  std::condition_variable cv_free_, cv_job_;
-  std::vector<std::thread> pool_;
-  bool stop_ = false;
-  std::string err_;
+// One pass's DpePassInput and the storage its pointers borrow (the decode cache owns the pixels).
+struct PassInput {
+  std::vector<int> ids;   // the reference image, then its source views
+  std::vector<const float*> images;
+  std::vector<DpeCamera> cams;
+  Mat edge, edge_low, label;
+  int W = 0, H = 0;
+  DpePassInput in;
 };
 
-// InuputInitialization + SupportInitialization (DPE.cpp:733-914, 1025-1052), the pass, the epilogue
-bool process_problem(Problem& p, ImageCache& cache, std::map<int, ImageState>& states,
-                     const std::map<int, DepthMap>& depth_src, const DpePipelineOptions& opt, Runner& run,
-                     VizWriter* viz, std::string& err) {
+// InuputInitialization + SupportInitialization (DPE.cpp:733-914, 1025-1052): cameras and level
+// images, the depth range (into p.params), the support maps, seed and salt.  in.depths stays null.
+bool build_pass_input(Problem& p, ImageCache& cache, uint64_t base_seed, PassInput& pi, std::string& err) {
   DpePatchMatchParams& P = p.params;
-  std::vector<int> ids{p.ref_image_id};
-  ids.insert(ids.end(), p.src_image_ids.begin(), p.src_image_ids.end());
-  if ((int)ids.size() > DPE_MAX_IMAGES) { err = "Can't process so much images: " + std::to_string(ids.size()); return false; }
+  pi.ids.assign(1, p.ref_image_id);
+  pi.ids.insert(pi.ids.end(), p.src_image_ids.begin(), p.src_image_ids.end());
+  if ((int)pi.ids.size() > DPE_MAX_IMAGES) { err = "Can't process so much images: " + std::to_string(pi.ids.size()); return false; }
   int fw, fh;
-  if (!cache.full(ids[0], fw, fh, err)) return false;
-  std::vector<const float*> images;
-  std::vector<DpeCamera> cams(ids.size());
-  int W = 0, H = 0;
-  for (size_t k = 0; k < ids.size(); ++k) {
-    DpeCamera& cam = cams[k];
-    if (!read_camera((fs::path(p.dense_folder) / "cams" / (fmt_index(ids[k]) + "_cam.txt")).string(), cam, err)) return false;
-    cam.width = fw; cam.height = fh;
+  if (!cache.full(pi.ids[0], fw, fh, err)) return false;
+  pi.cams.resize(pi.ids.size());
+  for (size_t k = 0; k < pi.ids.size(); ++k) {
+    DpeCamera& cam = pi.cams[k];
+    if (!read_camera(cam_path(p.dense_folder, pi.ids[k]), cam, err)) return false;
     int w, h;
-    const std::vector<float>* img = cache.level(ids[k], p.scale_size, w, h, err);
+    const std::vector<float>* img = cache.level(pi.ids[k], p.scale_size, w, h, err);
     if (!img) return false;
-    if (p.scale_size != 1) {
-      const float sx = w / (float)fw, sy = h / (float)fh;
-      cam.K[0] *= sx; cam.K[2] *= sx; cam.K[4] *= sy; cam.K[5] *= sy;
-      cam.width = w; cam.height = h;
-    }
-    if (k == 0) { W = w; H = h; }
-    images.push_back(img->data());
+    if (p.scale_size != 1) scale_intrinsics(cam, w / (float)fw, h / (float)fh);
+    cam.width = w; cam.height = h;   // scale 1: the full size
+    if (k == 0) { pi.W = w; pi.H = h; }
+    pi.images.push_back(img->data());
   }
-  const size_t L = (size_t)W * H;
-  P.depth_min = cams[0].depth_min * 0.6f;
-  P.depth_max = cams[0].depth_max * 1.2f;
-  P.num_images = (int)ids.size();
-  // with the default runner the state stays in HBM (dpe_state_save / dpe_pm_stage_resident): the
-  // prior, the source depths and the epilogue are all on the device, nothing is copied back per pass
-  const bool resident = run.ctx != nullptr;
-  std::vector<std::vector<float>> dep_store;
-  std::vector<const float*> depths(ids.size(), nullptr);
-  if (P.geom_consistency && !resident) {
-    dep_store.reserve(ids.size());
-    for (size_t k = 1; k < ids.size(); ++k) {
-      auto it = depth_src.find(ids[k]);
-      if (it == depth_src.end()) { err = "no depth map of source image " + std::to_string(ids[k]); return false; }
-      dep_store.push_back(rescaled(it->second.d, it->second.w, it->second.h, W, H));
-      depths[k] = dep_store.back().data();
-    }
-  }
-  const ImageState* prev = (!resident && states.count(p.ref_image_id)) ? &states.at(p.ref_image_id) : nullptr;
-  std::vector<float> planes(resident ? 0 : L * 4, 0.0f);
-  std::vector<uint8_t> weak(resident ? 0 : L, DPE_STRONG);
-  std::vector<uint32_t> sel(resident ? 0 : L, 0u);
-  if (resident) {
-    // nothing to build on the host
-  } else if (P.use_APD) {
-    if (!prev) { err = "Can't find weak info of image " + std::to_string(p.ref_image_id); return false; }
-    weak = rescaled(prev->weak, prev->w, prev->h, W, H);
-  }
-  if (!resident && P.state != DPE_FIRST_INIT) {
-    if (!prev) { err = "no prior depth/normal of image " + std::to_string(p.ref_image_id); return false; }
-    const std::vector<float> d = rescaled(prev->depth, prev->w, prev->h, W, H);
-    const std::vector<float> n = rescaled(prev->normal, prev->w, prev->h, W, H, 3);
-    for (size_t i = 0; i < L; ++i) {
-      planes[4 * i + 0] = n[3 * i + 0]; planes[4 * i + 1] = n[3 * i + 1]; planes[4 * i + 2] = n[3 * i + 2];
-      planes[4 * i + 3] = d[i];
-    }
-    sel = rescaled(prev->sel, prev->w, prev->h, W, H);
-  }
-  DpePassInput in;
+  const int W = pi.W, H = pi.H;
+  P.depth_min = pi.cams[0].depth_min * 0.6f;
+  P.depth_max = pi.cams[0].depth_max * 1.2f;
+  P.num_images = (int)pi.ids.size();
+  DpePassInput& in = pi.in;
   std::memset(&in, 0, sizeof(in));
-  in.width = W; in.height = H; in.num_images = (int)ids.size();
-  in.images = images.data();
-  in.cams = cams.data();
-  in.depths = (P.geom_consistency && !resident) ? depths.data() : nullptr;
-  Mat edge, edge_low, label;
+  in.width = W; in.height = H; in.num_images = (int)pi.ids.size();
+  in.images = pi.images.data();
+  in.cams = pi.cams.data();
   if (P.use_edge || P.use_limit) {
     const int s = scale_index(p.scale_size);
     const int max_s = P.high_res_img ? scale_index(P.max_scale_size) : s;
-    if (!read_support(p, "edges_" + std::to_string(s) + ".dmb", edge, err)) return false;
-    if (!read_support(p, "edges_" + std::to_string(max_s) + ".dmb", edge_low, err)) return false;
-    if (edge.rows != H || edge.cols != W || edge.type != CV_8UC1) { err = "edge map size/type mismatch in " + p.result_folder; return false; }
-    in.edge = edge.ptr<uint8_t>();
-    in.edge_low_res = edge_low.ptr<uint8_t>();
-    in.low_width = edge_low.cols; in.low_height = edge_low.rows;
+    if (!read_support(p, "edges_" + std::to_string(s) + ".dmb", pi.edge, err)) return false;
+    if (!read_support(p, "edges_" + std::to_string(max_s) + ".dmb", pi.edge_low, err)) return false;
+    if (pi.edge.rows != H || pi.edge.cols != W || pi.edge.type != CV_8UC1) { err = "edge map size/type mismatch in " + p.result_folder; return false; }
+    in.edge = pi.edge.ptr<uint8_t>();
+    in.edge_low_res = pi.edge_low.ptr<uint8_t>();
+    in.low_width = pi.edge_low.cols; in.low_height = pi.edge_low.rows;
   }
   if (P.use_label) {
-    if (!read_support(p, "labels_" + std::to_string(scale_index(p.scale_size)) + ".dmb", label, err)) return false;
-    if (label.rows != H || label.cols != W || label.type != CV_32SC1) { err = "label map size/type mismatch in " + p.result_folder; return false; }
-    in.label = label.ptr<int32_t>();
+    if (!read_support(p, "labels_" + std::to_string(scale_index(p.scale_size)) + ".dmb", pi.label, err)) return false;
+    if (pi.label.rows != H || pi.label.cols != W || pi.label.type != CV_32SC1) { err = "label map size/type mismatch in " + p.result_folder; return false; }
+    in.label = pi.label.ptr<int32_t>();
   }
   in.params = P;
-  in.seed = opt.base_seed ^ ((uint64_t)p.ref_image_id * 0x9E3779B97F4A7C15ull);
+  in.seed = base_seed ^ ((uint64_t)p.ref_image_id * 0x9E3779B97F4A7C15ull);
   in.pass_salt = (uint32_t)p.iteration;
-  in.image_ids = ids.data();        // pyramid levels stay in HBM across passes (keyed by id and size)
-  if (resident) {
-    int rc = dpe_pm_stage_resident(run.ctx, &in, p.ref_image_id);
-    if (rc == 0) rc = dpe_pm_execute(run.ctx, nullptr);
-    if (rc == 0) rc = dpe_state_save(run.ctx, p.ref_image_id);
-    if (rc != 0) { err = "PatchMatch pass failed (" + std::to_string(rc) + "): " + dpe_last_error(); return false; }
-    if (opt.keep_intermediate) {
-      ImageState s;
-      if (!fetch_state(run.ctx, p.ref_image_id, s, err)) return false;
-      if (!write_state_maps(p, s, err)) return false;
-    }
-    if (viz)   // main.cpp:448-454, from the saved (post-epilogue) state; the stream orders the next pass after it
-      for (int kind = 0; kind < 3; ++kind)
-        if (!viz->submit(p.ref_image_id, kind, P.depth_min, P.depth_max, W, H,
-                         (fs::path(p.result_folder) / (kVizNames[kind] + std::to_string(p.iteration) + ".jpg")).string(), err))
-          return false;
-    return true;
-  }
-  std::vector<float> costs(L);
-  DpePassState st{planes.data(), weak.data(), sel.data(), costs.data()};
-  const int rc = run.fn(run.user, &in, &st);
-  if (rc != 0) {
-    err = "PatchMatch pass failed (" + std::to_string(rc) + "): " + (run.ctx ? std::string(dpe_last_error()) : "runner");
-    return false;
-  }
-  // epilogue (main.cpp:423-437): depth outside [dmin, dmax] -> 0 and UNKNOWN
-  ImageState s;
-  s.w = W; s.h = H;
-  s.depth.resize(L); s.normal.resize(L * 3); s.weak = weak; s.sel = sel;
-  for (size_t i = 0; i < L; ++i) {
-    float d = planes[4 * i + 3];
-    if (d < P.depth_min || d > P.depth_max) { d = 0.0f; s.weak[i] = DPE_UNKNOWN; }
-    s.depth[i] = d;
-    s.normal[3 * i + 0] = planes[4 * i + 0]; s.normal[3 * i + 1] = planes[4 * i + 1]; s.normal[3 * i + 2] = planes[4 * i + 2];
-  }
-  if (opt.keep_intermediate && !write_state_maps(p, s, err)) return false;
-  if (opt.viz) {   // main.cpp:448-454 on the host (a runner hook keeps the state here)
-    std::vector<uint8_t> bgr(L * 3);
-    for (int kind = 0; kind < 3; ++kind) {
-      viz_render(kind, W, H, s.depth.data(), s.normal.data(), s.weak.data(), P.depth_min, P.depth_max, bgr.data());
-      if (!write_jpeg((fs::path(p.result_folder) / (kVizNames[kind] + std::to_string(p.iteration) + ".jpg")).string(), bgr.data(),
-                      W, H, 3, kVizQuality, err))
-        return false;
-    }
-  }
-  states[p.ref_image_id] = std::move(s);
+  in.image_ids = pi.ids.data();        // pyramid levels stay in HBM across passes (keyed by id and size)
   return true;
 }
 
@@ -543,34 +380,97 @@ bool write_outputs(const Problem& p, const ImageState& s, const DpePipelineOptio
   return true;
 }
 
-int run(const char* dense_folder, const DpePipelineOptions& opt) {
-  std::string& err = g_err;
-  err.clear();
-  const double t_start = now_s();
-  for (double& t : g_times) t = 0.0;
-  const int world = std::max(1, opt.world_size), rank = opt.rank;
-  if (world > 1 && !opt.allgather) { err = "world_size > 1 needs an all-gather"; return 1; }
-  if (rank < 0 || rank >= world) { err = "bad rank"; return 1; }
-  const bool jacobi = world > 1 || opt.schedule == DPE_SCHEDULE_JACOBI;
-  const std::string dense(dense_folder);
-  std::error_code ec;
-  fs::create_directories(fs::path(dense) / kOutName, ec);
+// One fusion view: camera, colour image (decode + RescaleImageAndCamera) and block mask of problem
+// `p` at the size of its final state `st`, whose maps the view borrows.
+bool load_fusion_view(const Problem& p, const ImageState& st, bool use_block, FusionView& v, std::string& err) {
+  v.image_id = p.ref_image_id;
+  v.src_ids = p.src_image_ids;
+  DpeCamera cam;
+  if (!read_camera(cam_path(p.dense_folder, p.ref_image_id), cam, err)) return false;
+  ColorImage img;
+  if (!read_bgr(image_path(p.dense_folder, p.ref_image_id), img, err)) return false;
+  if (img.w != st.w || img.h != st.h) {   // RescaleImageAndCamera (DPE.cpp:1123-1144), per channel
+    std::vector<uint8_t> ch((size_t)img.w * img.h), och((size_t)st.w * st.h);
+    v.bgr.assign((size_t)st.w * st.h * 3, 0);
+    for (int k = 0; k < 3; ++k) {
+      for (size_t q = 0; q < ch.size(); ++q) ch[q] = img.bgr[3 * q + k];
+      resize_u8(ch.data(), img.w, img.h, och.data(), st.w, st.h);
+      for (size_t q = 0; q < och.size(); ++q) v.bgr[3 * q + k] = och[q];
+    }
+    scale_intrinsics(cam, st.w / (float)img.w, st.h / (float)img.h);
+  } else {
+    v.bgr = std::move(img.bgr);
+  }
+  cam.width = st.w; cam.height = st.h;
+  if (use_block) {
+    GrayImage b;
+    if (!read_gray((fs::path(p.dense_folder) / "blocks" / ("mask_" + std::to_string(p.ref_image_id) + ".jpg")).string(), b, err)) return false;
+    if (b.w != st.w || b.h != st.h) { err = "block mask size differs from the depth map"; return false; }
+    v.block = std::move(b.px);
+  }
+  v.view.width = st.w; v.view.height = st.h;
+  v.view.cam = cam;
+  v.view.depth = st.depth.data();
+  v.view.normal = st.normal.data();
+  v.weak = st.weak.data();
+  return true;
+}
+
+// The state of one dpe_run_pipeline call and its phases, in the order run() calls them.  A phase
+// returns false when the run ends there with `err` set.  With several ranks a phase's own failure
+// is not such an end: it raises the rank's flag (ranks.fail) and the rank goes on joining the
+// collectives, doing no more work (rank_group.h).
+struct PipelineRun {
+  PipelineRun(const std::string& dense_folder, const DpePipelineOptions& o, std::string& e)
+      : opt(o), dense(dense_folder), err(e), ranks(o), cache(dense_folder),
+        jacobi(ranks.multi() || o.schedule == DPE_SCHEDULE_JACOBI) {}
+
+  const DpePipelineOptions& opt;
+  const std::string dense;
+  std::string& err;
+  RankGroup ranks;
   std::vector<Problem> problems;
-  if (!generate_sample_list(dense, problems, err)) return 1;
-  ImageCache cache(dense);
-  double t_mark = now_s();
-  {   // every image of the run decoded once, on the host threads
+  ImageCache cache;
+  const bool jacobi;
+  // with the default runner the state stays in HBM (dpe_state_save / dpe_pm_stage_resident): the
+  // prior, the source depths and the epilogue are all on the device, nothing is copied back per pass
+  bool resident = false;
+  Runner runner;
+  std::unique_ptr<VizWriter> viz;   // declared after `runner`: joined before the context goes
+  int w0 = 0, h0 = 0;               // the full image size (CheckImages: all the same)
+  int round_num = 0, iteration_index = 0;
+  std::map<int, ImageState> states;      // final states; with a runner hook also every pass's prior
+  std::map<int, DepthMap> depth_cur;     // runner hook: the current depth map of every image of the run
+  std::map<int, ImageState> fusion_states;   // what RunFusion reads: this rank's states and the gathered ones
+
+  Problem& problem_of(int rank, size_t k) { return problems[ranks.block(rank)[k]]; }
+  // one rank has nobody to wait for: its first failure ends the run
+  bool single_rank_failed() {
+    if (ranks.multi() || !ranks.failed()) return false;
+    err = ranks.first_error();
+    return true;
+  }
+  bool images_error(const std::string& detail) {
+    err = "Images may error, check it! " + detail;
+    std::cerr << "Images may error, check it!\n";
+    return false;
+  }
+
+  bool load_problems() {
+    std::error_code ec;
+    fs::create_directories(fs::path(dense) / kOutName, ec);
+    return generate_sample_list(dense, problems, err);
+  }
+
+  // every image of the run decoded once, on the host threads; CheckImages (main.cpp:310-329); the split
+  bool decode_and_check_images() {
     std::vector<int> ids;
     for (const Problem& p : problems) {
       ids.push_back(p.ref_image_id);
       for (int s : p.src_image_ids) ids.push_back(s);
     }
-    const int nt = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
     std::string perr;
-    if (!cache.prefetch(ids, nt, perr)) { err = "Images may error, check it! " + perr; std::cerr << "Images may error, check it!\n"; return 1; }
-  }
-  {   // CheckImages (main.cpp:310-329)
-    int w0 = 0, h0 = 0;
+    if (!cache.prefetch(ids, perr)) return images_error(perr);
     bool ok = !problems.empty();
     for (size_t i = 0; ok && i < problems.size(); ++i) {
       int w, h;
@@ -578,403 +478,421 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
       else if (i == 0) { w0 = w; h0 = h; }
       else if (w != w0 || h != h0) ok = false;
     }
-    if (!ok) { err = "Images may error, check it! " + err; std::cerr << "Images may error, check it!\n"; return 1; }
+    if (!ok) return images_error(err);
+    const int n = (int)problems.size();
+    // every rank reads the same pair.txt, so every rank takes this exit together (no collective yet)
+    if (ranks.world() > n) {
+      err = "world_size " + std::to_string(ranks.world()) + " exceeds the " + std::to_string(n) + " problems";
+      return false;
+    }
+    ranks.split(n);
+    return true;
   }
-  const int n = (int)problems.size();
-  // every rank reads the same pair.txt, so every rank takes this exit together (no collective yet)
-  if (world > n) { err = "world_size " + std::to_string(world) + " exceeds the " + std::to_string(n) + " problems"; return 1; }
-  std::vector<std::vector<int>> blocks(world);
-  for (int r = 0; r < world; ++r) for (int i = r * n / world; i < (r + 1) * n / world; ++i) blocks[r].push_back(i);
-  // Multi-rank failure handling: a rank whose own work fails keeps joining the collectives with a
-  // failure flag in its message, so every rank sees it at the same exchange and all return 1 together
-  // (an early return on one rank would leave the others blocked in the all-gather).
-  bool failed = false;
-  std::string first_err;
-  auto fail = [&](const std::string& e) { if (!failed) { failed = true; first_err = e; } };
-  // A collective that fails on this rank may leave peers waiting in theirs: the optional abort hook
-  // (ncclCommAbort in bin/dpe) makes them fail fast instead of waiting for RCCL's timeout.  Without
-  // one (torch / gloo hooks from Python) the peers wait for their backend's own timeout.
-  auto abort_peers = [&]() { if (opt.abort_collectives) (void)opt.abort_collectives(opt.abort_user); };
-  // all-gather of `per` floats per rank plus one status float; false (err set) when any rank failed
-  auto exchange = [&](std::vector<float>& send, std::vector<float>& recv) -> bool {
-    const size_t per = send.size();
-    send.push_back(failed ? 1.0f : 0.0f);
-    recv.assign((per + 1) * world, 0.0f);
-    if (opt.allgather(opt.allgather_user, send.data(), per + 1, recv.data()) != 0) {
-      err = "all-gather failed";
-      abort_peers();
-      return false;
-    }
-    send.pop_back();
-    std::vector<float> packed(per * world);
-    int bad = -1;
-    for (int r = 0; r < world; ++r) {
-      std::memcpy(packed.data() + (size_t)r * per, recv.data() + (size_t)r * (per + 1), per * sizeof(float));
-      if (bad < 0 && recv[(size_t)r * (per + 1) + per] != 0.0f) bad = r;
-    }
-    recv.swap(packed);
-    if (bad >= 0) {
-      err = bad == rank ? first_err : "rank " + std::to_string(bad) + " failed";
-      return false;
-    }
-    return true;
-  };
-  // the ranks' failure flags, one float each over the host hook; false (err set) when any rank failed
-  auto status_exchange = [&]() -> bool {
-    float flag = failed ? 1.0f : 0.0f;
-    std::vector<float> all(world, 0.0f);
-    if (opt.allgather(opt.allgather_user, &flag, 1, all.data()) != 0) { err = "all-gather failed"; abort_peers(); return false; }
-    for (int r = 0; r < world; ++r)
-      if (all[r] != 0.0f) { err = r == rank ? first_err : "rank " + std::to_string(r) + " failed"; return false; }
-    return true;
-  };
-  // DPE_FAULT_INJECT="before:R" / "after:R" (tests): rank R fails locally just before / after the
-  // first resident depth exchange's collectives (read per run)
-  const std::pair<int, int> fault = [] {
-    const char* e = std::getenv("DPE_FAULT_INJECT");
-    if (!e) return std::make_pair(-1, -1);
-    const std::string v(e);
-    const size_t c = v.find(':');
-    if (c == std::string::npos) return std::make_pair(-1, -1);
-    return std::make_pair(v.compare(0, c, "before") == 0 ? 0 : (v.compare(0, c, "after") == 0 ? 1 : -1), std::atoi(v.c_str() + c + 1));
-  }();
-  bool fault_done = false;
-  auto fault_at = [&](int when, int r) -> bool {
-    if (fault_done || fault.first != when || fault.second != r) return false;
-    fault_done = true;
-    return true;
-  };
-  Runner runner;
-  if (opt.runner) { runner.fn = opt.runner; runner.user = opt.runner_user; }
-  else {
+
+  bool open_runner() {
+    if (opt.runner) { runner.fn = opt.runner; runner.user = opt.runner_user; return true; }
     runner.ctx = dpe_create(opt.gpu_index);
-    if (!runner.ctx) fail(std::string("dpe_create: ") + dpe_last_error());
-    else { runner.fn = native_runner; runner.user = runner.ctx; }
-    if (world == 1 && failed) { err = first_err; return 1; }
+    if (!runner.ctx) ranks.fail(std::string("dpe_create: ") + dpe_last_error());
+    else { runner.fn = native_runner; runner.user = runner.ctx; resident = true; }
+    return !single_rank_failed();
   }
-  int w0, h0;
-  cache.full(problems[0].ref_image_id, w0, h0, err);
-  int round_num = 1, max_size = std::max(w0, h0);   // ComputeRoundNum (main.cpp:390-408)
-  while (max_size > 800) { max_size /= 2; round_num++; }
-  round_num = std::max(round_num, 2);
-  if (opt.verbose && rank == 0) {
-    // std::cout as main.cpp:489, 504 (the pybind module redirects it into sys.stdout)
-    std::cout << "There are " << n << " images to be processed!" << std::endl;
-    std::cout << "There are " << round_num << " resolution stages for coarse-to-fine processing!" << std::endl;
-    std::cout << "Iteration nums: " << round_num * 4 << std::endl;
+
+  void compute_round_num() {   // ComputeRoundNum (main.cpp:390-408)
+    int max_size = std::max(w0, h0);
+    round_num = 1;
+    while (max_size > 800) { max_size /= 2; round_num++; }
+    round_num = std::max(round_num, 2);
+    for (auto& p : problems) p.params.max_scale_size = std::max(1, (int)std::pow(2, round_num - 1));
+    if (opt.verbose && ranks.rank() == 0) {
+      // std::cout as main.cpp:489, 504 (the pybind module redirects it into sys.stdout)
+      std::cout << "There are " << problems.size() << " images to be processed!" << std::endl;
+      std::cout << "There are " << round_num << " resolution stages for coarse-to-fine processing!" << std::endl;
+      std::cout << "Iteration nums: " << round_num * 4 << std::endl;
+    }
   }
-  g_times[1] = now_s() - t_mark;
-  t_mark = now_s();
-  roctxRangePushA("GetProblemEdges");
-  {   // GetProblemEdges for every scale of the schedule (main.cpp:494-501); images are independent,
-      // so a pool of host threads takes them round-robin (the decode cache is filled first)
-    std::vector<GrayImage> grey(blocks[rank].size());
-    for (size_t k = 0; k < blocks[rank].size(); ++k) {
+
+  // GetProblemEdges for every scale of the schedule (main.cpp:494-501); images are independent,
+  // so a pool of host threads takes them round-robin (the decode cache is filled first)
+  bool edge_prepass() {
+    const std::vector<int>& mine = ranks.mine();
+    roctxRangePushA("GetProblemEdges");
+    std::vector<GrayImage> grey(mine.size());
+    for (size_t k = 0; k < mine.size(); ++k) {
       int fw, fh;
-      const std::vector<float>* f = cache.full(problems[blocks[rank][k]].ref_image_id, fw, fh, err);
-      if (!f) return 1;   // decoded in CheckImages above: cannot fail here
+      const std::vector<float>* f = cache.full(problems[mine[k]].ref_image_id, fw, fh, err);
+      if (!f) return false;   // decoded in CheckImages above: cannot fail here
       grey[k].w = fw; grey[k].h = fh;
       grey[k].px.resize(f->size());
       for (size_t q = 0; q < f->size(); ++q) grey[k].px[q] = (uint8_t)(*f)[q];
     }
-    const int nt = (int)std::max<size_t>(1, std::min<size_t>({grey.size(), (size_t)16,
-                                                              (size_t)std::max(1u, std::thread::hardware_concurrency())}));
+    const int nt = std::max(1, std::min<int>(host_threads(), (int)grey.size()));
     // the data-parallel stages (resize, Sobel / NMS, Roberts) on the runner's GPU, the scan-order and
     // RNG-order parts (hysteresis walk, Connect, HoughLinesP) on the host threads
     std::mutex edge_mu;
     EdgeDevice edev{runner.ctx, &edge_mu};
     std::vector<std::string> terr(nt);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-      pool.emplace_back([&, t]() {
-        for (size_t k = t; k < grey.size(); k += nt) {
-          const Problem& p = problems[blocks[rank][k]];
-          for (int i = 0; i < round_num && terr[t].empty(); ++i)
-            if (!get_problem_edges(grey[k], (int)std::pow(2, round_num - 1 - i), p.result_folder, p.params.use_edge,
-                                   p.params.use_label, p.params.high_res_img, terr[t], &edev, opt.viz) && terr[t].empty())
-              terr[t] = "EdgeSegment failed";
-        }
-      });
-    for (auto& th : pool) th.join();
-    for (auto& e : terr) if (!e.empty()) { fail(e); break; }
+    run_on_threads(nt, [&](int t) {
+      for (size_t k = t; k < grey.size(); k += nt) {
+        const Problem& p = problems[mine[k]];
+        for (int i = 0; i < round_num && terr[t].empty(); ++i)
+          if (!get_problem_edges(grey[k], (int)std::pow(2, round_num - 1 - i), p.result_folder, p.params.use_edge,
+                                 p.params.use_label, p.params.high_res_img, terr[t], &edev, opt.viz) && terr[t].empty())
+            terr[t] = "EdgeSegment failed";
+      }
+    });
     roctxRangePop();
-    if (world == 1 && failed) return 1;
+    for (auto& e : terr) if (!e.empty()) { ranks.fail(e); break; }
+    return !single_rank_failed();
   }
-  g_times[2] = now_s() - t_mark;
-  t_mark = now_s();
-  for (auto& p : problems) p.params.max_scale_size = std::max(1, (int)std::pow(2, round_num - 1));
-  std::map<int, ImageState> states;
-  std::map<int, DepthMap> depth_cur;
-  int iteration_index = 0;
-  const bool resident = runner.ctx != nullptr;
-  std::unique_ptr<VizWriter> viz;   // declared after `runner`: joined before the context goes
-  if (opt.viz && resident) viz.reset(new VizWriter(runner.ctx, w0, h0));
-  double t_pass = 0.0, t_xchg = 0.0;   // g_times[6] / [5]
-  for (int i = 0; i < round_num; ++i) {
-    for (int j = -1; j < 3; ++j) {
-      const double tp0 = now_s();
-      if (resident && jacobi && !failed && dpe_state_snapshot(runner.ctx) != 0) fail(dpe_last_error());
-      const std::map<int, DepthMap> snapshot = (jacobi && !resident) ? depth_cur : std::map<int, DepthMap>{};
-      const auto& depth_src = jacobi ? snapshot : depth_cur;
-      // pass size: ImageCache::level's rounding of the first image (CheckImages: all the same size)
-      const int scale = (int)std::pow(2, round_num - 1 - i);
-      const int pw = scale == 1 ? w0 : std_round(w0 * (1.0f / (float)scale));
-      const int ph = scale == 1 ? h0 : std_round(h0 * (1.0f / (float)scale));
-      for (int pi : blocks[rank]) {
-        if (failed) break;
-        Problem& p = problems[pi];
-        p.iteration = iteration_index;
-        p.scale_size = scale;
-        p.params.scale_size = p.scale_size;
-        pass_params(p.params, i, j);
-        if (opt.max_iterations > 0) p.params.max_iterations = opt.max_iterations;
-        if (opt.photometric_only) p.params.geom_consistency = false;
-        std::string perr;
-        const std::string rname = "ProcessProblem round " + std::to_string(i) + " pass " + std::to_string(j + 1) +
-                                  " image " + std::to_string(p.ref_image_id);
-        roctxRangePushA(rname.c_str());
-        const bool ok = process_problem(p, cache, states, depth_src, opt, runner, viz.get(), perr);
-        roctxRangePop();
-        if (!ok) { fail(perr); break; }
-        if (!resident) {
-          const ImageState& s = states[p.ref_image_id];
-          depth_cur[p.ref_image_id] = DepthMap{s.w, s.h, s.depth};
-        }
+
+  // stage, execute and save in HBM; nothing comes back unless the intermediate maps are asked for
+  bool run_resident_pass(const Problem& p, const PassInput& pi, std::string& perr) {
+    int rc = dpe_pm_stage_resident(runner.ctx, &pi.in, p.ref_image_id);
+    if (rc == 0) rc = dpe_pm_execute(runner.ctx, nullptr);
+    if (rc == 0) rc = dpe_state_save(runner.ctx, p.ref_image_id);
+    if (rc != 0) { perr = "PatchMatch pass failed (" + std::to_string(rc) + "): " + dpe_last_error(); return false; }
+    if (opt.keep_intermediate) {
+      ImageState s;
+      if (!fetch_state(runner.ctx, p.ref_image_id, s, perr)) return false;
+      if (!write_state_maps(p, s, perr)) return false;
+    }
+    if (viz)   // main.cpp:448-454, from the saved (post-epilogue) state; the stream orders the next pass after it
+      for (int kind = 0; kind < 3; ++kind)
+        if (!viz->submit(p.ref_image_id, kind, p.params.depth_min, p.params.depth_max, pi.W, pi.H, viz_path(p, kind), perr))
+          return false;
+    return true;
+  }
+
+  // a runner hook keeps the state on the host: source depths and the prior rescaled here, the
+  // runner, then ProcessProblem's epilogue into `states`
+  bool run_hook_pass(const Problem& p, PassInput& pi, const std::map<int, DepthMap>& depth_src, std::string& perr) {
+    const DpePatchMatchParams& P = p.params;
+    const int W = pi.W, H = pi.H;
+    const size_t L = (size_t)W * H;
+    std::vector<std::vector<float>> dep_store;
+    std::vector<const float*> depths(pi.ids.size(), nullptr);
+    if (P.geom_consistency) {
+      dep_store.reserve(pi.ids.size());
+      for (size_t k = 1; k < pi.ids.size(); ++k) {
+        auto it = depth_src.find(pi.ids[k]);
+        if (it == depth_src.end()) { perr = "no depth map of source image " + std::to_string(pi.ids[k]); return false; }
+        dep_store.push_back(rescaled(it->second.d, it->second.w, it->second.h, W, H));
+        depths[k] = dep_store.back().data();
       }
-      // the pass round's GPU work is finished before its clock stops (and, multi-rank, before the
-      // exchange's clock starts): with one rank the passes are otherwise only enqueued here
-      if (resident && !failed && dpe_sync(runner.ctx) != 0) fail(dpe_last_error());
-      if (world == 1 && failed) { err = first_err; return 1; }
-      const double tx0 = now_s();
-      t_pass += tx0 - tp0;
-      if (world > 1 && resident) {   // all-gather of the depth maps from / into the HBM-resident states
-        // Two collectives per exchange, both joined by every rank whatever happened locally:
-        //  1. the ranks' status flags over the host hook (one float each).  A local error before it
-        //     (the pass, the exchange buffers, the export) raises the flag and every rank returns 1
-        //     at this exchange;
-        //  2. the depth maps (nmax maps per rank), device to device, or one device -> host -> device
-        //     hop through the host hook.  An error after (1) can no longer stop the others, who are
-        //     committed to (2): the rank still joins (2), records the error and reports it at the
-        //     next exchange's (1) or at the final status exchange after the passes.
-        size_t nmax = 0;
-        for (auto& b : blocks) nmax = std::max(nmax, b.size());
-        const size_t per = (size_t)pw * ph, cnt = nmax * per;
-        float* dsend = dpe_device_buffer(runner.ctx, 0, cnt);
-        float* drecv = dsend ? dpe_device_buffer(runner.ctx, 1, cnt * world) : nullptr;
-        bool dev_ok = drecv != nullptr;
-        if (!dev_ok) fail(dpe_last_error());
-        for (size_t k = 0; dev_ok && !failed && k < blocks[rank].size(); ++k)
-          if (dpe_state_export_depth(runner.ctx, problems[blocks[rank][k]].ref_image_id, dsend + k * per, nullptr) != 0)
-            fail(dpe_last_error());
-        // the exports run on the context's stream; the collective reads dsend from another one
-        if (dev_ok && !failed && dpe_sync(runner.ctx) != 0) fail(dpe_last_error());
-        if (fault_at(0, rank)) fail("injected fault before the exchange");
-        if (!status_exchange()) return 1;
-        if (opt.allgather_device) {
-          if (opt.allgather_device(opt.allgather_device_user, dsend, cnt, drecv) != 0) {
-            err = "all-gather failed";
-            abort_peers();
-            return 1;
-          }
-        } else {   // host hook: one device -> host -> device hop of the packed maps
-          std::vector<float> hs(cnt, 0.0f), hr(cnt * world, 0.0f);
-          if (dpe_device_copy(runner.ctx, hs.data(), dsend, cnt * sizeof(float), 1) != 0) fail(dpe_last_error());
-          if (opt.allgather(opt.allgather_user, hs.data(), cnt, hr.data()) != 0) {
-            err = "all-gather failed";
-            abort_peers();
-            return 1;
-          }
-          if (!failed && dpe_device_copy(runner.ctx, drecv, hr.data(), hr.size() * sizeof(float), 0) != 0)
-            fail(dpe_last_error());
-        }
-        if (fault_at(1, rank)) fail("injected fault after the exchange");
-        for (int r = 0; r < world; ++r) {
-          if (r == rank) continue;
-          for (size_t k = 0; k < blocks[r].size(); ++k)
-            if (!failed && dpe_state_import_depth(runner.ctx, problems[blocks[r][k]].ref_image_id, pw, ph,
-                                                  drecv + (size_t)r * cnt + k * per, nullptr) != 0)
-              fail(dpe_last_error());   // reported at the next exchange's status step
-        }
-        if (!failed && dpe_sync(runner.ctx) != 0) fail(dpe_last_error());   // imports done: the exchange's end
-      } else if (world > 1) {   // all-gather of the depth maps (the pass's only cross-image data)
-        size_t nmax = 0;
-        for (auto& b : blocks) nmax = std::max(nmax, b.size());
-        const size_t per = (size_t)pw * ph;
-        std::vector<float> send(nmax * per, 0.0f), recv;
-        for (size_t k = 0; !failed && k < blocks[rank].size(); ++k) {
-          const auto& d = depth_cur[problems[blocks[rank][k]].ref_image_id];
-          std::memcpy(send.data() + k * per, d.d.data(), per * 4);
-        }
-        if (!exchange(send, recv)) return 1;
-        for (int r = 0; r < world; ++r)
-          for (size_t k = 0; k < blocks[r].size(); ++k) {
-            const float* src = recv.data() + ((size_t)r * nmax + k) * per;
-            depth_cur[problems[blocks[r][k]].ref_image_id] = DepthMap{pw, ph, std::vector<float>(src, src + per)};
-          }
+      pi.in.depths = depths.data();
+    }
+    const ImageState* prev = states.count(p.ref_image_id) ? &states.at(p.ref_image_id) : nullptr;
+    std::vector<float> planes(L * 4, 0.0f);
+    std::vector<uint8_t> weak(L, DPE_STRONG);
+    std::vector<uint32_t> sel(L, 0u);
+    if (P.use_APD) {
+      if (!prev) { perr = "Can't find weak info of image " + std::to_string(p.ref_image_id); return false; }
+      weak = rescaled(prev->weak, prev->w, prev->h, W, H);
+    }
+    if (P.state != DPE_FIRST_INIT) {
+      if (!prev) { perr = "no prior depth/normal of image " + std::to_string(p.ref_image_id); return false; }
+      const std::vector<float> d = rescaled(prev->depth, prev->w, prev->h, W, H);
+      const std::vector<float> n = rescaled(prev->normal, prev->w, prev->h, W, H, 3);
+      for (size_t i = 0; i < L; ++i) {
+        planes[4 * i + 0] = n[3 * i + 0]; planes[4 * i + 1] = n[3 * i + 1]; planes[4 * i + 2] = n[3 * i + 2];
+        planes[4 * i + 3] = d[i];
       }
-      if (world > 1) t_xchg += now_s() - tx0;
-      if (opt.verbose && rank == 0) std::cout << "Iteration " << iteration_index + 1 << " / " << round_num * 4 << " done" << std::endl;
-      iteration_index++;
+      sel = rescaled(prev->sel, prev->w, prev->h, W, H);
+    }
+    std::vector<float> costs(L);
+    DpePassState st{planes.data(), weak.data(), sel.data(), costs.data()};
+    const int rc = runner.fn(runner.user, &pi.in, &st);
+    if (rc != 0) { perr = "PatchMatch pass failed (" + std::to_string(rc) + "): runner"; return false; }
+    // epilogue (main.cpp:423-437): depth outside [dmin, dmax] -> 0 and UNKNOWN
+    ImageState s;
+    s.w = W; s.h = H;
+    s.depth.resize(L); s.normal.resize(L * 3); s.weak = weak; s.sel = sel;
+    for (size_t i = 0; i < L; ++i) {
+      float d = planes[4 * i + 3];
+      if (d < P.depth_min || d > P.depth_max) { d = 0.0f; s.weak[i] = DPE_UNKNOWN; }
+      s.depth[i] = d;
+      s.normal[3 * i + 0] = planes[4 * i + 0]; s.normal[3 * i + 1] = planes[4 * i + 1]; s.normal[3 * i + 2] = planes[4 * i + 2];
+    }
+    if (opt.keep_intermediate && !write_state_maps(p, s, perr)) return false;
+    if (opt.viz) {   // main.cpp:448-454 on the host
+      std::vector<uint8_t> bgr(L * 3);
+      for (int kind = 0; kind < 3; ++kind) {
+        viz_render(kind, W, H, s.depth.data(), s.normal.data(), s.weak.data(), P.depth_min, P.depth_max, bgr.data());
+        if (!write_jpeg(viz_path(p, kind), bgr.data(), W, H, 3, kVizQuality, perr)) return false;
+      }
+    }
+    states[p.ref_image_id] = std::move(s);
+    return true;
+  }
+
+  // pass j of round i over this rank's images; the first failure raises the flag and ends the block
+  void run_block(int i, int j, int scale) {
+    // runner hook, jacobi: every image of the block reads the depths of the previous pass round
+    const std::map<int, DepthMap> snapshot = (jacobi && !resident) ? depth_cur : std::map<int, DepthMap>{};
+    const auto& depth_src = jacobi ? snapshot : depth_cur;
+    for (int pi : ranks.mine()) {
+      if (ranks.failed()) break;
+      Problem& p = problems[pi];
+      p.iteration = iteration_index;
+      p.scale_size = scale;
+      p.params.scale_size = p.scale_size;
+      pass_params(p.params, i, j);
+      if (opt.max_iterations > 0) p.params.max_iterations = opt.max_iterations;
+      if (opt.photometric_only) p.params.geom_consistency = false;
+      std::string perr;
+      const std::string rname = "ProcessProblem round " + std::to_string(i) + " pass " + std::to_string(j + 1) +
+                                " image " + std::to_string(p.ref_image_id);
+      roctxRangePushA(rname.c_str());
+      PassInput in;
+      const bool ok = build_pass_input(p, cache, opt.base_seed, in, perr) &&
+                      (resident ? run_resident_pass(p, in, perr) : run_hook_pass(p, in, depth_src, perr));
+      roctxRangePop();
+      if (!ok) { ranks.fail(perr); break; }
+      if (!resident) {
+        const ImageState& s = states[p.ref_image_id];
+        depth_cur[p.ref_image_id] = DepthMap{s.w, s.h, s.depth};
+      }
     }
   }
-  g_times[3] = now_s() - t_mark;
-  g_times[5] = t_xchg;
-  g_times[6] = t_pass;
-  t_mark = now_s();
-  if (viz) {   // the pictures still being coded or written; their errors
+
+  // All-gather of the pw x ph depth maps from / into the HBM-resident states.  Two collectives, both
+  // joined by every rank whatever happened locally:
+  //  1. the ranks' status flags over the host hook.  A local error before it (the pass, the exchange
+  //     buffers, the export) raises the flag and every rank returns 1 at this exchange;
+  //  2. the depth maps (max_block maps per rank), device to device, or one device -> host -> device
+  //     hop through the host hook.  An error after (1) is recorded and reported at the next
+  //     exchange's (1) or at the final status exchange after the passes.
+  bool exchange_depths_resident(int pw, int ph) {
+    DpeContext* ctx = runner.ctx;
+    const int world = ranks.world(), rank = ranks.rank();
+    const size_t per = (size_t)pw * ph, cnt = ranks.max_block() * per;
+    float* dsend = dpe_device_buffer(ctx, 0, cnt);
+    float* drecv = dsend ? dpe_device_buffer(ctx, 1, cnt * world) : nullptr;
+    const bool dev_ok = drecv != nullptr;
+    if (!dev_ok) ranks.fail(dpe_last_error());
+    for (size_t k = 0; dev_ok && !ranks.failed() && k < ranks.mine().size(); ++k)
+      if (dpe_state_export_depth(ctx, problem_of(rank, k).ref_image_id, dsend + k * per, nullptr) != 0)
+        ranks.fail(dpe_last_error());
+    // the exports run on the context's stream; the collective reads dsend from another one
+    if (dev_ok && !ranks.failed() && dpe_sync(ctx) != 0) ranks.fail(dpe_last_error());
+    if (ranks.fault_at(RankGroup::kBeforeExchange)) ranks.fail("injected fault before the exchange");
+    if (!ranks.status_exchange(err)) return false;
+    if (ranks.has_device_hook()) {
+      if (!ranks.gather_device(dsend, cnt, drecv, err)) return false;
+    } else {   // host hook: one device -> host -> device hop of the packed maps
+      std::vector<float> hs(cnt, 0.0f), hr(cnt * world, 0.0f);
+      if (dpe_device_copy(ctx, hs.data(), dsend, cnt * sizeof(float), 1) != 0) ranks.fail(dpe_last_error());
+      if (!ranks.gather(hs.data(), cnt, hr.data(), err)) return false;
+      if (!ranks.failed() && dpe_device_copy(ctx, drecv, hr.data(), hr.size() * sizeof(float), 0) != 0)
+        ranks.fail(dpe_last_error());
+    }
+    if (ranks.fault_at(RankGroup::kAfterExchange)) ranks.fail("injected fault after the exchange");
+    for (int r = 0; r < world; ++r) {
+      if (r == rank) continue;
+      for (size_t k = 0; k < ranks.block(r).size(); ++k)
+        if (!ranks.failed() && dpe_state_import_depth(ctx, problem_of(r, k).ref_image_id, pw, ph,
+                                                      drecv + (size_t)r * cnt + k * per, nullptr) != 0)
+          ranks.fail(dpe_last_error());
+    }
+    if (!ranks.failed() && dpe_sync(ctx) != 0) ranks.fail(dpe_last_error());   // imports done: the exchange's end
+    return true;
+  }
+
+  // runner hook: all-gather of the depth maps (the pass's only cross-image data) into depth_cur
+  bool exchange_depths_host(int pw, int ph) {
+    const size_t per = (size_t)pw * ph, nmax = ranks.max_block();
+    std::vector<float> send(nmax * per, 0.0f), recv;
+    for (size_t k = 0; !ranks.failed() && k < ranks.mine().size(); ++k)
+      std::memcpy(send.data() + k * per, depth_cur[problem_of(ranks.rank(), k).ref_image_id].d.data(), per * 4);
+    if (!ranks.exchange(send, recv, err)) return false;
+    for (int r = 0; r < ranks.world(); ++r)
+      for (size_t k = 0; k < ranks.block(r).size(); ++k) {
+        const float* src = recv.data() + ((size_t)r * nmax + k) * per;
+        depth_cur[problem_of(r, k).ref_image_id] = DepthMap{pw, ph, std::vector<float>(src, src + per)};
+      }
+    return true;
+  }
+
+  bool run_pass_round(int i, int j) {
+    const double tp0 = now_s();
+    if (resident && jacobi && !ranks.failed() && dpe_state_snapshot(runner.ctx) != 0) ranks.fail(dpe_last_error());
+    // pass size: ImageCache::level's rounding of the first image (CheckImages: all the same size)
+    const int scale = (int)std::pow(2, round_num - 1 - i);
+    const int pw = scale == 1 ? w0 : std_round(w0 * (1.0f / (float)scale));
+    const int ph = scale == 1 ? h0 : std_round(h0 * (1.0f / (float)scale));
+    run_block(i, j, scale);
+    // the pass round's GPU work is finished before its clock stops (and, multi-rank, before the
+    // exchange's clock starts): with one rank the passes are otherwise only enqueued here
+    if (resident && !ranks.failed() && dpe_sync(runner.ctx) != 0) ranks.fail(dpe_last_error());
+    if (single_rank_failed()) return false;
+    const double tx0 = now_s();
+    g_times[kTimePassWork] += tx0 - tp0;
+    if (ranks.multi()) {
+      if (!(resident ? exchange_depths_resident(pw, ph) : exchange_depths_host(pw, ph))) return false;
+      g_times[kTimeExchange] += now_s() - tx0;
+    }
+    if (opt.verbose && ranks.rank() == 0)
+      std::cout << "Iteration " << iteration_index + 1 << " / " << round_num * 4 << " done" << std::endl;
+    iteration_index++;
+    return true;
+  }
+
+  void finish_viz() {   // the pictures still being coded or written; their errors
     std::string verr;
-    if (!viz->finish(verr)) fail(verr);
+    if (viz && !viz->finish(verr)) ranks.fail(verr);
   }
-  if (resident && !failed)   // the final states come back from HBM once
-    for (int pi : blocks[rank]) {
+
+  void collect_final_states() {   // the final states come back from HBM once
+    if (!resident || ranks.failed()) return;
+    for (int pi : ranks.mine()) {
       std::string ferr;
-      if (!fetch_state(runner.ctx, problems[pi].ref_image_id, states[problems[pi].ref_image_id], ferr)) { fail(ferr); break; }
+      const int id = problems[pi].ref_image_id;
+      if (!fetch_state(runner.ctx, id, states[id], ferr)) { ranks.fail(ferr); break; }
     }
-  if (!failed) {   // each image's .npy files on their own host thread (independent files)
-    const auto& blk = blocks[rank];
-    const int nt = (int)std::min<size_t>(blk.size(), std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())));
-    std::vector<std::string> werr(blk.size());
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nt; ++t)
-      pool.emplace_back([&, t]() {
-        for (size_t k = t; k < blk.size(); k += nt) {
-          const Problem& p = problems[blk[k]];
-          if (!write_outputs(p, states.at(p.ref_image_id), opt, werr[k]) && werr[k].empty()) werr[k] = "write failed";
-        }
-      });
-    for (auto& th : pool) th.join();
-    for (auto& e : werr) if (!e.empty()) { fail(e); break; }
   }
+
+  void write_all_outputs() {   // each image's .npy files on their own host thread (independent files)
+    if (ranks.failed()) return;
+    const std::vector<int>& mine = ranks.mine();
+    const int nt = std::max(1, std::min<int>(host_threads(), (int)mine.size()));
+    std::vector<std::string> werr(mine.size());
+    run_on_threads(nt, [&](int t) {
+      for (size_t k = t; k < mine.size(); k += nt) {
+        const Problem& p = problems[mine[k]];
+        if (!write_outputs(p, states.at(p.ref_image_id), opt, werr[k]) && werr[k].empty()) werr[k] = "write failed";
+      }
+    });
+    for (auto& e : werr) if (!e.empty()) { ranks.fail(e); break; }
+  }
+
+  // fusion_states: this rank's final states and, with several ranks, every other image's depth (the
+  // last exchange left it here), normals and pixel states (one more exchange)
+  bool gather_states_for_fusion() {
+    for (int pi : ranks.mine()) fusion_states[problems[pi].ref_image_id] = states[problems[pi].ref_image_id];
+    if (!ranks.multi()) return true;
+    const ImageState& s0 = states[problem_of(ranks.rank(), 0).ref_image_id];
+    const size_t per = (size_t)s0.w * s0.h, nmax = ranks.max_block();
+    std::vector<float> send(nmax * per * 4, 0.0f), recv;
+    for (size_t k = 0; k < ranks.mine().size(); ++k) {
+      const ImageState& st = states[problem_of(ranks.rank(), k).ref_image_id];
+      float* o = send.data() + k * per * 4;
+      std::memcpy(o, st.normal.data(), per * 12);
+      for (size_t i = 0; i < per; ++i) o[3 * per + i] = (float)st.weak[i];
+    }
+    if (!ranks.exchange(send, recv, err)) return false;
+    for (int r = 0; r < ranks.world(); ++r)
+      for (size_t k = 0; k < ranks.block(r).size(); ++k) {
+        const int id = problem_of(r, k).ref_image_id;
+        if (fusion_states.count(id)) continue;
+        const float* src = recv.data() + ((size_t)r * nmax + k) * per * 4;
+        ImageState st;
+        st.w = s0.w; st.h = s0.h;
+        if (resident) {
+          ImageState d;
+          if (!fetch_state(runner.ctx, id, d, err, true)) return false;
+          st.depth = std::move(d.depth);
+        } else {
+          st.depth = depth_cur[id].d;
+        }
+        st.normal.assign(src, src + 3 * per);
+        st.weak.resize(per);
+        for (size_t i = 0; i < per; ++i) st.weak[i] = (uint8_t)src[3 * per + i];
+        fusion_states[id] = std::move(st);
+      }
+    return true;
+  }
+
+  // each view on its own host thread (independent files, independent outputs)
+  bool load_fusion_views(std::vector<FusionView>& views) {
+    const size_t nv = problems.size();
+    views.resize(nv);
+    const bool use_block = fs::exists(fs::path(dense) / "blocks");
+    std::vector<std::string> verr(nv);
+    const int nt = std::max(1, std::min<int>(host_threads(), (int)nv));
+    run_on_threads(nt, [&](int t) {
+      for (size_t i = t; i < nv; i += nt)
+        if (!load_fusion_view(problems[i], fusion_states.at(problems[i].ref_image_id), use_block, views[i], verr[i]) &&
+            verr[i].empty())
+          verr[i] = "fusion view load failed";
+    });
+    for (auto& e : verr) if (!e.empty()) { err = e; return false; }
+    return true;
+  }
+
+  bool fuse_and_export(std::vector<FusionView>& views) {   // RunFusion + ExportPointCloud (main.cpp:578-580)
+    NativeFusion nf;
+    dpe_fusion_fn ffn = opt.fusion_runner;
+    void* fuser = opt.fusion_user;
+    if (!ffn) {
+      nf.ctx = runner.ctx;
+      if (!nf.ctx) {
+        nf.ctx = dpe_create(opt.gpu_index);
+        if (!nf.ctx) { err = std::string("dpe_create: ") + dpe_last_error(); return false; }
+        nf.own = true;
+      }
+      ffn = native_fusion; fuser = &nf;
+    }
+    std::vector<FusedPoint> cloud;
+    if (!run_fusion(views, ffn, fuser, cloud, err)) {
+      if (!opt.fusion_runner) err += std::string(": ") + (nf.err.empty() ? std::string(dpe_last_error()) : nf.err);
+      return false;
+    }
+    if (!export_point_cloud((fs::path(dense) / kOutName / "DPE.ply").string(), cloud, err)) return false;
+    if (opt.verbose) std::cout << "Fused " << cloud.size() << " points" << std::endl;
+    return true;
+  }
+
+  void remove_intermediate_maps() {   // the reference's clean-up (main.cpp:581-595)
+    for (int pi : ranks.mine())
+      for (int j = 0; j < round_num; j++) {
+        std::error_code ec;
+        fs::remove(fs::path(problems[pi].result_folder) / ("edges_" + std::to_string(j) + ".dmb"), ec);
+        fs::remove(fs::path(problems[pi].result_folder) / ("labels_" + std::to_string(j) + ".dmb"), ec);
+      }
+  }
+};
+
+int run(const char* dense_folder, const DpePipelineOptions& opt) {
+  std::string& err = g_err;
+  err.clear();
+  const double t_start = now_s();
+  for (double& t : g_times) t = 0.0;
+  if (opt.world_size > 1 && !opt.allgather) { err = "world_size > 1 needs an all-gather"; return 1; }
+  if (opt.rank < 0 || opt.rank >= std::max(1, opt.world_size)) { err = "bad rank"; return 1; }
+  PipelineRun r(dense_folder, opt, err);
+  RankGroup& ranks = r.ranks;
+  if (!r.load_problems()) return 1;
+  double t_mark = now_s();
+  auto lap = [&t_mark](TimeSlot slot) { const double t = now_s(); g_times[slot] = t - t_mark; t_mark = t; };
+  if (!r.decode_and_check_images()) return 1;
+  if (!r.open_runner()) return 1;
+  r.compute_round_num();
+  lap(kTimeDecode);
+  if (!r.edge_prepass()) return 1;
+  lap(kTimeEdges);
+  if (opt.viz && r.resident) r.viz.reset(new VizWriter(r.runner.ctx, r.w0, r.h0));
+  for (int i = 0; i < r.round_num; ++i)
+    for (int j = -1; j < 3; ++j)
+      if (!r.run_pass_round(i, j)) return 1;
+  lap(kTimePasses);
+  r.finish_viz();
+  r.collect_final_states();
+  r.write_all_outputs();
   // every rank learns here whether any rank failed after its last exchange (a rank returning alone
   // would leave the others' next collective, or their success, inconsistent with it)
-  if (world > 1 && !status_exchange()) return 1;
-  if (failed) { err = first_err; return 1; }
-  const double t_fusion0 = now_s();
-  g_times[7] = 0.0;
-  if (opt.fusion) {   // RunFusion (main.cpp:578-580)
-    std::map<int, ImageState> all;
-    for (int pi : blocks[rank]) all[problems[pi].ref_image_id] = states[problems[pi].ref_image_id];
-    if (world > 1) {   // the final normals and pixel states of every image (depths are in depth_cur)
-      const ImageState& s0 = states[problems[blocks[rank][0]].ref_image_id];
-      const size_t per = (size_t)s0.w * s0.h;
-      size_t nmax = 0;
-      for (auto& b : blocks) nmax = std::max(nmax, b.size());
-      std::vector<float> send(nmax * per * 4, 0.0f), recv(send.size() * world);
-      for (size_t k = 0; k < blocks[rank].size(); ++k) {
-        const ImageState& st = states[problems[blocks[rank][k]].ref_image_id];
-        float* o = send.data() + k * per * 4;
-        std::memcpy(o, st.normal.data(), per * 12);
-        for (size_t i = 0; i < per; ++i) o[3 * per + i] = (float)st.weak[i];
-      }
-      if (!exchange(send, recv)) return 1;
-      for (int r = 0; r < world; ++r)
-        for (size_t k = 0; k < blocks[r].size(); ++k) {
-          const int id = problems[blocks[r][k]].ref_image_id;
-          if (all.count(id)) continue;
-          const float* src = recv.data() + ((size_t)r * nmax + k) * per * 4;
-          ImageState st;
-          st.w = s0.w; st.h = s0.h;
-          if (resident) {
-            ImageState d;
-            if (!fetch_state(runner.ctx, id, d, err, true)) return 1;
-            st.depth = std::move(d.depth);
-          } else {
-            st.depth = depth_cur[id].d;
-          }
-          st.normal.assign(src, src + 3 * per);
-          st.weak.resize(per);
-          for (size_t i = 0; i < per; ++i) st.weak[i] = (uint8_t)src[3 * per + i];
-          all[id] = std::move(st);
-        }
-    }
-    if (rank == 0) {
-      std::vector<FusionView> views(problems.size());
-      const bool use_block = fs::exists(fs::path(dense) / "blocks");
-      // each view's camera, colour image (decode + RescaleImageAndCamera) and block mask on its own
-      // host thread (independent files, independent outputs)
-      std::vector<std::string> verr(problems.size());
-      auto load_view = [&](size_t i) -> bool {
-        std::string& err = verr[i];
-        const Problem& p = problems[i];
-        FusionView& v = views[i];
-        const ImageState& st = all.at(p.ref_image_id);
-        v.image_id = p.ref_image_id;
-        v.src_ids = p.src_image_ids;
-        DpeCamera cam;
-        if (!read_camera((fs::path(dense) / "cams" / (fmt_index(p.ref_image_id) + "_cam.txt")).string(), cam, err)) return false;
-        ColorImage img;
-        if (!read_bgr((fs::path(dense) / "images" / (fmt_index(p.ref_image_id) + ".jpg")).string(), img, err)) return false;
-        if (img.w != st.w || img.h != st.h) {   // RescaleImageAndCamera (DPE.cpp:1123-1144), per channel
-          const float sx = st.w / (float)img.w, sy = st.h / (float)img.h;
-          std::vector<uint8_t> ch((size_t)img.w * img.h), och((size_t)st.w * st.h);
-          v.bgr.assign((size_t)st.w * st.h * 3, 0);
-          for (int k = 0; k < 3; ++k) {
-            for (size_t q = 0; q < ch.size(); ++q) ch[q] = img.bgr[3 * q + k];
-            resize_u8(ch.data(), img.w, img.h, och.data(), st.w, st.h);
-            for (size_t q = 0; q < och.size(); ++q) v.bgr[3 * q + k] = och[q];
-          }
-          cam.K[0] *= sx; cam.K[2] *= sx; cam.K[4] *= sy; cam.K[5] *= sy;
-        } else {
-          v.bgr = std::move(img.bgr);
-        }
-        cam.width = st.w; cam.height = st.h;
-        if (use_block) {
-          GrayImage b;
-          if (!read_gray((fs::path(dense) / "blocks" / ("mask_" + std::to_string(p.ref_image_id) + ".jpg")).string(), b, err)) return false;
-          if (b.w != st.w || b.h != st.h) { err = "block mask size differs from the depth map"; return false; }
-          v.block = std::move(b.px);
-        }
-        v.view.width = st.w; v.view.height = st.h;
-        v.view.cam = cam;
-        v.view.depth = st.depth.data();
-        v.view.normal = st.normal.data();
-        v.weak = st.weak.data();
-        return true;
-      };
-      {
-        const size_t nv = problems.size();
-        const int nt = (int)std::min<size_t>(nv, std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())));
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t)
-          pool.emplace_back([&, t]() {
-            for (size_t i = t; i < nv; i += nt)
-              if (!load_view(i) && verr[i].empty()) verr[i] = "fusion view load failed";
-          });
-        for (auto& th : pool) th.join();
-        for (auto& e : verr) if (!e.empty()) { err = e; return 1; }
-      }
-      NativeFusion nf;
-      dpe_fusion_fn ffn = opt.fusion_runner;
-      void* fuser = opt.fusion_user;
-      if (!ffn) {
-        nf.ctx = runner.ctx;
-        if (!nf.ctx) {
-          nf.ctx = dpe_create(opt.gpu_index);
-          if (!nf.ctx) { err = std::string("dpe_create: ") + dpe_last_error(); return 1; }
-          nf.own = true;
-        }
-        ffn = native_fusion; fuser = &nf;
-      }
-      std::vector<FusedPoint> cloud;
-      if (!run_fusion(views, ffn, fuser, cloud, err)) {
-        if (!opt.fusion_runner) err += std::string(": ") + (nf.err.empty() ? std::string(dpe_last_error()) : nf.err);
-        return 1;
-      }
-      if (!export_point_cloud((fs::path(dense) / kOutName / "DPE.ply").string(), cloud, err)) return 1;
-      if (opt.verbose) std::cout << "Fused " << cloud.size() << " points" << std::endl;
-    }
-    g_times[7] = now_s() - t_fusion0;
+  if (ranks.multi() && !ranks.status_exchange(err)) return 1;
+  if (ranks.failed()) { err = ranks.first_error(); return 1; }
+  if (opt.fusion) {   // RunFusion (main.cpp:578-580) on rank 0, over every rank's final states
+    const double t_fusion0 = now_s();
+    if (!r.gather_states_for_fusion()) return 1;
+    std::vector<FusionView> views;
+    if (ranks.rank() == 0 && !(r.load_fusion_views(views) && r.fuse_and_export(views))) return 1;
+    g_times[kTimeFusion] = now_s() - t_fusion0;
   }
-  if (!opt.keep_intermediate)   // the reference's clean-up (main.cpp:581-595)
-    for (int pi : blocks[rank])
-      for (int j = 0; j < round_num; j++) {
-        std::error_code ec2;
-        fs::remove(fs::path(problems[pi].result_folder) / ("edges_" + std::to_string(j) + ".dmb"), ec2);
-        fs::remove(fs::path(problems[pi].result_folder) / ("labels_" + std::to_string(j) + ".dmb"), ec2);
-      }
-  if (opt.verbose && rank == 0) std::cout << "All done" << std::endl;
-  g_times[4] = now_s() - t_mark;
-  g_times[0] = now_s() - t_start;
+  if (!opt.keep_intermediate) r.remove_intermediate_maps();
+  if (opt.verbose && ranks.rank() == 0) std::cout << "All done" << std::endl;
+  g_times[kTimeOutputs] = now_s() - t_mark;
+  g_times[kTimeTotal] = now_s() - t_start;
   return 0;
 }
 

@@ -58,7 +58,10 @@ typedef int (*dpe_allgather_dev_fn)(void* user, const float* dev_send, size_t co
 typedef int (*dpe_abort_fn)(void* user);
 
 /* Fusion projection tests of one reference view: same contract as dpe_fusion_candidates
- * (include/dpe_mvs.h) over the given views (the default runs the HIP kernel on gpu_index). */
+ * (include/dpe_mvs.h) over the given views (the default runs the HIP kernel on gpu_index).
+ * Threading: the callback may be invoked from a thread other than the caller of dpe_run_pipeline
+ * (the pipeline fetches the next image's candidates on a worker thread while it fuses the current
+ * one), and never concurrently with itself: one call returns before the next begins. */
 typedef int (*dpe_fusion_fn)(void* user, const DpeFusionView* views, int n_views, int ref, const int* src, int ns,
                              int32_t* idx, float* val);
 

@@ -328,6 +328,45 @@ def test_failed_collective_aborts_peers(tmp_path, dense4):
     assert calls["allgather"] >= 1 and calls["abort"] >= 1, calls
 
 
+def recording_allgather(world, counts):
+    """An all-gather hook of one process standing for `world` ranks: records `count` and hands the
+    rank's own message back in every rank's slot."""
+    def hook(_user, send, count, recv):
+        counts.append(count)
+        for r in range(world):
+            C.memmove(C.byref(recv.contents, r * count * 4), send, count * 4)
+        return 0
+    return pipeline.ALLGATHER_FN(hook)
+
+
+@pytest.mark.parametrize("fusion", [False, True])
+def test_collective_sequence_is_pinned(tmp_path, dense4, fusion):
+    """The order, number and size of the host all-gathers of rank 0 of 2 with a runner hook: 64x48
+    images give 2 rounds of 4 passes (32x24, then 64x48), every pass round followed by one exchange
+    of nmax = 2 depth maps plus the status float; then the final status exchange; with fusion the
+    exchange of the final normals and pixel states (4 floats per pixel, 2 maps, the status float)."""
+    d = _copy(dense4, tmp_path, "seq")
+    o = pipeline.DpePipelineOptions()
+    pipeline.lib().dpe_pipeline_default_options(C.byref(o))
+    o.verbose = False
+    o.rank, o.world_size = 0, 2
+    counts = []
+    ag = recording_allgather(2, counts)
+    o.allgather = ag
+    runner = oracle_runner()
+    o.runner = C.cast(runner[0], C.c_void_p)
+    o.runner_user = C.cast(runner[1], C.c_void_p)
+    if fusion:
+        o.fusion = True
+        o.fusion_runner = C.cast(oracle.fusion_runner()[0], C.c_void_p)
+    rc = pipeline.lib().dpe_run_pipeline(d.encode(), C.byref(o))
+    assert rc == 0, pipeline.lib().dpe_pipeline_last_error().decode()
+    expected = [2 * 32 * 24 + 1] * 4 + [2 * 64 * 48 + 1] * 4 + [1]
+    if fusion:
+        expected.append(2 * 64 * 48 * 4 + 1)
+    assert counts == expected, counts
+
+
 def _rank_fail_main(rank, world, port, folder, mode, q):
     """One rank of a 2-rank run that must fail on every rank without hanging: `mode` "one_problem"
     (world_size > problems) or "rank1_runner" (rank 1's pass runner fails in its third pass)."""

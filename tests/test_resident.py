@@ -5,6 +5,7 @@ selected_views.bin round trip, main.cpp:439-446, DPE.cpp:826-911), rescales prio
 there and applies ProcessProblem's epilogue there.  The host-buffer path (any custom runner, here the
 oracle) is the checker: outputs must be byte-identical for both schedules, with the intermediate maps
 written, and with two ranks exchanging depth maps between passes."""
+import ctypes as C
 import os
 import shutil
 import socket
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 from DPE_MVS import _abi, pipeline, synthetic
-from test_pipeline import oracle_runner, _copy, OUTS
+from test_pipeline import oracle_runner, recording_allgather, _copy, OUTS
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +87,23 @@ def test_resident_two_ranks_match_one_rank_jacobi(tmp_path, dense4):
                                      verbose=False) == 0
     mp.start_processes(_rank_main, args=(2, _free_port(), two), nprocs=2, join=True, start_method="spawn")
     _same(_outputs(one, 4), _outputs(two, 4))
+
+
+def test_resident_collective_sequence_is_pinned(tmp_path, dense4):
+    """The host all-gathers of rank 0 of 2 with the HIP runner and no device hook: every pass round's
+    exchange is the status floats, then nmax = 2 packed depth maps (32x24 in round 0, 64x48 in round
+    1); after the passes the final status exchange."""
+    d = _copy(dense4, tmp_path, "seq")
+    o = pipeline.DpePipelineOptions()
+    pipeline.lib().dpe_pipeline_default_options(C.byref(o))
+    o.verbose = False
+    o.rank, o.world_size = 0, 2
+    counts = []
+    ag = recording_allgather(2, counts)
+    o.allgather = ag
+    rc = pipeline.lib().dpe_run_pipeline(d.encode(), C.byref(o))
+    assert rc == 0, pipeline.lib().dpe_pipeline_last_error().decode()
+    assert counts == [1, 2 * 32 * 24] * 4 + [1, 2 * 64 * 48] * 4 + [1], counts
 
 
 def _rank_main_devhook(rank, world, port, folder, fault, q):

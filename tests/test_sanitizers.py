@@ -1,7 +1,8 @@
 """SURVEY.md §5 "ASan/UBSan on the CPU transcription": the oracle's restatement of DPE.cu (every pass
 type, edges / labels / geometric consistency / WEAK pixels on) and the host pipeline's image code
 (JPEG decode, EdgeSegment and its restated OpenCV operations, the resamplers) run in executables
-built with -fsanitize=address,undefined -fno-sanitize-recover=all; any report aborts them."""
+built with -fsanitize=address,undefined -fno-sanitize-recover=all; any report aborts them.  The host
+pipeline's multi-rank protocol (RankGroup) runs the same way, and once more under -fsanitize=thread."""
 import os
 import subprocess
 
@@ -25,6 +26,17 @@ def test_oracle_under_asan_ubsan():
                        timeout=300, env=ENV)
     assert r.returncode == 0, r.stderr[-4000:]
     assert "runtime error" not in r.stderr and r.stdout.count(" ok ") == 3, r.stdout + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("binary", ["rank_group_asan", "rank_group_tsan"])
+def test_rank_group_under_sanitizers(binary):
+    """The multi-rank protocol of the host pipeline (host/rank_group.cpp) alone: three ranks on three
+    threads over an in-process all-gather, under ASan + UBSan and under TSan."""
+    _build("sanitize-ranks", os.path.join(ROOT, "dpe-mvs_amd"))
+    r = subprocess.run([os.path.join(ROOT, "dpe-mvs_amd", "bin", binary)], capture_output=True, text=True, timeout=120,
+                       env=dict(ENV, TSAN_OPTIONS="halt_on_error=1"))
+    assert r.returncode == 0, r.stdout + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "rank group sanitize ok" in r.stdout, r.stdout + r.stderr[-2000:]
 
 
 @pytest.mark.timeout(900)
