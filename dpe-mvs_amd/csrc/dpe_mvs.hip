@@ -22,6 +22,7 @@
 #include <utility>
 #include <vector>
 
+#include "pass_tables.h"
 #include "pass_kernels.h"
 #include "pass_refine.h"
 #include "pass_fusion.h"
@@ -252,6 +253,9 @@ static void compute_pass_constants(PassConst& pc) {
   pc.gn_shift = sri < 1 ? 1 : sri;
   pc.half_rows = std::min(pc.H, 2 * 16 * (((pc.H / 2) + 15) / 16));
   pc.weak_nn = pc.P.weak_radius >= 0 && pc.P.weak_increment > 0 ? (2 * pc.P.weak_radius) / pc.P.weak_increment + 1 : 0;
+  // float tables of per-pixel expressions that do not depend on the pixel (same bits, pass_tables.h)
+  for (int v = 1; v < pc.N; ++v) pc.base_len[v] = baseline_length(rc.c, pc.cams[v].c);
+  build_spat36(pc.P.sigma_spatial, pc.spat36);
 }
 
 #if DPE_POOL_STATS

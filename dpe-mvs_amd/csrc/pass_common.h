@@ -32,6 +32,8 @@ struct PassConst {
   int gn_shift;
   uint32_t gn_shift_m;       // floor(2^32 / gn_shift) (2^32 - 1 for 1): x % gn_shift as a multiply (gn_mod)
   int weak_nn;               // side of the weak sweep's neighbour patches, (2 weak_radius) / weak_increment + 1 (0 if radius < 0)
+  float base_len[DPE_MAX_IMAGES];   // |C_0 - C_v|, baseline_and_weights' summand (pass_tables.h; [0] unused)
+  float spat36[36];                 // spatial term of the 5/2 patch's bilateral weights (pass_tables.h)
   DpePatchMatchParams P;
   DpeCamera cams[DPE_MAX_IMAGES];
   ViewConst vc[DPE_MAX_IMAGES];
@@ -78,6 +80,14 @@ struct DevBufs {
 // DPE_UNCLAMPED=0 (A/B only): every fast Old-NCC patch keeps its tap clamps (taps_unclamped unused)
 #ifndef DPE_UNCLAMPED
 #define DPE_UNCLAMPED 1
+#endif
+// DPE_AB_OFF=<bits> (A/B only, same results): the set-up work outside the tap loops as it was before
+//   1  baseline lengths per pixel (not PassConst::base_len)     2  spatial weight term per tap (not ::spat36)
+//   4  the strong sweep's slot list, selected-view list and refinement hypotheses on one lane per pixel
+//   8  LocalRefine's hypothesis depths divided again on lane 0 of DepthToWeak (not read from its lanes)
+//  16  the strong pools' last rounds split as before: cost vectors up to 16 jobs, refinement never
+#ifndef DPE_AB_OFF
+#define DPE_AB_OFF 0
 #endif
 #define DPE_POOL_STATS (((DPE_DIAG) >> 4) & 1)
 #define DPE_PHASE_PROF ((DPE_DIAG) & 1)
@@ -282,17 +292,19 @@ DEV void refine_angle(const Rng& rs, uint32_t w_angles, int k, float pert, float
   const float a = (u32_to_uniform(rng_word(rs, w_angles + (uint32_t)k)) - 0.5f) * pert;
   d_sincosf(a, s, c);
 }
-// random_normal from its pre-flip normal
-DEV float4 random_normal_from(const DpeCamera& c, int px, int py, const float* n0, float depth) {
+// random_normal from its pre-flip normal and the view direction vd at its depth
+DEV float4 random_normal_vd(const float4& vd, const float* n0) {
   float4 n = make_float4(n0[0], n0[1], n0[2], 0.0f);
-  const float4 vd = view_direction(c, px, py, depth);
   if (n.x * vd.x + n.y * vd.y + n.z * vd.z > 0.0f) { n.x = -n.x; n.y = -n.y; n.z = -n.z; }
   normalize3(n);
   return n;
 }
-// perturbed_normal from the angles' sines and cosines sc = {s1, c1, s2, c2, s3, c3}
-DEV float4 perturbed_normal_from(const DpeCamera& c, int px, int py, const float4& normal, const float* sc) {
-  const float4 vd = view_direction(c, px, py, 1.0f);
+DEV float4 random_normal_from(const DpeCamera& c, int px, int py, const float* n0, float depth) {
+  return random_normal_vd(view_direction(c, px, py, depth), n0);
+}
+// perturbed_normal from the angles' sines and cosines sc = {s1, c1, s2, c2, s3, c3} and the view
+// direction vd at depth 1
+DEV float4 perturbed_normal_vd(const float4& vd, const float4& normal, const float* sc) {
   const float s1 = sc[0], c1 = sc[1], s2 = sc[2], c2 = sc[3], s3 = sc[4], c3 = sc[5];
   const float R0 = c2 * c3, R1 = c3 * s1 * s2 - c1 * s3, R2 = s1 * s3 + c1 * c3 * s2;
   const float R3 = c2 * s3, R4 = c1 * c3 + s1 * s2 * s3, R5 = c1 * s2 * s3 - c3 * s1;
@@ -303,6 +315,9 @@ DEV float4 perturbed_normal_from(const DpeCamera& c, int px, int py, const float
   if (np.x * vd.x + np.y * vd.y + np.z * vd.z >= 0.0f) np = normal;
   normalize3(np);
   return np;
+}
+DEV float4 perturbed_normal_from(const DpeCamera& c, int px, int py, const float4& normal, const float* sc) {
+  return perturbed_normal_vd(view_direction(c, px, py, 1.0f), normal, sc);
 }
 
 // ------------------------------------------------------------------------------ homography
@@ -679,6 +694,16 @@ DEV float bilateral_weight(int i, int j, float pix, float cpix, float ss, float 
   return d_expf(-sd / (2.0f * ss * ss) - cd / (2.0f * sc * sc));
 }
 
+// bilateral_weight of tap k = a * 6 + b of the default 5/2 patch (offsets -5 + 2a, -5 + 2b): the
+// spatial term -sd / (2 ss ss) comes from the pass table, the same bits (pass_tables.h)
+DEV float bilateral_weight36(const PassConst& pc, int k, float pix, float cpix) {
+  const float sc = pc.P.sigma_color;
+  if constexpr ((DPE_AB_OFF) & 2)
+    return bilateral_weight(-5 + 2 * (k / 6), -5 + 2 * (k % 6), pix, cpix, pc.P.sigma_spatial, sc);
+  const float cd = __builtin_fabsf(pix - cpix);
+  return d_expf(pc.spat36[k] - cd / (2.0f * sc * sc));
+}
+
 // The reference-patch half of ncc_finalize, computed once per patch: (1/s_w, s_ref/s_w, var_ref)
 // with the same operations, so ncc_finalize_pre(pre..., src sums) == ncc_finalize(ref sums, src sums).
 DEV void ncc_pre(float s_ref, float s_rr, float s_w, float& inv, float& mref, float& var_ref) {
@@ -793,7 +818,6 @@ struct Patch36 {
 };
 DEV void make_patch36(Patch36& P, const PassConst& pc, const DevBufs& B, int px, int py) {
   const int W = pc.W, Hh = pc.H;
-  const float ss = pc.P.sigma_spatial, sc = pc.P.sigma_color;
   const float rc = ref_texel(B.ref, W, Hh, px, py);
   P.px = px; P.py = py;
   float s_ref = 0, s_rr = 0, s_w = 0;
@@ -805,7 +829,7 @@ DEV void make_patch36(Patch36& P, const PassConst& pc, const DevBufs& B, int px,
     for (int b = 0; b < 6; ++b) {
       const int j = -5 + 2 * b;
       const float rp = ref_texel(B.ref, W, Hh, px + i, py + j);
-      const float w = bilateral_weight(i, j, rp, rc, ss, sc);
+      const float w = bilateral_weight36(pc, a * 6 + b, rp, rc);
       const float wr = w * rp;
       r_ref = r_ref + wr;
       r_rr = __builtin_fmaf(wr, rp, r_rr);

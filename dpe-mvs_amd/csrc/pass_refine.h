@@ -36,8 +36,7 @@ DEV void patch_lds_build(float* pw, const PassConst& pc, const DevBufs& B, int p
   for (int r = 0; r < R; ++r) {
     const int k = t + r * S;
     if (k >= 36) break;
-    const int i = -5 + 2 * (k / 6), j = -5 + 2 * (k % 6);
-    const float w = bilateral_weight(i, j, rp[r], rc, pc.P.sigma_spatial, pc.P.sigma_color);
+    const float w = bilateral_weight36(pc, k, rp[r], rc);
     pw[2 * k] = w;
     pw[2 * k + 1] = w * rp[r];
     pw[72 + k] = rp[r];
@@ -236,10 +235,13 @@ DEV void baseline_and_weights(const PassConst& pc, uint32_t sel, const uint8_t* 
     const int vi = si - 1;
     if (isSet(sel, vi)) {
       weight_normal += vw[vi];
-      const DpeCamera& cs = pc.cams[si];
-      const float d0 = c0.c[0] - cs.c[0], d1 = c0.c[1] - cs.c[1], d2 = c0.c[2] - cs.c[2];
-      const float tv = d0 * d0 + d1 * d1 + d2 * d2;
-      base_line += __builtin_sqrtf(tv);
+      if constexpr ((DPE_AB_OFF) & 1) {
+        const DpeCamera& cs = pc.cams[si];
+        const float d0 = c0.c[0] - cs.c[0], d1 = c0.c[1] - cs.c[1], d2 = c0.c[2] - cs.c[2];
+        const float tv = d0 * d0 + d1 * d1 + d2 * d2;
+        base_line += __builtin_sqrtf(tv);
+      } else
+        base_line += pc.base_len[si];              // the same sqrtf, once per pass (pass_tables.h)
       valid++;
     }
   }
@@ -310,13 +312,14 @@ __global__ void __launch_bounds__(64 * kBwD2W, kTapWaves) k_depth_to_weak(const 
   __shared__ float s_patch[kBwD2W][108];
   __shared__ float s_pc[kBwD2W][64];              // [0..60] cost curve, [61] LocalRefine's cost_now
   __shared__ float s_lr[kBwD2W][11];              // LocalRefine's hypothesis costs (pd -5..5)
+  __shared__ float s_ld[kBwD2W][11];              // and their depths
   const PassConst& pc = *pcp;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int W = pc.W, H = pc.H;
   const long pix = (long)xcd_remap(blockIdx.x, gridDim.x, B.xcd_rows * 16 * ((pc.W + kBwD2W - 1) / kBwD2W)) * kBwD2W + wave;
   if (pix >= (long)W * H) return;                 // wave-uniform
-  const int x = (int)(pix % W), y = (int)(pix / W);
-  const int center = (int)pix;
+  const int center = (int)pix;                    // < W * H, which fits an int (DevBufs are indexed by int)
+  const int x = center % W, y = center / W;       // 32-bit and wave-uniform: scalar, not a 64-bit VALU division
   const int min_margin = kD2WMargin;
   if (x < min_margin || y < min_margin || x >= W - min_margin || y >= H - min_margin) {
     if (lane == 0) B.weak[center] = DPE_UNKNOWN;
@@ -378,7 +381,10 @@ __global__ void __launch_bounds__(64 * kBwD2W, kTapWaves) k_depth_to_weak(const 
       lr /= weight_normal;
     }
     s_pc[wave][lane] = val;
-    if (LR && lane >= radius - 5 && lane <= radius + 5) s_lr[wave][lane - (radius - 5)] = lr;
+    if (LR && lane >= radius - 5 && lane <= radius + 5) {
+      s_lr[wave][lane - (radius - 5)] = lr;
+      s_ld[wave][lane - (radius - 5)] = p_depth;       // LocalRefine's hypothesis depth, the same expression
+    }
   }
   wave_sync();
   PHASE(3);
@@ -395,7 +401,7 @@ __global__ void __launch_bounds__(64 * kBwD2W, kTapWaves) k_depth_to_weak(const 
   // LocalRefine's choice (DPE.cu:2807-2834): the in-range hypothesis of least cost in pd order
   float min_cost = 2.0f, best_depth = od;
   for (int pd = -5; pd <= 5; ++pd) {
-    const float p_depth = c0.K[0] * base_line / (disp + (float)pd);
+    const float p_depth = ((DPE_AB_OFF) & 8) ? c0.K[0] * base_line / (disp + (float)pd) : s_ld[wave][pd + 5];
     if (p_depth < pc.P.depth_min || p_depth > pc.P.depth_max) continue;
     const float tcv = s_lr[wave][pd + 5];
     if (tcv < min_cost) { min_cost = tcv; best_depth = p_depth; }

@@ -15,6 +15,7 @@
 #include "pass_common.h"
 #include "pass_refine.h"
 #include "lds_layout.h"
+#include "pool_tail.h"
 
 namespace dpe {
 
@@ -369,7 +370,7 @@ DEV int acmh_candidate(const PassConst& pc, const float* __restrict__ costs, int
 }
 
 // ------------------------------------------------------------------------------ strong sweep
-constexpr int kTailJobs = 16;   // a last round of at most this many jobs is split by patch rows
+constexpr int kTailJobs = kTailLdsJobs;   // the carve's tail region holds 18 floats for each (pool_tail.h)
 // the strong sweep's LDS carve per wave (lds_layout.h: P pixels, C candidate lanes, nv source views)
 template <int P, int C> using StrongCarveT = lds::StrongCarve<P, C, kTailJobs>;
 __host__ __device__ inline int strong_lds_per_wave(int P, int C, int nv) {
@@ -390,6 +391,69 @@ DEV bool job_decode(const int* cnt, int j, int& p, int& r) {
   return false;
 }
 
+// One job of a pool's last round: the Old NCC of plane `pl` in view v at pixel (qx, qy), reference
+// patch `pw` with ncc_pre sums `sm`; its cost goes to *out.
+struct TailJob {
+  const float* pw; const float* sm; float* out;
+  int qx, qy, v;
+  float4 pl;
+};
+#if DPE_POOL_STATS   // tools/pool_stats.py: last rounds of pool k by lanes per job: [k][0] 6, [1] 3, [2] 2, [3] unsplit
+static __device__ unsigned long long g_tail[2][4];
+#define TAIL_STAT(k, npc) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_tail[k][(npc) == 6 ? 0 : (npc) == 3 ? 1 : (npc) == 2 ? 2 : 3], 1ull); } while (0)
+#else
+#define TAIL_STAT(k, npc) do {} while (0)
+#endif
+// A pool's last round of `tail` <= kTailMaxJobs jobs (fast patches), split by patch rows over the
+// lanes as pool_tail.h maps them; every lane of the wave calls this, converged.  job(t) describes
+// job t of the round.  A lane computes its rows with lds_row (the operations of lds_taps); the row
+// triplets are added to zero in row order as lds_taps adds them, so the cost has ncc_old_lds's bits.
+// With two lanes per job the first lane's partial (rows 0..2) goes to the second by a lane shuffle
+// and the second adds its rows 3..5 to it; otherwise all six triplets meet in LDS (`tb`, the carve's
+// tail region) and the job's last lane adds them.
+template <int U8, class JobFn>
+DEV void pool_tail_split(int tail, int lane, float* tb, const PassConst& pc, const DevBufs& B, JobFn job) {
+  const TailLane tl = tail_lane(tail, lane);
+  const bool two = tail_lanes_per_job(tail) == 2;
+  TailJob J = {};
+  bool outside = true;
+  float acc[3] = {0.0f, 0.0f, 0.0f};
+  if (tl.job >= 0) {
+    J = job(tl.job);
+    const Homog H = make_homography(pc, J.v, J.pl);
+    outside = center_outside(pc, J.v, H, J.qx, J.qy);
+    if (!outside) {
+      const bool fr = rcp_range_ok(H, (float)(J.qx - 5), (float)(J.qx + 5), (float)(J.qy - 5), (float)(J.qy + 5));
+      for (int a = tl.row0; a < tl.row0 + tl.rows; ++a) {
+        float r3[3];
+        if (fr) lds_row<U8, true>(J.pw, J.qx, J.qy, pc, B, J.v, H, a, r3);
+        else lds_row<U8, false>(J.pw, J.qx, J.qy, pc, B, J.v, H, a, r3);
+        if (two && !tl.last) { acc[0] += r3[0]; acc[1] += r3[1]; acc[2] += r3[2]; }
+        else { float* t3 = tb + tail_lds_slot(tail, tl.job, a); t3[0] = r3[0]; t3[1] = r3[1]; t3[2] = r3[2]; }
+      }
+    }
+  }
+  // the partial of the lane below (the same job's first lane when this is its second)
+  const int below = lane > 0 ? lane - 1 : 0;
+  const float p0 = __shfl(acc[0], below), p1 = __shfl(acc[1], below), p2 = __shfl(acc[2], below);
+  wave_sync();
+  if (tl.job >= 0 && tl.last) {
+    float cst = 2.0f;
+    if (outside) {
+      count_work(B, 1, 0);
+    } else {
+      count_work(B, 1, 36);
+      float s_src = two ? p0 : 0.0f, s_ss = two ? p1 : 0.0f, s_rs = two ? p2 : 0.0f;
+      for (int a = two ? 3 : 0; a < 6; ++a) {
+        const float* r3 = tb + tail_lds_slot(tail, tl.job, a);
+        s_src += r3[0]; s_ss += r3[1]; s_rs += r3[2];
+      }
+      cst = ncc_finalize_pre(J.sm[0], J.sm[1], J.sm[2], s_src, s_ss, s_rs);
+    }
+    *J.out = cst;
+  }
+}
+
 // waves per workgroup: 2 (4 before round 5's end; 2 fits the first half-sweep beside GenNeighbours
 // better: wall -0.6 ms together with DepthToWeak at 1, profiles/r05ao_ab_wgsize2.log)
 constexpr int kBwStrong = 2;
@@ -401,6 +465,13 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
   const int nlist = *nlist_p;
   constexpr int C = EDGE ? 16 : 8;
   constexpr int P = 64 / C;
+  // the sections that used to run on one lane per pixel (slot list, selected-view list, refinement
+  // hypotheses) spread over the pixel's lanes.  Not in the f32-texel instantiation, which has no
+  // registers to spare: its edge-mode kernel went from 0 to 8 B/lane of scratch with them.
+  constexpr bool kSpread = !((DPE_AB_OFF) & 4) && U8 != TEX_F32;
+  // likewise the wider pool tails (last rounds of 17..32 jobs split, and the refinement pool's split
+  // at all): 8 B/lane of scratch in the same kernel
+  constexpr bool kWideTails = !((DPE_AB_OFF) & 16) && U8 != TEX_F32;
   const PassConst& pc = *pcp;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int ps = lane / C, c = lane % C;
@@ -507,13 +578,29 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
   }
   wave_sync();
   PHASE(1);
-  if (c == 0) {
-    int n = 0;
-    if (active) {
-      for (int k = 0; k <= C; ++k) if (alias[k] == k) slots[n++] = k;
-      if (fast) patch_lds_pre(pw, sums_all[ps * 4 + 0], sums_all[ps * 4 + 1], sums_all[ps * 4 + 2]);
+  if constexpr (!kSpread) {
+    if (c == 0) {
+      int n = 0;
+      if (active) {
+        for (int k = 0; k <= C; ++k) if (alias[k] == k) slots[n++] = k;
+        if (fast) patch_lds_pre(pw, sums_all[ps * 4 + 0], sums_all[ps * 4 + 1], sums_all[ps * 4 + 2]);
+      }
+      misc[SC::MI_JOBS] = n;
     }
-    misc[SC::MI_JOBS] = n;
+  } else {
+    // the job slots (k with alias[k] == k, ascending): lane c owns slot c, and its place in the list
+    // is the number of owners below it among the pixel's lanes; slot C (the current plane) goes last
+    const bool own = active && alias[c] == c;
+    const uint32_t bits = (uint32_t)(__ballot(own) >> (lane - c)) & ((1u << C) - 1u);
+    if (own) slots[__popc(bits & ((1u << c) - 1u))] = c;
+    if (c == 0) {
+      int n = __popc(bits);
+      if (active) {
+        if (alias[C] == C) slots[n++] = C;
+        if (fast) patch_lds_pre(pw, sums_all[ps * 4 + 0], sums_all[ps * 4 + 1], sums_all[ps * 4 + 2]);
+      }
+      misc[SC::MI_JOBS] = n;
+    }
   }
   wave_sync();
   PHASE(2);
@@ -525,11 +612,20 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     for (int q = 0; q < P; ++q) { cnt[q] = ib_all[q * ibs + SC::IB_MISC + 1]; S += cnt[q]; }
     int q, r;
     const int total = S * nv, tail = total & 63;
-    // a last round with at most kTailJobs jobs: each job's 6 patch rows go to 64 / tail lanes (rows
-    // per lane 1 or 2), the row sums meet in LDS, and one lane per job adds them in row order
-    const bool split = fast && tail > 0 && tail <= kTailJobs;
+    // a last round of at most kTailMaxJobs jobs is split by patch rows (pool_tail_split)
+    constexpr int kMaxTail = kWideTails ? kTailMaxJobs : kTailLdsJobs;
+    const bool split = fast && tail > 0 && tail <= kMaxTail;
     POOL_STAT(0, total);
+    if (tail > 0) TAIL_STAT(0, split ? tail_lanes_per_job(tail) : 1);
     const int jend = split ? total - tail : total;
+    // cost-vector job j as the split last round sees it: slot list entry j % S of view j / S + 1
+    auto cv_job = [&](int j) {
+      job_decode<P>(cnt, j % S, q, r);
+      const int slot = ib_all[q * ibs + SC::ib_slots(nv) + r], v = j / S + 1;
+      const int cq = list[wbase + q];
+      return TailJob{pw_all + q * 108, sums_all + q * 4, cost_all + (q * (C + 1) + slot) * nv + v - 1,
+                     cq % W, cq / W, v, cpl_all[q * (C + 1) + slot]};
+    };
     for (int j = lane; j < jend; j += 64) {
       job_decode<P>(cnt, j % S, q, r);
       const int* iq = ib_all + q * ibs;
@@ -541,48 +637,7 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
       cost_all[(q * (C + 1) + slot) * nv + v - 1] =
           ncc_old_any<U8>(fast, pw_all + q * 108, sm[0], sm[1], sm[2], qx, qy, pc, B, v, pl);
     }
-    if (split) {
-      float* tb = wl + SC::tail(nv);                     // [job][row][3]
-      const int rpp = 64 / tail >= 6 ? 1 : 2, npc = 6 / rpp;            // rows per lane, lanes per job
-      if (lane < tail * npc) {
-        const int j = jend + lane / npc, a0 = (lane % npc) * rpp;
-        job_decode<P>(cnt, j % S, q, r);
-        const int slot = ib_all[q * ibs + SC::ib_slots(nv) + r], v = j / S + 1;
-        const int cq = list[wbase + q];
-        const int qx = cq % W, qy = cq / W;
-        const Homog H = make_homography(pc, v, cpl_all[q * (C + 1) + slot]);
-        if (!center_outside(pc, v, H, qx, qy)) {
-          const bool fr = rcp_range_ok(H, (float)(qx - 5), (float)(qx + 5), (float)(qy - 5), (float)(qy + 5));
-          for (int a = a0; a < a0 + rpp; ++a) {
-            float* r3 = tb + ((lane / npc) * 6 + a) * 3;
-            if (fr) lds_row<U8, true>(pw_all + q * 108, qx, qy, pc, B, v, H, a, r3);
-            else lds_row<U8, false>(pw_all + q * 108, qx, qy, pc, B, v, H, a, r3);
-          }
-        }
-      }
-      wave_sync();
-      if (lane < tail) {
-        const int j = jend + lane;
-        job_decode<P>(cnt, j % S, q, r);
-        const int slot = ib_all[q * ibs + SC::ib_slots(nv) + r], v = j / S + 1;
-        const int cq = list[wbase + q];
-        const Homog H = make_homography(pc, v, cpl_all[q * (C + 1) + slot]);
-        float cst = 2.0f;
-        if (center_outside(pc, v, H, cq % W, cq / W)) {
-          count_work(B, 1, 0);
-        } else {
-          count_work(B, 1, 36);
-          float s_src = 0, s_ss = 0, s_rs = 0;
-          for (int a = 0; a < 6; ++a) {
-            const float* r3 = tb + (lane * 6 + a) * 3;
-            s_src += r3[0]; s_ss += r3[1]; s_rs += r3[2];
-          }
-          const float* sm = sums_all + q * 4;
-          cst = ncc_finalize_pre(sm[0], sm[1], sm[2], s_src, s_ss, s_rs);
-        }
-        cost_all[(q * (C + 1) + slot) * nv + v - 1] = cst;
-      }
-    }
+    if (split) pool_tail_split<U8>(tail, lane, wl + SC::tail(nv), pc, B, [&](int t) { return cv_job(jend + t); });
   }
   wave_sync();
   PHASE(3);
@@ -654,14 +709,35 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
   view_sample_coop(sp, (int*)ref, nv, c, C, active, rs, vwl, B.vw + (size_t)center * DPE_MAX_IMAGES);
   PHASE(12);
   uint32_t tsv = 0; float wnorm = 0.0f;
-  if (c == 0) {
-    int ns = 0;
-    if (active) {
-      rng_seek(rs, 15);
-      for (int i = 0; i < nv; ++i) if (vwl[i] > 0) { setBit(tsv, i); wnorm += vwl[i]; sel_list[ns++] = i; }
-      sums_all[ps * 4 + 3] = wnorm;
+  if constexpr (!kSpread) {
+    if (c == 0) {
+      int ns = 0;
+      if (active) {
+        rng_seek(rs, 15);
+        for (int i = 0; i < nv; ++i) if (vwl[i] > 0) { setBit(tsv, i); wnorm += vwl[i]; sel_list[ns++] = i; }
+        sums_all[ps * 4 + 3] = wnorm;
+      }
+      misc[SC::MI_NSEL] = ns;
     }
-    misc[SC::MI_NSEL] = ns;
+  } else {
+    // selected views (vw > 0), C views per ballot; view v's place in sel_list is the number of
+    // selected views below it.  wnorm adds integers below 2^24: exact, so the order is free.
+    for (int v0 = 0; v0 < nv; v0 += C) {
+      const bool on = active && v0 + c < nv && vwl[v0 + c] > 0;
+      tsv |= ((uint32_t)(__ballot(on) >> (lane - c)) & ((1u << C) - 1u)) << v0;
+    }
+    for (int v = c; v < nv; v += C)
+      if (isSet(tsv, v)) sel_list[__popc(tsv & ((1u << v) - 1u))] = v;
+    if (c == 0) {
+      if (active) {
+        rng_seek(rs, 15);
+        int wi = 0;
+        for (int i = 0; i < nv; ++i) wi += vwl[i];
+        wnorm = (float)wi;
+        sums_all[ps * 4 + 3] = wnorm;
+      }
+      misc[SC::MI_NSEL] = __popc(tsv);
+    }
   }
   wave_sync();
   PHASE(7);
@@ -707,7 +783,31 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     }
   }
   wave_sync();
-  if (active && c == 0) {
+  if constexpr (kSpread) {
+    // lanes 0..4 of the pixel build one hypothesis each from lane 0's accepted plane and depth:
+    // (normal, depth) = (now, rand), (rand, now), (rand, rand), (perturbed, now), (now, perturbed).
+    // Lanes 1..3 share one view_direction call (at depth_now, or at 1 for the perturbed normal).
+    const int l0 = lane - c;
+    const float4 pn = make_float4(__shfl(pnow.x, l0), __shfl(pnow.y, l0), __shfl(pnow.z, l0), __shfl(pnow.w, l0));
+    const float dn = __shfl(depth_now, l0);
+    if (active && c < 5) {
+      float4 h = pn;
+      if (c >= 1 && c <= 3) {
+        const float4 vd = view_direction(c0, x, y, c == 3 ? 1.0f : dn);
+        h = c == 3 ? perturbed_normal_vd(vd, pn, rnd + 5) : random_normal_vd(vd, rnd + 1);
+      }
+      float dep = dn;
+      if (c == 0 || c == 2) {
+        const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
+        dep = rnd[0] * (dmax - dmin) + dmin;
+      } else if (c == 4) {
+        const float dminp = (1 - 0.02f) * dn, dmaxp = (1 + 0.02f) * dn;
+        dep = rnd[4] * (dmaxp - dminp) + dminp;
+      }
+      h.w = dist2origin(c0, x, y, dep, h);
+      hyp[c] = h;
+    }
+  } else if (active && c == 0) {
     const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
     const float depth_rand = rnd[0] * (dmax - dmin) + dmin;
     const float4 prand = random_normal_from(c0, x, y, rnd + 1, depth_now);
@@ -731,7 +831,16 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     for (int q = 0; q < P; ++q) cnt[q] = 5 * ib_all[q * ibs + SC::IB_MISC];
     POOL_STAT(1, [&] { int t = 0; for (int q = 0; q < P; ++q) t += cnt[q]; return t; }());
     int q, r;
-    for (int j = lane; job_decode<P>(cnt, j, q, r); j += 64) {
+    // a last round of at most kTailMaxJobs jobs is split by patch rows, as in the cost-vector pool
+    // (whose LDS tail region is free again here)
+    int total = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) total += cnt[p];
+    const int tail = total & 63;
+    const bool split = kWideTails && fast && tail > 0 && tail <= kTailMaxJobs;
+    if (tail > 0) TAIL_STAT(1, split ? tail_lanes_per_job(tail) : 1);
+    const int jend = split ? total - tail : total;
+    for (int j = lane; j < jend && job_decode<P>(cnt, j, q, r); j += 64) {
       const int* iq = ib_all + q * ibs;
       const int h = r % 5, k = r / 5;                      // the 5 hypotheses of one view adjacent
       const int cq = list[wbase + q];
@@ -739,6 +848,14 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
       ref_all[(q * 5 + h) * nv + k] = ncc_old_any<U8>(fast, pw_all + q * 108, sm[0], sm[1], sm[2], cq % W, cq / W, pc,
                                                       B, iq[SC::IB_SEL + k] + 1, hyp_all[q * 5 + h]);
     }
+    if (split)
+      pool_tail_split<U8>(tail, lane, wl + SC::tail(nv), pc, B, [&](int t) {
+        job_decode<P>(cnt, jend + t, q, r);
+        const int h = r % 5, k = r / 5;
+        const int cq = list[wbase + q];
+        return TailJob{pw_all + q * 108, sums_all + q * 4, ref_all + (q * 5 + h) * nv + k,
+                       cq % W, cq / W, ib_all[q * ibs + SC::IB_SEL + k] + 1, hyp_all[q * 5 + h]};
+      });
   }
   wave_sync();
   PHASE(10);

@@ -51,6 +51,12 @@ extern "C" void dpe_dbg_pool_stats_f32(unsigned long long out[24], int reset) {
   if (reset) { unsigned long long z[24] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_pool), z, sizeof(z)); }
 }
 #endif
+#if DPE_POOL_STATS
+extern "C" void dpe_dbg_tail_stats_f32(unsigned long long out[8], int reset) {
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_tail), sizeof(dpe::g_tail));
+  if (reset) { unsigned long long z[8] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_tail), z, sizeof(z)); }
+}
+#endif
 #if DPE_LINE_STATS
 extern "C" void dpe_dbg_line_stats_f32(unsigned long long out[16], int reset) {
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_lstat), sizeof(dpe::g_lstat));

@@ -62,4 +62,8 @@ for path in libs:
     best = min(res[path], key=lambda t: t[0])
     d = {k: round(v, 2) for k, v in zip(names, best)}
     d["wall_ms"] = round(min(wall[path]), 2)
+    # every round, so that a difference can be set against a library's own round-to-round spread
+    d["wall_rounds_ms"] = [round(w, 2) for w in wall[path]]
+    d["wall_spread_ms"] = round(max(wall[path]) - min(wall[path]), 2)
+    d["total_rounds_ms"] = [round(t[0], 2) for t in res[path]]
     print(os.path.basename(path), json.dumps(d), flush=True)

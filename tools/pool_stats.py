@@ -44,4 +44,20 @@ for k in range(6):
     if waves:
         print(f"{NAMES[k]:26s} waves {waves:10d}  jobs/wave {jobs / waves:7.1f}  rounds/wave {rounds / waves:5.2f}  "
               f"lanes busy per round {jobs / max(rounds, 1):5.1f} of 64", flush=True)
+# last rounds of the strong sweep's two pools by split width (csrc/pool_tail.h): a round split over n
+# lanes per job runs 6 / n of the 6 patch rows, so it counts as 1 / n of a round
+tails = [0] * 8
+tbuf = (C.c_ulonglong * 8)()
+for fn in ("dpe_dbg_tail_stats_tap", "dpe_dbg_tail_stats_f32"):
+    if hasattr(lib, fn):
+        getattr(lib, fn)(tbuf, 1)
+        for k in range(8):
+            tails[k] += tbuf[k]
+for k in range(2):
+    n6, n3, n2, n1 = tails[4 * k: 4 * k + 4]
+    jobs, rounds, waves = tot[3 * k: 3 * k + 3]
+    if waves:
+        eff = rounds - n6 * (1 - 1 / 6) - n3 * (1 - 1 / 3) - n2 * (1 - 1 / 2)
+        print(f"{NAMES[k]:26s} last rounds: 6 lanes/job {n6:9d}  3 lanes/job {n3:9d}  2 lanes/job {n2:9d}  unsplit {n1:9d}  "
+              f"rounds/wave with split rounds by their rows {eff / waves:5.2f}", flush=True)
 lib.dpe_destroy(ctx)
