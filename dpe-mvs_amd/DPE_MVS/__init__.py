@@ -12,11 +12,14 @@ from __future__ import annotations
 
 
 def dpe_mvs(dense_folder: str, gpu_index: int = 0, verbose: bool = True, fusion: bool = False, viz: bool = False,
-            depth: bool = True, normal: bool = False, weak: bool = False, edge: bool = False) -> int:
-    """Run the DPE-MVS pipeline from Python (same signature as the reference's DPE_MVS.dpe_mvs,
-    src/DPE_MVS/__init__.py:6-17): the C++ host pipeline through the pybind11 module `_dpe`."""
+            depth: bool = True, normal: bool = False, weak: bool = False, edge: bool = False, *,
+            fusion_mode: str = "eth3d") -> int:
+    """Run the DPE-MVS pipeline from Python (the nine arguments of the reference's DPE_MVS.dpe_mvs,
+    src/DPE_MVS/__init__.py:6-17, in their positions): the C++ host pipeline through the pybind11
+    module `_dpe`.  `fusion_mode` (keyword only): "eth3d" = RunFusion, what the reference's pipeline
+    calls; "tat_intermediate" / "tat_advanced" = its two Tanks-and-Temples fusions."""
     from ._dpe import dpe_mvs as _native
-    return _native(dense_folder, gpu_index, verbose, fusion, viz, depth, normal, weak, edge)
+    return _native(dense_folder, gpu_index, verbose, fusion, viz, depth, normal, weak, edge, fusion_mode=fusion_mode)
 
 
 __all__ = ["dpe_mvs", "native", "synthetic", "pipeline"]

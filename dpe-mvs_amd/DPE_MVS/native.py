@@ -20,6 +20,7 @@ EXPORTED = [
     "dpe_pm_execute", "dpe_pm_fetch", "dpe_pm_run", "dpe_pm_device_planes", "dpe_pm_export_depth",
     "dpe_pm_last_timings", "dpe_set_timing", "dpe_set_counting", "dpe_pm_last_counts",
     "dpe_fusion_stage", "dpe_fusion_candidates",
+    "dpe_fusion_tat_begin", "dpe_fusion_tat_image", "dpe_fusion_tat_wait", "dpe_fusion_tat_mask",
     "dpe_pm_stage_resident", "dpe_state_save", "dpe_state_snapshot", "dpe_state_fetch", "dpe_state_export_depth",
     "dpe_state_import_depth", "dpe_state_clear", "dpe_device_buffer", "dpe_device_copy",
     "dpe_resize_linear", "dpe_resize_u8", "dpe_canny", "dpe_roberts_threshold",
@@ -71,6 +72,15 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_fusion_stage.restype = C.c_int
     lib.dpe_fusion_candidates.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.dpe_fusion_candidates.restype = C.c_int
+    lib.dpe_fusion_tat_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dpe_fusion_tat_begin.restype = C.c_int
+    lib.dpe_fusion_tat_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dpe_fusion_tat_image.restype = C.c_int
+    lib.dpe_fusion_tat_wait.argtypes = [C.c_void_p]
+    lib.dpe_fusion_tat_wait.restype = C.c_int
+    lib.dpe_fusion_tat_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.dpe_fusion_tat_mask.restype = C.c_int
     lib.dpe_resize_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
     lib.dpe_resize_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
     lib.dpe_canny.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]

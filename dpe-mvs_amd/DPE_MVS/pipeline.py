@@ -45,7 +45,21 @@ class DpePipelineOptions(C.Structure):
         ("max_iterations", C.c_int), ("photometric_only", C.c_bool),
         ("allgather_device", C.c_void_p), ("allgather_device_user", C.c_void_p),
         ("abort_collectives", C.c_void_p), ("abort_user", C.c_void_p),
+        ("fusion_mode", C.c_int),
     ]
+
+
+FUSION_ETH3D, FUSION_TAT_INTERMEDIATE, FUSION_TAT_ADVANCED = 0, 1, 2
+FUSION_MODES = {"eth3d": FUSION_ETH3D, "tat_intermediate": FUSION_TAT_INTERMEDIATE, "tat_advanced": FUSION_TAT_ADVANCED}
+
+
+class DpeFusedPoint(C.Structure):   # include/dpe_mvs.h
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("b", C.c_float), ("g", C.c_float), ("r", C.c_float)]
+
+
+class DpeHostTatView(C.Structure):   # include/dpe_host.h
+    _fields_ = [("image_id", C.c_int), ("src_ids", C.c_void_p), ("n_src", C.c_int), ("view", _abi.DpeFusionView),
+                ("bgr", C.c_void_p), ("block", C.c_void_p), ("mask", C.c_void_p)]
 
 
 class PipelineError(RuntimeError):
@@ -85,6 +99,10 @@ def lib() -> C.CDLL:
                                                     C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dpe_host_viz_render.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                           C.c_void_p]
+        L.dpe_host_fusion_tat_run.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.dpe_host_fusion_tat_run.restype = C.c_longlong
+        L.dpe_host_fusion_tat_thresholds.argtypes = [C.c_void_p, C.c_int]
+        L.dpe_host_fusion_tat_angle_test.argtypes = [C.c_float, C.c_int]
         _lib = L
     return _lib
 
@@ -183,6 +201,65 @@ def viz_render(kind: int, depth=None, normal=None, weak=None, dmin: float = 0, d
     if lib().dpe_host_viz_render(kind, w, h, ptr(d), ptr(n), ptr(k), dmin, dmax, out.ctypes.data) != 0:
         raise PipelineError("viz_render failed")
     return out
+
+
+# ------------------------------------------------------------------------------ Tanks-and-Temples fusions (C++, fusion_tat.cpp)
+def _fusion_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in FUSION_MODES:
+            raise ValueError(f"fusion_mode must be one of {sorted(FUSION_MODES)}, not {mode!r}")
+        return FUSION_MODES[mode]
+    return int(mode)
+
+
+def fusion_tat_run(views, mode, gpu_index: int = -1, cap: int | None = None):
+    """RunFusion_TAT_Intermediate / RunFusion_TAT_advanced (DPE.cpp:1372-1689) over `views`: dicts with
+    image_id, src_ids, cam (DpeCamera), depth f32 [H, W], normal f32 [H, W, 3], bgr u8 [H, W, 3], block
+    u8 [H, W] or None, in fusion order.  gpu_index < 0: the serial loops as the reference writes them;
+    else the device path of the pipeline on that GPU.  `cap`: points to return at most (default: all).
+    Returns (points f32 [min(n, cap), 6]: x y z b g r, masks: one u8 [H, W] per view -- filled by the
+    serial loops only --, n)."""
+    arr = (DpeHostTatView * len(views))()
+    keep, masks, total = [], [], 0
+    for k, v in enumerate(views):
+        d = np.ascontiguousarray(v["depth"], np.float32)
+        n = np.ascontiguousarray(v["normal"], np.float32)
+        c = np.ascontiguousarray(v["bgr"], np.uint8)
+        b = None if v.get("block") is None else np.ascontiguousarray(v["block"], np.uint8)
+        s = np.ascontiguousarray(v["src_ids"], np.int32)
+        m = np.zeros(d.shape, np.uint8)
+        keep += [d, n, c, b, s]
+        masks.append(m)
+        total += d.size
+        arr[k] = DpeHostTatView(int(v["image_id"]), s.ctypes.data, len(s),
+                                _abi.DpeFusionView(d.shape[1], d.shape[0], v["cam"], d.ctypes.data, n.ctypes.data),
+                                c.ctypes.data, None if b is None else b.ctypes.data, m.ctypes.data)
+    cap = total if cap is None else min(cap, total)
+    out = np.empty((max(cap, 1), 6), np.float32)
+    cnt = lib().dpe_host_fusion_tat_run(_fusion_mode(mode), arr, len(views), gpu_index, out.ctypes.data, cap)
+    if cnt < 0:
+        raise PipelineError("fusion_tat_run failed (bad argument, or no such device)")
+    return out[:min(cnt, cap)].copy(), masks, cnt
+
+
+def fusion_tat_serial(views, mode):
+    """The serial loops (the yardstick of the device path): (points f32 [n, 6], masks)."""
+    pts, masks, _ = fusion_tat_run(views, mode)
+    return pts, masks
+
+
+def fusion_tat_thresholds(n: int = 32) -> np.ndarray:
+    """D[k], k = 2..n-1: the smallest float dot product in [-1, 1] that passes the Intermediate angle
+    test at k (entries 0 and 1 are unused)."""
+    D = np.zeros(n, np.float32)
+    if lib().dpe_host_fusion_tat_thresholds(D.ctypes.data, n) != 0:
+        raise PipelineError("the angle threshold table does not verify")
+    return D
+
+
+def fusion_tat_angle_test(dot: float, k: int) -> bool:
+    """The serial loop's angle test at k: GetAngle(dot) < k * angle_grad + angle_base."""
+    return bool(lib().dpe_host_fusion_tat_angle_test(float(dot), k))
 
 
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)
@@ -368,7 +445,8 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
                      viz: bool = False, depth: bool = True, normal: bool = False, weak: bool = False,
                      edge: bool = False, schedule: str = "reference", dist=None, runner=None,
                      base_seed: int = 0x5EED, keep_intermediate: bool = False, fusion_runner=None,
-                     max_iterations: int = 0, photometric_only: bool = False, allgather_device=None) -> int:
+                     max_iterations: int = 0, photometric_only: bool = False, allgather_device=None,
+                     fusion_mode="eth3d") -> int:
     """RunDPEPipeline (main.cpp:474) through libdpe_host.  `dist`: an initialised torch.distributed
     (one process per GPU; problems split in contiguous blocks, depth maps all-gathered per pass).
     `runner`: (C function pointer, user pointer) of a dpe_pass_runner_fn; default the HIP library.
@@ -376,9 +454,13 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
     `max_iterations` (0 = the reference's 3) and `photometric_only` (no geometric passes) are the
     schedule knobs of BASELINE configs 1 and 2.  `allgather_device`: a Python callable
     (send_ptr, count, recv_ptr) -> int used as the device all-gather hook instead of the torch "nccl"
-    one (tests drive the device exchange path through it on one GPU)."""
+    one (tests drive the device exchange path through it on one GPU).  `fusion_mode`: "eth3d"
+    (RunFusion, the default), "tat_intermediate" or "tat_advanced" (the Tanks-and-Temples fusions, one
+    image at a time on the GPU; with a `fusion_runner` their serial loops on the host), or the integer
+    of DpePipelineOptions.fusion_mode."""
     o = DpePipelineOptions()
     lib().dpe_pipeline_default_options(C.byref(o))
+    o.fusion_mode = _fusion_mode(fusion_mode)
     o.gpu_index = gpu_index
     o.verbose, o.fusion, o.viz, o.depth, o.normal, o.weak, o.edge = verbose, fusion, viz, depth, normal, weak, edge
     o.schedule = {"reference": SCHEDULE_REFERENCE, "jacobi": SCHEDULE_JACOBI}[schedule]
@@ -413,7 +495,8 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
 
 
 def dpe_mvs(dense_folder: str, gpu_index: int = 0, verbose: bool = True, fusion: bool = False, viz: bool = False,
-            depth: bool = True, normal: bool = False, weak: bool = False, edge: bool = False) -> int:
+            depth: bool = True, normal: bool = False, weak: bool = False, edge: bool = False, *,
+            fusion_mode: str = "eth3d") -> int:
     """DPE_MVS.dpe_mvs through the pybind11 module (csrc/bindings.cpp:31-43 equivalent)."""
     from ._dpe import dpe_mvs as _native
-    return _native(dense_folder, gpu_index, verbose, fusion, viz, depth, normal, weak, edge)
+    return _native(dense_folder, gpu_index, verbose, fusion, viz, depth, normal, weak, edge, fusion_mode=fusion_mode)

@@ -13,6 +13,7 @@
 
 #include "pass_common.h"
 #include "pass_fusion.h"
+#include "pass_fusion_tat.h"
 
 namespace {
 
@@ -108,6 +109,7 @@ struct DpeContext {
   Stream aux;                        // GenNeighbours beside the first strong half-sweep
   Event ev_fork, ev_join, ev_ei;
   Event ev_done;                     // end of the last dpe_pm_execute's work on its stream
+  Event ev_tat;                      // end of the last copy-out of dpe_fusion_tat_image (on `aux`)
   Event ev_start;                    // timing: start of the pass
   std::vector<Event> ev;             // timing: (start, end) per launch class slot
   std::mutex viz_mu;                 // guards viz_ev (dpe_state_render_wait runs on other host threads)
@@ -176,6 +178,18 @@ struct DpeContext {
   DevArr<int32_t> fz_idx;
   DevArr<float> fz_val;
   int fz_n = 0;
+  // the Tanks-and-Temples fusions (dpe_fusion_tat_begin / dpe_fusion_tat_image), over the staged views
+  std::vector<DevArr<uint8_t>> tat_bgr, tat_block, tat_mask;
+  DevArr<dpe::TatViewDev> tat_views;
+  bool tat_ready = false;
+  DevArr<float> tat_dthr;            // dot-product thresholds of the angle test, by k
+  DevArr<int> tat_last, tat_agg;     // per (view, pixel) last hit of the block / per (view, chunk) carry
+  DevArr<int> tat_cnt, tat_tot;      // fused pixels per chunk -> offsets; the image's total
+  DevArr<uint8_t> tat_emit;
+  DevArr<dpe::TatPoint> tat_rec;     // per pixel: the point it contributes
+  DevArr<dpe::TatPoint> tat_out[2];  // compacted points, double-buffered: the copy-out of one image
+  int tat_turn = 0;                  //   runs on `aux` beside the kernels of the next
+  bool tat_copying = false;          // ev_tat recorded and not yet waited for
   // viz medium results (dpe_state_render*): scratch, allocated on first use
   DevArr<uint8_t> viz_bgr;           // the rendered picture
   DevArr<int16_t> viz_blocks;        // its quantised JPEG blocks

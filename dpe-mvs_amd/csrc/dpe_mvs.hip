@@ -26,6 +26,7 @@
 #include "pass_kernels.h"
 #include "pass_refine.h"
 #include "pass_fusion.h"
+#include "pass_fusion_tat.h"
 #include "pass_sweep.h"
 #include "pass_edges.h"
 #include "pass_viz.h"
@@ -111,7 +112,7 @@ DpeContext* dpe_create(int device) {
   c->device = device;
   if (c->stream.create() != hipSuccess) { g_err = "dpe_create: stream"; return nullptr; }
   if (c->aux.create() != hipSuccess || c->ev_fork.create() != hipSuccess || c->ev_join.create() != hipSuccess ||
-      c->ev_ei.create() != hipSuccess || c->ev_done.create() != hipSuccess ||
+      c->ev_ei.create() != hipSuccess || c->ev_done.create() != hipSuccess || c->ev_tat.create() != hipSuccess ||
       c->ev_start.create(hipEventDefault) != hipSuccess) {
     g_err = "dpe_create: aux stream";
     return nullptr;
@@ -138,7 +139,12 @@ DpeContext* dpe_create(int device) {
 //     and the JPEG blocks when they ran on a caller's stream (publish_foreign); the two exports only
 //     read, and dpe_state_render synchronises its stream itself.
 //   * The EdgeSegment stages and the fusion calls use the context's stream and scratch of their own,
-//     and synchronise the stream before they return.
+//     and synchronise the stream before they return.  dpe_fusion_tat_image does so too (its kernels
+//     have finished when it returns) and then leaves ONE copy in flight: the points of the image, on
+//     the aux stream into the caller's buffer, with `ev_tat` recorded behind it.  The next
+//     dpe_fusion_tat_image launches its kernels first (they write the other half of the double
+//     buffer), then waits for that event before it enqueues its own copy; dpe_fusion_tat_begin,
+//     dpe_fusion_tat_wait and dpe_destroy (which synchronises aux) wait for it as well.
 
 // Host-waits for the work of the last dpe_pm_execute, which may have been enqueued on a caller
 // stream: staging, fetching and freeing must not overwrite or release buffers that pass still uses.
@@ -1499,6 +1505,7 @@ extern "C" int dpe_jpeg_blocks_device(DpeContext* c, const uint8_t* host_bgr, in
 
 extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n) {
   TRY(enter(c, views && n >= 1, "dpe_fusion_stage: bad argument"));
+  c->tat_ready = false;   // the colours and masks of dpe_fusion_tat_begin belong to the views staged before
   c->fz_depth.resize(n); c->fz_normal.resize(n); c->fz_host.assign(n, FusionViewDev{});
   std::vector<DpeCamera> cams(n);
   for (int i = 0; i < n; ++i) {
@@ -1539,6 +1546,123 @@ extern "C" int dpe_fusion_candidates(DpeContext* c, int ref, const int* src, int
   HIPC(hipMemcpyAsync(idx, c->fz_idx.p, L * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPC(hipMemcpyAsync(val, c->fz_val.p, L * ns * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
+  return DPE_OK;
+}
+
+// host-waits for the copy-out of the last dpe_fusion_tat_image
+static hipError_t tat_wait_copy(DpeContext* c) {
+  hipError_t e = hipSuccess;
+  if (c->tat_copying) { e = hipEventSynchronize(c->ev_tat); c->tat_copying = false; }
+  return e;
+}
+
+extern "C" int dpe_fusion_tat_begin(DpeContext* c, const uint8_t* const* bgr, const uint8_t* const* block) {
+  TRY(enter(c, bgr != nullptr, "dpe_fusion_tat_begin: bad argument"));
+  if (c->fz_n < 1) { g_err = "dpe_fusion_tat_begin: nothing staged"; return DPE_ERR_STATE; }
+  const int n = c->fz_n;
+  for (int i = 0; i < n; ++i)
+    if (!bgr[i]) { g_err = "dpe_fusion_tat_begin: missing colour image"; return DPE_ERR_ARG; }
+  HIPC(host_wait(c));
+  HIPC(tat_wait_copy(c));
+  c->tat_ready = false;
+  c->tat_bgr.resize(n); c->tat_block.resize(n); c->tat_mask.resize(n);
+  std::vector<TatViewDev> tv(n);
+  for (int i = 0; i < n; ++i) {
+    const size_t L = (size_t)c->fz_host[i].w * c->fz_host[i].h;
+    HIPC(c->tat_bgr[i].ensure(3 * L));
+    HIPC(c->tat_mask[i].ensure(L));
+    HIPC(hipMemcpyAsync(c->tat_bgr[i].p, bgr[i], 3 * L, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(c->tat_mask[i].p, 0, L, c->stream));
+    const bool blk = block && block[i];
+    if (blk) {
+      HIPC(c->tat_block[i].ensure(L));
+      HIPC(hipMemcpyAsync(c->tat_block[i].p, block[i], L, hipMemcpyHostToDevice, c->stream));
+    }
+    tv[i] = TatViewDev{c->tat_bgr[i].p, blk ? c->tat_block[i].p : nullptr, c->tat_mask[i].p};
+  }
+  HIPC(c->tat_views.ensure(n));
+  HIPC(hipMemcpyAsync(c->tat_views.p, tv.data(), n * sizeof(TatViewDev), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  c->tat_ready = true;
+  return DPE_OK;
+}
+
+extern "C" int dpe_fusion_tat_image(DpeContext* c, int mode, int ref, const int* src, int ns, const float* dot_thresholds,
+                                    DpeFusedPoint* out, size_t cap, size_t* n_out) {
+  static_assert(sizeof(DpeFusedPoint) == sizeof(TatPoint), "DpeFusedPoint layout");
+  TRY(enter(c, n_out && ns >= 0 && (ns == 0 || src) && (out || cap == 0), "dpe_fusion_tat_image: bad argument"));
+  if (!c->tat_ready) { g_err = "dpe_fusion_tat_image: dpe_fusion_tat_begin has not run"; return DPE_ERR_STATE; }
+  if (mode != DPE_FUSION_TAT_INTERMEDIATE && mode != DPE_FUSION_TAT_ADVANCED) { g_err = "dpe_fusion_tat_image: bad mode"; return DPE_ERR_ARG; }
+  if (ref < 0 || ref >= c->fz_n) { g_err = "dpe_fusion_tat_image: bad reference view"; return DPE_ERR_ARG; }
+  if (ns > kTatMaxSrc) { g_err = "dpe_fusion_tat_image: more than 31 source views"; return DPE_ERR_TOO_MANY; }
+  for (int j = 0; j < ns; ++j) {
+    if (src[j] < 0 || src[j] >= c->fz_n) { g_err = "dpe_fusion_tat_image: bad source view"; return DPE_ERR_ARG; }
+    // the kernels read the masks of the source views while they write the reference view's
+    if (src[j] == ref) { g_err = "dpe_fusion_tat_image: the reference view is among its sources"; return DPE_ERR_ARG; }
+  }
+  if (mode == DPE_FUSION_TAT_INTERMEDIATE && ns >= 2 && !dot_thresholds) { g_err = "dpe_fusion_tat_image: no thresholds"; return DPE_ERR_ARG; }
+  *n_out = 0;
+  if (ns < 2) {   // the k loop starts at 2 (DPE.cpp:1504): no point, no mask
+    HIPC(tat_wait_copy(c));
+    return DPE_OK;
+  }
+  const size_t L = (size_t)c->fz_host[ref].w * c->fz_host[ref].h;
+  const int nch = (int)((L + kTatChunk - 1) / kTatChunk);
+  DevArr<TatPoint>& dout = c->tat_out[c->tat_turn];
+  HIPC(c->fz_src.ensure(ns));
+  HIPC(c->tat_dthr.ensure(kTatMaxSrc + 1));
+  HIPC(c->tat_last.ensure(L * ns));
+  HIPC(c->tat_agg.ensure((size_t)nch * ns));
+  HIPC(c->tat_cnt.ensure(nch));
+  HIPC(c->tat_tot.ensure(1));
+  HIPC(c->tat_emit.ensure(L));
+  HIPC(c->tat_rec.ensure(L));
+  HIPC(dout.ensure(L));
+  hipStream_t s;
+  HIPC(enqueue_stream(c, nullptr, &s));
+  float dthr[kTatMaxSrc + 1] = {0};
+  if (mode == DPE_FUSION_TAT_INTERMEDIATE)
+    for (int k = 2; k <= ns; ++k) dthr[k] = dot_thresholds[k];
+  // (the stream is synchronised below, before `dthr` and the caller's `src` go out of scope)
+  HIPC(hipMemcpyAsync(c->fz_src.p, src, ns * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(c->tat_dthr.p, dthr, sizeof(dthr), hipMemcpyHostToDevice, s));
+  k_tat_hit_scan<<<nch, kTatChunk, 0, s>>>(c->fz_cams.p, c->fz_views.p, c->tat_views.p, ref, c->fz_src.p, ns, nch,
+                                          c->tat_last.p, c->tat_agg.p);
+  k_tat_chunk_carry<<<ns, 256, 0, s>>>(nch, c->tat_agg.p);
+  k_tat_decide<<<nch, kTatChunk, 0, s>>>(c->fz_cams.p, c->fz_views.p, c->tat_views.p, ref, c->fz_src.p, ns, nch, mode,
+                                        c->tat_dthr.p, c->tat_last.p, c->tat_agg.p, c->tat_rec.p, c->tat_emit.p,
+                                        c->tat_cnt.p);
+  k_tat_offsets<<<1, 256, 0, s>>>(nch, c->tat_cnt.p, c->tat_tot.p);
+  k_tat_fill<<<nch, kTatChunk, 0, s>>>((int)L, c->tat_emit.p, c->tat_rec.p, c->tat_cnt.p, dout.p);
+  HIPC(hipGetLastError());
+  int total = 0;
+  HIPC(hipMemcpyAsync(&total, c->tat_tot.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  HIPC(tat_wait_copy(c));   // the copy-out of the image before ran beside these kernels
+  if (total < 0 || (size_t)total > L) { g_err = "dpe_fusion_tat_image: bad point count"; return DPE_ERR_STATE; }
+  *n_out = (size_t)total;
+  if ((size_t)total > cap) { g_err = "dpe_fusion_tat_image: output buffer too small"; return DPE_ERR_ARG; }
+  if (total > 0) {
+    HIPC(hipMemcpyAsync(out, dout.p, (size_t)total * sizeof(TatPoint), hipMemcpyDeviceToHost, c->aux));
+    HIPC(hipEventRecord(c->ev_tat, c->aux));
+    c->tat_copying = true;
+    c->tat_turn ^= 1;
+  }
+  return DPE_OK;
+}
+
+extern "C" int dpe_fusion_tat_wait(DpeContext* c) {
+  TRY(enter(c, true, "dpe_fusion_tat_wait: null context"));
+  HIPC(tat_wait_copy(c));
+  return DPE_OK;
+}
+
+extern "C" int dpe_fusion_tat_mask(DpeContext* c, int view, uint8_t* mask) {
+  TRY(enter(c, mask != nullptr, "dpe_fusion_tat_mask: bad argument"));
+  if (!c->tat_ready) { g_err = "dpe_fusion_tat_mask: dpe_fusion_tat_begin has not run"; return DPE_ERR_STATE; }
+  if (view < 0 || view >= c->fz_n) { g_err = "dpe_fusion_tat_mask: bad view"; return DPE_ERR_ARG; }
+  HIPC(host_wait(c));
+  HIPC(hipMemcpy(mask, c->tat_mask[view].p, (size_t)c->fz_host[view].w * c->fz_host[view].h, hipMemcpyDeviceToHost));
   return DPE_OK;
 }
 

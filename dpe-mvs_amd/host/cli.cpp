@@ -1,7 +1,10 @@
 // cli.cpp — the `dpe` command line, same positional arguments as the reference's `DPE` binary
 // (main.cpp:602-635):
 //
-//     dpe dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge]
+//     dpe dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge] [fusion_mode]
+//
+// fusion_mode (an addition: the reference calls RunFusion and has to be rebuilt for the others):
+// eth3d (0, the default), tat_intermediate (1) or tat_advanced (2).
 //
 // One process per GPU: launched under torchrun (or any launcher that sets RANK / WORLD_SIZE /
 // LOCAL_RANK), each rank takes a contiguous block of reference images on GPU LOCAL_RANK and the
@@ -106,6 +109,12 @@ int main(int argc, char** argv) {
   if (argc >= 8) o.normal = std::atoi(argv[7]);
   if (argc >= 9) o.weak = std::atoi(argv[8]);
   if (argc >= 10) o.edge = std::atoi(argv[9]);
+  if (argc >= 11) {   // not in the reference, which is hard-wired to RunFusion: 0 | eth3d, 1 | tat_intermediate, 2 | tat_advanced
+    const std::string m = argv[10];
+    o.fusion_mode = m == "eth3d" ? DPE_FUSION_ETH3D : m == "tat_intermediate" ? DPE_FUSION_TAT_INTERMEDIATE
+                  : m == "tat_advanced" ? DPE_FUSION_TAT_ADVANCED
+                  : (m.size() == 1 && m[0] >= '0' && m[0] <= '9') ? m[0] - '0' : -1;   // the pipeline refuses the rest
+  }
   const char* ws = std::getenv("WORLD_SIZE");
   Rccl rccl;
   if (ws && std::atoi(ws) > 1) {

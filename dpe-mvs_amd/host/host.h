@@ -97,10 +97,17 @@ struct FusionView {
   std::vector<uint8_t> block;        // blocks/mask_<id>.jpg at the map size, or empty
   std::vector<uint8_t> mask;         // fusion masks (set by run_fusion)
 };
-struct FusedPoint { float x, y, z, b, g, r; };
+using FusedPoint = DpeFusedPoint;   // x, y, z, b, g, r
 bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
                 std::string& err);
 FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const float* bgr);
 bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& cloud, std::string& err);
+// fusion_tat.cpp: RunFusion_TAT_Intermediate / RunFusion_TAT_advanced (DPE.cpp:1372-1689), `mode` =
+// DPE_FUSION_TAT_*.  ctx == nullptr: the reference's serial loops on the host; else every image on
+// the device (the serial loops still run when a reference is among its own sources or an id repeats).
+bool run_fusion_tat(std::vector<FusionView>& views, int mode, DpeContext* ctx, std::vector<FusedPoint>& cloud,
+                    std::string& err);
+// D[k], k = 2..n-1: smallest dot product in [-1, 1] that passes the Intermediate angle test at k
+bool tat_thresholds(float* D, int n, std::string& err);
 
 }  // namespace dpe_host

@@ -16,7 +16,9 @@
 // labels_<s>.dmb that are missing are computed by EdgeSegment (edges.cpp) and written.
 // fusion = true runs RunFusion (fusion.cpp) on rank 0 after the outputs: the per-(pixel, view)
 // projection tests on the GPU (dpe_fusion_candidates), the order-dependent rest on the host; with
-// several ranks the final normals and pixel states are all-gathered first.  As in the reference the
+// several ranks the final normals and pixel states are all-gathered first.  fusion_mode selects the
+// reference's two Tanks-and-Temples fusions instead (fusion_tat.cpp): one image at a time on the GPU,
+// or, with a fusion_runner hook, their serial loops on the host.  As in the reference the
 // edges_/labels_ maps are deleted at the end unless keep_intermediate.
 //
 // viz = true writes the reference's medium results: depth_<it>.jpg / normal_<it>.jpg / weak_<it>.jpg
@@ -833,7 +835,9 @@ struct PipelineRun {
       ffn = native_fusion; fuser = &nf;
     }
     std::vector<FusedPoint> cloud;
-    if (!run_fusion(views, ffn, fuser, cloud, err)) {
+    if (opt.fusion_mode != DPE_FUSION_ETH3D) {   // the Tanks-and-Temples variants: on the device, or (hook) serial
+      if (!run_fusion_tat(views, opt.fusion_mode, opt.fusion_runner ? nullptr : nf.ctx, cloud, err)) return false;
+    } else if (!run_fusion(views, ffn, fuser, cloud, err)) {
       if (!opt.fusion_runner) err += std::string(": ") + (nf.err.empty() ? std::string(dpe_last_error()) : nf.err);
       return false;
     }
@@ -859,6 +863,11 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
   for (double& t : g_times) t = 0.0;
   if (opt.world_size > 1 && !opt.allgather) { err = "world_size > 1 needs an all-gather"; return 1; }
   if (opt.rank < 0 || opt.rank >= std::max(1, opt.world_size)) { err = "bad rank"; return 1; }
+  if (opt.fusion_mode != DPE_FUSION_ETH3D && opt.fusion_mode != DPE_FUSION_TAT_INTERMEDIATE &&
+      opt.fusion_mode != DPE_FUSION_TAT_ADVANCED) {
+    err = "bad fusion_mode " + std::to_string(opt.fusion_mode) + " (0 = ETH3D, 1 = TAT intermediate, 2 = TAT advanced)";
+    return 1;
+  }
   PipelineRun r(dense_folder, opt, err);
   RankGroup& ranks = r.ranks;
   if (!r.load_problems()) return 1;

@@ -18,6 +18,8 @@
  *   Connect                   DPE.cpp:27-127     dpe_host_connect
  *   RunFusion / ExportPointCloud DPE.cpp:1220,532 inside dpe_run_pipeline (fusion = true): projection
  *                                                tests on the GPU (dpe_fusion_candidates), serial rest
+ *   RunFusion_TAT_Intermediate DPE.cpp:1372      inside dpe_run_pipeline, fusion_mode = DPE_FUSION_TAT_*: one
+ *   RunFusion_TAT_advanced    DPE.cpp:1542       image at a time on the GPU (dpe_fusion_tat_image)
  *   cv::imread(IMREAD_COLOR)  DPE.cpp:1253       dpe_host_read_bgr
  *   cv::HoughLinesP           DPE.cpp:186        dpe_host_hough_lines_p
  *   ShowDepthMap              DPE.cpp:384-448    dpe_host_viz_render(DPE_VIZ_DEPTH)  (viz = true: on the
@@ -85,6 +87,11 @@ typedef struct DpePipelineOptions {
   dpe_allgather_dev_fn allgather_device; void* allgather_device_user;   /* optional (see above); with the
                                default runner it is used instead of `allgather` for the depth maps */
   dpe_abort_fn abort_collectives; void* abort_user;   /* optional (see dpe_abort_fn) */
+  int fusion_mode;          /* DPE_FUSION_ETH3D (0, the default): RunFusion, what RunDPEPipeline calls;
+                               DPE_FUSION_TAT_INTERMEDIATE / DPE_FUSION_TAT_ADVANCED: the Tanks-and-Temples
+                               variants (DPE.cpp:1372-1689), whole image on the GPU; with a fusion_runner
+                               hook (no GPU) their serial loops run on the host and the hook is not called.
+                               Any other value fails */
 } DpePipelineOptions;
 
 void dpe_pipeline_default_options(DpePipelineOptions* opt);
@@ -160,6 +167,39 @@ int dpe_host_write_jpeg(const char* path, const uint8_t* pixels, int w, int h, i
  * (normal f32 [h][w][3]) or DPE_VIZ_WEAK (weak u8 [h][w]); the other inputs may be NULL.  0 on success. */
 int dpe_host_viz_render(int kind, int w, int h, const float* depth, const float* normal, const uint8_t* weak,
                         float depth_min, float depth_max, uint8_t* bgr);
+
+/*
+ * The Tanks-and-Temples fusions as the reference writes them (DPE.cpp:1372-1689): the serial loops,
+ * with the per-view entries that are never reset between pixels.  The yardstick of
+ * dpe_fusion_tat_image (dpe_mvs.h) and what fusion_mode runs without a GPU.
+ *   dpe_host_fusion_tat_serial      fuses views[0..n-1] in order, `mode` = DPE_FUSION_TAT_*; src_ids are
+ *                                   image ids (pair.txt order); bgr u8 [H][W][3]; block u8 [H][W] or NULL;
+ *                                   mask (u8 [H][W], or NULL) receives the view's final fusion mask.
+ *                                   Writes up to `cap` points and returns their number, or -1.
+ *   dpe_host_fusion_tat_run         the same views through the path dpe_run_pipeline takes: gpu_index < 0
+ *                                   the serial loops (= dpe_host_fusion_tat_serial), else every image on
+ *                                   that device (stage, begin, one dpe_fusion_tat_image per view, in a
+ *                                   context of its own); `mask` is filled by the serial loops only.
+ *                                   tools/fusion_prof.py times one against the other.
+ *   dpe_host_fusion_tat_thresholds  D[k], k = 2..n-1: the smallest float in [-1, 1] whose GetAngle is
+ *                                   below the Intermediate angle threshold at k (what the device test
+ *                                   `dot >= D[k]` needs).  0, or nonzero when the table does not verify.
+ *   dpe_host_fusion_tat_angle_test  the serial loop's own test: GetAngle(dot) < k * 3 deg + 4 deg.
+ */
+typedef struct DpeHostTatView {
+  int image_id;
+  const int* src_ids;
+  int n_src;
+  DpeFusionView view;
+  const uint8_t* bgr;
+  const uint8_t* block;
+  uint8_t* mask;
+} DpeHostTatView;
+long long dpe_host_fusion_tat_serial(int mode, const DpeHostTatView* views, int n, DpeFusedPoint* out, size_t cap);
+long long dpe_host_fusion_tat_run(int mode, const DpeHostTatView* views, int n, int gpu_index, DpeFusedPoint* out,
+                                  size_t cap);
+int dpe_host_fusion_tat_thresholds(float* D, int n);
+int dpe_host_fusion_tat_angle_test(float dot, int k);
 
 #ifdef __cplusplus
 }

@@ -311,6 +311,35 @@ int dpe_fusion_stage(DpeContext* ctx, const DpeFusionView* views, int n_views);
  * HOST output buffers of W*H*ns int32 / W*H*ns*3 floats.  Synchronous. */
 int dpe_fusion_candidates(DpeContext* ctx, int ref, const int* src, int ns, int32_t* idx, float* val);
 
+/*
+ * The two Tanks-and-Temples fusions, RunFusion_TAT_Intermediate (DPE.cpp:1372-1540) and
+ * RunFusion_TAT_advanced (DPE.cpp:1542-1689), one whole image on the device (csrc/pass_fusion_tat.h):
+ * these variants set only the fused pixel's own mask, so the pixels of an image are independent and
+ * only the images are sequential.  The reference's per-view `diff` entries, never reset between
+ * pixels, are reproduced as a last-hit carry over the raster.
+ *
+ * dpe_fusion_tat_begin:  after dpe_fusion_stage; uploads the colour image (u8 [H][W][3] BGR at the map
+ *                  size) and the optional block mask (u8 [H][W]; `block` or an entry may be NULL) of every
+ *                  staged view and zeroes the fusion masks.  Synchronous.
+ * dpe_fusion_tat_image:  fuses reference view `ref` against src[0..ns-1] (indices of staged views, none
+ *                  equal to `ref`, ns <= 31) in `mode` (DPE_FUSION_TAT_*).  Images must be fused in the
+ *                  run's order: the masks of earlier calls are read.  dot_thresholds[k], k = 2..ns: the
+ *                  smallest dot product in [-1, 1] that passes the angle test at k (Intermediate;
+ *                  dpe_host_fusion_tat_thresholds builds it; ignored for Advanced).  *n receives the
+ *                  number of points, in raster order; more than `cap` is DPE_ERR_ARG.  The kernels have
+ *                  finished on return, but the copy of the points into `out` runs on beside the next
+ *                  call's kernels: `out` is complete, and may be released, when the next
+ *                  dpe_fusion_tat_image, dpe_fusion_tat_wait or dpe_destroy returns.
+ * dpe_fusion_tat_mask:   host copy of a view's fusion mask u8 [H][W] (tests).  Synchronous.
+ */
+enum { DPE_FUSION_ETH3D = 0, DPE_FUSION_TAT_INTERMEDIATE = 1, DPE_FUSION_TAT_ADVANCED = 2 };
+typedef struct DpeFusedPoint { float x, y, z, b, g, r; } DpeFusedPoint;   /* PointList: world point, float BGR */
+int dpe_fusion_tat_begin(DpeContext* ctx, const uint8_t* const* bgr, const uint8_t* const* block);
+int dpe_fusion_tat_image(DpeContext* ctx, int mode, int ref, const int* src, int ns, const float* dot_thresholds,
+                         DpeFusedPoint* out, size_t cap, size_t* n);
+int dpe_fusion_tat_wait(DpeContext* ctx);
+int dpe_fusion_tat_mask(DpeContext* ctx, int view, uint8_t* mask);
+
 /* Page-locks (pins) / releases a caller's host buffer so that device -> host copies into it run at
  * full PCIe rate (hipHostRegister; the host fusion pins its candidate buffers).  Nonzero when the
  * runtime refuses (no device, limits): the buffer then stays pageable and every call still works. */
