@@ -166,7 +166,8 @@ struct DpeContext {
   DevArr<int> tab_right, tab_down;   // FindNearestStrongPoint tables
   DevArr<int> gn_ovf;                // GenNeighbours pixels left to the scratch kernel (k_gen_neighbours_lds)
   DevArr<float> gn_tab;              // normalised image coordinates per column / row (k_gn_tables)
-  DevArr<int> lists, row_counts, list_totals;   // per-colour pixel lists for the sweeps
+  // the pass's pixel lists; their regions are named by PassLists (pass_lists.h)
+  DevArr<int> lists, row_counts, list_totals;   // pixel indices / per-row counts / one total per list
   DevArr<int> part_cnt;                          // per colour: chunk counts / offsets of the weak-list partition
   dpe::DevBufs bufs;
   // fusion (dpe_fusion_stage / dpe_fusion_candidates)

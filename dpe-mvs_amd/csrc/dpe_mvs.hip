@@ -8,6 +8,8 @@
 //   * the bilinear texture path is a padded quad-texel image in HBM (one 16-B load per tap);
 //   * cuRAND states (48 B/px + curand_init) are replaced by counter-based Philox;
 //   * errors are return codes (no exit()).
+// dpe_pm_stage is stage_impl's named steps; dpe_pm_execute is the named steps of one pass ("one
+// pass" below) over the pixel-list layout of pass_lists.h.
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include <algorithm>
@@ -619,8 +621,9 @@ static int ensure_working_set(DpeContext* c, int W, int H) {
   HIPC(c->radius.ensure(L));
   HIPC(c->tab_right.ensure(L)); HIPC(c->tab_down.ensure(L));
   HIPC(c->gn_ovf.ensure(L + 64)); HIPC(c->gn_tab.ensure((size_t)W + H));
-  HIPC(c->lists.ensure(6 * (L / 2 + 64) + 3 * (L + 64))); HIPC(c->row_counts.ensure(4 * (size_t)H + 4)); HIPC(c->list_totals.ensure(16));
-  HIPC(c->part_cnt.ensure(2 * ((L / 2 + 1) / kPartChunk + 2)));
+  const PassLists lay(W, H, c->hc.half_rows);   // the layout dpe_pm_execute carves them by (pass_lists.h)
+  HIPC(c->lists.ensure((size_t)lay.lists_len())); HIPC(c->row_counts.ensure(lay.row_counts_len()));
+  HIPC(c->list_totals.ensure(PassLists::kTotals)); HIPC(c->part_cnt.ensure(lay.part_cnt_len()));
   DevBufs& B = c->bufs;
   B.planes = c->planes.p; B.planes_snap = c->planes_snap.p; B.fit_plane = c->fit_plane.p;
   B.planes0 = c->planes0.p;
@@ -694,304 +697,91 @@ extern "C" int dpe_pm_stage_resident(DpeContext* c, const DpePassInput* in, int 
   return stage_impl(c, in, src);
 }
 
-extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
-  TRY(enter(c, true, "dpe_pm_execute: null context"));
-  if (!c->staged) { g_err = "dpe_pm_execute: call dpe_pm_stage first"; return DPE_ERR_STATE; }
-  Range range_("dpe_pm_execute");
-  hipStream_t s;
-  // a previous execute, possibly on another stream, still uses the working buffers this one resets
-  HIPC(enqueue_stream(c, stream_, &s));
-  const PassConst& pc = c->hc;
-  const PassConst* dpc = c->dc.p;
-  const int W = pc.W, H = pc.H, nv = pc.N - 1;
-  const size_t L = (size_t)W * H;
-  DevBufs B = c->bufs;
-  B.cnt = nullptr;
-  {   // tuning knob: block rows per XCD chunk (see xcd_remap); DPE_XCD_ROWS=0 disables
-    const char* e = getenv("DPE_XCD_ROWS");
-    B.xcd_rows = e ? atoi(e) : kDefaultXcdRows;
-  }
-#if DPE_PHASE_PROF
-  HIPC(c->phase.ensure(32 * 64));
-  HIPC(hipMemsetAsync(c->phase.p, 0, 32 * 64 * sizeof(unsigned long long), s));
-  B.phase = c->phase.p;
-#endif
-  if (c->counting) {
-    HIPC(c->cnt.ensure(DPE_NUM_CLASSES * 4));
-    HIPC(hipMemsetAsync(c->cnt.p, 0, DPE_NUM_CLASSES * 4 * sizeof(unsigned long long), s));
-  }
-  // per-launch events: slot pairs (start, end) + class id; one slot per class section of the
-  // launch sequence (setup, init, 5 per iteration, filter, DepthToWeak, LocalRefine)
-  const bool timing = c->timing;
-  const int max_slots = 5 + 5 * std::max(0, pc.P.max_iterations);
-  while (timing && (int)c->ev.size() < 2 * max_slots) {
-    Event e;
-    HIPC(e.create(hipEventDefault));
-    c->ev.push_back(std::move(e));
-  }
-  int nev = 0;
-  bool slot_overflow = false;   // more timed sections than slots: fail the timed execute loudly
-  std::vector<int> ev_class(timing ? max_slots : 0);
-  for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->launches[k] = 0;
-  static const char* const kClassName[DPE_NUM_CLASSES] = {"setup", "init", "strong", "ransac", "weak", "filter",
-                                                           "depth_to_weak", "local_refine"};
-  auto begin = [&](int cls) -> DevBufs {
-    roctxRangePushA(kClassName[cls]);
-    DevBufs Bc = B;
-    if (c->counting) Bc.cnt = c->cnt.p + 4 * cls;
-    c->launches[cls]++;
-    if (timing && nev < max_slots) { ev_class[nev] = cls; (void)hipEventRecord(c->ev[2 * nev], s); }
-    else if (timing) slot_overflow = true;
-    return Bc;
-  };
-  auto end = [&]() {
-    if (timing && nev < max_slots) { (void)hipEventRecord(c->ev[2 * nev + 1], s); nev++; }
-    roctxRangePop();
-  };
+// ------------------------------------------------------------------------------ one pass
+// dpe_pm_execute: what it records about itself (PassRecorder), its state (PassRun) and its steps, in
+// the order of RunPatchMatch's launch sequence (DPE.cu:3150-3226).
 
-  if (timing) (void)hipEventRecord(c->ev_start, s);
-#if DPE_GN_ONCE
-  // Timing builds only (pass_common.h): GenNeighbours runs in the first execute after a stage and its
-  // outputs (nb, weak_rel, and complex_, which GenEdgeInform rewrites: restored after it) are kept
-  // for the next executes of the same staged state, which then skip it -- the same results
-  // (GenNeighbours depends only on the staged state), and the pass time without GenNeighbours on the
-  // critical path.  An execute that fails forgets them.
-  const bool gn_skip = c->gn_done_for_stage;
-  struct GnGuard {
-    DpeContext* c;
-    bool ok = false;
-    ~GnGuard() { if (!ok) c->gn_done_for_stage = false; }
-  } gn_guard{c};
-#else
-  constexpr bool gn_skip = false;   // GenNeighbours runs in every execute
+static const char* const kClassName[DPE_NUM_CLASSES] = {"setup", "init", "strong", "ransac", "weak", "filter",
+                                                         "depth_to_weak", "local_refine"};
+
+// Everything an execute records beside its results: per-class timing events, section counts
+// (launches[]), the counting buffer, roctx ranges and the DPE_PHASE_PROF cycle sums.  The launch
+// sequence is cut into class sections (setup, init, 5 per iteration, filter, DepthToWeak,
+// LocalRefine), each a Section in a scope of its own.
+struct PassRecorder {
+  DpeContext* c = nullptr;
+  hipStream_t s = nullptr;
+  const DevBufs* base = nullptr;   // the pass's buffers
+  bool timing = false, slot_overflow = false;
+  int max_slots = 0, nev = 0;   // timing: (start, end) event pairs available / used
+  std::vector<int> ev_class;    //   and the class of each (empty unless timing)
+
+  // Resets the execute's diagnostics on `s_` and marks the start of the pass.  B (which gets the phase
+  // buffer of a DPE_PHASE_PROF build) outlives the sections.
+  int start(DpeContext* c_, hipStream_t s_, DevBufs& B) {
+    c = c_; s = s_; base = &B;
+    timing = c->timing;
+#if DPE_PHASE_PROF
+    HIPC(c->phase.ensure(32 * 64));
+    HIPC(hipMemsetAsync(c->phase.p, 0, 32 * 64 * sizeof(unsigned long long), s));
+    B.phase = c->phase.p;
 #endif
-  // initial state (the reference uploads it in CudaSpaceInitialization, DPE.cpp:964-1015)
-  k_pass_init<<<(unsigned)((L + 255) / 256), 256, 0, s>>>((const uint4*)c->planes0.p, c->weak0.p, c->sel0.p, (uint4*)B.planes,
-                                                          B.weak, B.sel, (uint32_t*)B.costs, (uint4*)B.vw, L);
-  // the rest of the initial state is first read by the setup chain (or, after it joins the pass
-  // stream, by RANSACToGetFitPlane and the weak sweeps): it is cleared on the setup chain's stream
-  auto clear_setup_state = [&](hipStream_t q) -> int {
-    HIPC(hipMemsetAsync(B.fit_plane, 0, L * sizeof(float4), q));
-    HIPC(hipMemsetAsync(B.complex_, 0, L * sizeof(float), q));
-    if (!gn_skip) HIPC(hipMemsetAsync(B.weak_rel, 0xFF, L, q));   // GenNeighbours writes 0 / 1 for every WEAK pixel
-    if (!gn_skip) HIPC(hipMemsetAsync(B.nb, 0xFF, L * 9 * sizeof(short2), q));
-    HIPC(hipMemsetAsync(B.nearest, 0xFF, L * sizeof(short2), q));
-    HIPC(hipMemsetAsync(B.edge_neigh, 0xFF, L * 8 * sizeof(short2), q));
-    HIPC(hipMemsetAsync(B.lab_bound, 0xFF, L * 8 * sizeof(short2), q));
-    HIPC(hipMemsetAsync(B.radius, 0, L * sizeof(int), q));
+    if (c->counting) {
+      HIPC(c->cnt.ensure(DPE_NUM_CLASSES * 4));
+      HIPC(hipMemsetAsync(c->cnt.p, 0, DPE_NUM_CLASSES * 4 * sizeof(unsigned long long), s));
+    }
+    max_slots = 5 + 5 * std::max(0, c->hc.P.max_iterations);
+    while (timing && (int)c->ev.size() < 2 * max_slots) {
+      Event e;
+      HIPC(e.create(hipEventDefault));
+      c->ev.push_back(std::move(e));
+    }
+    ev_class.assign(timing ? max_slots : 0, 0);
+    for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->launches[k] = 0;
+    if (timing) (void)hipEventRecord(c->ev_start, s);
     return DPE_OK;
+  }
+
+  // One class section: opened where it is declared, closed where its scope ends, also on an early
+  // return (the roctx range is popped; the end event is recorded only if the start event was).
+  struct Section {
+    DevBufs B;   // the pass's buffers, with the class's counters in a counting execute
+    PassRecorder& r;
+    int slot = -1;
+    Section(PassRecorder& r_, int cls) : B(*r_.base), r(r_) {
+      roctxRangePushA(kClassName[cls]);
+      if (r.c->counting) B.cnt = r.c->cnt.p + 4 * cls;
+      r.c->launches[cls]++;
+      if (r.timing && r.nev < r.max_slots) { slot = r.nev; r.ev_class[slot] = cls; (void)hipEventRecord(r.c->ev[2 * slot], r.s); }
+      else if (r.timing) r.slot_overflow = true;   // more timed sections than slots: finish() fails loudly
+    }
+    ~Section() {
+      if (slot >= 0) { (void)hipEventRecord(r.c->ev[2 * slot + 1], r.s); r.nev++; }
+      roctxRangePop();
+    }
+    Section(const Section&) = delete;
   };
 
-  const dim3 fb(16, 16), fg((W + 15) / 16, (H + 15) / 16);
-  const dim3 rb(16, kRansacThreads / 16), rg((W + 15) / 16, (H + rb.y - 1) / rb.y);
-  const dim3 hb(32, 4), hg((((W + 1) / 2) + 31) / 32, (pc.half_rows + 3) / 4);
-
-  DevBufs Bc;
-
-  // RunPatchMatch launch sequence (DPE.cu:3150-3226)
-  // DPE_OVERLAP=0 keeps one stream (profiling runs whose per-kernel durations must not overlap);
-  // timed / counting executes keep one stream too (per-class events)
-  static const bool overlap_env = [] { const char* e = getenv("DPE_OVERLAP"); return !(e && atoi(e) == 0); }();
-  // (the join into `s` sits in the first strong half-sweep, so a pass without iterations keeps one stream)
-  const bool overlap = overlap_env && !timing && !c->counting && pc.P.max_iterations >= 1;
-  const long list_stride = (long)(L / 2 + 64);
-  int* weak_list = c->lists.p + 4 * list_stride;     // all WEAK pixels (list_totals slot 4)
-  int* failed_list = weak_list + L + 64;             // colour-0 pixels whose GenNeighbours failed (slot 5)
-  int* side_lists = failed_list + list_stride;       // per colour: the weak list partitioned by patch side
-  // The whole setup chain (GenEdgeInform, FindNearestStrongPoint's tables, the WEAK list,
-  // GenNeighbours, NeigbourUpdate) runs on the aux stream `a`, forked at the start of the pass beside
-  // RandomInitialization; the first strong half-sweep waits for GenEdgeInform's edge rays only.
-  // GenNeighbours + NeigbourUpdate only decide which WEAK pixels join the strong lists; nothing the
-  // first strong half-sweep (iteration 0, colour 0) or RandomInitialization reads is written by them,
-  // and GenNeighbours reads the staged planes, not the ones those two rewrite.  So that half-sweep
-  // runs over the pre-GenNeighbours colour-0 strong list, and the colour-0 pixels whose GenNeighbours
-  // failed (NeigbourUpdate makes them UNKNOWN) get the same half-sweep (same snapshot) once the
-  // streams join.  Pixels of one half-sweep are independent, so this is the reference's order of
-  // results (GPU test test_overlapped_and_sequential_schedules_agree).
-  const hipStream_t a = overlap ? c->aux : s;
-  auto sweep_lists = [&](const DevBufs& Bl) {   // per-colour strong / weak lists of the sweeps
-    k_list_count<0><<<(pc.half_rows + 3) / 4, 256, 0, s>>>(dpc, Bl, c->row_counts.p);
-    k_list_scan<0><<<1, 256, 0, s>>>(dpc, c->row_counts.p, c->list_totals.p);
-    k_list_fill<0><<<(pc.half_rows + 3) / 4, 256, 0, s>>>(dpc, Bl, c->row_counts.p, c->lists.p, list_stride);
-  };
-  Bc = begin(DPE_CLASS_SETUP);
-  if (overlap) {   // pre-GenNeighbours sweep lists (the colour-0 strong list is the one used)
-    sweep_lists(Bc);
-    HIPC(hipEventRecord(c->ev_fork, s));
-    HIPC(hipStreamWaitEvent(a, c->ev_fork, 0));
-  }
-  if (const int rc = clear_setup_state(a); rc != DPE_OK) return rc;
-  k_gen_edge_inform<<<fg, fb, 0, a>>>(dpc, Bc);
-  if (pc.P.use_edge) k_edge_rays<<<(unsigned)(3 * (W + H) - 2), 64, 0, a>>>(dpc, Bc);
-#if DPE_GN_ONCE
-  if (gn_skip) HIPC(hipMemcpyAsync(B.complex_, c->gn_complex.p, L * sizeof(float), hipMemcpyDeviceToDevice, a));
-#endif
-  if (overlap) HIPC(hipEventRecord(c->ev_ei, a));
-  k_strong_tables_scan<<<(unsigned)(W + H), 64, 0, a>>>(dpc, Bc, c->tab_right.p, c->tab_down.p);
-  k_find_nearest_strong<<<fg, fb, 0, a>>>(dpc, Bc, c->tab_right.p, c->tab_down.p);
-  // list of all WEAK pixels, then GenNeighbours one thread per WEAK pixel
-  k_list_count<1><<<(H + 3) / 4, 256, 0, a>>>(dpc, Bc, c->row_counts.p + 2 * (size_t)H + 2);
-  k_list_scan<1><<<1, 64, 0, a>>>(dpc, c->row_counts.p + 2 * (size_t)H + 2, c->list_totals.p + 4);
-  k_list_fill<1><<<(H + 3) / 4, 256, 0, a>>>(dpc, Bc, c->row_counts.p + 2 * (size_t)H + 2, weak_list, (long)L);
-  if (gn_skip) {
-  } else if (pc.P.rotate_time <= 4) {
-    // the scratch-free kernel; pixels with more support points than its LDS slots (none at the
-    // BASELINE workloads) or a NaN go to the scratch kernel, a small persistent grid that loops over
-    // that overflow list (list_totals slot 6)
-    k_gn_tables<<<(unsigned)((W + H + 255) / 256), 256, 0, a>>>(dpc, c->gn_tab.p);
-    HIPC(hipMemsetAsync(c->list_totals.p + 6, 0, sizeof(int), a));
-    const unsigned gg = (unsigned)((L + kGnBT - 1) / kGnBT);
-    const int* cnt = c->list_totals.p + 4;
-    if (c->gn_slots == 8)   // test setting: most pixels overflow into the scratch kernel
-      k_gen_neighbours_lds<8><<<gg, kGnBT, 0, a>>>(dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, c->list_totals.p + 6);
-    else if (pc.P.rotate_time <= 2 && c->gn_slots != 64)   // at most 16 x rotate_time support points
-      k_gen_neighbours_lds<32><<<gg, kGnBT, 0, a>>>(dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, c->list_totals.p + 6);
-    else
-      k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, c->list_totals.p + 6);
-    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(dpc, Bc, c->gn_ovf.p, c->list_totals.p + 6);
-  } else {
-    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(dpc, Bc, weak_list, c->list_totals.p + 4);
-  }
-#if DPE_GN_ONCE
-  if (!gn_skip) {
-    HIPC(c->gn_complex.ensure(L));
-    HIPC(hipMemcpyAsync(c->gn_complex.p, B.complex_, L * sizeof(float), hipMemcpyDeviceToDevice, a));
-    c->gn_done_for_stage = true;
-  }
-#endif
-  k_neighbour_update<<<fg, fb, 0, a>>>(dpc, Bc);
-  if (overlap) {
-    k_list_count<2><<<(pc.half_rows + 3) / 4, 256, 0, a>>>(dpc, Bc, c->row_counts.p);
-    k_list_scan<2><<<1, 64, 0, a>>>(dpc, c->row_counts.p, c->list_totals.p + 5);
-    k_list_fill<2><<<(pc.half_rows + 3) / 4, 256, 0, a>>>(dpc, Bc, c->row_counts.p, failed_list, list_stride);
-    HIPC(hipEventRecord(c->ev_join, a));
-  } else {
-    sweep_lists(Bc);   // weak_info is fixed from here until DepthToWeak
-  }
-  end();
-  Bc = begin(DPE_CLASS_INIT);
-  if (c->img_cls != IMG_F32) k_random_init<kTexInit><<<fg, fb, 0, s>>>(dpc, Bc); else k_random_init<TEX_F32><<<fg, fb, 0, s>>>(dpc, Bc);
-  end();
-  if (overlap) HIPC(hipStreamWaitEvent(s, c->ev_ei, 0));   // the strong sweeps read GenEdgeInform's rays
-  HIPC(hipGetLastError());
-  auto strong_sweep = [&](const DevBufs& Bs, int it, const int* lst, const int* cnt) {
-    const bool edge = pc.P.use_edge;
-    const int P = edge ? 4 : 8, C = edge ? 16 : 8;
-    const size_t lds = (size_t)kBwStrong * strong_lds_per_wave(P, C, nv) * sizeof(float);
-    const unsigned grid = (unsigned)((L / 2 + 1 + kBwStrong * P - 1) / (kBwStrong * P));
-    launch_strong(edge, c->img_cls, grid, lds, s, dpc, Bs, it, lst, cnt);
-  };
-  for (int it = 0; it < pc.P.max_iterations; ++it) {
-    for (int colour = 0; colour < 2; ++colour) {
-      k_snapshot<<<(unsigned)((L + 255) / 256), 256, 0, s>>>((const uint4*)B.planes, (const uint32_t*)B.costs, B.sel,
-                                                          (uint4*)B.planes_snap, (uint32_t*)B.costs_snap, B.sel_snap, L);
-      Bc = begin(DPE_CLASS_STRONG);
-      strong_sweep(Bc, it, c->lists.p + (colour * 2 + 0) * list_stride, c->list_totals.p + colour * 2 + 0);
-      if (overlap && it == 0 && colour == 0) {
-        // the colour-0 pixels whose GenNeighbours failed (UNKNOWN after NeigbourUpdate), same snapshot
-        HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-        strong_sweep(Bc, it, failed_list, c->list_totals.p + 5);
-        sweep_lists(Bc);   // the sweep lists after NeigbourUpdate (weak_info is fixed until DepthToWeak)
+  // After the last launch: timings[] (0: ev_start to the last section's end; 1 + class: the summed
+  // sections), the phase report, counts[] (4k + 3: the section counts).
+  int finish() {
+    if (slot_overflow) {   // per-class times would silently miss launches
+      HIPC(hipStreamSynchronize(s));
+      g_err = "dpe_pm_execute: more timed launch sections than timing slots (" + std::to_string(max_slots) + ")";
+      return DPE_ERR_STATE;
+    }
+    if (timing && nev > 0) {
+      HIPC(hipEventSynchronize(c->ev[2 * nev - 1]));
+      for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->timings[k] = 0.0f;
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, c->ev_start, c->ev[2 * nev - 1]);
+      c->timings[0] = ms;
+      for (int e = 0; e < nev; ++e) {
+        (void)hipEventElapsedTime(&ms, c->ev[2 * e], c->ev[2 * e + 1]);
+        c->timings[1 + ev_class[e]] += ms;
       }
-      end();
     }
-    HIPC(hipGetLastError());
-    // The two colours' weak sweeps read only STRONG pixels' state besides their own pixel (planes and
-    // selected views of the GenNeighbours support points, DPE.cu:1690-1725; the NCC-New patches come
-    // from the images), and write only their own pixel, so they are independent: the colour-1 sweep
-    // runs on the aux stream beside the colour-0 one (the launch tails overlap).  Each colour's
-    // RANSACToGetFitPlane over that colour's weak list runs on that colour's stream just before its
-    // sweep (a fit reads STRONG pixels and writes its own pixel's fit plane, which only its own weak
-    // update reads).
-    const unsigned rl_grid = (unsigned)((L / 2 + 1 + kRansacThreads - 1) / kRansacThreads);
-    if (overlap) {   // fork first: the colour-1 fit must not wait for the colour-0 one
-      HIPC(hipEventRecord(c->ev_fork, s));
-      HIPC(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
-    }
-    Bc = begin(DPE_CLASS_RANSAC);
-    for (int colour = 1; colour >= 0; --colour) {
-      const hipStream_t sr = colour == 1 ? a : s;
-      k_ransac_fit<<<rl_grid, kRansacThreads, 0, sr>>>(dpc, Bc, it, c->lists.p + (colour * 2 + 1) * list_stride,
-                                                        c->list_totals.p + colour * 2 + 1);
-    }
-    end();
-    for (int colour = 0; colour < 2; ++colour) {
-      Bc = begin(DPE_CLASS_WEAK);
-      {
-        const hipStream_t sw = colour == 1 ? a : s;
-        const int* lst = c->lists.p + (colour * 2 + 1) * list_stride;
-        const int* cnt = c->list_totals.p + colour * 2 + 1;
-        if (pc.P.use_radius) {   // the fits just set the radii: partition the list by centre-patch side
-          const unsigned pg = (unsigned)((L / 2 + 1 + kPartChunk - 1) / kPartChunk);
-          int* pcnt = c->part_cnt.p + colour * (pg + 2);
-          int* out = side_lists + colour * list_stride;
-          k_part_count<<<pg, 256, 0, sw>>>(dpc, Bc, lst, cnt, pcnt);
-          k_part_scan<<<1, 256, 0, sw>>>(cnt, pcnt, c->list_totals.p + 8 + colour);
-          k_part_fill<<<pg, 256, 0, sw>>>(dpc, Bc, lst, cnt, pcnt, c->list_totals.p + 8 + colour, out);
-          lst = out;
-        }
-        constexpr int C = kWeakLanes, P = 64 / C;
-        const size_t per_wave = (size_t)P * weak_lds_per_pixel(nv) * sizeof(float);
-        const int wpb = per_wave * 4 <= 64 * 1024 ? 4 : (per_wave * 2 <= 64 * 1024 ? 2 : 1);
-        const unsigned grid = (unsigned)((L / 2 + 1 + wpb * P - 1) / (wpb * P));
-        // U8 texels for 8-bit images; F16 (exact for quarter-integer grey levels) for the coarse levels
-        if (c->img_cls == IMG_U8) k_weak_coop<kTexWeak, C><<<grid, 64 * wpb, per_wave * wpb, sw>>>(dpc, Bc, it, lst, cnt);
-        else if (c->img_cls == IMG_Q) k_weak_coop<TEX_F16, C><<<grid, 64 * wpb, per_wave * wpb, sw>>>(dpc, Bc, it, lst, cnt);
-        else k_weak_coop<TEX_F32, C><<<grid, 64 * wpb, per_wave * wpb, sw>>>(dpc, Bc, it, lst, cnt);
-      }
-      end();
-    }
-    if (overlap) {
-      HIPC(hipEventRecord(c->ev_join, c->aux));
-      HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-    }
-    HIPC(hipGetLastError());
-  }
-  Bc = begin(DPE_CLASS_FILTER);
-  k_depth_normal<<<fg, fb, 0, s>>>(dpc, Bc);
-  for (int colour = 0; colour < 2; ++colour) k_filter<<<hg, hb, 0, s>>>(dpc, Bc, colour);   // hb: 32 x 4 = kFilterThreads
-  end();
-  // LocalRefine on the 6-px border (which DepthToWeak leaves to it) reads and writes only its own
-  // pixel's plane besides the images and source depths (DPE.cu:2749-2835), and DepthToWeak writes
-  // only interior pixels: the two are independent, so the border kernel runs on the aux stream
-  // beside DepthToWeak (launched first: it is small and would otherwise wait for DepthToWeak's slots)
-  if (overlap) {
-    HIPC(hipEventRecord(c->ev_fork, s));
-    HIPC(hipStreamWaitEvent(a, c->ev_fork, 0));
-    Bc = begin(DPE_CLASS_LOCAL_REFINE);
-    launch_local_refine(c->img_cls, (long)L, W, H, nv, a, dpc, Bc);
-    end();
-    HIPC(hipEventRecord(c->ev_join, a));
-  }
-  Bc = begin(DPE_CLASS_DEPTH_TO_WEAK);
-  launch_depth_to_weak(c->img_cls, (long)L, s, dpc, Bc);
-  end();
-  if (overlap) {
-    HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
-  } else {
-    Bc = begin(DPE_CLASS_LOCAL_REFINE);
-    launch_local_refine(c->img_cls, (long)L, W, H, nv, s, dpc, Bc);
-    end();
-  }
-  HIPC(hipGetLastError());
-  if (slot_overflow) {   // per-class times would silently miss launches
-    HIPC(hipStreamSynchronize(s));
-    g_err = "dpe_pm_execute: more timed launch sections than timing slots (" + std::to_string(max_slots) + ")";
-    return DPE_ERR_STATE;
-  }
-  if (timing && nev > 0) {
-    HIPC(hipEventSynchronize(c->ev[2 * nev - 1]));
-    for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->timings[k] = 0.0f;
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, c->ev_start, c->ev[2 * nev - 1]);
-    c->timings[0] = ms;
-    for (int e = 0; e < nev; ++e) {
-      (void)hipEventElapsedTime(&ms, c->ev[2 * e], c->ev[2 * e + 1]);
-      c->timings[1 + ev_class[e]] += ms;
-    }
-  }
 #if DPE_PHASE_PROF
-  {
     unsigned long long ph32[32 * 64], ph[64] = {};
     HIPC(hipMemcpyAsync(ph32, c->phase.p, sizeof(ph32), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
@@ -1000,13 +790,333 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
     for (int k = 0; k < 64; ++k) tot[k / 16] += ph[k];
     for (int k = 0; k < 64; ++k)
       if (ph[k]) fprintf(stderr, "PHASE %d.%d %.4e cycles %.1f%%\n", k / 16, k % 16, (double)ph[k], 100.0 * ph[k] / tot[k / 16]);
+#endif
+    if (c->counting) {
+      HIPC(hipMemcpyAsync(c->counts, c->cnt.p, sizeof(c->counts), hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      for (int k = 0; k < DPE_NUM_CLASSES; ++k) c->counts[4 * k + 3] = (unsigned long long)c->launches[k];
+    }
+    return DPE_OK;
+  }
+};
+using Section = PassRecorder::Section;
+
+// The state of one execute.  Every pointer into the list buffers comes from `lay` (pass_lists.h).
+// Streams: overlapped schedule, `s` is the pass stream and `a` the context's aux stream; one-stream
+// schedule (timed and counting executes, whose per-class events must not overlap; DPE_OVERLAP=0, for
+// profiles whose kernel durations must not; a pass without iterations, since the join into `s` sits
+// in the first strong half-sweep): a == s, and fork() and the joins do nothing.
+struct PassRun {
+  DpeContext* c;
+  hipStream_t s, a;
+  bool overlap;
+  const PassConst& pc;   // host copy of the pass constants
+  const PassConst* dpc;  //   and the device copy the kernels read
+  DevBufs B;
+  PassLists lay;
+  size_t L;              // pixels
+  int nv;                // source views
+  bool gn_skip = false;  // DPE_GN_ONCE builds: GenNeighbours' outputs of this staged state are kept
+  PassRecorder rec;
+
+  PassRun(DpeContext* c_, hipStream_t s_)
+      : c(c_), s(s_), a(s_), pc(c_->hc), dpc(c_->dc.p), B(c_->bufs), lay(pc.W, pc.H, pc.half_rows),
+        L((size_t)pc.W * pc.H), nv(pc.N - 1) {
+    static const bool overlap_env = [] { const char* e = getenv("DPE_OVERLAP"); return !(e && atoi(e) == 0); }();   // once per process
+    overlap = overlap_env && !c->timing && !c->counting && pc.P.max_iterations >= 1;
+    if (overlap) a = c->aux;
+    B.cnt = nullptr;
+    const char* e = getenv("DPE_XCD_ROWS");   // tuning knob, read on every execute: block rows per XCD
+    B.xcd_rows = e ? atoi(e) : kDefaultXcdRows;   //   chunk (see xcd_remap); 0 disables
+  }
+  // `a` continues from here on `s`
+  hipError_t fork(hipEvent_t ev) const {
+    const hipError_t e = overlap ? hipEventRecord(ev, s) : hipSuccess;
+    return e != hipSuccess || !overlap ? e : hipStreamWaitEvent(a, ev, 0);
+  }
+  // `s` continues after what `a` holds now: join(), or its two halves around launches on `s`
+  hipError_t aux_done(hipEvent_t ev) const { return overlap ? hipEventRecord(ev, a) : hipSuccess; }
+  hipError_t wait_aux(hipEvent_t ev) const { return overlap ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  hipError_t join(hipEvent_t ev) const { const hipError_t e = aux_done(ev); return e != hipSuccess ? e : wait_aux(ev); }
+
+  int* list(PassLists::Region r) const { return c->lists.p + r.off; }
+  int* rows(PassLists::Region r) const { return c->row_counts.p + r.off; }
+  int* total(int slot) const { return c->list_totals.p + slot; }
+  int* chunk_counts(int colour) const { return c->part_cnt.p + lay.chunk_counts(colour).off; }
+  dim3 px_grid() const { return dim3((pc.W + 15) / 16, (pc.H + 15) / 16); }   // of kPxBlock threads: one per pixel
+};
+static const dim3 kPxBlock(16, 16);
+
+// One pixel-list build (pass_sweep.h, MODE 0 / 1 / 2) on stream `st`: row counts, their scan, fill.
+// MODE 0 builds the four sweep lists, consecutive from `list` with their totals consecutive from
+// `total`; `stride` lies between them (the one-list modes never use theirs).
+template <int MODE>
+static void build_lists(const PassRun& X, hipStream_t st, const DevBufs& Bl, PassLists::Region rows, int total,
+                        PassLists::Region list) {
+  const unsigned grid = (unsigned)(((MODE == 1 ? X.pc.H : X.pc.half_rows) + 3) / 4);   // a wave per row (list_rows<MODE>)
+  const long stride = MODE == 1 ? X.lay.px() : list.len;
+  int* rc = X.rows(rows);
+  k_list_count<MODE><<<grid, 256, 0, st>>>(X.dpc, Bl, rc);
+  k_list_scan<MODE><<<1, 64 * list_count<MODE>(), 0, st>>>(X.dpc, rc, X.total(total));
+  k_list_fill<MODE><<<grid, 256, 0, st>>>(X.dpc, Bl, rc, X.list(list), stride);
+}
+// the per-colour strong / weak lists of the sweeps, on `s`
+static void sweep_lists(const PassRun& X, const DevBufs& Bl) {
+  build_lists<0>(X, X.s, Bl, X.lay.sweep_rows(), PassLists::total_sweep(0, 0), X.lay.sweep(0, 0));
+}
+
+// The part of the initial state that the setup chain reads first (or, after it joins the pass
+// stream, RANSACToGetFitPlane and the weak sweeps): cleared on the setup chain's stream `st`.
+static int clear_setup_state(const PassRun& X, hipStream_t st) {
+  const DevBufs& B = X.B;
+  const size_t L = X.L;
+  HIPC(hipMemsetAsync(B.fit_plane, 0, L * sizeof(float4), st));
+  HIPC(hipMemsetAsync(B.complex_, 0, L * sizeof(float), st));
+  if (!X.gn_skip) HIPC(hipMemsetAsync(B.weak_rel, 0xFF, L, st));   // GenNeighbours writes 0 / 1 for every WEAK pixel
+  if (!X.gn_skip) HIPC(hipMemsetAsync(B.nb, 0xFF, L * 9 * sizeof(short2), st));
+  HIPC(hipMemsetAsync(B.nearest, 0xFF, L * sizeof(short2), st));
+  HIPC(hipMemsetAsync(B.edge_neigh, 0xFF, L * 8 * sizeof(short2), st));
+  HIPC(hipMemsetAsync(B.lab_bound, 0xFF, L * 8 * sizeof(short2), st));
+  HIPC(hipMemsetAsync(B.radius, 0, L * sizeof(int), st));
+  return DPE_OK;
+}
+
+// GenNeighbours, one thread per pixel of the all-WEAK list, on `a`.
+static int gen_neighbours(PassRun& X, const DevBufs& Bc) {
+  DpeContext* c = X.c;
+  const hipStream_t a = X.a;
+  const int* weak_list = X.list(X.lay.all_weak());
+  const int* cnt = X.total(PassLists::kTotAllWeak);
+  if (X.gn_skip) {
+  } else if (X.pc.P.rotate_time <= 4) {
+    // the scratch-free kernel; pixels with more support points than its LDS slots (none at the
+    // BASELINE workloads) or a NaN go to the scratch kernel, a small persistent grid that loops over
+    // that overflow list (its count: the GenNeighbours-overflow total, dpe_pm_last_stat)
+    int* ovf = X.total(PassLists::kTotGnOverflow);
+    k_gn_tables<<<(unsigned)((X.pc.W + X.pc.H + 255) / 256), 256, 0, a>>>(X.dpc, c->gn_tab.p);
+    HIPC(hipMemsetAsync(ovf, 0, sizeof(int), a));
+    const unsigned gg = (unsigned)((X.L + kGnBT - 1) / kGnBT);
+    if (c->gn_slots == 8)   // test setting: most pixels overflow into the scratch kernel
+      k_gen_neighbours_lds<8><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
+    else if (X.pc.P.rotate_time <= 2 && c->gn_slots != 64)   // at most 16 x rotate_time support points
+      k_gen_neighbours_lds<32><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
+    else
+      k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
+    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, c->gn_ovf.p, ovf);
+  } else {
+    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, weak_list, cnt);
+  }
+#if DPE_GN_ONCE
+  if (!X.gn_skip) {   // kept for the next executes of this staged state (see dpe_pm_execute)
+    HIPC(c->gn_complex.ensure(X.L));
+    HIPC(hipMemcpyAsync(c->gn_complex.p, X.B.complex_, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
+    c->gn_done_for_stage = true;
   }
 #endif
-  if (c->counting) {
-    HIPC(hipMemcpyAsync(c->counts, c->cnt.p, sizeof(c->counts), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (int k = 0; k < DPE_NUM_CLASSES; ++k) c->counts[4 * k + 3] = (unsigned long long)c->launches[k];
+  return DPE_OK;
+}
+
+// The setup chain: GenEdgeInform and its edge rays, FindNearestStrongPoint's tables, the all-WEAK
+// list, GenNeighbours, NeigbourUpdate, then the pixel lists.  Streams: all of it on `a`; overlapped,
+// `s` first builds the pre-GenNeighbours sweep lists and forks `a`, which marks ev_ei behind the
+// edge rays and ev_join at its end.
+// Why the fork is legal: GenNeighbours + NeigbourUpdate only decide which WEAK pixels join the strong
+// lists.  Nothing RandomInitialization or the first strong half-sweep (iteration 0, colour 0) reads
+// is written by them, and GenNeighbours reads the staged planes, not the ones those two rewrite; that
+// half-sweep needs GenEdgeInform's edge rays only (ev_ei).  So it runs over the pre-GenNeighbours
+// colour-0 strong list, and the colour-0 pixels whose GenNeighbours failed (NeigbourUpdate makes them
+// UNKNOWN; the failed list) get the same half-sweep, same snapshot, once the streams join
+// (strong_half_sweep).  Pixels of one half-sweep are independent, so this is the reference's order of
+// results (GPU test test_overlapped_and_sequential_schedules_agree).
+static int setup_chain(PassRun& X) {
+  DpeContext* c = X.c;
+  const PassConst& pc = X.pc;
+  const hipStream_t a = X.a;
+  Section sec(X.rec, DPE_CLASS_SETUP);
+  const DevBufs& Bc = sec.B;
+  if (X.overlap) sweep_lists(X, Bc);   // pre-GenNeighbours: the colour-0 strong list is the one used
+  HIPC(X.fork(c->ev_fork));
+  TRY(clear_setup_state(X, a));
+  k_gen_edge_inform<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc);
+  if (pc.P.use_edge) k_edge_rays<<<(unsigned)(3 * (pc.W + pc.H) - 2), 64, 0, a>>>(X.dpc, Bc);
+#if DPE_GN_ONCE   // GenEdgeInform rewrites complex_: GenNeighbours' kept one is restored after it
+  if (X.gn_skip) HIPC(hipMemcpyAsync(X.B.complex_, c->gn_complex.p, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
+#endif
+  HIPC(X.aux_done(c->ev_ei));
+  k_strong_tables_scan<<<(unsigned)(pc.W + pc.H), 64, 0, a>>>(X.dpc, Bc, c->tab_right.p, c->tab_down.p);
+  k_find_nearest_strong<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc, c->tab_right.p, c->tab_down.p);
+  build_lists<1>(X, a, Bc, X.lay.all_weak_rows(), PassLists::kTotAllWeak, X.lay.all_weak());
+  TRY(gen_neighbours(X, Bc));
+  k_neighbour_update<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc);
+  // weak_info is fixed from here until DepthToWeak.  Overlapped, `s` may be inside its first strong
+  // half-sweep: `a` builds the failed list only (regions of its own in every list buffer), and `s`
+  // rebuilds the sweep lists after the join
+  if (X.overlap) build_lists<2>(X, a, Bc, X.lay.failed_rows(), PassLists::kTotFailed, X.lay.failed());
+  else sweep_lists(X, Bc);
+  HIPC(X.aux_done(c->ev_join));
+  return DPE_OK;
+}
+
+// RandomInitialization, on `s`; the strong sweeps behind it read GenEdgeInform's rays (ev_ei).
+static int random_initialization(PassRun& X) {
+  {
+    Section sec(X.rec, DPE_CLASS_INIT);
+    if (X.c->img_cls != IMG_F32) k_random_init<kTexInit><<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
+    else k_random_init<TEX_F32><<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
   }
+  HIPC(X.wait_aux(X.c->ev_ei));
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+// CheckerboardPropagationStrong + refinement over one list, on `s`
+static void strong_sweep(const PassRun& X, const DevBufs& Bs, int it, PassLists::Region list, int total) {
+  const bool edge = X.pc.P.use_edge;
+  const int P = edge ? 4 : 8, C = edge ? 16 : 8;
+  const size_t lds = (size_t)kBwStrong * strong_lds_per_wave(P, C, X.nv) * sizeof(float);
+  const unsigned grid = (unsigned)((X.L / 2 + 1 + kBwStrong * P - 1) / (kBwStrong * P));
+  launch_strong(edge, X.c->img_cls, grid, lds, X.s, X.dpc, Bs, it, X.list(list), X.total(total));
+}
+
+// One colour's strong half-sweep over the snapshot of the state before it, on `s`.  Overlapped, the
+// first one of the pass (over the pre-GenNeighbours list) is where `s` joins the setup chain
+// (ev_join): it then sweeps the failed list over the same snapshot and builds the final sweep lists.
+static int strong_half_sweep(PassRun& X, int it, int colour) {
+  const DevBufs& B = X.B;
+  k_snapshot<<<(unsigned)((X.L + 255) / 256), 256, 0, X.s>>>((const uint4*)B.planes, (const uint32_t*)B.costs, B.sel,
+                                                               (uint4*)B.planes_snap, (uint32_t*)B.costs_snap, B.sel_snap, X.L);
+  Section sec(X.rec, DPE_CLASS_STRONG);
+  strong_sweep(X, sec.B, it, X.lay.sweep(colour, 0), PassLists::total_sweep(colour, 0));
+  if (X.overlap && it == 0 && colour == 0) {
+    HIPC(X.wait_aux(X.c->ev_join));
+    strong_sweep(X, sec.B, it, X.lay.failed(), PassLists::kTotFailed);
+    sweep_lists(X, sec.B);
+  }
+  return DPE_OK;
+}
+
+// CheckerboardPropagationWeak + refinement over one colour's weak list, on stream `st`
+static void weak_sweep(const PassRun& X, const DevBufs& Bc, int it, int colour, hipStream_t st) {
+  const int* lst = X.list(X.lay.sweep(colour, 1));
+  const int* cnt = X.total(PassLists::total_sweep(colour, 1));
+  if (X.pc.P.use_radius) {   // the fits just set the radii: partition the list by centre-patch side
+    const unsigned pg = (unsigned)X.lay.chunks();
+    int* pcnt = X.chunk_counts(colour);
+    int* tot = X.total(PassLists::total_side(colour));
+    int* out = X.list(X.lay.side(colour));
+    k_part_count<<<pg, 256, 0, st>>>(X.dpc, Bc, lst, cnt, pcnt);
+    k_part_scan<<<1, 256, 0, st>>>(cnt, pcnt, tot);
+    k_part_fill<<<pg, 256, 0, st>>>(X.dpc, Bc, lst, cnt, pcnt, tot, out);
+    lst = out;
+  }
+  constexpr int C = kWeakLanes, P = 64 / C;
+  const size_t per_wave = (size_t)P * weak_lds_per_pixel(X.nv) * sizeof(float);
+  const int wpb = per_wave * 4 <= 64 * 1024 ? 4 : (per_wave * 2 <= 64 * 1024 ? 2 : 1);
+  const unsigned grid = (unsigned)((X.L / 2 + 1 + wpb * P - 1) / (wpb * P));
+  // U8 texels for 8-bit images; F16 (exact for quarter-integer grey levels) for the coarse levels
+  if (X.c->img_cls == IMG_U8) k_weak_coop<kTexWeak, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+  else if (X.c->img_cls == IMG_Q) k_weak_coop<TEX_F16, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+  else k_weak_coop<TEX_F32, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+}
+
+// RANSACToGetFitPlane and the weak sweeps of one iteration.  Streams: colour 0 on `s`, colour 1 on
+// `a`, forked before the fits (the colour-1 fit must not wait for the colour-0 one) and joined behind
+// the sweeps.
+// Why the fork is legal: a weak sweep reads only STRONG pixels' state besides its own pixel (planes
+// and selected views of the GenNeighbours support points, DPE.cu:1690-1725; the NCC-New patches come
+// from the images) and writes only its own pixel, so the two colours are independent (their launch
+// tails overlap).  A fit reads STRONG pixels and writes its own pixel's fit plane, which only its
+// own weak update reads, so each colour's fits run on that colour's stream just before its sweep.
+static int fits_and_weak_sweeps(PassRun& X, int it) {
+  const unsigned rl_grid = (unsigned)((X.L / 2 + 1 + kRansacThreads - 1) / kRansacThreads);
+  HIPC(X.fork(X.c->ev_fork));
+  {
+    Section sec(X.rec, DPE_CLASS_RANSAC);
+    for (int colour = 1; colour >= 0; --colour)
+      k_ransac_fit<<<rl_grid, kRansacThreads, 0, colour == 1 ? X.a : X.s>>>(
+          X.dpc, sec.B, it, X.list(X.lay.sweep(colour, 1)), X.total(PassLists::total_sweep(colour, 1)));
+  }
+  for (int colour = 0; colour < 2; ++colour) {
+    Section sec(X.rec, DPE_CLASS_WEAK);
+    weak_sweep(X, sec.B, it, colour, colour == 1 ? X.a : X.s);
+  }
+  HIPC(X.join(X.c->ev_join));
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+// GetDepthandNormal and CheckerboardFilterStrong, on `s`
+static void filter(PassRun& X) {
+  const dim3 hb(32, 4), hg((((X.pc.W + 1) / 2) + 31) / 32, (X.pc.half_rows + 3) / 4);   // hb: 32 x 4 = kFilterThreads
+  Section sec(X.rec, DPE_CLASS_FILTER);
+  k_depth_normal<<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
+  for (int colour = 0; colour < 2; ++colour) k_filter<<<hg, hb, 0, X.s>>>(X.dpc, sec.B, colour);
+}
+
+// DepthToWeak (LocalRefine fused for interior pixels) on `s`, and LocalRefine on the 6-px border that
+// DepthToWeak leaves to it: overlapped on `a` beside DepthToWeak, else on `s` behind it.
+// Why the fork is legal: the border LocalRefine reads and writes only its own pixel's plane besides
+// the images and source depths (DPE.cu:2749-2835), and DepthToWeak writes only interior pixels.  The
+// border kernel is launched first: it is small and would otherwise wait for DepthToWeak's slots.
+static int depth_to_weak(PassRun& X) {
+  DpeContext* c = X.c;
+  auto border_local_refine = [&](hipStream_t st) {
+    Section sec(X.rec, DPE_CLASS_LOCAL_REFINE);
+    launch_local_refine(c->img_cls, (long)X.L, X.pc.W, X.pc.H, X.nv, st, X.dpc, sec.B);
+  };
+  HIPC(X.fork(c->ev_fork));
+  if (X.overlap) border_local_refine(X.a);
+  HIPC(X.aux_done(c->ev_join));
+  {
+    Section sec(X.rec, DPE_CLASS_DEPTH_TO_WEAK);
+    launch_depth_to_weak(c->img_cls, (long)X.L, X.s, X.dpc, sec.B);
+  }
+  HIPC(X.wait_aux(c->ev_join));
+  if (!X.overlap) border_local_refine(X.s);
+  HIPC(hipGetLastError());
+  return DPE_OK;
+}
+
+#if DPE_GN_ONCE
+// Timing builds only (pass_common.h): GenNeighbours runs in the first execute after a stage and its
+// outputs (nb, weak_rel, and complex_, which GenEdgeInform rewrites: restored after it) are kept for
+// the next executes of the same staged state, which then skip it -- the same results (GenNeighbours
+// depends only on the staged state), and the pass time without GenNeighbours on the critical path.
+// An execute that fails forgets them.
+struct GnGuard {
+  DpeContext* c;
+  bool ok = false;
+  ~GnGuard() { if (!ok) c->gn_done_for_stage = false; }
+};
+#endif
+
+extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
+  TRY(enter(c, true, "dpe_pm_execute: null context"));
+  if (!c->staged) { g_err = "dpe_pm_execute: call dpe_pm_stage first"; return DPE_ERR_STATE; }
+  Range range_("dpe_pm_execute");
+  hipStream_t s;
+  // a previous execute, possibly on another stream, still uses the working buffers this one resets
+  HIPC(enqueue_stream(c, stream_, &s));
+  PassRun X(c, s);
+  TRY(X.rec.start(c, s, X.B));
+#if DPE_GN_ONCE
+  X.gn_skip = c->gn_done_for_stage;
+  GnGuard gn_guard{c};
+#endif
+  // initial state (the reference uploads it in CudaSpaceInitialization, DPE.cpp:964-1015); the rest
+  // of it is cleared by the setup chain
+  k_pass_init<<<(unsigned)((X.L + 255) / 256), 256, 0, s>>>((const uint4*)c->planes0.p, c->weak0.p, c->sel0.p, (uint4*)X.B.planes,
+                                                            X.B.weak, X.B.sel, (uint32_t*)X.B.costs, (uint4*)X.B.vw, X.L);
+  TRY(setup_chain(X));
+  TRY(random_initialization(X));
+  for (int it = 0; it < X.pc.P.max_iterations; ++it) {
+    for (int colour = 0; colour < 2; ++colour) TRY(strong_half_sweep(X, it, colour));
+    HIPC(hipGetLastError());
+    TRY(fits_and_weak_sweeps(X, it));
+  }
+  filter(X);
+  TRY(depth_to_weak(X));
+  TRY(X.rec.finish());
   HIPC(mark_pending(c, s));
 #if DPE_GN_ONCE
   gn_guard.ok = true;
@@ -1688,7 +1798,7 @@ extern "C" long long dpe_pm_last_stat(DpeContext* c, int stat) {
   if (!c || !c->staged || stat != DPE_STAT_GN_DEFERRED || !c->list_totals.p) return -1;
   int v = 0;   // waits for this context's pass only (not the whole device)
   if (hipSetDevice(c->device) != hipSuccess || wait_pending(c) != hipSuccess || hipStreamSynchronize(c->aux) != hipSuccess ||
-      hipMemcpyAsync(&v, c->list_totals.p + 6, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync(&v, c->list_totals.p + PassLists::kTotGnOverflow, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return -1;
   return v;

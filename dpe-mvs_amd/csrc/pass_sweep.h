@@ -15,6 +15,7 @@
 #include "pass_common.h"
 #include "pass_refine.h"
 #include "lds_layout.h"
+#include "pass_lists.h"
 #include "pool_tail.h"
 
 namespace dpe {
@@ -104,7 +105,7 @@ __global__ void k_list_fill(const PassConst* __restrict__ pcp, DevBufs B, const 
 // pixels one after the other.  After the fits, each colour's weak list is stably partitioned into
 // side >= 4 then side < 4 pixels (chunks of kPartChunk entries: count, scan, fill), so almost every
 // wave holds one side.  Pixels of a half-sweep are independent, so the order changes no result.
-constexpr int kPartChunk = 1024;
+// (kPartChunk: pass_lists.h, which sizes the chunk counts by it)
 DEV int weak_side(const PassConst& pc, const DevBufs& B, int center) {
   const int rad = B.radius[center], inc = MAXo(2, d2i(2.0 * rad / 5.0));
   return rad >= 0 ? (2 * rad) / inc + 1 : 0;

@@ -399,6 +399,45 @@ def test_zero_iterations_joins_the_aux_stream(ctx):
     assert_same(ctx.run(inp, st), oracle.run_pass(inp, st), "max_iterations 0")
 
 
+@pytest.mark.parametrize("W,H,iters", [(77, 33, 3), (12, 40, 3), (12, 40, 0)])
+def test_untimed_timed_and_counting_executes(ctx, W, H, iters):
+    # One staged pass, executed untimed (two streams when it iterates), timed and counting (one stream,
+    # per-class events / counters): each gives the oracle's bits, and the recorder reports the class
+    # sections of the launch sequence: setup, init, per iteration 2 strong + 1 ransac + 2 weak, filter,
+    # DepthToWeak, LocalRefine.
+    from DPE_MVS import native
+    sc = synthetic.make_scene(W, H, 3)
+    p = _params("refine_iter", iters=iters)
+    st = synthetic.gt_state(sc, seed=W + H)
+    inp = synthetic.pass_input(sc, p, depths=synthetic.src_depths(sc), seed=W * 7 + 3)
+    want = oracle.run_pass(inp, st)
+    sections = {"setup": 1, "init": 1, "strong": 2 * iters, "ransac": iters, "weak": 2 * iters, "filter": 1,
+                "depth_to_weak": 1, "local_refine": 1}
+    ctx.stage(inp, st)
+    try:
+        ctx.execute()
+        assert_same(ctx.fetch(), want, f"{W}x{H} it={iters} untimed")
+        ctx.set_timing(True)
+        ctx.execute()
+        assert_same(ctx.fetch(), want, f"{W}x{H} it={iters} timed")
+        t = ctx.timings()
+        ctx.set_timing(False)
+        ctx.set_counting(True)
+        ctx.execute()
+        assert_same(ctx.fetch(), want, f"{W}x{H} it={iters} counting")
+        n = ctx.counts()
+    finally:
+        ctx.set_timing(False)
+        ctx.set_counting(False)
+    print("timings", t, "counts", n)
+    assert {k: n[k]["launches"] for k in native.CLASSES} == sections
+    # the sections are disjoint intervals of one stream inside [start, last end]; what may exceed the
+    # total is f32 rounding: 21 elapsed times and the library's 20 f32 additions, each <= 2^-24 total
+    assert t["total"] > 0
+    assert sum(t[k] for k in native.CLASSES) <= t["total"] * (1 + 41 * 2.0 ** -24)
+    assert all(t[k] == 0 for k in native.CLASSES if sections[k] == 0)
+
+
 def _random_case(seed):
     """A seeded random pass configuration: size, views, pass type and the schedule's switches
     (rotate_time, labels, edge limit, radius map, resolution class, iterations, peak radius,
