@@ -92,6 +92,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_state_fetch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]
     lib.dpe_state_fetch.restype = C.c_int
+    lib.dpe_device_buffer.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    lib.dpe_device_buffer.restype = C.c_void_p
     lib.dpe_sync.argtypes = [C.c_void_p]
     lib.dpe_sync.restype = C.c_int
     lib.dpe_state_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]

@@ -1,6 +1,8 @@
 // dpe_context.h -- what a DpeContext (include/dpe_mvs.h) holds: device arrays, streams and events that
-// own their HIP resources, the cached images, the resident states and the context itself.  Internal
-// to csrc/dpe_mvs.hip.
+// own their HIP resources, the cached images, the resident states and the context itself, its members
+// grouped by the unit that owns them.  Internal to the library and shared by its units (dpe_mvs.hip,
+// dpe_state.hip, dpe_edges.hip, dpe_viz.hip, dpe_fusion.hip): every type here is an ordinary named
+// type and the byte counter has one definition in the process.  Includes no kernel header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -12,12 +14,12 @@
 #include <vector>
 
 #include "pass_common.h"
-#include "pass_fusion.h"
-#include "pass_fusion_tat.h"
+#include "tap_launch.h"          // ImgClass
+#include "dpe_fusion_types.h"
 
-namespace {
+namespace dpe {
 
-std::atomic<long long> g_live_bytes{0};   // dpe_live_device_bytes: what every DevArr of the process holds
+inline std::atomic<long long> g_live_bytes{0};   // dpe_live_device_bytes: what every DevArr of the process holds
 
 // A device array that owns its allocation (move-only; freed with its owner).  ensure() only grows,
 // and keeps 256 bytes behind the last element.
@@ -72,13 +74,11 @@ struct Event {
   operator hipEvent_t() const { return e; }
 };
 
-}  // namespace
-
 // An image kept in HBM across passes (DpePassInput.image_ids): its f32 grey levels and the gather
 // layouts built from them.
 struct CachedImage {
   int id = 0, W = 0, H = 0;
-  int cls = dpe::IMG_F32;   // ImgClass of the grey levels
+  int cls = IMG_F32;        // ImgClass of the grey levels
   DevArr<float> plain;
   DevArr<uint32_t> q8;      // TEX_U8 quad texels (8-bit images)
   DevArr<uint2> q16;        // TEX_F16 quad texels (8-bit images)
@@ -89,7 +89,7 @@ struct CachedImage {
 };
 
 // Per-image pipeline state kept in HBM between passes (the reference's depths.dmb / normals.dmb /
-// weak.bin / selected_views.bin round trip, main.cpp:439-446 -> DPE.cpp:826-911).
+// weak.bin / selected_views.bin round trip, main.cpp:439-446 -> DPE.cpp:826-911).  dpe_state.hip.
 struct ResState {
   int w = 0, h = 0;
   bool full = false;          // planes / weak / sel of a pass of this image; false: depth only (imported)
@@ -101,32 +101,9 @@ struct ResState {
   bool has_snap = false;
 };
 
-// Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
-// reverse order: the streams and events are declared first and so outlive every buffer.
-struct DpeContext {
-  int device = 0;
-  Stream stream;
-  Stream aux;                        // GenNeighbours beside the first strong half-sweep
-  Event ev_fork, ev_join, ev_ei;
-  Event ev_done;                     // end of the last dpe_pm_execute's work on its stream
-  Event ev_tat;                      // end of the last copy-out of dpe_fusion_tat_image (on `aux`)
-  Event ev_start;                    // timing: start of the pass
-  std::vector<Event> ev;             // timing: (start, end) per launch class slot
-  std::mutex viz_mu;                 // guards viz_ev (dpe_state_render_wait runs on other host threads)
-  std::map<const void*, Event> viz_ev;   // per host block buffer: end of the last copy into it
-  std::map<int, ResState> rstore;    // node addresses are stable: StageSrc points into it
-  DevArr<float> xbuf[2];             // dpe_device_buffer: exchange buffers of the multi-rank schedule
-  // EdgeSegment stages (dpe_canny / dpe_resize_* / dpe_roberts_threshold): scratch
-  DevArr<uint8_t> e_a, e_b, e_map;
-  DevArr<float> e_fa, e_fb;
-  DevArr<int> e_rows, e_mag, e_itab;
-  DevArr<int16_t> e_dx, e_dy;
-  DevArr<float> e_ftab;
-  DevArr<short> e_stab;
-  bool snap_mode = false;            // stage_resident reads source depths from the Jacobi snapshots
-  std::vector<std::unique_ptr<CachedImage>> icache;
-  uint64_t icache_clock = 0;
-  bool pending = false;              // ev_done recorded and not yet waited for
+// What the pass works in (dpe_mvs.hip: dpe_pm_stage / dpe_pm_execute): its settings and records, the
+// staged inputs, the initial state, the working set and the pixel lists.
+struct PassWork {
   bool staged = false;
 #if DPE_GN_ONCE
   bool gn_done_for_stage = false;    // GenNeighbours' outputs of this staged state are kept
@@ -140,15 +117,15 @@ struct DpeContext {
   unsigned long long counts[DPE_NUM_CLASSES * 4] = {0};
   DevArr<unsigned long long> cnt;
   DevArr<unsigned long long> phase;  // DPE_PHASE_PROF builds: per-phase cycle sums
-  dpe::PassConst hc;                 // host copy of the pass constants
-  DevArr<dpe::PassConst> dc;
+  PassConst hc;                      // host copy of the pass constants
+  DevArr<PassConst> dc;
   // inputs
   DevArr<float> img_plain[DPE_MAX_IMAGES];  // plain f32 images (ref used directly)
   DevArr<float4> imgq[DPE_MAX_IMAGES];
   DevArr<uint32_t> imgq8_all;        // all 8-bit quad images, TEX_U8 layout, one allocation
   DevArr<uint2> imgq16_all;          //   and TEX_F16 layout (32-bit tap offsets)
   DevArr<uint32_t> imgqp_all;        //   and TEX_P16 column pairs
-  int img_cls = dpe::IMG_F32;        // ImgClass of the pass (the narrowest class of its views)
+  int img_cls = IMG_F32;             // ImgClass of the pass (the narrowest class of its views)
   DevArr<float> depth[DPE_MAX_IMAGES];
   DevArr<uint8_t> edge, edge_low;
   DevArr<int> label;
@@ -169,33 +146,86 @@ struct DpeContext {
   // the pass's pixel lists; their regions are named by PassLists (pass_lists.h)
   DevArr<int> lists, row_counts, list_totals;   // pixel indices / per-row counts / one total per list
   DevArr<int> part_cnt;                          // per colour: chunk counts / offsets of the weak-list partition
-  dpe::DevBufs bufs;
-  // fusion (dpe_fusion_stage / dpe_fusion_candidates)
-  std::vector<DevArr<float>> fz_depth, fz_normal;
-  std::vector<dpe::FusionViewDev> fz_host;
-  DevArr<dpe::FusionViewDev> fz_views;
-  DevArr<DpeCamera> fz_cams;
-  DevArr<int> fz_src;
-  DevArr<int32_t> fz_idx;
-  DevArr<float> fz_val;
-  int fz_n = 0;
-  // the Tanks-and-Temples fusions (dpe_fusion_tat_begin / dpe_fusion_tat_image), over the staged views
-  std::vector<DevArr<uint8_t>> tat_bgr, tat_block, tat_mask;
-  DevArr<dpe::TatViewDev> tat_views;
-  bool tat_ready = false;
-  DevArr<float> tat_dthr;            // dot-product thresholds of the angle test, by k
-  DevArr<int> tat_last, tat_agg;     // per (view, pixel) last hit of the block / per (view, chunk) carry
-  DevArr<int> tat_cnt, tat_tot;      // fused pixels per chunk -> offsets; the image's total
-  DevArr<uint8_t> tat_emit;
-  DevArr<dpe::TatPoint> tat_rec;     // per pixel: the point it contributes
-  DevArr<dpe::TatPoint> tat_out[2];  // compacted points, double-buffered: the copy-out of one image
-  int tat_turn = 0;                  //   runs on `aux` beside the kernels of the next
-  bool tat_copying = false;          // ev_tat recorded and not yet waited for
-  // viz medium results (dpe_state_render*): scratch, allocated on first use
-  DevArr<uint8_t> viz_bgr;           // the rendered picture
-  DevArr<int16_t> viz_blocks;        // its quantised JPEG blocks
-  DevArr<uint16_t> viz_q;            // quantisation tables of viz_quality (64 luma + 64 chroma)
-  int viz_quality = 0;
-  DevArr<float4> viz_planes;         // dpe_viz_render_arrays: the caller's arrays
-  DevArr<uint8_t> viz_weak;
+  DevBufs bufs;
+};
+
+// EdgeSegment stages (dpe_edges.hip: dpe_canny / dpe_resize_* / dpe_roberts_threshold): scratch
+struct EdgeScratch {
+  DevArr<uint8_t> a, b, map;
+  DevArr<float> fa, fb;
+  DevArr<int> rows, mag, itab;
+  DevArr<int16_t> dx, dy;
+  DevArr<float> ftab;
+  DevArr<short> stab;
+};
+
+// the views of a fusion (dpe_fusion.hip: dpe_fusion_stage / dpe_fusion_candidates)
+struct FusionStage {
+  std::vector<DevArr<float>> depth, normal;
+  std::vector<FusionViewDev> host;
+  DevArr<FusionViewDev> views;
+  DevArr<DpeCamera> cams;
+  DevArr<int> src;
+  DevArr<int32_t> idx;
+  DevArr<float> val;
+  int n = 0;
+};
+
+// the Tanks-and-Temples fusions (dpe_fusion.hip: dpe_fusion_tat_begin / dpe_fusion_tat_image), over the
+// staged views.  `ev` is declared first and so outlives the buffers.
+struct TatFusion {
+  Event ev;                          // end of the last copy-out of dpe_fusion_tat_image (on the aux stream)
+  std::vector<DevArr<uint8_t>> bgr, block, mask;
+  DevArr<TatViewDev> views;
+  bool ready = false;
+  DevArr<float> dthr;                // dot-product thresholds of the angle test, by k
+  DevArr<int> last, agg;             // per (view, pixel) last hit of the block / per (view, chunk) carry
+  DevArr<int> cnt, tot;              // fused pixels per chunk -> offsets; the image's total
+  DevArr<uint8_t> emit;
+  DevArr<TatPoint> rec;              // per pixel: the point it contributes
+  DevArr<TatPoint> out[2];           // compacted points, double-buffered: the copy-out of one image
+  int turn = 0;                      //   runs on the aux stream beside the kernels of the next
+  bool copying = false;              // `ev` recorded and not yet waited for
+  // the colours and masks of dpe_fusion_tat_begin belong to the views staged before: a new
+  // dpe_fusion_stage makes dpe_fusion_tat_image wait for a new dpe_fusion_tat_begin
+  void views_restaged() { ready = false; }
+};
+
+// viz medium results (dpe_viz.hip: dpe_state_render*): scratch, allocated on first use.  `ev` is
+// declared first and so outlives the buffers.
+struct VizScratch {
+  std::mutex mu;                     // guards ev (dpe_state_render_wait runs on other host threads)
+  std::map<const void*, Event> ev;   // per host block buffer: end of the last copy into it
+  DevArr<uint8_t> bgr;               // the rendered picture
+  DevArr<int16_t> blocks;            // its quantised JPEG blocks
+  DevArr<uint16_t> q;                // quantisation tables of `quality` (64 luma + 64 chroma)
+  int quality = 0;
+  DevArr<float4> planes;             // dpe_viz_render_arrays: the caller's arrays
+  DevArr<uint8_t> weak;
+};
+
+}  // namespace dpe
+
+// Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
+// reverse order: the streams and events are declared first and so outlive every buffer (the events of
+// one group alone, tat.ev and viz.ev, are the first members of their group).
+struct DpeContext {
+  int device = 0;
+  dpe::Stream stream;
+  dpe::Stream aux;                   // GenNeighbours beside the first strong half-sweep
+  dpe::Event ev_fork, ev_join, ev_ei;
+  dpe::Event ev_done;                // end of the last dpe_pm_execute's work on its stream
+  dpe::Event ev_start;               // timing: start of the pass
+  std::vector<dpe::Event> ev;        // timing: (start, end) per launch class slot
+  bool pending = false;              // ev_done recorded and not yet waited for
+  std::map<int, dpe::ResState> rstore;   // node addresses are stable: StageSrc points into it
+  bool snap_mode = false;            // stage_resident reads source depths from the Jacobi snapshots
+  dpe::DevArr<float> xbuf[2];        // dpe_device_buffer: exchange buffers of the multi-rank schedule
+  std::vector<std::unique_ptr<dpe::CachedImage>> icache;
+  uint64_t icache_clock = 0;
+  dpe::PassWork pass;
+  dpe::EdgeScratch edges;
+  dpe::FusionStage fz;
+  dpe::TatFusion tat;
+  dpe::VizScratch viz;
 };

@@ -1,5 +1,9 @@
-// dpe_mvs.hip — the C-ABI library (include/dpe_mvs.h): context, HBM staging and the launch
-// sequence of one PatchMatch pass on gfx950.
+// dpe_mvs.hip — the main unit of the C-ABI library (include/dpe_mvs.h): the context's life cycle,
+// the entry-point rules every unit shares (dpe_entry.h: error string, prologue, waiting), HBM staging
+// and the launch sequence of one PatchMatch pass on gfx950.  The other entry points are in units of
+// their own: dpe_state.hip (resident states, exchange buffers), dpe_edges.hip (EdgeSegment stages),
+// dpe_viz.hip (viz medium results) and dpe_fusion.hip (the fusions); the strong sweep, DepthToWeak
+// and LocalRefine launch from tap_launch.hip / tap_f32.hip.
 //
 // Replaces DPE::CudaSpaceInitialization / SetDataPassHelperInCuda / RunPatchMatch / getters
 // (DPE.cpp:916-1121, DPE.cu:3126-3249).  Differences by design:
@@ -11,28 +15,21 @@
 // dpe_pm_stage is stage_impl's named steps; dpe_pm_execute is the named steps of one pass ("one
 // pass" below) over the pixel-list layout of pass_lists.h.
 #include <hip/hip_runtime.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <atomic>
-#include <map>
 #include <memory>
-#include <mutex>
 #include <utility>
 #include <vector>
 
 #include "pass_tables.h"
 #include "pass_kernels.h"
 #include "pass_refine.h"
-#include "pass_fusion.h"
-#include "pass_fusion_tat.h"
 #include "pass_sweep.h"
-#include "pass_edges.h"
-#include "pass_viz.h"
 #include "tap_launch.h"
+#include "dpe_entry.h"
 #include "dpe_context.h"
 
 using namespace dpe;
@@ -40,35 +37,7 @@ using namespace dpe;
 static const int kDefaultXcdRows = 1;
 static constexpr int kWeakLanes = 16;   // lanes per weak pixel in k_weak_coop
 
-namespace {
-
-thread_local std::string g_err;
-
-// roctx ranges (SURVEY.md §5 tracing): host-side enqueue regions of the pass, visible in
-// `rocprofv3 --marker-trace` beside the kernel trace
-struct Range {
-  explicit Range(const char* m) { roctxRangePushA(m); }
-  ~Range() { roctxRangePop(); }
-  Range(const Range&) = delete;
-  Range& operator=(const Range&) = delete;
-};
-
-#define HIPC(expr)                                                                  \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess) {                                                         \
-      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
-      return DPE_ERR_HIP;                                                           \
-    }                                                                               \
-  } while (0)
-
-// a step of a longer sequence: its DPE_* code ends the caller unless it is DPE_OK
-#define TRY(expr)                                                                   \
-  do {                                                                              \
-    if (const int rc_ = (expr); rc_ != DPE_OK) return rc_;                          \
-  } while (0)
-
-}  // namespace
+thread_local std::string dpe::g_err;
 
 extern "C" {
 
@@ -114,7 +83,7 @@ DpeContext* dpe_create(int device) {
   c->device = device;
   if (c->stream.create() != hipSuccess) { g_err = "dpe_create: stream"; return nullptr; }
   if (c->aux.create() != hipSuccess || c->ev_fork.create() != hipSuccess || c->ev_join.create() != hipSuccess ||
-      c->ev_ei.create() != hipSuccess || c->ev_done.create() != hipSuccess || c->ev_tat.create() != hipSuccess ||
+      c->ev_ei.create() != hipSuccess || c->ev_done.create() != hipSuccess || c->tat.ev.create() != hipSuccess ||
       c->ev_start.create(hipEventDefault) != hipSuccess) {
     g_err = "dpe_create: aux stream";
     return nullptr;
@@ -143,47 +112,39 @@ DpeContext* dpe_create(int device) {
 //   * The EdgeSegment stages and the fusion calls use the context's stream and scratch of their own,
 //     and synchronise the stream before they return.  dpe_fusion_tat_image does so too (its kernels
 //     have finished when it returns) and then leaves ONE copy in flight: the points of the image, on
-//     the aux stream into the caller's buffer, with `ev_tat` recorded behind it.  The next
+//     the aux stream into the caller's buffer, with `tat.ev` recorded behind it.  The next
 //     dpe_fusion_tat_image launches its kernels first (they write the other half of the double
 //     buffer), then waits for that event before it enqueues its own copy; dpe_fusion_tat_begin,
 //     dpe_fusion_tat_wait and dpe_destroy (which synchronises aux) wait for it as well.
+// The helpers that carry it (declared and described in dpe_entry.h, for every unit):
 
-// Host-waits for the work of the last dpe_pm_execute, which may have been enqueued on a caller
-// stream: staging, fetching and freeing must not overwrite or release buffers that pass still uses.
-static hipError_t wait_pending(DpeContext* c) {
+hipError_t dpe::wait_pending(DpeContext* c) {
   hipError_t e = hipSuccess;
   if (c->pending) { e = hipEventSynchronize(c->ev_done); c->pending = false; }
   return e;
 }
 
-// Host-waits until the context is quiet: the pending work, then everything on its own stream.
-static hipError_t host_wait(DpeContext* c) {
+hipError_t dpe::host_wait(DpeContext* c) {
   const hipError_t e = wait_pending(c);
   return e != hipSuccess ? e : hipStreamSynchronize(c->stream);
 }
 
-// The stream an entry point enqueues on (the caller's, or the context's for nullptr), after making it
-// wait for the pending work.
-static hipError_t enqueue_stream(DpeContext* c, void* caller_stream, hipStream_t* s) {
+hipError_t dpe::enqueue_stream(DpeContext* c, void* caller_stream, hipStream_t* s) {
   *s = caller_stream ? (hipStream_t)caller_stream : (hipStream_t)c->stream;
   return c->pending ? hipStreamWaitEvent(*s, c->ev_done, 0) : hipSuccess;
 }
 
-// Makes the work enqueued on `s` so far the pending work that later calls wait for.
-static hipError_t mark_pending(DpeContext* c, hipStream_t s) {
+hipError_t dpe::mark_pending(DpeContext* c, hipStream_t s) {
   const hipError_t e = hipEventRecord(c->ev_done, s);
   if (e == hipSuccess) c->pending = true;
   return e;
 }
 
-// The same for work that went on a caller's stream; the context's own stream orders its work itself.
-static hipError_t publish_foreign(DpeContext* c, hipStream_t s) {
+hipError_t dpe::publish_foreign(DpeContext* c, hipStream_t s) {
   return s == (hipStream_t)c->stream ? hipSuccess : mark_pending(c, s);
 }
 
-// The prologue of an entry point: clears the thread's error, refuses a null context or bad arguments
-// with DPE_ERR_ARG and `bad_args`, and selects the context's device.
-static int enter(DpeContext* c, bool args_ok, const char* bad_args) {
+int dpe::enter(DpeContext* c, bool args_ok, const char* bad_args) {
   g_err.clear();
   if (!c || !args_ok) { g_err = bad_args; return DPE_ERR_ARG; }
   HIPC(hipSetDevice(c->device));
@@ -209,7 +170,7 @@ void dpe_destroy(DpeContext* c) {
 
 long long dpe_live_device_bytes(void) { return g_live_bytes.load(); }
 
-void dpe_set_timing(DpeContext* c, int enable) { if (c) c->timing = enable != 0; }
+void dpe_set_timing(DpeContext* c, int enable) { if (c) c->pass.timing = enable != 0; }
 
 }  // extern "C"
 
@@ -266,17 +227,12 @@ static void compute_pass_constants(PassConst& pc) {
   build_spat36(pc.P.sigma_spatial, pc.spat36);
 }
 
+// this unit's own copies of the DPE_DIAG counters (tap_launch.h)
 #if DPE_POOL_STATS
-extern "C" void dpe_dbg_pool_stats_main(unsigned long long out[24], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_pool), sizeof(dpe::g_pool));
-  if (reset) { unsigned long long z[24] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_pool), z, sizeof(z)); }
-}
+DPE_DBG_READER(pool, main, dpe::g_pool, 24)
 #endif
 #if DPE_LINE_STATS
-extern "C" void dpe_dbg_line_stats_main(unsigned long long out[16], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_lstat), sizeof(dpe::g_lstat));
-  if (reset) { unsigned long long z[16] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_lstat), z, sizeof(z)); }
-}
+DPE_DBG_READER(line, main, dpe::g_lstat, 16)
 #endif
 #if DPE_GN_TIMES
 extern "C" void dpe_dbg_gn_times(unsigned int* out, int n) {
@@ -428,15 +384,15 @@ static int build_f32_quads(hipStream_t s, const float* plain, int W, int H, floa
 // tap offsets), sized for N views and bound into the pass's DevBufs.
 static int bind_packed_arrays(DpeContext* c, int cls, int W, int H, int N) {
   const size_t plane = quad_plane(W, H), pplane = pair_plane(W, H);
-  DevBufs& B = c->bufs;
+  DevBufs& B = c->pass.bufs;
   if (cls == IMG_U8) {
-    HIPC(c->imgq8_all.ensure(plane * N));
-    B.img8 = (const uint8_t*)c->imgq8_all.p; B.img8_view = (uint32_t)(plane * 4);
+    HIPC(c->pass.imgq8_all.ensure(plane * N));
+    B.img8 = (const uint8_t*)c->pass.imgq8_all.p; B.img8_view = (uint32_t)(plane * 4);
   }
-  HIPC(c->imgq16_all.ensure(plane * N));
-  HIPC(c->imgqp_all.ensure(pplane * N));
-  B.img16 = (const uint8_t*)c->imgq16_all.p; B.img16_view = (uint32_t)(plane * 8);
-  B.imgp = (const uint8_t*)c->imgqp_all.p; B.imgp_view = (uint32_t)(pplane * 4);
+  HIPC(c->pass.imgq16_all.ensure(plane * N));
+  HIPC(c->pass.imgqp_all.ensure(pplane * N));
+  B.img16 = (const uint8_t*)c->pass.imgq16_all.p; B.img16_view = (uint32_t)(plane * 8);
+  B.imgp = (const uint8_t*)c->pass.imgqp_all.p; B.imgp_view = (uint32_t)(pplane * 4);
   return DPE_OK;
 }
 
@@ -490,15 +446,15 @@ static int stage_images_cached(DpeContext* c, const DpePassInput* in) {
     TRY(cached_image(c, in->image_ids[i], in->images[i], W, H, call_clock, &ent[i]));
     view_cls[i] = ent[i]->cls;
   }
-  const int cls = c->img_cls = pass_class(W, H, N, view_cls);
-  DevBufs& B = c->bufs;
+  const int cls = c->pass.img_cls = pass_class(W, H, N, view_cls);
+  DevBufs& B = c->pass.bufs;
   if (cls != IMG_F32) {
     TRY(bind_packed_arrays(c, cls, W, H, N));
     for (int i = 0; i < N; ++i) {
       if (cls == IMG_U8)
-        HIPC(hipMemcpyAsync(c->imgq8_all.p + plane * i, ent[i]->q8.p, plane * 4, hipMemcpyDeviceToDevice, c->stream));
-      HIPC(hipMemcpyAsync(c->imgq16_all.p + plane * i, ent[i]->q16.p, plane * 8, hipMemcpyDeviceToDevice, c->stream));
-      HIPC(hipMemcpyAsync(c->imgqp_all.p + pplane * i, ent[i]->qp.p, pplane * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPC(hipMemcpyAsync(c->pass.imgq8_all.p + plane * i, ent[i]->q8.p, plane * 4, hipMemcpyDeviceToDevice, c->stream));
+      HIPC(hipMemcpyAsync(c->pass.imgq16_all.p + plane * i, ent[i]->q16.p, plane * 8, hipMemcpyDeviceToDevice, c->stream));
+      HIPC(hipMemcpyAsync(c->pass.imgqp_all.p + pplane * i, ent[i]->qp.p, pplane * 4, hipMemcpyDeviceToDevice, c->stream));
     }
   } else {
     for (int i = 0; i < N; ++i) {
@@ -521,22 +477,22 @@ static int stage_images_direct(DpeContext* c, const DpePassInput* in) {
   int view_cls[DPE_MAX_IMAGES];
   for (int i = 0; i < N; ++i)   // one f32 view decides: the rest are not scanned
     view_cls[i] = i > 0 && view_cls[i - 1] == IMG_F32 ? IMG_F32 : image_class(in->images[i], L);
-  const int cls = c->img_cls = pass_class(W, H, N, view_cls);
-  DevBufs& B = c->bufs;
+  const int cls = c->pass.img_cls = pass_class(W, H, N, view_cls);
+  DevBufs& B = c->pass.bufs;
   if (cls != IMG_F32) TRY(bind_packed_arrays(c, cls, W, H, N));
   for (int i = 0; i < N; ++i) {
-    HIPC(c->img_plain[i].ensure(L));
-    HIPC(hipMemcpyAsync(c->img_plain[i].p, in->images[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPC(c->pass.img_plain[i].ensure(L));
+    HIPC(hipMemcpyAsync(c->pass.img_plain[i].p, in->images[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (cls != IMG_F32) {
-      TRY(build_packed_layouts(c->stream, c->img_plain[i].p, W, H, cls == IMG_U8 ? c->imgq8_all.p + plane * i : nullptr,
-                               c->imgq16_all.p + plane * i, c->imgqp_all.p + pplane * i));
+      TRY(build_packed_layouts(c->stream, c->pass.img_plain[i].p, W, H, cls == IMG_U8 ? c->pass.imgq8_all.p + plane * i : nullptr,
+                               c->pass.imgq16_all.p + plane * i, c->pass.imgqp_all.p + pplane * i));
     } else {
-      HIPC(c->imgq[i].ensure(plane));
-      TRY(build_f32_quads(c->stream, c->img_plain[i].p, W, H, c->imgq[i].p));
-      B.imgq[i] = c->imgq[i].p;
+      HIPC(c->pass.imgq[i].ensure(plane));
+      TRY(build_f32_quads(c->stream, c->pass.img_plain[i].p, W, H, c->pass.imgq[i].p));
+      B.imgq[i] = c->pass.imgq[i].p;
     }
   }
-  B.ref = c->img_plain[0].p;
+  B.ref = c->pass.img_plain[0].p;
   return DPE_OK;
 }
 
@@ -547,36 +503,36 @@ static int stage_source_depths(DpeContext* c, const DpePassInput* in, const Stag
   const size_t L = (size_t)W * H;
   const dim3 rb2(32, 8), rg2((W + 31) / 32, (H + 7) / 8);
   for (int i = 1; i < in->num_images; ++i) {
-    HIPC(c->depth[i].ensure(L));
+    HIPC(c->pass.depth[i].ensure(L));
     if (src.st) {
-      HIPC(hipMemcpyAsync(c->depth[i].p, in->depths[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      HIPC(hipMemcpyAsync(c->pass.depth[i].p, in->depths[i], L * sizeof(float), hipMemcpyHostToDevice, c->stream));
     } else {
       const ResState* r = src.dep[i];
       if (src.dep_snap)
-        k_rescale_nearest<float><<<rg2, rb2, 0, c->stream>>>(r->snap.p, r->snap_w, r->snap_h, c->depth[i].p, W, H, 0.0f);
+        k_rescale_nearest<float><<<rg2, rb2, 0, c->stream>>>(r->snap.p, r->snap_w, r->snap_h, c->pass.depth[i].p, W, H, 0.0f);
       else
-        k_rescale_depth<<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->depth[i].p, W, H);
+        k_rescale_depth<<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->pass.depth[i].p, W, H);
       HIPC(hipGetLastError());
     }
-    c->bufs.depth[i] = c->depth[i].p;
+    c->pass.bufs.depth[i] = c->pass.depth[i].p;
   }
   return DPE_OK;
 }
 
 static int stage_edge_label_maps(DpeContext* c, const DpePassInput* in) {
   const size_t L = (size_t)in->width * in->height, LL = (size_t)in->low_width * in->low_height;
-  DevBufs& B = c->bufs;
+  DevBufs& B = c->pass.bufs;
   if (in->params.use_edge || in->params.use_limit) {
-    HIPC(c->edge.ensure(L));
-    HIPC(c->edge_low.ensure(LL));
-    HIPC(hipMemcpyAsync(c->edge.p, in->edge, L, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->edge_low.p, in->edge_low_res, LL, hipMemcpyHostToDevice, c->stream));
-    B.edge = c->edge.p; B.edge_low = c->edge_low.p;
+    HIPC(c->pass.edge.ensure(L));
+    HIPC(c->pass.edge_low.ensure(LL));
+    HIPC(hipMemcpyAsync(c->pass.edge.p, in->edge, L, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->pass.edge_low.p, in->edge_low_res, LL, hipMemcpyHostToDevice, c->stream));
+    B.edge = c->pass.edge.p; B.edge_low = c->pass.edge_low.p;
   }
   if (in->params.use_label) {
-    HIPC(c->label.ensure(L));
-    HIPC(hipMemcpyAsync(c->label.p, in->label, L * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    B.label = c->label.p;
+    HIPC(c->pass.label.ensure(L));
+    HIPC(hipMemcpyAsync(c->pass.label.p, in->label, L * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    B.label = c->pass.label.p;
   }
   return DPE_OK;
 }
@@ -587,25 +543,25 @@ static int stage_initial_state(DpeContext* c, const DpePassInput* in, const Stag
   const DpePatchMatchParams& P = in->params;
   const int W = in->width, H = in->height;
   const size_t L = (size_t)W * H;
-  HIPC(c->planes0.ensure(L)); HIPC(c->weak0.ensure(L)); HIPC(c->sel0.ensure(L));
+  HIPC(c->pass.planes0.ensure(L)); HIPC(c->pass.weak0.ensure(L)); HIPC(c->pass.sel0.ensure(L));
   if (const DpePassState* st = src.st) {
-    HIPC(hipMemcpyAsync(c->planes0.p, st->planes, L * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    if (P.use_APD) HIPC(hipMemcpyAsync(c->weak0.p, st->weak_info, L, hipMemcpyHostToDevice, c->stream));
-    else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));   // DPE.cpp:873-881
-    HIPC(hipMemcpyAsync(c->sel0.p, st->selected_views, L * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(c->pass.planes0.p, st->planes, L * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    if (P.use_APD) HIPC(hipMemcpyAsync(c->pass.weak0.p, st->weak_info, L, hipMemcpyHostToDevice, c->stream));
+    else HIPC(hipMemsetAsync(c->pass.weak0.p, DPE_STRONG, L, c->stream));   // DPE.cpp:873-881
+    HIPC(hipMemcpyAsync(c->pass.sel0.p, st->selected_views, L * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     return DPE_OK;
   }
   const ResState* r = src.prior;
   const dim3 rb2(32, 8), rg2((W + 31) / 32, (H + 7) / 8);
   if (P.state != DPE_FIRST_INIT) {
-    k_rescale_nearest<float4><<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->planes0.p, W, H, make_float4(0, 0, 0, 0));
-    k_rescale_nearest<uint32_t><<<rg2, rb2, 0, c->stream>>>(r->sel.p, r->w, r->h, c->sel0.p, W, H, 0u);
+    k_rescale_nearest<float4><<<rg2, rb2, 0, c->stream>>>(r->planes.p, r->w, r->h, c->pass.planes0.p, W, H, make_float4(0, 0, 0, 0));
+    k_rescale_nearest<uint32_t><<<rg2, rb2, 0, c->stream>>>(r->sel.p, r->w, r->h, c->pass.sel0.p, W, H, 0u);
   } else {
-    HIPC(hipMemsetAsync(c->planes0.p, 0, L * sizeof(float4), c->stream));
-    HIPC(hipMemsetAsync(c->sel0.p, 0, L * sizeof(uint32_t), c->stream));
+    HIPC(hipMemsetAsync(c->pass.planes0.p, 0, L * sizeof(float4), c->stream));
+    HIPC(hipMemsetAsync(c->pass.sel0.p, 0, L * sizeof(uint32_t), c->stream));
   }
-  if (P.use_APD) k_rescale_nearest<uint8_t><<<rg2, rb2, 0, c->stream>>>(r->weak.p, r->w, r->h, c->weak0.p, W, H, (uint8_t)0);
-  else HIPC(hipMemsetAsync(c->weak0.p, DPE_STRONG, L, c->stream));
+  if (P.use_APD) k_rescale_nearest<uint8_t><<<rg2, rb2, 0, c->stream>>>(r->weak.p, r->w, r->h, c->pass.weak0.p, W, H, (uint8_t)0);
+  else HIPC(hipMemsetAsync(c->pass.weak0.p, DPE_STRONG, L, c->stream));
   HIPC(hipGetLastError());
   return DPE_OK;
 }
@@ -613,25 +569,25 @@ static int stage_initial_state(DpeContext* c, const DpePassInput* in, const Stag
 // The buffers a pass works in, sized for W x H and bound into the pass's DevBufs.
 static int ensure_working_set(DpeContext* c, int W, int H) {
   const size_t L = (size_t)W * H;
-  HIPC(c->planes.ensure(L)); HIPC(c->planes_snap.ensure(L)); HIPC(c->fit_plane.ensure(L));
-  HIPC(c->costs.ensure(L)); HIPC(c->costs_snap.ensure(L)); HIPC(c->complex_.ensure(L));
-  HIPC(c->sel.ensure(L)); HIPC(c->sel_snap.ensure(L));
-  HIPC(c->weak.ensure(L)); HIPC(c->weak_rel.ensure(L)); HIPC(c->vw.ensure(L * DPE_MAX_IMAGES));
-  HIPC(c->nb.ensure(L * 9)); HIPC(c->nearest.ensure(L)); HIPC(c->edge_neigh.ensure(L * 8)); HIPC(c->lab_bound.ensure(L * 8));
-  HIPC(c->radius.ensure(L));
-  HIPC(c->tab_right.ensure(L)); HIPC(c->tab_down.ensure(L));
-  HIPC(c->gn_ovf.ensure(L + 64)); HIPC(c->gn_tab.ensure((size_t)W + H));
-  const PassLists lay(W, H, c->hc.half_rows);   // the layout dpe_pm_execute carves them by (pass_lists.h)
-  HIPC(c->lists.ensure((size_t)lay.lists_len())); HIPC(c->row_counts.ensure(lay.row_counts_len()));
-  HIPC(c->list_totals.ensure(PassLists::kTotals)); HIPC(c->part_cnt.ensure(lay.part_cnt_len()));
-  DevBufs& B = c->bufs;
-  B.planes = c->planes.p; B.planes_snap = c->planes_snap.p; B.fit_plane = c->fit_plane.p;
-  B.planes0 = c->planes0.p;
-  B.costs = c->costs.p; B.costs_snap = c->costs_snap.p; B.complex_ = c->complex_.p;
-  B.sel = c->sel.p; B.sel_snap = c->sel_snap.p;
-  B.weak = c->weak.p; B.weak_rel = c->weak_rel.p; B.vw = c->vw.p;
-  B.nb = c->nb.p; B.nearest = c->nearest.p; B.edge_neigh = c->edge_neigh.p; B.lab_bound = c->lab_bound.p;
-  B.radius = c->radius.p;
+  HIPC(c->pass.planes.ensure(L)); HIPC(c->pass.planes_snap.ensure(L)); HIPC(c->pass.fit_plane.ensure(L));
+  HIPC(c->pass.costs.ensure(L)); HIPC(c->pass.costs_snap.ensure(L)); HIPC(c->pass.complex_.ensure(L));
+  HIPC(c->pass.sel.ensure(L)); HIPC(c->pass.sel_snap.ensure(L));
+  HIPC(c->pass.weak.ensure(L)); HIPC(c->pass.weak_rel.ensure(L)); HIPC(c->pass.vw.ensure(L * DPE_MAX_IMAGES));
+  HIPC(c->pass.nb.ensure(L * 9)); HIPC(c->pass.nearest.ensure(L)); HIPC(c->pass.edge_neigh.ensure(L * 8)); HIPC(c->pass.lab_bound.ensure(L * 8));
+  HIPC(c->pass.radius.ensure(L));
+  HIPC(c->pass.tab_right.ensure(L)); HIPC(c->pass.tab_down.ensure(L));
+  HIPC(c->pass.gn_ovf.ensure(L + 64)); HIPC(c->pass.gn_tab.ensure((size_t)W + H));
+  const PassLists lay(W, H, c->pass.hc.half_rows);   // the layout dpe_pm_execute carves them by (pass_lists.h)
+  HIPC(c->pass.lists.ensure((size_t)lay.lists_len())); HIPC(c->pass.row_counts.ensure(lay.row_counts_len()));
+  HIPC(c->pass.list_totals.ensure(PassLists::kTotals)); HIPC(c->pass.part_cnt.ensure(lay.part_cnt_len()));
+  DevBufs& B = c->pass.bufs;
+  B.planes = c->pass.planes.p; B.planes_snap = c->pass.planes_snap.p; B.fit_plane = c->pass.fit_plane.p;
+  B.planes0 = c->pass.planes0.p;
+  B.costs = c->pass.costs.p; B.costs_snap = c->pass.costs_snap.p; B.complex_ = c->pass.complex_.p;
+  B.sel = c->pass.sel.p; B.sel_snap = c->pass.sel_snap.p;
+  B.weak = c->pass.weak.p; B.weak_rel = c->pass.weak_rel.p; B.vw = c->pass.vw.p;
+  B.nb = c->pass.nb.p; B.nearest = c->pass.nearest.p; B.edge_neigh = c->pass.edge_neigh.p; B.lab_bound = c->pass.lab_bound.p;
+  B.radius = c->pass.radius.p;
   return DPE_OK;
 }
 
@@ -640,19 +596,19 @@ static int stage_impl(DpeContext* c, const DpePassInput* in, const StageSrc& src
   TRY(stage_check_args(in));
   HIPC(hipSetDevice(c->device));
   HIPC(wait_pending(c));   // an earlier execute on a caller stream may still read what is overwritten here
-  set_pass_constants(c->hc, in);
-  HIPC(c->dc.ensure(1));
-  HIPC(hipMemcpyAsync(c->dc.p, &c->hc, sizeof(PassConst), hipMemcpyHostToDevice, c->stream));
-  std::memset(&c->bufs, 0, sizeof(c->bufs));
+  set_pass_constants(c->pass.hc, in);
+  HIPC(c->pass.dc.ensure(1));
+  HIPC(hipMemcpyAsync(c->pass.dc.p, &c->pass.hc, sizeof(PassConst), hipMemcpyHostToDevice, c->stream));
+  std::memset(&c->pass.bufs, 0, sizeof(c->pass.bufs));
   TRY(in->image_ids ? stage_images_cached(c, in) : stage_images_direct(c, in));
   if (in->params.geom_consistency) TRY(stage_source_depths(c, in, src));
   TRY(stage_edge_label_maps(c, in));
   TRY(stage_initial_state(c, in, src));
   TRY(ensure_working_set(c, in->width, in->height));
   HIPC(hipStreamSynchronize(c->stream));
-  c->staged = true;
+  c->pass.staged = true;
 #if DPE_GN_ONCE
-  c->gn_done_for_stage = false;
+  c->pass.gn_done_for_stage = false;
 #endif
   return DPE_OK;
 }
@@ -720,24 +676,24 @@ struct PassRecorder {
   // buffer of a DPE_PHASE_PROF build) outlives the sections.
   int start(DpeContext* c_, hipStream_t s_, DevBufs& B) {
     c = c_; s = s_; base = &B;
-    timing = c->timing;
+    timing = c->pass.timing;
 #if DPE_PHASE_PROF
-    HIPC(c->phase.ensure(32 * 64));
-    HIPC(hipMemsetAsync(c->phase.p, 0, 32 * 64 * sizeof(unsigned long long), s));
-    B.phase = c->phase.p;
+    HIPC(c->pass.phase.ensure(32 * 64));
+    HIPC(hipMemsetAsync(c->pass.phase.p, 0, 32 * 64 * sizeof(unsigned long long), s));
+    B.phase = c->pass.phase.p;
 #endif
-    if (c->counting) {
-      HIPC(c->cnt.ensure(DPE_NUM_CLASSES * 4));
-      HIPC(hipMemsetAsync(c->cnt.p, 0, DPE_NUM_CLASSES * 4 * sizeof(unsigned long long), s));
+    if (c->pass.counting) {
+      HIPC(c->pass.cnt.ensure(DPE_NUM_CLASSES * 4));
+      HIPC(hipMemsetAsync(c->pass.cnt.p, 0, DPE_NUM_CLASSES * 4 * sizeof(unsigned long long), s));
     }
-    max_slots = 5 + 5 * std::max(0, c->hc.P.max_iterations);
+    max_slots = 5 + 5 * std::max(0, c->pass.hc.P.max_iterations);
     while (timing && (int)c->ev.size() < 2 * max_slots) {
       Event e;
       HIPC(e.create(hipEventDefault));
       c->ev.push_back(std::move(e));
     }
     ev_class.assign(timing ? max_slots : 0, 0);
-    for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->launches[k] = 0;
+    for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->pass.launches[k] = 0;
     if (timing) (void)hipEventRecord(c->ev_start, s);
     return DPE_OK;
   }
@@ -750,8 +706,8 @@ struct PassRecorder {
     int slot = -1;
     Section(PassRecorder& r_, int cls) : B(*r_.base), r(r_) {
       roctxRangePushA(kClassName[cls]);
-      if (r.c->counting) B.cnt = r.c->cnt.p + 4 * cls;
-      r.c->launches[cls]++;
+      if (r.c->pass.counting) B.cnt = r.c->pass.cnt.p + 4 * cls;
+      r.c->pass.launches[cls]++;
       if (r.timing && r.nev < r.max_slots) { slot = r.nev; r.ev_class[slot] = cls; (void)hipEventRecord(r.c->ev[2 * slot], r.s); }
       else if (r.timing) r.slot_overflow = true;   // more timed sections than slots: finish() fails loudly
     }
@@ -772,18 +728,18 @@ struct PassRecorder {
     }
     if (timing && nev > 0) {
       HIPC(hipEventSynchronize(c->ev[2 * nev - 1]));
-      for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->timings[k] = 0.0f;
+      for (int k = 0; k <= DPE_NUM_CLASSES; ++k) c->pass.timings[k] = 0.0f;
       float ms = 0;
       (void)hipEventElapsedTime(&ms, c->ev_start, c->ev[2 * nev - 1]);
-      c->timings[0] = ms;
+      c->pass.timings[0] = ms;
       for (int e = 0; e < nev; ++e) {
         (void)hipEventElapsedTime(&ms, c->ev[2 * e], c->ev[2 * e + 1]);
-        c->timings[1 + ev_class[e]] += ms;
+        c->pass.timings[1 + ev_class[e]] += ms;
       }
     }
 #if DPE_PHASE_PROF
     unsigned long long ph32[32 * 64], ph[64] = {};
-    HIPC(hipMemcpyAsync(ph32, c->phase.p, sizeof(ph32), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(ph32, c->pass.phase.p, sizeof(ph32), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     for (int k = 0; k < 32 * 64; ++k) ph[k % 64] += ph32[k];
     unsigned long long tot[4] = {0, 0, 0, 0};
@@ -791,10 +747,10 @@ struct PassRecorder {
     for (int k = 0; k < 64; ++k)
       if (ph[k]) fprintf(stderr, "PHASE %d.%d %.4e cycles %.1f%%\n", k / 16, k % 16, (double)ph[k], 100.0 * ph[k] / tot[k / 16]);
 #endif
-    if (c->counting) {
-      HIPC(hipMemcpyAsync(c->counts, c->cnt.p, sizeof(c->counts), hipMemcpyDeviceToHost, s));
+    if (c->pass.counting) {
+      HIPC(hipMemcpyAsync(c->pass.counts, c->pass.cnt.p, sizeof(c->pass.counts), hipMemcpyDeviceToHost, s));
       HIPC(hipStreamSynchronize(s));
-      for (int k = 0; k < DPE_NUM_CLASSES; ++k) c->counts[4 * k + 3] = (unsigned long long)c->launches[k];
+      for (int k = 0; k < DPE_NUM_CLASSES; ++k) c->pass.counts[4 * k + 3] = (unsigned long long)c->pass.launches[k];
     }
     return DPE_OK;
   }
@@ -820,10 +776,10 @@ struct PassRun {
   PassRecorder rec;
 
   PassRun(DpeContext* c_, hipStream_t s_)
-      : c(c_), s(s_), a(s_), pc(c_->hc), dpc(c_->dc.p), B(c_->bufs), lay(pc.W, pc.H, pc.half_rows),
+      : c(c_), s(s_), a(s_), pc(c_->pass.hc), dpc(c_->pass.dc.p), B(c_->pass.bufs), lay(pc.W, pc.H, pc.half_rows),
         L((size_t)pc.W * pc.H), nv(pc.N - 1) {
     static const bool overlap_env = [] { const char* e = getenv("DPE_OVERLAP"); return !(e && atoi(e) == 0); }();   // once per process
-    overlap = overlap_env && !c->timing && !c->counting && pc.P.max_iterations >= 1;
+    overlap = overlap_env && !c->pass.timing && !c->pass.counting && pc.P.max_iterations >= 1;
     if (overlap) a = c->aux;
     B.cnt = nullptr;
     const char* e = getenv("DPE_XCD_ROWS");   // tuning knob, read on every execute: block rows per XCD
@@ -839,10 +795,10 @@ struct PassRun {
   hipError_t wait_aux(hipEvent_t ev) const { return overlap ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
   hipError_t join(hipEvent_t ev) const { const hipError_t e = aux_done(ev); return e != hipSuccess ? e : wait_aux(ev); }
 
-  int* list(PassLists::Region r) const { return c->lists.p + r.off; }
-  int* rows(PassLists::Region r) const { return c->row_counts.p + r.off; }
-  int* total(int slot) const { return c->list_totals.p + slot; }
-  int* chunk_counts(int colour) const { return c->part_cnt.p + lay.chunk_counts(colour).off; }
+  int* list(PassLists::Region r) const { return c->pass.lists.p + r.off; }
+  int* rows(PassLists::Region r) const { return c->pass.row_counts.p + r.off; }
+  int* total(int slot) const { return c->pass.list_totals.p + slot; }
+  int* chunk_counts(int colour) const { return c->pass.part_cnt.p + lay.chunk_counts(colour).off; }
   dim3 px_grid() const { return dim3((pc.W + 15) / 16, (pc.H + 15) / 16); }   // of kPxBlock threads: one per pixel
 };
 static const dim3 kPxBlock(16, 16);
@@ -893,24 +849,24 @@ static int gen_neighbours(PassRun& X, const DevBufs& Bc) {
     // BASELINE workloads) or a NaN go to the scratch kernel, a small persistent grid that loops over
     // that overflow list (its count: the GenNeighbours-overflow total, dpe_pm_last_stat)
     int* ovf = X.total(PassLists::kTotGnOverflow);
-    k_gn_tables<<<(unsigned)((X.pc.W + X.pc.H + 255) / 256), 256, 0, a>>>(X.dpc, c->gn_tab.p);
+    k_gn_tables<<<(unsigned)((X.pc.W + X.pc.H + 255) / 256), 256, 0, a>>>(X.dpc, c->pass.gn_tab.p);
     HIPC(hipMemsetAsync(ovf, 0, sizeof(int), a));
     const unsigned gg = (unsigned)((X.L + kGnBT - 1) / kGnBT);
-    if (c->gn_slots == 8)   // test setting: most pixels overflow into the scratch kernel
-      k_gen_neighbours_lds<8><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
-    else if (X.pc.P.rotate_time <= 2 && c->gn_slots != 64)   // at most 16 x rotate_time support points
-      k_gen_neighbours_lds<32><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
+    if (c->pass.gn_slots == 8)   // test setting: most pixels overflow into the scratch kernel
+      k_gen_neighbours_lds<8><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
+    else if (X.pc.P.rotate_time <= 2 && c->pass.gn_slots != 64)   // at most 16 x rotate_time support points
+      k_gen_neighbours_lds<32><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
     else
-      k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->gn_tab.p, c->gn_ovf.p, ovf);
-    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, c->gn_ovf.p, ovf);
+      k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
+    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, c->pass.gn_ovf.p, ovf);
   } else {
     k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, weak_list, cnt);
   }
 #if DPE_GN_ONCE
   if (!X.gn_skip) {   // kept for the next executes of this staged state (see dpe_pm_execute)
-    HIPC(c->gn_complex.ensure(X.L));
-    HIPC(hipMemcpyAsync(c->gn_complex.p, X.B.complex_, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
-    c->gn_done_for_stage = true;
+    HIPC(c->pass.gn_complex.ensure(X.L));
+    HIPC(hipMemcpyAsync(c->pass.gn_complex.p, X.B.complex_, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
+    c->pass.gn_done_for_stage = true;
   }
 #endif
   return DPE_OK;
@@ -940,11 +896,11 @@ static int setup_chain(PassRun& X) {
   k_gen_edge_inform<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc);
   if (pc.P.use_edge) k_edge_rays<<<(unsigned)(3 * (pc.W + pc.H) - 2), 64, 0, a>>>(X.dpc, Bc);
 #if DPE_GN_ONCE   // GenEdgeInform rewrites complex_: GenNeighbours' kept one is restored after it
-  if (X.gn_skip) HIPC(hipMemcpyAsync(X.B.complex_, c->gn_complex.p, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
+  if (X.gn_skip) HIPC(hipMemcpyAsync(X.B.complex_, c->pass.gn_complex.p, X.L * sizeof(float), hipMemcpyDeviceToDevice, a));
 #endif
   HIPC(X.aux_done(c->ev_ei));
-  k_strong_tables_scan<<<(unsigned)(pc.W + pc.H), 64, 0, a>>>(X.dpc, Bc, c->tab_right.p, c->tab_down.p);
-  k_find_nearest_strong<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc, c->tab_right.p, c->tab_down.p);
+  k_strong_tables_scan<<<(unsigned)(pc.W + pc.H), 64, 0, a>>>(X.dpc, Bc, c->pass.tab_right.p, c->pass.tab_down.p);
+  k_find_nearest_strong<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc, c->pass.tab_right.p, c->pass.tab_down.p);
   build_lists<1>(X, a, Bc, X.lay.all_weak_rows(), PassLists::kTotAllWeak, X.lay.all_weak());
   TRY(gen_neighbours(X, Bc));
   k_neighbour_update<<<X.px_grid(), kPxBlock, 0, a>>>(X.dpc, Bc);
@@ -961,7 +917,7 @@ static int setup_chain(PassRun& X) {
 static int random_initialization(PassRun& X) {
   {
     Section sec(X.rec, DPE_CLASS_INIT);
-    if (X.c->img_cls != IMG_F32) k_random_init<kTexInit><<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
+    if (X.c->pass.img_cls != IMG_F32) k_random_init<kTexInit><<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
     else k_random_init<TEX_F32><<<X.px_grid(), kPxBlock, 0, X.s>>>(X.dpc, sec.B);
   }
   HIPC(X.wait_aux(X.c->ev_ei));
@@ -975,7 +931,7 @@ static void strong_sweep(const PassRun& X, const DevBufs& Bs, int it, PassLists:
   const int P = edge ? 4 : 8, C = edge ? 16 : 8;
   const size_t lds = (size_t)kBwStrong * strong_lds_per_wave(P, C, X.nv) * sizeof(float);
   const unsigned grid = (unsigned)((X.L / 2 + 1 + kBwStrong * P - 1) / (kBwStrong * P));
-  launch_strong(edge, X.c->img_cls, grid, lds, X.s, X.dpc, Bs, it, X.list(list), X.total(total));
+  launch_strong(edge, X.c->pass.img_cls, grid, lds, X.s, X.dpc, Bs, it, X.list(list), X.total(total));
 }
 
 // One colour's strong half-sweep over the snapshot of the state before it, on `s`.  Overlapped, the
@@ -1014,8 +970,8 @@ static void weak_sweep(const PassRun& X, const DevBufs& Bc, int it, int colour, 
   const int wpb = per_wave * 4 <= 64 * 1024 ? 4 : (per_wave * 2 <= 64 * 1024 ? 2 : 1);
   const unsigned grid = (unsigned)((X.L / 2 + 1 + wpb * P - 1) / (wpb * P));
   // U8 texels for 8-bit images; F16 (exact for quarter-integer grey levels) for the coarse levels
-  if (X.c->img_cls == IMG_U8) k_weak_coop<kTexWeak, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
-  else if (X.c->img_cls == IMG_Q) k_weak_coop<TEX_F16, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+  if (X.c->pass.img_cls == IMG_U8) k_weak_coop<kTexWeak, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+  else if (X.c->pass.img_cls == IMG_Q) k_weak_coop<TEX_F16, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
   else k_weak_coop<TEX_F32, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
 }
 
@@ -1062,14 +1018,14 @@ static int depth_to_weak(PassRun& X) {
   DpeContext* c = X.c;
   auto border_local_refine = [&](hipStream_t st) {
     Section sec(X.rec, DPE_CLASS_LOCAL_REFINE);
-    launch_local_refine(c->img_cls, (long)X.L, X.pc.W, X.pc.H, X.nv, st, X.dpc, sec.B);
+    launch_local_refine(c->pass.img_cls, (long)X.L, X.pc.W, X.pc.H, X.nv, st, X.dpc, sec.B);
   };
   HIPC(X.fork(c->ev_fork));
   if (X.overlap) border_local_refine(X.a);
   HIPC(X.aux_done(c->ev_join));
   {
     Section sec(X.rec, DPE_CLASS_DEPTH_TO_WEAK);
-    launch_depth_to_weak(c->img_cls, (long)X.L, X.s, X.dpc, sec.B);
+    launch_depth_to_weak(c->pass.img_cls, (long)X.L, X.s, X.dpc, sec.B);
   }
   HIPC(X.wait_aux(c->ev_join));
   if (!X.overlap) border_local_refine(X.s);
@@ -1086,13 +1042,13 @@ static int depth_to_weak(PassRun& X) {
 struct GnGuard {
   DpeContext* c;
   bool ok = false;
-  ~GnGuard() { if (!ok) c->gn_done_for_stage = false; }
+  ~GnGuard() { if (!ok) c->pass.gn_done_for_stage = false; }
 };
 #endif
 
 extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   TRY(enter(c, true, "dpe_pm_execute: null context"));
-  if (!c->staged) { g_err = "dpe_pm_execute: call dpe_pm_stage first"; return DPE_ERR_STATE; }
+  if (!c->pass.staged) { g_err = "dpe_pm_execute: call dpe_pm_stage first"; return DPE_ERR_STATE; }
   Range range_("dpe_pm_execute");
   hipStream_t s;
   // a previous execute, possibly on another stream, still uses the working buffers this one resets
@@ -1100,12 +1056,12 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
   PassRun X(c, s);
   TRY(X.rec.start(c, s, X.B));
 #if DPE_GN_ONCE
-  X.gn_skip = c->gn_done_for_stage;
+  X.gn_skip = c->pass.gn_done_for_stage;
   GnGuard gn_guard{c};
 #endif
   // initial state (the reference uploads it in CudaSpaceInitialization, DPE.cpp:964-1015); the rest
   // of it is cleared by the setup chain
-  k_pass_init<<<(unsigned)((X.L + 255) / 256), 256, 0, s>>>((const uint4*)c->planes0.p, c->weak0.p, c->sel0.p, (uint4*)X.B.planes,
+  k_pass_init<<<(unsigned)((X.L + 255) / 256), 256, 0, s>>>((const uint4*)c->pass.planes0.p, c->pass.weak0.p, c->pass.sel0.p, (uint4*)X.B.planes,
                                                             X.B.weak, X.B.sel, (uint32_t*)X.B.costs, (uint4*)X.B.vw, X.L);
   TRY(setup_chain(X));
   TRY(random_initialization(X));
@@ -1126,14 +1082,14 @@ extern "C" int dpe_pm_execute(DpeContext* c, void* stream_) {
 
 extern "C" int dpe_pm_fetch(DpeContext* c, const DpePassState* st) {
   TRY(enter(c, st != nullptr, "dpe_pm_fetch: null argument"));
-  if (!c->staged) { g_err = "dpe_pm_fetch: nothing staged"; return DPE_ERR_STATE; }
+  if (!c->pass.staged) { g_err = "dpe_pm_fetch: nothing staged"; return DPE_ERR_STATE; }
   Range range_("dpe_pm_fetch");
-  const size_t L = (size_t)c->hc.W * c->hc.H;
+  const size_t L = (size_t)c->pass.hc.W * c->pass.hc.H;
   HIPC(host_wait(c));
-  if (st->planes) HIPC(hipMemcpy(st->planes, c->bufs.planes, L * sizeof(float4), hipMemcpyDeviceToHost));
-  if (st->weak_info) HIPC(hipMemcpy(st->weak_info, c->bufs.weak, L, hipMemcpyDeviceToHost));
-  if (st->selected_views) HIPC(hipMemcpy(st->selected_views, c->bufs.sel, L * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (st->costs) HIPC(hipMemcpy(st->costs, c->bufs.costs, L * sizeof(float), hipMemcpyDeviceToHost));
+  if (st->planes) HIPC(hipMemcpy(st->planes, c->pass.bufs.planes, L * sizeof(float4), hipMemcpyDeviceToHost));
+  if (st->weak_info) HIPC(hipMemcpy(st->weak_info, c->pass.bufs.weak, L, hipMemcpyDeviceToHost));
+  if (st->selected_views) HIPC(hipMemcpy(st->selected_views, c->pass.bufs.sel, L * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (st->costs) HIPC(hipMemcpy(st->costs, c->pass.bufs.costs, L * sizeof(float), hipMemcpyDeviceToHost));
   return DPE_OK;
 }
 
@@ -1145,660 +1101,29 @@ extern "C" int dpe_pm_run(DpeContext* c, const DpePassInput* in, const DpePassSt
   return dpe_pm_fetch(c, st);
 }
 
-extern "C" void* dpe_pm_device_planes(DpeContext* c) { return (c && c->staged) ? (void*)c->bufs.planes : nullptr; }
-
-__global__ void k_export_depth(const float4* __restrict__ p, float* __restrict__ d, size_t L) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L) d[i] = p[i].w;
-}
-
-extern "C" int dpe_pm_export_depth(DpeContext* c, float* dev_dst, void* stream_) {
-  TRY(enter(c, dev_dst != nullptr, "dpe_pm_export_depth: null argument"));
-  if (!c->staged) { g_err = "dpe_pm_export_depth: nothing staged"; return DPE_ERR_STATE; }
-  hipStream_t s;
-  HIPC(enqueue_stream(c, stream_, &s));   // after the pass that writes the planes
-  const size_t L = (size_t)c->hc.W * c->hc.H;
-  k_export_depth<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(c->bufs.planes, dev_dst, L);
-  HIPC(hipGetLastError());
-  return DPE_OK;
-}
-
-// ------------------------------------------------------------------------------ resident state
-// ProcessProblem's epilogue (main.cpp:423-437) on the pass outputs, into the image's resident state
-__global__ void k_state_save(const float4* __restrict__ planes, const uint8_t* __restrict__ weak,
-                             const uint32_t* __restrict__ sel, float dmin, float dmax, float4* __restrict__ op,
-                             uint8_t* __restrict__ ow, uint32_t* __restrict__ os, size_t L) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= L) return;
-  float4 p = planes[i];
-  uint8_t w = weak[i];
-  if (p.w < dmin || p.w > dmax) { p.w = 0.0f; w = DPE_UNKNOWN; }
-  op[i] = p; ow[i] = w; os[i] = sel[i];
-}
-__global__ void k_depth_of(const float4* __restrict__ p, float* __restrict__ d, size_t L) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L) d[i] = p[i].w;
-}
-__global__ void k_depth_into(const float* __restrict__ d, float4* __restrict__ p, size_t L) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < L) p[i].w = d[i];
-}
-
-extern "C" int dpe_state_save(DpeContext* c, int image_id) {
-  TRY(enter(c, true, "dpe_state_save: null context"));
-  if (!c->staged) { g_err = "dpe_state_save: nothing staged"; return DPE_ERR_STATE; }
-  Range range_("dpe_state_save");
-  const int W = c->hc.W, H = c->hc.H;
-  const size_t L = (size_t)W * H;
-  hipStream_t s;
-  HIPC(enqueue_stream(c, nullptr, &s));   // the context's stream, after the pass that wrote the outputs
-  ResState* r = &c->rstore[image_id];
-  HIPC(r->planes.ensure(L)); HIPC(r->weak.ensure(L)); HIPC(r->sel.ensure(L));
-  r->w = W; r->h = H; r->full = true;
-  k_state_save<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(c->bufs.planes, c->bufs.weak, c->bufs.sel, c->hc.P.depth_min,
-                                                          c->hc.P.depth_max, r->planes.p, r->weak.p, r->sel.p, L);
-  HIPC(hipGetLastError());
-  HIPC(mark_pending(c, s));   // the next execute / stage waits for the save too
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_fetch(DpeContext* c, int image_id, int* w, int* h, float* depth, float* normal, uint8_t* weak,
-                               uint32_t* sel) {
-  TRY(enter(c, true, "dpe_state_fetch: null context"));
-  auto it = c->rstore.find(image_id);
-  if (it == c->rstore.end()) { g_err = "dpe_state_fetch: no state of image " + std::to_string(image_id); return DPE_ERR_STATE; }
-  const ResState* r = &it->second;
-  if (w) *w = r->w;
-  if (h) *h = r->h;
-  const size_t L = (size_t)r->w * r->h;
-  HIPC(host_wait(c));
-  if (depth || normal) {
-    std::vector<float4> p(L);
-    HIPC(hipMemcpy(p.data(), r->planes.p, L * sizeof(float4), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < L; ++i) {
-      if (depth) depth[i] = p[i].w;
-      if (normal) { normal[3 * i] = p[i].x; normal[3 * i + 1] = p[i].y; normal[3 * i + 2] = p[i].z; }
-    }
-  }
-  if (weak || sel) {
-    if (!r->full) { g_err = "dpe_state_fetch: image " + std::to_string(image_id) + " holds a depth map only"; return DPE_ERR_STATE; }
-    if (weak) HIPC(hipMemcpy(weak, r->weak.p, L, hipMemcpyDeviceToHost));
-    if (sel) HIPC(hipMemcpy(sel, r->sel.p, L * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  }
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_snapshot(DpeContext* c) {
-  TRY(enter(c, true, "dpe_state_snapshot: null context"));
-  hipStream_t s;
-  HIPC(enqueue_stream(c, nullptr, &s));
-  for (auto& kv : c->rstore) {
-    ResState* r = &kv.second;
-    const size_t L = (size_t)r->w * r->h;
-    HIPC(r->snap.ensure(L));
-    k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(r->planes.p, r->snap.p, L);
-    r->snap_w = r->w; r->snap_h = r->h;
-    r->has_snap = true;
-  }
-  HIPC(hipGetLastError());
-  HIPC(mark_pending(c, s));
-  c->snap_mode = true;
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_export_depth(DpeContext* c, int image_id, float* dev_dst, void* stream_) {
-  TRY(enter(c, dev_dst != nullptr, "dpe_state_export_depth: null argument"));
-  auto it = c->rstore.find(image_id);
-  if (it == c->rstore.end()) { g_err = "dpe_state_export_depth: no state of image " + std::to_string(image_id); return DPE_ERR_STATE; }
-  hipStream_t s;
-  HIPC(enqueue_stream(c, stream_, &s));
-  const size_t L = (size_t)it->second.w * it->second.h;
-  k_depth_of<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(it->second.planes.p, dev_dst, L);
-  HIPC(hipGetLastError());
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_import_depth(DpeContext* c, int image_id, int w, int h, const float* dev_src, void* stream_) {
-  TRY(enter(c, dev_src && w > 0 && h > 0, "dpe_state_import_depth: bad argument"));
-  hipStream_t s;
-  HIPC(enqueue_stream(c, stream_, &s));   // an execute may still read this state's depth
-  ResState* r = &c->rstore[image_id];
-  const size_t L = (size_t)w * h;
-  if (r->w != w || r->h != h) {
-    HIPC(r->planes.ensure(L));
-    HIPC(hipMemsetAsync(r->planes.p, 0, L * sizeof(float4), s));
-    r->w = w; r->h = h; r->full = false;
-  }
-  k_depth_into<<<(unsigned)((L + 255) / 256), 256, 0, s>>>(dev_src, r->planes.p, L);
-  HIPC(hipGetLastError());
-  HIPC(publish_foreign(c, s));   // later stages on the context stream read it
-  return DPE_OK;
-}
-
-extern "C" float* dpe_device_buffer(DpeContext* c, int slot, size_t count) {
-  g_err.clear();
-  if (!c || slot < 0 || slot > 1) { g_err = "dpe_device_buffer: bad argument"; return nullptr; }
-  if (hipSetDevice(c->device) != hipSuccess) { g_err = "dpe_device_buffer: hipSetDevice"; return nullptr; }
-  if (c->xbuf[slot].n < count) {
-    if (host_wait(c) != hipSuccess) { g_err = "dpe_device_buffer: sync"; return nullptr; }
-    if (c->xbuf[slot].ensure(count) != hipSuccess) { g_err = "dpe_device_buffer: hipMalloc"; return nullptr; }
-  }
-  return c->xbuf[slot].p;
-}
-
-extern "C" int dpe_sync(DpeContext* c) {
-  TRY(enter(c, true, "dpe_sync: null context"));
-  HIPC(host_wait(c));
-  return DPE_OK;
-}
-
-extern "C" int dpe_device_copy(DpeContext* c, void* dst, const void* src, size_t bytes, int kind) {
-  TRY(enter(c, dst && src && kind >= 0 && kind <= 2, "dpe_device_copy: bad argument"));
-  HIPC(host_wait(c));
-  const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : (kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
-  HIPC(hipMemcpy(dst, src, bytes, k));
-  return DPE_OK;
-}
-
-// ------------------------------------------------------------------------------ EdgeSegment stages
-namespace {
-// cv::resize INTER_LINEAR CV_32F taps (host/hostio.cpp linear_taps)
-void f32_taps(int n_src, int n_dst, int* s0, int* s1, float* a0, float* a1) {
-  const double scale = 1.0 / ((double)n_dst / n_src);
-  for (int d = 0; d < n_dst; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int sidx = (int)std::floor(f);
-    f -= (float)sidx;
-    if (sidx < 0) { f = 0; sidx = 0; }
-    if (sidx >= n_src - 1) { f = 0; sidx = n_src - 1; }
-    s0[d] = sidx; s1[d] = std::min(sidx + 1, n_src - 1);
-    a0[d] = 1.0f - f; a1[d] = f;
-  }
-}
-// cv::resize INTER_LINEAR CV_8U taps (host/edges.cpp lin_tab): 11-bit weights, cvRound half to even
-int u8_taps(int ssize, int dsize, int* ofs, short* a) {
-  const double scale = 1.0 / ((double)dsize / ssize);
-  int xmax = dsize;
-  for (int d = 0; d < dsize; ++d) {
-    float f = (float)((d + 0.5) * scale - 0.5);
-    int sidx = (int)std::floor(f);
-    f -= (float)sidx;
-    if (sidx < 0) { f = 0; sidx = 0; }
-    if (sidx + 1 >= ssize) {
-      xmax = std::min(xmax, d);
-      if (sidx >= ssize - 1) { f = 0; sidx = ssize - 1; }
-    }
-    ofs[d] = sidx;
-    const float c0 = 1.0f - f, c1 = f;
-    a[2 * d] = (short)std::min(32767, std::max(-32768, (int)std::nearbyint(c0 * 2048.0f)));
-    a[2 * d + 1] = (short)std::min(32767, std::max(-32768, (int)std::nearbyint(c1 * 2048.0f)));
-  }
-  return xmax;
-}
-}  // namespace
-
-extern "C" int dpe_resize_linear(DpeContext* c, const float* src, int w, int h, float* dst, int nw, int nh) {
-  TRY(enter(c, src && dst && w >= 1 && h >= 1 && nw >= 1 && nh >= 1, "dpe_resize_linear: bad argument"));
-  if (w == nw && h == nh) { std::memcpy(dst, src, sizeof(float) * (size_t)w * h); return DPE_OK; }
-  std::vector<int> it(2 * (size_t)(nw + nh));
-  std::vector<float> ft(2 * (size_t)(nw + nh));
-  f32_taps(w, nw, it.data(), it.data() + nw, ft.data(), ft.data() + nw);
-  f32_taps(h, nh, it.data() + 2 * nw, it.data() + 2 * nw + nh, ft.data() + 2 * nw, ft.data() + 2 * nw + nh);
-  HIPC(c->e_fa.ensure((size_t)w * h)); HIPC(c->e_fb.ensure((size_t)nw * nh));
-  HIPC(c->e_rows.ensure((size_t)h * nw));   // f32 rows stored in the int scratch (same size)
-  HIPC(c->e_itab.ensure(it.size())); HIPC(c->e_ftab.ensure(ft.size()));
-  HIPC(hipMemcpyAsync(c->e_fa.p, src, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemcpyAsync(c->e_itab.p, it.data(), it.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemcpyAsync(c->e_ftab.p, ft.data(), ft.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  float* rows = (float*)c->e_rows.p;
-  const dim3 b(32, 8);
-  k_resize_linear_h<<<dim3((nw + 31) / 32, (h + 7) / 8), b, 0, c->stream>>>(c->e_fa.p, w, h, c->e_itab.p, c->e_itab.p + nw,
-                                                                            c->e_ftab.p, c->e_ftab.p + nw, rows, nw);
-  k_resize_linear_v<<<dim3((nw + 31) / 32, (nh + 7) / 8), b, 0, c->stream>>>(rows, nw, c->e_itab.p + 2 * nw,
-                                                                             c->e_itab.p + 2 * nw + nh, c->e_ftab.p + 2 * nw,
-                                                                             c->e_ftab.p + 2 * nw + nh, c->e_fb.p, nh);
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(dst, c->e_fb.p, sizeof(float) * (size_t)nw * nh, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-// device-to-device core of dpe_resize_u8 (src / dst in the context's scratch)
-static int resize_u8_dev(DpeContext* c, const uint8_t* dsrc, int w, int h, uint8_t* ddst, int nw, int nh) {
-  const dim3 b(32, 8);
-  if (w == nw && h == nh) { HIPC(hipMemcpyAsync(ddst, dsrc, (size_t)w * h, hipMemcpyDeviceToDevice, c->stream)); return DPE_OK; }
-  const double scale_x = 1.0 / ((double)nw / w), scale_y = 1.0 / ((double)nh / h);
-  const int isx = (int)std::lround(scale_x), isy = (int)std::lround(scale_y);
-  const bool area_fast = std::fabs(scale_x - isx) < 2.220446049250313e-16 && std::fabs(scale_y - isy) < 2.220446049250313e-16;
-  if (area_fast && isx == 2 && isy == 2) {   // INTER_LINEAR at exactly 1/2 = INTER_AREA's fast path
-    k_resize_u8_half<<<dim3((nw + 31) / 32, (nh + 7) / 8), b, 0, c->stream>>>(dsrc, w, ddst, nw, nh);
-    HIPC(hipGetLastError());
-    return DPE_OK;
-  }
-  std::vector<int> ofs((size_t)nw + nh);
-  std::vector<short> a(2 * ((size_t)nw + nh));
-  const int xmax = u8_taps(w, nw, ofs.data(), a.data());
-  (void)u8_taps(h, nh, ofs.data() + nw, a.data() + 2 * nw);
-  int xv = 0;                                 // VResizeLinear: 16-lane, then 8-lane vector blocks
-  for (; xv <= nw - 16; xv += 16) {}
-  for (; xv < nw - 8; xv += 8) {}
-  HIPC(c->e_rows.ensure((size_t)h * nw)); HIPC(c->e_itab.ensure(ofs.size())); HIPC(c->e_stab.ensure(a.size()));
-  HIPC(hipMemcpyAsync(c->e_itab.p, ofs.data(), ofs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemcpyAsync(c->e_stab.p, a.data(), a.size() * sizeof(short), hipMemcpyHostToDevice, c->stream));
-  k_resize_u8_h<<<dim3((nw + 31) / 32, (h + 7) / 8), b, 0, c->stream>>>(dsrc, w, h, c->e_itab.p, c->e_stab.p, xmax,
-                                                                        c->e_rows.p, nw);
-  k_resize_u8_v<<<dim3((nw + 31) / 32, (nh + 7) / 8), b, 0, c->stream>>>(c->e_rows.p, h, nw, c->e_itab.p + nw,
-                                                                         c->e_stab.p + 2 * nw, xv, ddst, nh);
-  HIPC(hipGetLastError());
-  return DPE_OK;
-}
-
-extern "C" int dpe_resize_u8(DpeContext* c, const uint8_t* src, int w, int h, uint8_t* dst, int nw, int nh) {
-  TRY(enter(c, src && dst && w >= 1 && h >= 1 && nw >= 1 && nh >= 1, "dpe_resize_u8: bad argument"));
-  HIPC(c->e_a.ensure((size_t)w * h)); HIPC(c->e_b.ensure((size_t)nw * nh));
-  HIPC(hipMemcpyAsync(c->e_a.p, src, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
-  TRY(resize_u8_dev(c, c->e_a.p, w, h, c->e_b.p, nw, nh));
-  HIPC(hipMemcpyAsync(dst, c->e_b.p, (size_t)nw * nh, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-extern "C" int dpe_roberts_threshold(DpeContext* c, const uint8_t* src, int w, int h, int thr, uint8_t* dst) {
-  TRY(enter(c, src && dst && w >= 1 && h >= 1, "dpe_roberts_threshold: bad argument"));
-  HIPC(c->e_a.ensure((size_t)w * h)); HIPC(c->e_b.ensure((size_t)w * h));
-  HIPC(hipMemcpyAsync(c->e_a.p, src, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
-  k_roberts_threshold<<<dim3((w + 31) / 32, (h + 7) / 8), dim3(32, 8), 0, c->stream>>>(c->e_a.p, w, h, thr, c->e_b.p);
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(dst, c->e_b.p, (size_t)w * h, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-extern "C" int dpe_canny(DpeContext* c, const uint8_t* src, int w, int h, double low_thresh, double high_thresh, uint8_t* dst) {
-  TRY(enter(c, src && dst && w >= 1 && h >= 1, "dpe_canny: bad argument"));
-  Range range_("dpe_canny");
-  if (low_thresh > high_thresh) std::swap(low_thresh, high_thresh);   // canny.cpp threshold handling
-  low_thresh = std::min(32767.0, low_thresh);
-  high_thresh = std::min(32767.0, high_thresh);
-  if (low_thresh > 0) low_thresh *= low_thresh;
-  if (high_thresh > 0) high_thresh *= high_thresh;
-  const int low = (int)std::floor(low_thresh), high = (int)std::floor(high_thresh);
-  const int ms = w + 2;
-  const size_t L = (size_t)w * h, M = (size_t)ms * (h + 2);
-  HIPC(c->e_a.ensure(L)); HIPC(c->e_dx.ensure(L)); HIPC(c->e_dy.ensure(L)); HIPC(c->e_mag.ensure(M)); HIPC(c->e_map.ensure(M));
-  HIPC(hipMemcpyAsync(c->e_a.p, src, L, hipMemcpyHostToDevice, c->stream));
-  const dim3 b(32, 8), g((ms + 31) / 32, (h + 2 + 7) / 8);
-  k_canny_sobel<<<g, b, 0, c->stream>>>(c->e_a.p, w, h, c->e_dx.p, c->e_dy.p, c->e_mag.p);
-  k_canny_nms<<<g, b, 0, c->stream>>>(c->e_dx.p, c->e_dy.p, c->e_mag.p, w, h, low, high, c->e_map.p);
-  HIPC(hipGetLastError());
-  std::vector<uint8_t> map(M);
-  HIPC(hipMemcpyAsync(map.data(), c->e_map.p, M, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  // hysteresis: 8-connected growth through candidates from every strong candidate (any order: the
-  // closure is the same set)
-  std::vector<size_t> stack;
-  stack.reserve(L / 8 + 16);
-  for (size_t i = 0; i < M; ++i) if (map[i] == 2) stack.push_back(i);
-  const long off[8] = {-ms - 1, -ms, -ms + 1, -1, 1, ms - 1, ms, ms + 1};
-  while (!stack.empty()) {
-    const size_t i = stack.back();
-    stack.pop_back();
-    for (long o : off) {
-      const size_t j = (size_t)((long)i + o);
-      if (!map[j]) { map[j] = 2; stack.push_back(j); }
-    }
-  }
-  for (int y = 0; y < h; ++y)
-    for (int x = 0; x < w; ++x) dst[(size_t)y * w + x] = map[(size_t)(y + 1) * ms + x + 1] == 2 ? 255 : 0;
-  return DPE_OK;
-}
-
-extern "C" void dpe_state_clear(DpeContext* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  (void)host_wait(c);
-  c->rstore.clear();
-  c->snap_mode = false;
-#if DPE_GN_ONCE
-  c->gn_done_for_stage = false;
-#endif
-}
-
-extern "C" int dpe_host_pin(void* ptr, size_t bytes) {
-  if (!ptr || bytes == 0) return DPE_ERR_ARG;
-  return hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess ? DPE_OK : DPE_ERR_HIP;
-}
-extern "C" int dpe_host_unpin(void* ptr) {
-  if (!ptr) return DPE_ERR_ARG;
-  return hipHostUnregister(ptr) == hipSuccess ? DPE_OK : DPE_ERR_HIP;
-}
-
-// ---------------------------------------------------------------- viz medium results (pass_viz.h)
-static std::atomic<long long> g_viz_launches{0};
-
-extern "C" long long dpe_viz_launches(void) { return g_viz_launches.load(); }
-
-static size_t viz_block_values(int w, int h) { return (size_t)((w + 15) / 16) * ((h + 15) / 16) * 6 * 64; }
-
-// the picture of (planes, weak) into c->viz_bgr on stream s
-static int viz_enqueue_render(DpeContext* c, int kind, const float4* planes, const uint8_t* weak, int w, int h, float dmin,
-                              float dmax, hipStream_t s) {
-  const size_t L = (size_t)w * h;
-  HIPC(c->viz_bgr.ensure(3 * L));
-  k_viz_render<<<(unsigned)((L + 1023) / 1024), 256, 0, s>>>(kind, planes, weak, dmin, dmax, c->viz_bgr.p, L);
-  HIPC(hipGetLastError());
-  g_viz_launches++;
-  return DPE_OK;
-}
-
-// the JPEG front half of c->viz_bgr (w x h) into c->viz_blocks on stream s
-static int viz_enqueue_front(DpeContext* c, int w, int h, int quality, hipStream_t s) {
-  if (c->viz_quality != quality) {   // first use, or another quality: no kernel may still read the old tables
-    HIPC(hipStreamSynchronize(s));
-    HIPC(hipStreamSynchronize(c->stream));
-    uint16_t q[128];
-    dpe_jpeg::quant_tables(quality, q);
-    HIPC(c->viz_q.ensure(128));
-    HIPC(hipMemcpy(c->viz_q.p, q, sizeof(q), hipMemcpyHostToDevice));
-    c->viz_quality = quality;
-  }
-  HIPC(c->viz_blocks.ensure(viz_block_values(w, h)));
-  k_jpeg_front<<<dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)), 384, 0, s>>>(c->viz_bgr.p, w, h, c->viz_q.p,
-                                                                                        c->viz_blocks.p);
-  HIPC(hipGetLastError());
-  g_viz_launches++;
-  return DPE_OK;
-}
-
-static const ResState* viz_state(DpeContext* c, int image_id, int kind, const char* who) {
-  if (kind != DPE_VIZ_DEPTH && kind != DPE_VIZ_NORMAL && kind != DPE_VIZ_WEAK) { g_err = std::string(who) + ": bad kind"; return nullptr; }
-  auto it = c->rstore.find(image_id);
-  if (it == c->rstore.end()) { g_err = std::string(who) + ": no state of image " + std::to_string(image_id); return nullptr; }
-  if (!it->second.full) { g_err = std::string(who) + ": image " + std::to_string(image_id) + " holds a depth map only"; return nullptr; }
-  return &it->second;
-}
-
-extern "C" int dpe_state_render(DpeContext* c, int image_id, int kind, float dmin, float dmax, uint8_t* host_bgr) {
-  TRY(enter(c, host_bgr != nullptr, "dpe_state_render: null argument"));
-  const ResState* r = viz_state(c, image_id, kind, "dpe_state_render");
-  if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
-  hipStream_t s;
-  HIPC(enqueue_stream(c, nullptr, &s));
-  TRY(viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s));
-  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, (size_t)r->w * r->h * 3, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_render_jpeg_blocks(DpeContext* c, int image_id, int kind, float dmin, float dmax, int quality,
-                                            int16_t* host_blocks, size_t cap, void* stream_) {
-  TRY(enter(c, host_blocks != nullptr, "dpe_state_render_jpeg_blocks: null argument"));
-  if (quality < 1 || quality > 100) { g_err = "dpe_state_render_jpeg_blocks: bad quality"; return DPE_ERR_ARG; }
-  const ResState* r = viz_state(c, image_id, kind, "dpe_state_render_jpeg_blocks");
-  if (!r) return g_err.find("bad kind") != std::string::npos ? DPE_ERR_ARG : DPE_ERR_STATE;
-  const size_t n = viz_block_values(r->w, r->h);
-  if (cap < n) { g_err = "dpe_state_render_jpeg_blocks: block buffer too small"; return DPE_ERR_ARG; }
-  hipStream_t s;
-  HIPC(enqueue_stream(c, stream_, &s));   // after the save that wrote the state
-  TRY(viz_enqueue_render(c, kind, r->planes.p, r->weak.p, r->w, r->h, dmin, dmax, s));
-  TRY(viz_enqueue_front(c, r->w, r->h, quality, s));
-  HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, s));
-  hipEvent_t ev = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(c->viz_mu);
-    auto it = c->viz_ev.find(host_blocks);
-    if (it == c->viz_ev.end()) {
-      Event fresh;
-      HIPC(fresh.create());
-      it = c->viz_ev.emplace(host_blocks, std::move(fresh)).first;
-    }
-    ev = it->second;
-  }
-  HIPC(hipEventRecord(ev, s));
-  HIPC(publish_foreign(c, s));   // the scratch is reused, and the state rewritten, by later work of the context
-  return DPE_OK;
-}
-
-extern "C" int dpe_state_render_wait(DpeContext* c, const int16_t* host_blocks) {
-  g_err.clear();   // (not enter(): the lookup comes before the device is selected, and any host thread may call)
-  if (!c || !host_blocks) { g_err = "dpe_state_render_wait: null argument"; return DPE_ERR_ARG; }
-  hipEvent_t ev = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(c->viz_mu);
-    auto it = c->viz_ev.find(host_blocks);
-    if (it == c->viz_ev.end()) { g_err = "dpe_state_render_wait: no render into this buffer"; return DPE_ERR_ARG; }
-    ev = it->second;
-  }
-  HIPC(hipSetDevice(c->device));
-  HIPC(hipEventSynchronize(ev));
-  return DPE_OK;
-}
-
-extern "C" int dpe_viz_render_arrays(DpeContext* c, int kind, int w, int h, const float* depth, const float* normal,
-                                     const uint8_t* weak, float dmin, float dmax, uint8_t* host_bgr) {
-  TRY(enter(c, host_bgr && w >= 1 && h >= 1, "dpe_viz_render_arrays: bad argument"));
-  if (kind == DPE_VIZ_DEPTH ? !depth : kind == DPE_VIZ_NORMAL ? !normal : kind == DPE_VIZ_WEAK ? !weak : true) {
-    g_err = "dpe_viz_render_arrays: bad kind or missing array";
-    return DPE_ERR_ARG;
-  }
-  const size_t L = (size_t)w * h;
-  std::vector<float4> p(L);
-  for (size_t i = 0; i < L; ++i)
-    p[i] = make_float4(normal ? normal[3 * i] : 0.f, normal ? normal[3 * i + 1] : 0.f, normal ? normal[3 * i + 2] : 0.f,
-                       depth ? depth[i] : 0.f);
-  HIPC(host_wait(c));
-  HIPC(c->viz_planes.ensure(L));
-  HIPC(c->viz_weak.ensure(L));
-  HIPC(hipMemcpy(c->viz_planes.p, p.data(), L * sizeof(float4), hipMemcpyHostToDevice));
-  if (weak) HIPC(hipMemcpy(c->viz_weak.p, weak, L, hipMemcpyHostToDevice));
-  else HIPC(hipMemset(c->viz_weak.p, 0, L));
-  TRY(viz_enqueue_render(c, kind, c->viz_planes.p, c->viz_weak.p, w, h, dmin, dmax, c->stream));
-  HIPC(hipMemcpyAsync(host_bgr, c->viz_bgr.p, 3 * L, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-extern "C" int dpe_jpeg_blocks_device(DpeContext* c, const uint8_t* host_bgr, int w, int h, int quality, int16_t* host_blocks,
-                                      size_t cap) {
-  TRY(enter(c, host_bgr && host_blocks && w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && quality >= 1 && quality <= 100,
-            "dpe_jpeg_blocks_device: bad argument"));
-  const size_t n = viz_block_values(w, h);
-  if (cap < n) { g_err = "dpe_jpeg_blocks_device: block buffer too small"; return DPE_ERR_ARG; }
-  HIPC(host_wait(c));
-  HIPC(c->viz_bgr.ensure((size_t)w * h * 3));
-  HIPC(hipMemcpy(c->viz_bgr.p, host_bgr, (size_t)w * h * 3, hipMemcpyHostToDevice));
-  TRY(viz_enqueue_front(c, w, h, quality, c->stream));
-  HIPC(hipMemcpyAsync(host_blocks, c->viz_blocks.p, n * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n) {
-  TRY(enter(c, views && n >= 1, "dpe_fusion_stage: bad argument"));
-  c->tat_ready = false;   // the colours and masks of dpe_fusion_tat_begin belong to the views staged before
-  c->fz_depth.resize(n); c->fz_normal.resize(n); c->fz_host.assign(n, FusionViewDev{});
-  std::vector<DpeCamera> cams(n);
-  for (int i = 0; i < n; ++i) {
-    const DpeFusionView& v = views[i];
-    if (v.width < 1 || v.height < 1 || !v.depth || !v.normal) { g_err = "dpe_fusion_stage: bad view"; return DPE_ERR_ARG; }
-    const size_t L = (size_t)v.width * v.height;
-    HIPC(c->fz_depth[i].ensure(L));
-    HIPC(c->fz_normal[i].ensure(3 * L));
-    HIPC(hipMemcpyAsync(c->fz_depth[i].p, v.depth, L * 4, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemcpyAsync(c->fz_normal[i].p, v.normal, 3 * L * 4, hipMemcpyHostToDevice, c->stream));
-    c->fz_host[i] = FusionViewDev{c->fz_depth[i].p, c->fz_normal[i].p, v.width, v.height};
-    cams[i] = v.cam;
-  }
-  HIPC(c->fz_views.ensure(n));
-  HIPC(c->fz_cams.ensure(n));
-  HIPC(hipMemcpyAsync(c->fz_views.p, c->fz_host.data(), n * sizeof(FusionViewDev), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemcpyAsync(c->fz_cams.p, cams.data(), n * sizeof(DpeCamera), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  c->fz_n = n;
-  return DPE_OK;
-}
-
-extern "C" int dpe_fusion_candidates(DpeContext* c, int ref, const int* src, int ns, int32_t* idx, float* val) {
-  TRY(enter(c, src && idx && val && ns >= 0, "dpe_fusion_candidates: bad argument"));
-  if (c->fz_n < 1) { g_err = "dpe_fusion_candidates: nothing staged"; return DPE_ERR_STATE; }
-  if (ref < 0 || ref >= c->fz_n) { g_err = "dpe_fusion_candidates: bad reference view"; return DPE_ERR_ARG; }
-  for (int j = 0; j < ns; ++j)
-    if (src[j] < 0 || src[j] >= c->fz_n) { g_err = "dpe_fusion_candidates: bad source view"; return DPE_ERR_ARG; }
-  if (ns == 0) return DPE_OK;
-  const size_t L = (size_t)c->fz_host[ref].w * c->fz_host[ref].h;
-  HIPC(c->fz_src.ensure(ns));
-  HIPC(c->fz_idx.ensure(L * ns));
-  HIPC(c->fz_val.ensure(L * ns * 3));
-  HIPC(hipMemcpyAsync(c->fz_src.p, src, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  k_fusion_candidates<<<(unsigned)((L + 255) / 256), 256, 0, c->stream>>>(c->fz_cams.p, c->fz_views.p, ref, c->fz_src.p, ns,
-                                                                         c->fz_idx.p, c->fz_val.p);
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(idx, c->fz_idx.p, L * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(val, c->fz_val.p, L * ns * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  return DPE_OK;
-}
-
-// host-waits for the copy-out of the last dpe_fusion_tat_image
-static hipError_t tat_wait_copy(DpeContext* c) {
-  hipError_t e = hipSuccess;
-  if (c->tat_copying) { e = hipEventSynchronize(c->ev_tat); c->tat_copying = false; }
-  return e;
-}
-
-extern "C" int dpe_fusion_tat_begin(DpeContext* c, const uint8_t* const* bgr, const uint8_t* const* block) {
-  TRY(enter(c, bgr != nullptr, "dpe_fusion_tat_begin: bad argument"));
-  if (c->fz_n < 1) { g_err = "dpe_fusion_tat_begin: nothing staged"; return DPE_ERR_STATE; }
-  const int n = c->fz_n;
-  for (int i = 0; i < n; ++i)
-    if (!bgr[i]) { g_err = "dpe_fusion_tat_begin: missing colour image"; return DPE_ERR_ARG; }
-  HIPC(host_wait(c));
-  HIPC(tat_wait_copy(c));
-  c->tat_ready = false;
-  c->tat_bgr.resize(n); c->tat_block.resize(n); c->tat_mask.resize(n);
-  std::vector<TatViewDev> tv(n);
-  for (int i = 0; i < n; ++i) {
-    const size_t L = (size_t)c->fz_host[i].w * c->fz_host[i].h;
-    HIPC(c->tat_bgr[i].ensure(3 * L));
-    HIPC(c->tat_mask[i].ensure(L));
-    HIPC(hipMemcpyAsync(c->tat_bgr[i].p, bgr[i], 3 * L, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipMemsetAsync(c->tat_mask[i].p, 0, L, c->stream));
-    const bool blk = block && block[i];
-    if (blk) {
-      HIPC(c->tat_block[i].ensure(L));
-      HIPC(hipMemcpyAsync(c->tat_block[i].p, block[i], L, hipMemcpyHostToDevice, c->stream));
-    }
-    tv[i] = TatViewDev{c->tat_bgr[i].p, blk ? c->tat_block[i].p : nullptr, c->tat_mask[i].p};
-  }
-  HIPC(c->tat_views.ensure(n));
-  HIPC(hipMemcpyAsync(c->tat_views.p, tv.data(), n * sizeof(TatViewDev), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  c->tat_ready = true;
-  return DPE_OK;
-}
-
-extern "C" int dpe_fusion_tat_image(DpeContext* c, int mode, int ref, const int* src, int ns, const float* dot_thresholds,
-                                    DpeFusedPoint* out, size_t cap, size_t* n_out) {
-  static_assert(sizeof(DpeFusedPoint) == sizeof(TatPoint), "DpeFusedPoint layout");
-  TRY(enter(c, n_out && ns >= 0 && (ns == 0 || src) && (out || cap == 0), "dpe_fusion_tat_image: bad argument"));
-  if (!c->tat_ready) { g_err = "dpe_fusion_tat_image: dpe_fusion_tat_begin has not run"; return DPE_ERR_STATE; }
-  if (mode != DPE_FUSION_TAT_INTERMEDIATE && mode != DPE_FUSION_TAT_ADVANCED) { g_err = "dpe_fusion_tat_image: bad mode"; return DPE_ERR_ARG; }
-  if (ref < 0 || ref >= c->fz_n) { g_err = "dpe_fusion_tat_image: bad reference view"; return DPE_ERR_ARG; }
-  if (ns > kTatMaxSrc) { g_err = "dpe_fusion_tat_image: more than 31 source views"; return DPE_ERR_TOO_MANY; }
-  for (int j = 0; j < ns; ++j) {
-    if (src[j] < 0 || src[j] >= c->fz_n) { g_err = "dpe_fusion_tat_image: bad source view"; return DPE_ERR_ARG; }
-    // the kernels read the masks of the source views while they write the reference view's
-    if (src[j] == ref) { g_err = "dpe_fusion_tat_image: the reference view is among its sources"; return DPE_ERR_ARG; }
-  }
-  if (mode == DPE_FUSION_TAT_INTERMEDIATE && ns >= 2 && !dot_thresholds) { g_err = "dpe_fusion_tat_image: no thresholds"; return DPE_ERR_ARG; }
-  *n_out = 0;
-  if (ns < 2) {   // the k loop starts at 2 (DPE.cpp:1504): no point, no mask
-    HIPC(tat_wait_copy(c));
-    return DPE_OK;
-  }
-  const size_t L = (size_t)c->fz_host[ref].w * c->fz_host[ref].h;
-  const int nch = (int)((L + kTatChunk - 1) / kTatChunk);
-  DevArr<TatPoint>& dout = c->tat_out[c->tat_turn];
-  HIPC(c->fz_src.ensure(ns));
-  HIPC(c->tat_dthr.ensure(kTatMaxSrc + 1));
-  HIPC(c->tat_last.ensure(L * ns));
-  HIPC(c->tat_agg.ensure((size_t)nch * ns));
-  HIPC(c->tat_cnt.ensure(nch));
-  HIPC(c->tat_tot.ensure(1));
-  HIPC(c->tat_emit.ensure(L));
-  HIPC(c->tat_rec.ensure(L));
-  HIPC(dout.ensure(L));
-  hipStream_t s;
-  HIPC(enqueue_stream(c, nullptr, &s));
-  float dthr[kTatMaxSrc + 1] = {0};
-  if (mode == DPE_FUSION_TAT_INTERMEDIATE)
-    for (int k = 2; k <= ns; ++k) dthr[k] = dot_thresholds[k];
-  // (the stream is synchronised below, before `dthr` and the caller's `src` go out of scope)
-  HIPC(hipMemcpyAsync(c->fz_src.p, src, ns * sizeof(int), hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(c->tat_dthr.p, dthr, sizeof(dthr), hipMemcpyHostToDevice, s));
-  k_tat_hit_scan<<<nch, kTatChunk, 0, s>>>(c->fz_cams.p, c->fz_views.p, c->tat_views.p, ref, c->fz_src.p, ns, nch,
-                                          c->tat_last.p, c->tat_agg.p);
-  k_tat_chunk_carry<<<ns, 256, 0, s>>>(nch, c->tat_agg.p);
-  k_tat_decide<<<nch, kTatChunk, 0, s>>>(c->fz_cams.p, c->fz_views.p, c->tat_views.p, ref, c->fz_src.p, ns, nch, mode,
-                                        c->tat_dthr.p, c->tat_last.p, c->tat_agg.p, c->tat_rec.p, c->tat_emit.p,
-                                        c->tat_cnt.p);
-  k_tat_offsets<<<1, 256, 0, s>>>(nch, c->tat_cnt.p, c->tat_tot.p);
-  k_tat_fill<<<nch, kTatChunk, 0, s>>>((int)L, c->tat_emit.p, c->tat_rec.p, c->tat_cnt.p, dout.p);
-  HIPC(hipGetLastError());
-  int total = 0;
-  HIPC(hipMemcpyAsync(&total, c->tat_tot.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  HIPC(tat_wait_copy(c));   // the copy-out of the image before ran beside these kernels
-  if (total < 0 || (size_t)total > L) { g_err = "dpe_fusion_tat_image: bad point count"; return DPE_ERR_STATE; }
-  *n_out = (size_t)total;
-  if ((size_t)total > cap) { g_err = "dpe_fusion_tat_image: output buffer too small"; return DPE_ERR_ARG; }
-  if (total > 0) {
-    HIPC(hipMemcpyAsync(out, dout.p, (size_t)total * sizeof(TatPoint), hipMemcpyDeviceToHost, c->aux));
-    HIPC(hipEventRecord(c->ev_tat, c->aux));
-    c->tat_copying = true;
-    c->tat_turn ^= 1;
-  }
-  return DPE_OK;
-}
-
-extern "C" int dpe_fusion_tat_wait(DpeContext* c) {
-  TRY(enter(c, true, "dpe_fusion_tat_wait: null context"));
-  HIPC(tat_wait_copy(c));
-  return DPE_OK;
-}
-
-extern "C" int dpe_fusion_tat_mask(DpeContext* c, int view, uint8_t* mask) {
-  TRY(enter(c, mask != nullptr, "dpe_fusion_tat_mask: bad argument"));
-  if (!c->tat_ready) { g_err = "dpe_fusion_tat_mask: dpe_fusion_tat_begin has not run"; return DPE_ERR_STATE; }
-  if (view < 0 || view >= c->fz_n) { g_err = "dpe_fusion_tat_mask: bad view"; return DPE_ERR_ARG; }
-  HIPC(host_wait(c));
-  HIPC(hipMemcpy(mask, c->tat_mask[view].p, (size_t)c->fz_host[view].w * c->fz_host[view].h, hipMemcpyDeviceToHost));
-  return DPE_OK;
-}
-
 extern "C" int dpe_pm_last_timings(DpeContext* c, float* out, int n) {
   if (!c || !out) return 0;
   const int m = n < DPE_NUM_CLASSES + 1 ? n : DPE_NUM_CLASSES + 1;
-  for (int i = 0; i < m; ++i) out[i] = c->timings[i];
+  for (int i = 0; i < m; ++i) out[i] = c->pass.timings[i];
   return m;
 }
 
-extern "C" void dpe_set_counting(DpeContext* c, int enable) { if (c) c->counting = enable != 0; }
+extern "C" void dpe_set_counting(DpeContext* c, int enable) { if (c) c->pass.counting = enable != 0; }
 
 extern "C" int dpe_set_option(DpeContext* c, int option, int value) {
   g_err.clear();   // (touches no device)
   if (!c) { g_err = "dpe_set_option: null context"; return DPE_ERR_ARG; }
-  if (option == DPE_OPT_GN_SLOTS && (value == 0 || value == 8 || value == 32 || value == 64)) { c->gn_slots = value; return DPE_OK; }
+  if (option == DPE_OPT_GN_SLOTS && (value == 0 || value == 8 || value == 32 || value == 64)) { c->pass.gn_slots = value; return DPE_OK; }
   g_err = "dpe_set_option: unknown option or value";
   return DPE_ERR_ARG;
 }
 
 extern "C" long long dpe_pm_last_stat(DpeContext* c, int stat) {
-  if (c && c->staged && stat == DPE_STAT_TEX_CLASS) return c->img_cls;
-  if (!c || !c->staged || stat != DPE_STAT_GN_DEFERRED || !c->list_totals.p) return -1;
+  if (c && c->pass.staged && stat == DPE_STAT_TEX_CLASS) return c->pass.img_cls;
+  if (!c || !c->pass.staged || stat != DPE_STAT_GN_DEFERRED || !c->pass.list_totals.p) return -1;
   int v = 0;   // waits for this context's pass only (not the whole device)
   if (hipSetDevice(c->device) != hipSuccess || wait_pending(c) != hipSuccess || hipStreamSynchronize(c->aux) != hipSuccess ||
-      hipMemcpyAsync(&v, c->list_totals.p + PassLists::kTotGnOverflow, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync(&v, c->pass.list_totals.p + PassLists::kTotGnOverflow, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return -1;
   return v;
@@ -1807,6 +1132,6 @@ extern "C" long long dpe_pm_last_stat(DpeContext* c, int stat) {
 extern "C" int dpe_pm_last_counts(DpeContext* c, unsigned long long* out, int n) {
   if (!c || !out) return 0;
   const int m = n < DPE_NUM_CLASSES * 4 ? n : DPE_NUM_CLASSES * 4;
-  for (int i = 0; i < m; ++i) out[i] = c->counts[i];
+  for (int i = 0; i < m; ++i) out[i] = c->pass.counts[i];
   return m;
 }

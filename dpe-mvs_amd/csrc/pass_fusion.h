@@ -11,14 +11,9 @@
 // the reference's serial order (host/fusion.cpp).
 #pragma once
 #include "../../include/dpe_mvs.h"
+#include "dpe_fusion_types.h"   // FusionViewDev
 
 namespace dpe {
-
-struct FusionViewDev {
-  const float* depth;
-  const float* normal;
-  int w, h;
-};
 
 struct FP3 { float x, y, z; };
 

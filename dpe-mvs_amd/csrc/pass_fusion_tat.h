@@ -34,13 +34,7 @@ namespace dpe {
 constexpr int kTatChunk = 256;     // pixels per block of the scan, decide and fill kernels
 constexpr int kTatMaxSrc = 31;     // source views per image: one bit per k in the decide kernel
 
-struct TatViewDev {
-  const uint8_t* bgr;      // [H][W][3]
-  const uint8_t* block;    // [H][W] or nullptr
-  uint8_t* mask;           // [H][W] fusion mask
-};
-struct TatPoint { float x, y, z, b, g, r; };
-
+// (TatViewDev and TatPoint: dpe_fusion_types.h)
 struct TatEntry { float dist, depth, dot; int sp; };
 
 // DPE.cpp:1465-1471: the pixels the walk does not skip

@@ -550,7 +550,8 @@ __global__ void __launch_bounds__(64 * kBwLR, kTapWaves) k_local_refine_jobs(con
   if ((double)(t[11] - min_cost) > 0.1) B.planes[pix].w = best_depth;
 }
 
-// (non-template kernels: defined only in the translation unit that launches them, dpe_mvs.hip)
+// (non-template kernels: defined only in the translation unit that launches them, dpe_mvs.hip; of the
+// library's units only dpe_mvs.hip and the two tap units, which define DPE_TAP_TU, include this header)
 #ifndef DPE_TAP_TU
 // ------------------------------------------------------------------------------ FindNearestStrongPoint
 // Ring search r = 0..100 (DPE.cu:2855-2889) in O(1) per ring with two tables:

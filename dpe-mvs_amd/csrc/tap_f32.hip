@@ -13,16 +13,13 @@ namespace dpe {
 void launch_strong_f32(bool edge, unsigned grid, size_t lds, hipStream_t s, const PassConst* dpc, const DevBufs& B,
                        int it, const int* list, const int* count) {
   constexpr int T = 64 * kBwStrong;
-  if (lds > 65536) {   // dynamic LDS beyond the default limit (gfx950 has 160 KB per CU)
-    static bool once = false;
-    if (!once) {
-      once = true;
-      (void)hipFuncSetAttribute((const void*)k_strong_coop<TEX_F32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_strong_coop<TEX_F32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+  if (edge) {
+    allow_large_lds<k_strong_coop<TEX_F32, true>>(lds);
+    k_strong_coop<TEX_F32, true><<<grid, T, lds, s>>>(dpc, B, it, list, count);
+  } else {
+    allow_large_lds<k_strong_coop<TEX_F32, false>>(lds);
+    k_strong_coop<TEX_F32, false><<<grid, T, lds, s>>>(dpc, B, it, list, count);
   }
-  if (edge) k_strong_coop<TEX_F32, true><<<grid, T, lds, s>>>(dpc, B, it, list, count);
-  else k_strong_coop<TEX_F32, false><<<grid, T, lds, s>>>(dpc, B, it, list, count);
 }
 
 void launch_depth_to_weak_f32(unsigned grid, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
@@ -31,35 +28,17 @@ void launch_depth_to_weak_f32(unsigned grid, hipStream_t s, const PassConst* dpc
 
 void launch_local_refine_f32(unsigned grid, size_t lds, int border, hipStream_t s, const PassConst* dpc,
                              const DevBufs& B) {
-  if (lds > 65536) {
-    static bool once = false;
-    if (!once) {
-      once = true;
-      (void)hipFuncSetAttribute((const void*)k_local_refine_jobs<TEX_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-  }
+  allow_large_lds<k_local_refine_jobs<TEX_F32>>(lds);
   k_local_refine_jobs<TEX_F32><<<grid, 64 * kBwLR, lds, s>>>(dpc, B, border);
 }
 
 }  // namespace dpe
 
-// this unit's own copies of the DPE_DIAG counters (static __device__ in pass_common.h), summed by
-// tools/pool_stats.py and tools/line_stats.py with the other two units'
+// this unit's own copies of the DPE_DIAG counters
 #if DPE_POOL_STATS
-extern "C" void dpe_dbg_pool_stats_f32(unsigned long long out[24], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_pool), sizeof(dpe::g_pool));
-  if (reset) { unsigned long long z[24] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_pool), z, sizeof(z)); }
-}
-#endif
-#if DPE_POOL_STATS
-extern "C" void dpe_dbg_tail_stats_f32(unsigned long long out[8], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_tail), sizeof(dpe::g_tail));
-  if (reset) { unsigned long long z[8] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_tail), z, sizeof(z)); }
-}
+DPE_DBG_READER(pool, f32, dpe::g_pool, 24)
+DPE_DBG_READER(tail, f32, dpe::g_tail, 8)
 #endif
 #if DPE_LINE_STATS
-extern "C" void dpe_dbg_line_stats_f32(unsigned long long out[16], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_lstat), sizeof(dpe::g_lstat));
-  if (reset) { unsigned long long z[16] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_lstat), z, sizeof(z)); }
-}
+DPE_DBG_READER(line, f32, dpe::g_lstat, 16)
 #endif

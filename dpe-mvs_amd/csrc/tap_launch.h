@@ -1,7 +1,9 @@
 // tap_launch.h — source-image layout per kernel and the launchers of the tap kernels compiled in
-// their own translation units (tap_launch.hip; the f32-texel instantiations in tap_f32.hip).
+// their own translation units (tap_launch.hip; the f32-texel instantiations in tap_f32.hip), and what
+// the units that compile pass kernels share on the host side: allow_large_lds and DPE_DBG_READER.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "pass_common.h"
 
 // source-image layout of each kernel for 8-bit grey-level images (pass_common.h TEX_*): TEX_F16
@@ -34,4 +36,31 @@ void launch_strong_f32(bool edge, unsigned grid, size_t lds, hipStream_t s, cons
 void launch_depth_to_weak_f32(unsigned grid, hipStream_t s, const PassConst* dpc, const DevBufs& B);
 void launch_local_refine_f32(unsigned grid, size_t lds, int border, hipStream_t s, const PassConst* dpc,
                              const DevBufs& B);
+
+// Before a launch of `Kernel` with `bytes` of dynamic LDS: beyond the default 64 KB limit the kernel is
+// allowed gfx950's 160 KB per CU, once per (kernel, device).  Keying by device is a precaution: whether
+// the runtime keeps this function attribute per device has not been checked.  Threads that race here
+// all set the attribute (it is idempotent); none launches before its own call has returned.
+template <auto Kernel>
+inline void allow_large_lds(size_t bytes) {
+  if (bytes <= 65536) return;
+  constexpr int kDevices = 64;
+  static std::atomic<bool> done[kDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevices) dev = -1;   // unknown: set it every time
+  if (dev >= 0 && done[dev].load(std::memory_order_acquire)) return;
+  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (dev >= 0) done[dev].store(true, std::memory_order_release);
+}
 }  // namespace dpe
+
+// A reader of one of the DPE_DIAG counter arrays (static __device__ in pass_common.h / pass_sweep.h, so
+// every unit that launches counting kernels has its own copy): dpe_dbg_<kind>_stats_<unit>(out, reset)
+// copies the unit's `sym` (n values) out and optionally zeroes it.  tools/pool_stats.py and
+// tools/line_stats.py sum the units' (main, tap, f32).
+#define DPE_DBG_READER(kind, unit, sym, n)                                                              \
+  extern "C" void dpe_dbg_##kind##_stats_##unit(unsigned long long out[n], int reset) {                 \
+    static_assert(sizeof(sym) == (n) * sizeof(unsigned long long), "counter array size");               \
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(sym), sizeof(sym));                                       \
+    if (reset) { unsigned long long z[n] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(sym), z, sizeof(z)); } \
+  }

@@ -10,6 +10,10 @@
 // 21.81 -> 20.94 ms, wall 67.63 -> 65.73 ms (profiles/r05ad_ab_tapsched.log, bit-identical).  The
 // f32 instantiations still spill under the default (164-244 B/lane) and keep the iterative
 // scheduler in tap_f32.hip.  The weak sweep stays in dpe_mvs.hip with the default.
+// Of the library's units (the Makefile's table) only this one, tap_f32.hip and dpe_mvs.hip compile
+// pass kernels; each of the three has its own copy of the DPE_DIAG counters and its own readers
+// (DPE_DBG_READER, tap_launch.h), and a launch that needs more than 64 KB of LDS goes through
+// allow_large_lds (tap_launch.h).
 #define DPE_TAP_TU 1
 #include "tap_launch.h"
 #include "pass_refine.h"
@@ -20,17 +24,14 @@ namespace dpe {
 void launch_strong(bool edge, int cls, unsigned grid, size_t lds, hipStream_t s, const PassConst* dpc,
                    const DevBufs& B, int it, const int* list, const int* count) {
   constexpr int T = 64 * kBwStrong;
-  if (lds > 65536) {   // dynamic LDS beyond the default limit (gfx950 has 160 KB per CU)
-    static bool once = false;
-    if (!once) {
-      once = true;
-      (void)hipFuncSetAttribute((const void*)k_strong_coop<kTexStrong, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_strong_coop<kTexStrong, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-  }
   if (cls == IMG_F32) { launch_strong_f32(edge, grid, lds, s, dpc, B, it, list, count); return; }
-  if (edge) k_strong_coop<kTexStrong, true><<<grid, T, lds, s>>>(dpc, B, it, list, count);
-  else k_strong_coop<kTexStrong, false><<<grid, T, lds, s>>>(dpc, B, it, list, count);
+  if (edge) {
+    allow_large_lds<k_strong_coop<kTexStrong, true>>(lds);
+    k_strong_coop<kTexStrong, true><<<grid, T, lds, s>>>(dpc, B, it, list, count);
+  } else {
+    allow_large_lds<k_strong_coop<kTexStrong, false>>(lds);
+    k_strong_coop<kTexStrong, false><<<grid, T, lds, s>>>(dpc, B, it, list, count);
+  }
 }
 
 void launch_depth_to_weak(int cls, long L, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
@@ -46,34 +47,18 @@ void launch_local_refine(int cls, long L, int W, int H, int nv, hipStream_t s, c
   const unsigned g = (unsigned)((L + kBwLR * kLrPix - 1) / (kBwLR * kLrPix));
   if (g == 0) return;
   const size_t lds = (size_t)kBwLR * kLrPix * 12 * nv * 2 * sizeof(float);
-  if (lds > 65536) {
-    static bool once = false;
-    if (!once) {
-      once = true;
-      (void)hipFuncSetAttribute((const void*)k_local_refine_jobs<kTexLR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-  }
   if (cls == IMG_F32) { launch_local_refine_f32(g, lds, border, s, dpc, B); return; }
+  allow_large_lds<k_local_refine_jobs<kTexLR>>(lds);
   k_local_refine_jobs<kTexLR><<<g, 64 * kBwLR, lds, s>>>(dpc, B, border);
 }
 
 }  // namespace dpe
 
+// this unit's own copies of the DPE_DIAG counters
 #if DPE_POOL_STATS
-extern "C" void dpe_dbg_pool_stats_tap(unsigned long long out[24], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_pool), sizeof(dpe::g_pool));
-  if (reset) { unsigned long long z[24] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_pool), z, sizeof(z)); }
-}
-#endif
-#if DPE_POOL_STATS
-extern "C" void dpe_dbg_tail_stats_tap(unsigned long long out[8], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_tail), sizeof(dpe::g_tail));
-  if (reset) { unsigned long long z[8] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_tail), z, sizeof(z)); }
-}
+DPE_DBG_READER(pool, tap, dpe::g_pool, 24)
+DPE_DBG_READER(tail, tap, dpe::g_tail, 8)
 #endif
 #if DPE_LINE_STATS
-extern "C" void dpe_dbg_line_stats_tap(unsigned long long out[16], int reset) {
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(dpe::g_lstat), sizeof(dpe::g_lstat));
-  if (reset) { unsigned long long z[16] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(dpe::g_lstat), z, sizeof(z)); }
-}
+DPE_DBG_READER(line, tap, dpe::g_lstat, 16)
 #endif

@@ -333,7 +333,9 @@ def test_contexts_own_their_device_memory():
     """Every device allocation of a context is returned by dpe_state_clear / dpe_image_cache_clear /
     dpe_destroy: the library's count of live device bytes drops when states and cached images are
     cleared, and is back at its starting value once the contexts are closed (other contexts of the
-    process, such as this module's shared one, stay alive: compare with the start, not with 0)."""
+    process, such as this module's shared one, stay alive: compare with the start, not with 0).
+    The count is one counter for the whole library: on a fresh context the pass and then one call into
+    each other unit (edges, state, fusion, viz) must each make it grow."""
     from DPE_MVS import native
     before = native.live_device_bytes()
     inp, st = _ids_case(_texel_scene("u8"))
@@ -341,8 +343,26 @@ def test_contexts_own_their_device_memory():
     views = [(np.where(np.isfinite(v["depth"]), v["depth"], 0).astype(np.float32), v["normals"], cam)
              for v, cam in zip(tiny["views"], tiny["cams"])]
     img = np.ascontiguousarray(_texel_scene("u8")["images"][0][:48, :64])
-    a, b = native.PatchMatchContext(0), native.PatchMatchContext(0)
+    a, b, u = native.PatchMatchContext(0), native.PatchMatchContext(0), native.PatchMatchContext(0)
     try:
+        seen = [native.live_device_bytes()]
+
+        def grew(what):
+            seen.append(native.live_device_bytes())
+            assert seen[-1] > seen[-2], f"{what} allocated nothing that dpe_live_device_bytes counts"
+
+        u.run(inp, st)
+        grew("the pass")
+        u.resize_u8(np.zeros((12, 16), np.uint8), 8, 6)
+        grew("dpe_resize_u8")
+        assert native._LIB.dpe_device_buffer(u._ctx, 0, 64)
+        grew("dpe_device_buffer")
+        small = [(np.ones((6, 8), np.float32), np.zeros((6, 8, 3), np.float32), cam) for cam in tiny["cams"][:2]]
+        arr, keep = native.fusion_view_array(small)
+        assert native._LIB.dpe_fusion_stage(u._ctx, arr, 2) == _abi.DPE_OK
+        grew("dpe_fusion_stage")
+        u.viz_render_arrays(native.VIZ_DEPTH, depth=np.ones((6, 8), np.float32), dmin=0.5, dmax=2.0)
+        grew("dpe_viz_render_arrays")
         for c in (a, b):
             c.run(dict(inp, image_ids=[1, 2, 3, 4]), st)
             c.state_save(1)
@@ -361,7 +381,44 @@ def test_contexts_own_their_device_memory():
     finally:
         a.close()
         b.close()
+        u.close()
     assert native.live_device_bytes() == before
+
+
+def test_last_error_is_one_string_for_every_unit():
+    """dpe_last_error is one thread-local string for the whole library: an entry point of each unit
+    (edges, fusion, viz, state) refuses a call on the host, before any launch, with its own message,
+    and a following successful call into ANOTHER unit leaves the string empty.  Codes as
+    include/dpe_mvs.h documents them: DPE_ERR_ARG for the bad arguments, DPE_ERR_STATE for candidates
+    before staging and for a state that does not exist."""
+    import ctypes as C
+    from DPE_MVS import native
+    lib, ERR_ARG, ERR_STATE = native._LIB, -1, -4
+    last = lambda: lib.dpe_last_error().decode()  # noqa: E731
+    c = native.PatchMatchContext(0)
+    try:
+        u8, i32, f32 = np.zeros((6, 8), np.uint8), np.zeros(48, np.int32), np.zeros(144, np.float32)
+        out = np.zeros((6, 8, 3), np.uint8)
+        w, h = C.c_int(), C.c_int()
+        cases = [
+            (lambda: lib.dpe_canny(c._ctx, None, 8, 6, 50.0, 150.0, u8.ctypes.data), ERR_ARG, "dpe_canny: bad argument",
+             lambda: lib.dpe_sync(c._ctx)),                                               # edges, then state
+            (lambda: lib.dpe_fusion_candidates(c._ctx, 0, i32.ctypes.data, 1, i32.ctypes.data, f32.ctypes.data), ERR_STATE,
+             "dpe_fusion_candidates: nothing staged",
+             lambda: lib.dpe_resize_u8(c._ctx, u8.ctypes.data, 8, 6, out.ctypes.data, 4, 3)),   # fusion, then edges
+            (lambda: lib.dpe_state_render(c._ctx, 1, 7, 0.0, 1.0, out.ctypes.data), ERR_ARG, "dpe_state_render: bad kind",
+             lambda: lib.dpe_set_option(c._ctx, _abi.DPE_OPT_GN_SLOTS, 0)),              # viz, then the main unit
+            (lambda: lib.dpe_state_fetch(c._ctx, 12345, C.byref(w), C.byref(h), None, None, None, None), ERR_STATE,
+             "dpe_state_fetch: no state of image 12345",
+             lambda: lib.dpe_fusion_tat_wait(c._ctx)),                                    # state, then fusion
+        ]
+        for bad, code, message, good in cases:
+            assert bad() == code, message
+            assert last() == message
+            assert good() == _abi.DPE_OK, last()
+            assert last() == ""
+    finally:
+        c.close()
 
 
 def test_stage_waits_for_execute_on_a_foreign_stream(ctx):

@@ -1,24 +1,25 @@
 #!/usr/bin/env python3
-"""Per-kernel register / scratch / occupancy table of lib/libdpe_mvs.so's three translation units
-(hipcc -Rpass-analysis=kernel-resource-usage, each with the Makefile's flags: the default scheduler
-for csrc/dpe_mvs.hip (SLP vectorizer off) and csrc/tap_launch.hip, iterative-maxocc for
-csrc/tap_f32.hip).
-Usage: python tools/ru.py [extra hipcc flags...]"""
+"""Per-kernel register / scratch / occupancy table of lib/libdpe_mvs.so's translation units (hipcc
+-Rpass-analysis=kernel-resource-usage): the units and flags of dpe-mvs_amd/Makefile's table, compiled
+once more into a scratch folder.  Usage: python tools/ru.py [extra hipcc flags...]"""
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 
 ROOT = __file__.rsplit("/tools/", 1)[0]
-base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-        "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/dpe_ru.o"]
-out = subprocess.run(base + ["-fno-slp-vectorize", ROOT + "/dpe-mvs_amd/csrc/dpe_mvs.hip"] + sys.argv[1:],
-                     capture_output=True, text=True).stderr
-out += subprocess.run(base + [ROOT + "/dpe-mvs_amd/csrc/tap_launch.hip"] + sys.argv[1:],
-                      capture_output=True, text=True).stderr
-out += subprocess.run(base + ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc", ROOT + "/dpe-mvs_amd/csrc/tap_f32.hip"]
-                      + sys.argv[1:], capture_output=True, text=True).stderr
+objdir = tempfile.mkdtemp(prefix="dpe_ru_")
+try:
+    out = subprocess.run(["make", "-C", ROOT + "/dpe-mvs_amd", "-j16", "-Otarget", "OBJDIR=" + objdir, "objects",
+                          "EXTRA_FLAGS=" + " ".join(["-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:])],
+                         capture_output=True, text=True)
+finally:
+    shutil.rmtree(objdir, ignore_errors=True)
+if out.returncode:
+    sys.exit(out.stdout + out.stderr)
 rows, cur = [], None
-for line in out.splitlines():
+for line in (out.stdout + out.stderr).splitlines():
     m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         continue
