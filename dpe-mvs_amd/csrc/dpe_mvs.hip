@@ -222,6 +222,8 @@ static void compute_pass_constants(PassConst& pc) {
   pc.gn_shift = sri < 1 ? 1 : sri;
   pc.half_rows = std::min(pc.H, 2 * 16 * (((pc.H / 2) + 15) / 16));
   pc.weak_nn = pc.P.weak_radius >= 0 && pc.P.weak_increment > 0 ? (2 * pc.P.weak_radius) / pc.P.weak_increment + 1 : 0;
+  pc.tex_wide = tex_wide<TEX_F16>(pc.W);   // the 4-byte layouts' row coefficient fits at every supported width
+  static_assert(!tex_wide<TEX_P16>(16000) && !tex_wide<TEX_U8>(16000), "stage_check_args' width limit");
   // float tables of per-pixel expressions that do not depend on the pixel (same bits, pass_tables.h)
   for (int v = 1; v < pc.N; ++v) pc.base_len[v] = baseline_length(rc.c, pc.cams[v].c);
   build_spat36(pc.P.sigma_spatial, pc.spat36);
@@ -312,7 +314,11 @@ static int stage_check_args(const DpePassInput* in) {   // no HIP call
   if (in->num_images > DPE_MAX_IMAGES) { g_err = "dpe_pm_stage: num_images > 32 (DPE.cpp:762)"; return DPE_ERR_TOO_MANY; }
   if (in->num_images < 2 || in->width <= 0 || in->height <= 0) { g_err = "dpe_pm_stage: bad shape"; return DPE_ERR_ARG; }
   if (in->width > 32000 || in->height > 32000) { g_err = "dpe_pm_stage: image too large for short2 coordinates"; return DPE_ERR_ARG; }
-  // tap coordinates on the unit grid of [2^23, 2^24) (pass_common.h kTexMagic): 256 (lim + 1) < 2^22
+  // tap coordinates on the unit grid of [2^23, 2^24) (pass_common.h kTexMagic): 256 (lim + 1) < 2^22.
+  // It also keeps the texel indices below 0xC000 and the 4-byte layouts' row of texels below 64 KiB,
+  // which the fast taps' packed texel offset needs (tex_addr.h); the 8-byte layout's rows pass 64 KiB
+  // from W = 8190 on, and such a pass runs that layout's kernels with the four-instruction offset
+  // (PassConst::tex_wide, set per pass in compute_pass_constants).
   if (in->width > 16000 || in->height > 16000) { g_err = "dpe_pm_stage: image wider or taller than 16000 px"; return DPE_ERR_ARG; }
   const DpePatchMatchParams& P = in->params;
   if (P.rotate_time < 1 || P.rotate_time > 4) { g_err = "dpe_pm_stage: rotate_time must be in [1,4]"; return DPE_ERR_ARG; }
@@ -971,6 +977,7 @@ static void weak_sweep(const PassRun& X, const DevBufs& Bc, int it, int colour, 
   const unsigned grid = (unsigned)((X.L / 2 + 1 + wpb * P - 1) / (wpb * P));
   // U8 texels for 8-bit images; F16 (exact for quarter-integer grey levels) for the coarse levels
   if (X.c->pass.img_cls == IMG_U8) k_weak_coop<kTexWeak, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
+  else if (X.c->pass.img_cls == IMG_Q && X.pc.tex_wide) k_weak_coop<TEX_F16W, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
   else if (X.c->pass.img_cls == IMG_Q) k_weak_coop<TEX_F16, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
   else k_weak_coop<TEX_F32, C><<<grid, 64 * wpb, per_wave * wpb, st>>>(X.dpc, Bc, it, lst, cnt);
 }
@@ -1018,14 +1025,14 @@ static int depth_to_weak(PassRun& X) {
   DpeContext* c = X.c;
   auto border_local_refine = [&](hipStream_t st) {
     Section sec(X.rec, DPE_CLASS_LOCAL_REFINE);
-    launch_local_refine(c->pass.img_cls, (long)X.L, X.pc.W, X.pc.H, X.nv, st, X.dpc, sec.B);
+    launch_local_refine(c->pass.img_cls, X.pc.tex_wide, (long)X.L, X.pc.W, X.pc.H, X.nv, st, X.dpc, sec.B);
   };
   HIPC(X.fork(c->ev_fork));
   if (X.overlap) border_local_refine(X.a);
   HIPC(X.aux_done(c->ev_join));
   {
     Section sec(X.rec, DPE_CLASS_DEPTH_TO_WEAK);
-    launch_depth_to_weak(c->pass.img_cls, (long)X.L, X.s, X.dpc, sec.B);
+    launch_depth_to_weak(c->pass.img_cls, X.pc.tex_wide, (long)X.L, X.s, X.dpc, sec.B);
   }
   HIPC(X.wait_aux(c->ev_join));
   if (!X.overlap) border_local_refine(X.s);

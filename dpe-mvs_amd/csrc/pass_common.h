@@ -17,6 +17,7 @@
 #pragma once
 #include "device_math.h"
 #include "bres_walk.h"
+#include "tex_addr.h"
 #include "../../include/dpe_mvs.h"
 
 namespace dpe {
@@ -32,6 +33,8 @@ struct PassConst {
   int gn_shift;
   uint32_t gn_shift_m;       // floor(2^32 / gn_shift) (2^32 - 1 for 1): x % gn_shift as a multiply (gn_mod)
   int weak_nn;               // side of the weak sweep's neighbour patches, (2 weak_radius) / weak_increment + 1 (0 if radius < 0)
+  int tex_wide;              // frames too wide for the two-instruction texel offset in the 8-byte layout (tex_addr.h):
+                             // the host launches that layout's kernels as TEX_F16W (read on the host only)
   float base_len[DPE_MAX_IMAGES];   // |C_0 - C_v|, baseline_and_weights' summand (pass_tables.h; [0] unused)
   float spat36[36];                 // spatial term of the 5/2 patch's bilateral weights (pass_tables.h)
   DpePatchMatchParams P;
@@ -86,6 +89,10 @@ struct DevBufs {
 //   4  the strong sweep's slot list, selected-view list and refinement hypotheses on one lane per pixel
 //   8  LocalRefine's hypothesis depths divided again on lane 0 of DepthToWeak (not read from its lanes)
 //  16  the strong pools' last rounds split as before: cost vectors up to 16 jobs, refinement never
+//  32  the fast taps' texel offset in four instructions (tex_addr.h tex_offset4), not two (tex_offset2)
+//  64  (unused: the same offset in the weak sweep's sample_quad8 was measured and not adopted)
+// 128  the Old NCC's centre test always with the IEEE division and before the patch's reciprocal-range
+//      test, not after it with the 3-op exact reciprocal where the range holds
 #ifndef DPE_AB_OFF
 #define DPE_AB_OFF 0
 #endif
@@ -443,7 +450,6 @@ DEV float ref_texel(const float* ref, int W, int H, int x, int y) {
 // the float (one full-rate op in place of v_cvt_f32_ubyte0 + a multiply per axis).
 constexpr float kTexMagic = 49152.0f;             // 1.5 * 2^15
 constexpr uint32_t kTexMagicBits = 0x47400000u;   // its encoding
-constexpr uint32_t kTexMagicHi = 0x474000u;       // encoding >> 8: texel index bias of t >> 8
 constexpr float kTexUnit = 1.0f;                  // one texel in t units
 DEV float tex_tmax(int lim) { return kTexMagic + kTexUnit * (float)(lim + 1); }   // t of U = 256 lim + 256
 // clamped t of a tap with scaled row value Q (generic path: NaN -> kTexMagic)
@@ -491,17 +497,15 @@ DEV float sample_quad(const float4* __restrict__ q, int W, int H, float Qx, floa
 //     load; the row differences are one packed f16 subtraction (exact: integers <= 255), so each row
 //     interpolation is again one v_fma_mix_f32, now with fx/256 (exact) times (b-a): 2 more VALU ops
 //     per tap than TEX_F16 for half the footprint (and a layout whose windows copy as plain rows).
-enum { TEX_F32 = 0, TEX_U8 = 1, TEX_F16 = 2, TEX_P16 = 3 };
+// (the enum is in tex_addr.h, with TEX_F16W: TEX_F16's texels under the four-instruction offset)
 typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 typedef uint2 uint2_a4 __attribute__((aligned(4)));
 template <int T> DEV const uint8_t* tex_base(const DevBufs& B) {
-  return T == TEX_F16 ? B.img16 : (T == TEX_P16 ? B.imgp : B.img8);
+  return tex_bytes<T>() == 8 ? B.img16 : (T == TEX_P16 ? B.imgp : B.img8);
 }
 template <int T> DEV uint32_t tex_view(const DevBufs& B) {
-  return T == TEX_F16 ? B.img16_view : (T == TEX_P16 ? B.imgp_view : B.img8_view);
+  return tex_bytes<T>() == 8 ? B.img16_view : (T == TEX_P16 ? B.imgp_view : B.img8_view);
 }
-template <int T> constexpr uint32_t tex_bytes() { return T == TEX_F16 ? 8u : 4u; }
-template <int T> DEV uint32_t tex_stride(int W) { return (uint32_t)(W + (T == TEX_P16 ? 3 : 2)); }
 // the two row interpolations (r0 at y0, r1 at y1) of the texel at `p` for the x weight ax = fx / 256
 // texel loads of the fast taps; DPE_FAKE_GATHER (timing only): f16 values in [128, 256) / bytes made
 // from the address bits instead of memory
@@ -527,7 +531,7 @@ DEV void texel_rows(const uint8_t* p, float ax, float& r0, float& r1) {
     const uint32_t d = __builtin_bit_cast(uint32_t, df);
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r0) : "v"(ax), "v"(d), "v"(t.x));
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,1,1] op_sel_hi:[0,1,1]" : "=v"(r1) : "v"(ax), "v"(d), "v"(t.x));
-  } else if constexpr (T == TEX_F16) {
+  } else if constexpr (T == TEX_F16 || T == TEX_F16W) {
     // v_fma_mix_f32 is fma(ax, (float)half, (float)half) with one rounding; the compiler only forms
     // it under f32 denormal flushing, which cannot matter here (|ax*d| >= 2^-8 or 0, a integer)
     const uint2 t = LD_TEXEL_F16(p);
@@ -591,8 +595,9 @@ DEV void line_stat(int T, const void* p) {
     ++nl;
   }
   if ((int)(threadIdx.x & 63) == first) {
-    atomicAdd(&g_lstat[T][0], 1ull); atomicAdd(&g_lstat[T][1], nl);
-    atomicAdd(&g_lstat[T][2], ns); atomicAdd(&g_lstat[T][3], act);
+    const int Ti = T == TEX_F16W ? TEX_F16 : T;
+    atomicAdd(&g_lstat[Ti][0], 1ull); atomicAdd(&g_lstat[Ti][1], nl);
+    atomicAdd(&g_lstat[Ti][2], ns); atomicAdd(&g_lstat[Ti][3], act);
   }
 }
 #define LINE_STAT(T, p) line_stat(T, p)
@@ -600,36 +605,41 @@ DEV void line_stat(int T, const void* p) {
 #define LINE_STAT(T, p) do {} while (0)
 #endif
 
-// Fast-path tap constants of one (view, homography): the t clamps of the two axes and the view's
-// byte offset biased so that the t encodings index texels directly:
-//   offset = vofs + ((Uy >> 8) * stride + (Ux >> 8)) * bytes
-//          = vadj + ((bits(ty) >> 8) * stride + (bits(tx) >> 8)) * bytes   (mod 2^32)
-// with vadj = vofs - kTexMagicHi * (stride + 1) * bytes (bits(t) >> 8 = kTexMagicHi + (U >> 8) < 2^24,
-// so __umul24 sees the whole operand; the true offset is below 2^32, so the wrap-around cancels).
+// Fast-path tap constants of one (view, homography): the t clamps of the two axes and the texel
+// offset's two constants (tex_addr.h): the row coefficient `coef` of the layout (wave-uniform) and the
+// view's byte offset `vadj`, biased so that the t encodings index texels directly.  Layout T takes the
+// two-instruction offset unless it is TEX_F16W (frames too wide for it) or DPE_AB_OFF & 32.
 DEV f2v tex_tmax2(int W, int H) { return (f2v){tex_tmax(W), tex_tmax(H)}; }
-template <int T> DEV uint32_t tex_vadj(uint32_t vofs, uint32_t stride) {
-  return vofs - kTexMagicHi * (stride + 1u) * tex_bytes<T>();
+template <int T> constexpr bool tap_packed() { return !((DPE_AB_OFF) & 32) && T != TEX_F16W; }
+template <int T> DEV uint32_t tap_coef(uint32_t stride) { return tap_packed<T>() ? tex_coef<T>(stride) : stride; }
+template <int T> DEV uint32_t tap_vadj(uint32_t vofs, uint32_t stride) {
+  return tap_packed<T>() ? tex_vadj2<T>(vofs, stride) : tex_vadj<T>(vofs, stride);
+}
+// byte offset of the texel of the clamped coordinates with encodings (uy, ux)
+template <int T> DEV uint32_t tap_offset(uint32_t uy, uint32_t ux, uint32_t coef, uint32_t vadj) {
+  if constexpr (tap_packed<T>()) return tex_offset2(tex_pack(uy, ux), coef, vadj);
+  else return tex_offset4<T>(uy, ux, coef, vadj);
 }
 // clamped t of the fast path (no NaN there: rcp_range_ok)
 DEV float tex_t_fast(float t, float tmax) { return __builtin_amdgcn_fmed3f(t, kTexMagic, tmax); }
 
-// One bilinear tap of the 8-bit quad image (layout T) at the view offset `vadj` (tex_vadj), from
+// One bilinear tap of the 8-bit quad image (layout T) at the view offset `vadj` (tap_vadj), from
 // the homography h with scaled column coefficients (scale_cols) and its row terms
 // bxy = 256 (h0 x + h2, h3 x + h5), bz = h6 x + h8; column yf.  Bit-identical to sample_quad8 with
 // rcp_model's reciprocal when the tap's qz has a biased exponent in [1, 252] (rcp_range_ok), where
 // the bare v_rcp_f32 is restatement choice 8's tap reciprocal.
 template <int T>
-DEV float tap_u8_fast(const DevBufs& B, uint32_t vadj, uint32_t stride, f2v tmax, const float* h, f2v bxy, float bz,
+DEV float tap_u8_fast(const DevBufs& B, uint32_t vadj, uint32_t coef, f2v tmax, const float* h, f2v bxy, float bz,
                       float yf) {
   const f2v q = fma2((f2v){h[1], h[4]}, f2s(yf), bxy);
   const float iz = rcp_tap<true>(__builtin_fmaf(h[7], yf, bz));
   const f2v t = fma2(q, f2s(iz), f2s(kTexMagic + kTexUnit));
   const float ctx = tex_t_fast(t.x, tmax.x), cty = tex_t_fast(t.y, tmax.y);
   const uint32_t ux = __float_as_uint(ctx), uy = __float_as_uint(cty);
-  const uint8_t* p = tex_base<T>(B) + (vadj + (__umul24(uy >> 8, stride) + (ux >> 8)) * tex_bytes<T>());
+  const uint8_t* p = tex_base<T>(B) + tap_offset<T>(uy, ux, coef, vadj);
   LINE_STAT(T, p);
   const float ay = tex_frac(cty, uy);
-  if constexpr (T == TEX_F16 || T == TEX_P16) {
+  if constexpr (T != TEX_U8) {
     float r0, r1;
     texel_rows<T>(p, tex_frac(ctx, ux), r0, r1);
     return __builtin_fmaf(ay, r1 - r0, r0);
@@ -648,7 +658,7 @@ DEV float tap_u8_fast(const DevBufs& B, uint32_t vadj, uint32_t stride, f2v tmax
 // so each result is bit-identical to it.
 // `base` is the texel array the byte offsets index (tex_base of the layout; vadj selects the view).
 template <int T, bool CLAMP = true>
-DEV f2v tap2_at(const uint8_t* base, uint32_t vadj, uint32_t stride, f2v tmax, const float* h, f2v bxy, float bz, f2v yf) {
+DEV f2v tap2_at(const uint8_t* base, uint32_t vadj, uint32_t coef, f2v tmax, const float* h, f2v bxy, float bz, f2v yf) {
   const f2v qx = fma2(f2s(h[1]), yf, f2s(bxy.x));
   const f2v qy = fma2(f2s(h[4]), yf, f2s(bxy.y));
   const f2v qz = fma2(f2s(h[7]), yf, f2s(bz));
@@ -660,20 +670,21 @@ DEV f2v tap2_at(const uint8_t* base, uint32_t vadj, uint32_t stride, f2v tmax, c
   const float cy0 = CLAMP ? tex_t_fast(ty.x, tmax.y) : ty.x, cy1 = CLAMP ? tex_t_fast(ty.y, tmax.y) : ty.y;
   const uint32_t ux0 = __float_as_uint(cx0), ux1 = __float_as_uint(cx1);
   const uint32_t uy0 = __float_as_uint(cy0), uy1 = __float_as_uint(cy1);
-  const uint8_t* p0 = base + (vadj + (__umul24(uy0 >> 8, stride) + (ux0 >> 8)) * tex_bytes<T>());
-  const uint8_t* p1 = base + (vadj + (__umul24(uy1 >> 8, stride) + (ux1 >> 8)) * tex_bytes<T>());
+  const uint8_t* p0 = base + tap_offset<T>(uy0, ux0, coef, vadj);
+  const uint8_t* p1 = base + tap_offset<T>(uy1, ux1, coef, vadj);
   LINE_STAT(T, p0);
   LINE_STAT(T, p1);
-  const f2v ay = (f2v){tex_frac(cy0, uy0), tex_frac(cy1, uy1)};
   float a0, a1, b0, b1;
   texel_rows<T>(p0, tex_frac(cx0, ux0), a0, a1);
   texel_rows<T>(p1, tex_frac(cx1, ux1), b0, b1);
   const f2v r0 = (f2v){a0, b0}, r1 = (f2v){a1, b1};
+  // (the column weights after the rows: written before them, the strong sweep's 8-lane kernel spills 16 B)
+  const f2v ay = (f2v){tex_frac(cy0, uy0), tex_frac(cy1, uy1)};
   return fma2(ay, r1 - r0, r0);
 }
 template <int T>
-DEV f2v tap2_fast(const DevBufs& B, uint32_t vadj, uint32_t stride, f2v tmax, const float* h, f2v bxy, float bz, f2v yf) {
-  return tap2_at<T>(tex_base<T>(B), vadj, stride, tmax, h, bxy, bz, yf);
+DEV f2v tap2_fast(const DevBufs& B, uint32_t vadj, uint32_t coef, f2v tmax, const float* h, f2v bxy, float bz, f2v yf) {
+  return tap2_at<T>(tex_base<T>(B), vadj, coef, tmax, h, bxy, bz, yf);
 }
 
 // Sample of view v at the tap with scaled numerators (Qx, Qy) and reciprocal denominator iz.
@@ -797,6 +808,22 @@ DEV bool center_outside(const PassConst& pc, int v, const Homog& H, int px, int 
   const float2 pt = FAST ? project_h_fast(H, (float)px, (float)py) : project_h(H, (float)px, (float)py);
   const DpeCamera& sc = pc.cams[v];
   return pt.x >= (float)sc.width || pt.x < 0.0f || pt.y >= (float)sc.height || pt.y < 0.0f;
+}
+
+// center_outside of the centre of a 5/2 patch together with the patch's reciprocal-range test `ok`
+// (left unset when the centre is outside and DPE_AB_OFF & 128).  The range test first: where it holds,
+// the centre's denominator, one of the box's, has a biased exponent in [1, 252], so the 3-op
+// reciprocal is the IEEE quotient bit for bit (d_rcp_fast) and the test's outcome is the same.
+DEV bool center_outside_patch(const PassConst& pc, int v, const Homog& H, int px, int py, bool& ok) {
+  if constexpr ((DPE_AB_OFF) & 128) {
+    if (center_outside(pc, v, H, px, py)) return true;
+    ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
+    return false;
+  } else {
+    ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
+    if (__builtin_expect(ok, 1)) return center_outside<true>(pc, v, H, px, py);   // a branch: the division stays rare
+    return center_outside<false>(pc, v, H, px, py);
+  }
 }
 
 // ComputeBilateralNCCOld (DPE.cu:692-778), weights per tap.

@@ -68,7 +68,7 @@ template <int U8, bool CLAMP = true>
 DEV void taps36_at(const float* pw, int px, int py, f2v tmax, const uint8_t* base, uint32_t vofs, uint32_t stride,
                    const Homog& H0, float* acc) {
     const Homog H = scale_cols(H0);
-    const uint32_t vadj = tex_vadj<U8>(vofs, stride);
+    const uint32_t vadj = tap_vadj<U8>(vofs, stride), coef = tap_coef<U8>(stride);
     // packed form: (r_src, r_rs) accumulate as one pair; weights are (w, w*grey) pairs in LDS
     const f2v* wp = (const f2v*)pw;
     f2v s_sr = f2s(0.0f);
@@ -82,7 +82,7 @@ DEV void taps36_at(const float* pw, int px, int py, f2v tmax, const uint8_t* bas
       float r_ss = 0;
 #pragma unroll
       for (int b = 0; b < 6; b += 2) {
-        const f2v sp = tap2_at<U8, CLAMP>(base, vadj, stride, tmax, H.h, bxy, bz,
+        const f2v sp = tap2_at<U8, CLAMP>(base, vadj, coef, tmax, H.h, bxy, bz,
                                    (f2v){(float)(py - 5 + 2 * b), (float)(py - 3 + 2 * b)});
         const f2v w0 = wp[a * 6 + b], w1 = wp[a * 6 + b + 1];
         const float ws0 = w0.x * sp.x, ws1 = w1.x * sp.y;   // two plain multiplies: no operand packing
@@ -151,7 +151,7 @@ DEV void lds_row(const float* pw, int px, int py, const PassConst& pc, const Dev
   const Homog H = scale_cols(H0);
   const float x = (float)(px - 5 + 2 * a);
   if constexpr (U8 != TEX_F32 && FAST) {
-    const uint32_t stride = tex_stride<U8>(W), vadj = tex_vadj<U8>((uint32_t)v * tex_view<U8>(B), stride);
+    const uint32_t stride = tex_stride<U8>(W), vadj = tap_vadj<U8>((uint32_t)v * tex_view<U8>(B), stride), coef = tap_coef<U8>(stride);
     const f2v tmax = tex_tmax2(W, Hh);
     const f2v* wp = (const f2v*)pw;
     const f2v bxy = fma2((f2v){H.h[0], H.h[3]}, f2s(x), (f2v){H.h[2], H.h[5]}) * f2s(kTexUnit);
@@ -160,7 +160,7 @@ DEV void lds_row(const float* pw, int px, int py, const PassConst& pc, const Dev
     float r_ss = 0;
 #pragma unroll
     for (int b = 0; b < 6; b += 2) {
-      const f2v sp = tap2_fast<U8>(B, vadj, stride, tmax, H.h, bxy, bz, (f2v){(float)(py - 5 + 2 * b), (float)(py - 3 + 2 * b)});
+      const f2v sp = tap2_fast<U8>(B, vadj, coef, tmax, H.h, bxy, bz, (f2v){(float)(py - 5 + 2 * b), (float)(py - 3 + 2 * b)});
       const f2v w0 = wp[a * 6 + b], w1 = wp[a * 6 + b + 1];
       const float ws0 = w0.x * sp.x, ws1 = w1.x * sp.y;
       r_sr = fma2(w0, f2s(sp.x), r_sr);
@@ -194,10 +194,10 @@ template <int U8>
 DEV float ncc_old_lds(const float* pw, float s_ref, float s_rr, float s_w, int px, int py, const PassConst& pc,
                       const DevBufs& B, int v, const float4& pl) {
   const Homog H = make_homography(pc, v, pl);
-  if (center_outside(pc, v, H, px, py)) { count_work(B, 1, 0); return 2.0f; }
+  bool ok;
+  if (center_outside_patch(pc, v, H, px, py, ok)) { count_work(B, 1, 0); return 2.0f; }
   count_work(B, 1, 36);
   float a[3];
-  const bool ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
   PATCH_STAT(ok);
   if (ok) {
     // the clamp-free taps when every active lane's patch is inside the image with a texel to spare

@@ -422,9 +422,9 @@ DEV void pool_tail_split(int tail, int lane, float* tb, const PassConst& pc, con
   if (tl.job >= 0) {
     J = job(tl.job);
     const Homog H = make_homography(pc, J.v, J.pl);
-    outside = center_outside(pc, J.v, H, J.qx, J.qy);
+    bool fr;
+    outside = center_outside_patch(pc, J.v, H, J.qx, J.qy, fr);
     if (!outside) {
-      const bool fr = rcp_range_ok(H, (float)(J.qx - 5), (float)(J.qx + 5), (float)(J.qy - 5), (float)(J.qy + 5));
       for (int a = tl.row0; a < tl.row0 + tl.rows; ++a) {
         float r3[3];
         if (fr) lds_row<U8, true>(J.pw, J.qx, J.qy, pc, B, J.v, H, a, r3);
@@ -918,7 +918,7 @@ DEV void tab_taps(const PassConst& pc, const DevBufs& B, int v, const Homog& H0,
   const int n = NN > 0 ? NN : n_rt;
   const f2v* wp = (const f2v*)tw;            // (w, w*grey) pairs
   if constexpr (U8 != TEX_F32 && FAST) {
-    const uint32_t stride = tex_stride<U8>(W), vadj = tex_vadj<U8>((uint32_t)v * tex_view<U8>(B), stride);
+    const uint32_t stride = tex_stride<U8>(W), vadj = tap_vadj<U8>((uint32_t)v * tex_view<U8>(B), stride), coef = tap_coef<U8>(stride);
     const f2v tmax = tex_tmax2(W, Hh);
     f2v s_sr = f2s(0.0f);
     float s_ss = 0;
@@ -931,7 +931,7 @@ DEV void tab_taps(const PassConst& pc, const DevBufs& B, int v, const Homog& H0,
       float r_ss = 0;
 #pragma unroll
       for (int b = 0; b < (NN > 0 ? NN : n); ++b) {
-        const float sp = tap_u8_fast<U8>(B, vadj, stride, tmax, H.h, bxy, bz, (float)(cy - rad + b * inc));
+        const float sp = tap_u8_fast<U8>(B, vadj, coef, tmax, H.h, bxy, bz, (float)(cy - rad + b * inc));
         const f2v w = wp[a * n + b];
         r_sr = fma2(w, f2s(sp), r_sr);
         const float ws = w.x * sp;

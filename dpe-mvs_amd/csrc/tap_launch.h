@@ -18,17 +18,18 @@ constexpr int kTexInit = TEX_F16, kTexStrong = TEX_P16, kTexWeak = TEX_U8;
 constexpr int kTexD2W = TEX_F16, kTexLR = TEX_F16;
 
 // Launchers (tap_launch.hip).  cls: ImgClass of the staged images (IMG_U8 / IMG_Q: the half-precision
-// layouts are staged; IMG_F32: the f32 quad image only).
+// layouts are staged; IMG_F32: the f32 quad image only).  wide: PassConst::tex_wide, the TEX_F16 kernels
+// run as TEX_F16W (tex_addr.h).
 // CheckerboardPropagationStrong + refinement, one colour's list (edge: 4 pixels x 16 lanes per wave,
 // else 8 x 8); the grid and dynamic LDS are the caller's (strong_lds_per_wave).
 void launch_strong(bool edge, int cls, unsigned grid, size_t lds, hipStream_t s, const PassConst* dpc,
                    const DevBufs& B, int it, const int* list, const int* count);
 // DepthToWeak over the L pixels of the pass (one wave per pixel), with LocalRefine fused into its
 // epilogue for interior pixels
-void launch_depth_to_weak(int cls, long L, hipStream_t s, const PassConst* dpc, const DevBufs& B);
+void launch_depth_to_weak(int cls, bool wide, long L, hipStream_t s, const PassConst* dpc, const DevBufs& B);
 // LocalRefine (kLrPix pixels per wave), nv source views, over the border pixels the fused
 // DepthToWeak leaves
-void launch_local_refine(int cls, long L, int W, int H, int nv, hipStream_t s, const PassConst* dpc, const DevBufs& B);
+void launch_local_refine(int cls, bool wide, long L, int W, int H, int nv, hipStream_t s, const PassConst* dpc, const DevBufs& B);
 // the f32-texel instantiations of the three (tap_f32.hip, occupancy-first scheduler); the grid,
 // dynamic LDS and arguments are the launchers' above
 void launch_strong_f32(bool edge, unsigned grid, size_t lds, hipStream_t s, const PassConst* dpc, const DevBufs& B,

@@ -34,13 +34,15 @@ void launch_strong(bool edge, int cls, unsigned grid, size_t lds, hipStream_t s,
   }
 }
 
-void launch_depth_to_weak(int cls, long L, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
+void launch_depth_to_weak(int cls, bool wide, long L, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
   const unsigned g = (unsigned)((L + kBwD2W - 1) / kBwD2W);
   if (cls == IMG_F32) { launch_depth_to_weak_f32(g, s, dpc, B); return; }
-  k_depth_to_weak<kTexD2W, true><<<g, 64 * kBwD2W, 0, s>>>(dpc, B);
+  static_assert(kTexD2W == TEX_F16 && kTexLR == TEX_F16 && kTexStrong != TEX_F16, "the wide twins below");
+  if (wide) k_depth_to_weak<TEX_F16W, true><<<g, 64 * kBwD2W, 0, s>>>(dpc, B);
+  else k_depth_to_weak<kTexD2W, true><<<g, 64 * kBwD2W, 0, s>>>(dpc, B);
 }
 
-void launch_local_refine(int cls, long L, int W, int H, int nv, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
+void launch_local_refine(int cls, bool wide, long L, int W, int H, int nv, hipStream_t s, const PassConst* dpc, const DevBufs& B) {
   // with the fused DepthToWeak only its border pixels are left
   const int border = 1;
   L = border_count(W, H);
@@ -48,6 +50,11 @@ void launch_local_refine(int cls, long L, int W, int H, int nv, hipStream_t s, c
   if (g == 0) return;
   const size_t lds = (size_t)kBwLR * kLrPix * 12 * nv * 2 * sizeof(float);
   if (cls == IMG_F32) { launch_local_refine_f32(g, lds, border, s, dpc, B); return; }
+  if (wide) {
+    allow_large_lds<k_local_refine_jobs<TEX_F16W>>(lds);
+    k_local_refine_jobs<TEX_F16W><<<g, 64 * kBwLR, lds, s>>>(dpc, B, border);
+    return;
+  }
   allow_large_lds<k_local_refine_jobs<kTexLR>>(lds);
   k_local_refine_jobs<kTexLR><<<g, 64 * kBwLR, lds, s>>>(dpc, B, border);
 }
