@@ -26,9 +26,11 @@ EXPORTED = [
     "dpe_resize_linear", "dpe_resize_u8", "dpe_canny", "dpe_roberts_threshold",
     "dpe_state_render", "dpe_state_render_jpeg_blocks", "dpe_state_render_wait", "dpe_viz_render_arrays",
     "dpe_jpeg_blocks_device", "dpe_viz_launches", "dpe_live_device_bytes",
+    "dpe_state_point_cloud", "dpe_state_point_cloud_wait", "dpe_point_cloud_arrays", "dpe_points_launches",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
+POINTS_ALL, POINTS_STRONG = 1, 2
 
 CLASSES = ["setup", "init", "strong", "ransac", "weak", "filter", "depth_to_weak", "local_refine"]
 
@@ -94,6 +96,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_state_fetch.restype = C.c_int
     lib.dpe_device_buffer.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
     lib.dpe_device_buffer.restype = C.c_void_p
+    lib.dpe_device_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    lib.dpe_device_copy.restype = C.c_int
+    lib.dpe_state_import_depth.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.dpe_state_import_depth.restype = C.c_int
     lib.dpe_sync.argtypes = [C.c_void_p]
     lib.dpe_sync.restype = C.c_int
     lib.dpe_state_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]
@@ -110,6 +116,17 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_jpeg_blocks_device.restype = C.c_int
     lib.dpe_viz_launches.argtypes = []
     lib.dpe_viz_launches.restype = C.c_longlong
+    lib.dpe_state_point_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_abi.DpeCamera), C.c_void_p, C.c_float,
+                                          C.c_float, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    lib.dpe_state_point_cloud.restype = C.c_int
+    lib.dpe_state_point_cloud_wait.argtypes = [C.c_void_p, C.c_void_p]
+    lib.dpe_state_point_cloud_wait.restype = C.c_int
+    lib.dpe_point_cloud_arrays.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.POINTER(_abi.DpeCamera), C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t)]
+    lib.dpe_point_cloud_arrays.restype = C.c_int
+    lib.dpe_points_launches.argtypes = []
+    lib.dpe_points_launches.restype = C.c_longlong
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
@@ -270,6 +287,16 @@ class PatchMatchContext:
                                     out["normal"].ctypes.data, out["weak"].ctypes.data, out["sel"].ctypes.data), "dpe_state_fetch")
         return out
 
+    def state_import_depth(self, image_id: int, depth: np.ndarray):
+        """A depth-only state (what another rank's image is after an exchange) from a host f32 [H, W] map."""
+        d = np.ascontiguousarray(depth, np.float32)
+        dev = _LIB.dpe_device_buffer(self._ctx, 0, d.size)
+        if not dev:
+            raise DpeError("dpe_device_buffer failed: " + _LIB.dpe_last_error().decode(errors="replace"))
+        _check(_LIB.dpe_device_copy(self._ctx, dev, d.ctypes.data, d.nbytes, 0), "dpe_device_copy")
+        _check(_LIB.dpe_state_import_depth(self._ctx, int(image_id), d.shape[1], d.shape[0], dev, None), "dpe_state_import_depth")
+        _check(_LIB.dpe_sync(self._ctx), "dpe_sync")
+
     def _state_size(self, image_id: int):
         w, h = C.c_int(), C.c_int()
         _check(_LIB.dpe_state_fetch(self._ctx, int(image_id), C.byref(w), C.byref(h), None, None, None, None), "dpe_state_fetch")
@@ -315,6 +342,40 @@ class PatchMatchContext:
                "dpe_jpeg_blocks_device")
         return out
 
+    # per-image point clouds (ExportDepthImagePointCloud; include/dpe_mvs.h)
+    def state_point_cloud(self, image_id: int, mode: int, cam: _abi.DpeCamera, bgr: np.ndarray, dmin: float, dmax: float,
+                          cap: int | None = None) -> np.ndarray:
+        """The points f32 [n, 6] (x y z b g r) of a saved state on the device, in the reference's order; `cam`
+        and `bgr` uint8 [H, W, 3] at the state's size.  `cap`: size of the point buffer (default H * W)."""
+        w, h = self._state_size(image_id)
+        a = np.ascontiguousarray(bgr, np.uint8)
+        if a.shape != (h, w, 3):
+            raise ValueError(f"expected a uint8 [{h}, {w}, 3] BGR image")
+        cap = w * h if cap is None else int(cap)
+        out = np.empty((max(cap, 1), 6), np.float32)
+        n = C.c_size_t()
+        _check(_LIB.dpe_state_point_cloud(self._ctx, int(image_id), int(mode), C.byref(cam), a.ctypes.data, float(dmin), float(dmax),
+                                          out.ctypes.data, cap, C.byref(n), None), "dpe_state_point_cloud")
+        _check(_LIB.dpe_state_point_cloud_wait(self._ctx, out.ctypes.data), "dpe_state_point_cloud_wait")
+        return out[:n.value].copy()
+
+    def point_cloud_arrays(self, mode: int, depth, cam: _abi.DpeCamera, bgr, dmin: float, dmax: float, weak=None,
+                           cap: int | None = None) -> np.ndarray:
+        """The same kernels on caller arrays (diagnostic): depth f32 [H, W], weak u8 [H, W] or None, bgr uint8 [H, W, 3]."""
+        d = np.ascontiguousarray(depth, np.float32)
+        h, w = d.shape
+        a = np.ascontiguousarray(bgr, np.uint8)
+        if a.shape != (h, w, 3):
+            raise ValueError(f"expected a uint8 [{h}, {w}, 3] BGR image")
+        k = None if weak is None else np.ascontiguousarray(weak, np.uint8)
+        cap = w * h if cap is None else int(cap)
+        out = np.empty((max(cap, 1), 6), np.float32)
+        n = C.c_size_t()
+        _check(_LIB.dpe_point_cloud_arrays(self._ctx, int(mode), w, h, d.ctypes.data, None if k is None else k.ctypes.data,
+                                           C.byref(cam), a.ctypes.data, float(dmin), float(dmax), out.ctypes.data, cap, C.byref(n)),
+               "dpe_point_cloud_arrays")
+        return out[:n.value].copy()
+
     def device_planes(self) -> int:
         return int(_LIB.dpe_pm_device_planes(self._ctx) or 0)
 
@@ -325,6 +386,11 @@ class PatchMatchContext:
 def viz_launches() -> int:
     """Kernels of the viz medium results launched by this process so far."""
     return int(_LIB.dpe_viz_launches())
+
+
+def points_launches() -> int:
+    """Kernels of the per-image point clouds launched by this process so far."""
+    return int(_LIB.dpe_points_launches())
 
 
 def live_device_bytes() -> int:
@@ -350,4 +416,4 @@ def param_struct(**overrides) -> _abi.DpePatchMatchParams:
 
 Context = PatchMatchContext
 
-__all__ = ["PatchMatchContext", "Context", "viz_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]
+__all__ = ["PatchMatchContext", "Context", "viz_launches", "points_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]

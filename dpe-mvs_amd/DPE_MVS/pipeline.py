@@ -46,11 +46,16 @@ class DpePipelineOptions(C.Structure):
         ("allgather_device", C.c_void_p), ("allgather_device_user", C.c_void_p),
         ("abort_collectives", C.c_void_p), ("abort_user", C.c_void_p),
         ("fusion_mode", C.c_int),
+        ("point_cloud", C.c_int),
     ]
 
 
 FUSION_ETH3D, FUSION_TAT_INTERMEDIATE, FUSION_TAT_ADVANCED = 0, 1, 2
 FUSION_MODES = {"eth3d": FUSION_ETH3D, "tat_intermediate": FUSION_TAT_INTERMEDIATE, "tat_advanced": FUSION_TAT_ADVANCED}
+
+
+POINTS_OFF, POINTS_ALL, POINTS_STRONG = 0, 1, 2
+POINT_CLOUD_MODES = {"off": POINTS_OFF, "all": POINTS_ALL, "strong": POINTS_STRONG}
 
 
 class DpeFusedPoint(C.Structure):   # include/dpe_mvs.h
@@ -103,6 +108,12 @@ def lib() -> C.CDLL:
         L.dpe_host_fusion_tat_run.restype = C.c_longlong
         L.dpe_host_fusion_tat_thresholds.argtypes = [C.c_void_p, C.c_int]
         L.dpe_host_fusion_tat_angle_test.argtypes = [C.c_float, C.c_int]
+        L.dpe_host_depth_point_cloud.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_abi.DpeCamera),
+                                                 C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
+        L.dpe_host_depth_point_cloud.restype = C.c_longlong
+        L.dpe_host_rescale_image_and_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.POINTER(_abi.DpeCamera), C.c_void_p]
+        L.dpe_host_write_point_cloud.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -260,6 +271,60 @@ def fusion_tat_thresholds(n: int = 32) -> np.ndarray:
 def fusion_tat_angle_test(dot: float, k: int) -> bool:
     """The serial loop's angle test at k: GetAngle(dot) < k * angle_grad + angle_base."""
     return bool(lib().dpe_host_fusion_tat_angle_test(float(dot), k))
+
+
+# ------------------------------------------------------------------------------ per-image point clouds (C++, points.cpp)
+def _point_cloud_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in POINT_CLOUD_MODES:
+            raise ValueError(f"point_cloud must be one of {sorted(POINT_CLOUD_MODES)}, not {mode!r}")
+        return POINT_CLOUD_MODES[mode]
+    return int(mode)
+
+
+def copy_camera(cam: _abi.DpeCamera) -> _abi.DpeCamera:
+    out = _abi.DpeCamera()
+    C.memmove(C.byref(out), C.byref(cam), C.sizeof(_abi.DpeCamera))
+    return out
+
+
+def rescale_image_and_camera(bgr: np.ndarray, cam: _abi.DpeCamera, w: int, h: int):
+    """RescaleImageAndCamera (DPE.cpp:1123-1144): (uint8 [h, w, 3] BGR resized per channel, a copy of `cam`
+    with K[0], K[2] *= w / src_w and K[4], K[5] *= h / src_h); equal sizes give the image and K as they are."""
+    a = np.ascontiguousarray(bgr, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("expected a uint8 [H, W, 3] BGR image")
+    out, c = np.empty((h, w, 3), np.uint8), copy_camera(cam)
+    if lib().dpe_host_rescale_image_and_camera(a.ctypes.data, a.shape[1], a.shape[0], w, h, C.byref(c), out.ctypes.data) != 0:
+        raise PipelineError("rescale_image_and_camera: bad argument")
+    return out, c
+
+
+def depth_point_cloud(depth, cam: _abi.DpeCamera, bgr, depth_min: float, depth_max: float, mode=POINTS_ALL, weak=None,
+                      cap: int | None = None) -> np.ndarray:
+    """ExportDepthImagePointCloud (DPE.cpp:1691-1724) on the host: the points f32 [n, 6] (x y z b g r) of
+    depth f32 [H, W] in the reference's order (columns outside, rows inside).  `bgr` uint8 [h, w, 3] and
+    `cam` of another size go through rescale_image_and_camera first.  mode "all" / 1, or "strong" / 2
+    (a pixel whose `weak` state is not STRONG gets depth 0 before the range test).  `cap`: size of the
+    point buffer (default H * W); PipelineError when it is too small."""
+    d = np.ascontiguousarray(depth, np.float32)
+    h, w = d.shape
+    k = None if weak is None else np.ascontiguousarray(weak, np.uint8)
+    col, c = rescale_image_and_camera(bgr, cam, w, h)
+    cap = d.size if cap is None else int(cap)
+    out = np.empty((max(cap, 1), 6), np.float32)
+    n = lib().dpe_host_depth_point_cloud(_point_cloud_mode(mode), w, h, d.ctypes.data, None if k is None else k.ctypes.data,
+                                         C.byref(c), col.ctypes.data, depth_min, depth_max, out.ctypes.data, cap)
+    if n < 0:
+        raise PipelineError("depth_point_cloud failed (bad argument, or more points than cap)")
+    return out[:n].copy()
+
+
+def write_point_cloud(path: str, points: np.ndarray) -> None:
+    """ExportPointCloud (DPE.cpp:532-572): f32 [n, 6] points (x y z b g r) as the reference's binary PLY."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 6)
+    if lib().dpe_host_write_point_cloud(path.encode(), p.ctypes.data, len(p)) != 0:
+        raise PipelineError(f"cannot write {path}")
 
 
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)
@@ -446,7 +511,7 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
                      edge: bool = False, schedule: str = "reference", dist=None, runner=None,
                      base_seed: int = 0x5EED, keep_intermediate: bool = False, fusion_runner=None,
                      max_iterations: int = 0, photometric_only: bool = False, allgather_device=None,
-                     fusion_mode="eth3d") -> int:
+                     fusion_mode="eth3d", point_cloud=0) -> int:
     """RunDPEPipeline (main.cpp:474) through libdpe_host.  `dist`: an initialised torch.distributed
     (one process per GPU; problems split in contiguous blocks, depth maps all-gathered per pass).
     `runner`: (C function pointer, user pointer) of a dpe_pass_runner_fn; default the HIP library.
@@ -457,10 +522,13 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
     one (tests drive the device exchange path through it on one GPU).  `fusion_mode`: "eth3d"
     (RunFusion, the default), "tat_intermediate" or "tat_advanced" (the Tanks-and-Temples fusions, one
     image at a time on the GPU; with a `fusion_runner` their serial loops on the host), or the integer
-    of DpePipelineOptions.fusion_mode."""
+    of DpePipelineOptions.fusion_mode.  `point_cloud`: 0 / "off" (the default), 1 / "all" or 2 / "strong":
+    every reference image's point_<it>.ply (ExportDepthImagePointCloud) after the last pass of every
+    resolution round; "strong" keeps the STRONG pixels only (main.cpp:464)."""
     o = DpePipelineOptions()
     lib().dpe_pipeline_default_options(C.byref(o))
     o.fusion_mode = _fusion_mode(fusion_mode)
+    o.point_cloud = _point_cloud_mode(point_cloud)
     o.gpu_index = gpu_index
     o.verbose, o.fusion, o.viz, o.depth, o.normal, o.weak, o.edge = verbose, fusion, viz, depth, normal, weak, edge
     o.schedule = {"reference": SCHEDULE_REFERENCE, "jacobi": SCHEDULE_JACOBI}[schedule]

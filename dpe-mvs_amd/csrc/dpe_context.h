@@ -1,7 +1,7 @@
 // dpe_context.h -- what a DpeContext (include/dpe_mvs.h) holds: device arrays, streams and events that
 // own their HIP resources, the cached images, the resident states and the context itself, its members
 // grouped by the unit that owns them.  Internal to the library and shared by its units (dpe_mvs.hip,
-// dpe_state.hip, dpe_edges.hip, dpe_viz.hip, dpe_fusion.hip): every type here is an ordinary named
+// dpe_state.hip, dpe_edges.hip, dpe_viz.hip, dpe_fusion.hip, dpe_points.hip): every type here is an ordinary named
 // type and the byte counter has one definition in the process.  Includes no kernel header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -204,11 +204,23 @@ struct VizScratch {
   DevArr<uint8_t> weak;
 };
 
+// per-image point clouds (dpe_points.hip: dpe_state_point_cloud / dpe_point_cloud_arrays): scratch,
+// allocated on first use.  `ev` is declared first and so outlives the buffers.
+struct PointsScratch {
+  std::mutex mu;                     // guards ev (dpe_state_point_cloud_wait runs on other host threads)
+  std::map<const void*, Event> ev;   // per host point buffer: end of the last copy into it
+  DevArr<uint8_t> bgr;               // the colour image at the map size
+  DevArr<int> cnt, tot;              // valid pixels per (column, row segment) -> offsets; the image's total
+  DevArr<TatPoint> out;              // the points in the reference's order
+  DevArr<float4> planes;             // dpe_point_cloud_arrays: the caller's arrays
+  DevArr<uint8_t> weak;
+};
+
 }  // namespace dpe
 
 // Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
 // reverse order: the streams and events are declared first and so outlive every buffer (the events of
-// one group alone, tat.ev and viz.ev, are the first members of their group).
+// one group alone, tat.ev, viz.ev and points.ev, are the first members of their group).
 struct DpeContext {
   int device = 0;
   dpe::Stream stream;
@@ -228,4 +240,5 @@ struct DpeContext {
   dpe::FusionStage fz;
   dpe::TatFusion tat;
   dpe::VizScratch viz;
+  dpe::PointsScratch points;
 };

@@ -1,0 +1,100 @@
+// pass_points.h — ExportDepthImagePointCloud (DPE.cpp:1691-1724) on the GPU: one image's depth map
+// back-projected into coloured points, in the reference's order.
+//
+// The reference walks `for i < cols, for j < rows`: COLUMN-major, unlike every other compaction here.
+// A pixel's rank is the number of valid pixels in the columns before its own plus the valid pixels
+// above it in its column.  The image is cut into cells of one column by kPtsSeg rows:
+//
+//   k_pts_count    one thread per cell: the valid pixels of the cell into cnt[column * nseg + segment],
+//                  which is the order the reference visits the cells in
+//   k_pts_offsets  exclusive sum-scan of cnt in that order (one block), the image's total into *tot
+//   k_pts_fill     one thread per cell again: its pixels top to bottom into out[cnt[cell]...]
+//
+// No atomics, so the order is the reference's whatever the schedule.  A block is kPtsCols adjacent
+// columns of one segment and a thread keeps its column, so at every row the lanes of a wave read
+// adjacent pixels of one image row: depth, pixel state and colour are read along the rows they are
+// stored in, once for the counts and once for the fill.  The counts need no exchange between lanes.
+//
+// mode DPE_POINTS_STRONG (main.cpp:464): a pixel that is not STRONG has its depth REPLACED by 0 before
+// the test, so with depth_min <= 0 it is emitted at depth 0, as the reference's code would.
+// The test `depth < depth_min || depth > depth_max || isnan(depth)`: NaN on the bit pattern.
+#pragma once
+#include "fusion_world.h"
+#include "dpe_fusion_types.h"   // TatPoint (= DpeFusedPoint)
+
+namespace dpe {
+
+constexpr int kPtsCols = 256;   // columns per block
+constexpr int kPtsSeg = 32;     // rows per cell
+
+__device__ inline float pts_depth(int mode, const float4* __restrict__ planes, const uint8_t* __restrict__ weak, size_t p) {
+  const float d = planes[p].w;
+  return (mode == DPE_POINTS_STRONG && weak[p] != DPE_STRONG) ? 0.0f : d;
+}
+
+__device__ inline bool pts_valid(float d, float dmin, float dmax) {
+  const bool is_nan = (__float_as_uint(d) & 0x7FFFFFFFu) > 0x7F800000u;
+  return !(d < dmin || d > dmax || is_nan);
+}
+
+// grid (ceil(w / kPtsCols), nseg)
+__global__ void __launch_bounds__(kPtsCols) k_pts_count(int mode, const float4* __restrict__ planes,
+                                                        const uint8_t* __restrict__ weak, int w, int h, int nseg,
+                                                        float dmin, float dmax, int* __restrict__ cnt) {
+  const int c = blockIdx.x * kPtsCols + threadIdx.x;
+  if (c >= w) return;
+  const int seg = blockIdx.y;
+  const int j0 = seg * kPtsSeg, j1 = min(h, j0 + kPtsSeg);
+  int n = 0;
+  for (int j = j0; j < j1; ++j)
+    n += pts_valid(pts_depth(mode, planes, weak, (size_t)j * w + c), dmin, dmax) ? 1 : 0;
+  cnt[(size_t)c * nseg + seg] = n;
+}
+
+// exclusive scan of the ncell cell counts in place (one 256-thread block); the total into *tot
+__global__ void __launch_bounds__(256) k_pts_offsets(int ncell, int* __restrict__ cnt, int* __restrict__ tot) {
+  __shared__ int s4[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int acc = 0;
+  for (int k0 = 0; k0 < ncell; k0 += 256) {
+    const int k = k0 + (int)threadIdx.x;
+    const int c = k < ncell ? cnt[k] : 0;
+    int incl = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o);
+      if (lane >= o) incl += t;
+    }
+    if (lane == 63) s4[wave] = incl;
+    __syncthreads();
+    int before = acc;
+    for (int v = 0; v < wave; ++v) before += s4[v];
+    const int all = s4[0] + s4[1] + s4[2] + s4[3];
+    __syncthreads();
+    if (k < ncell) cnt[k] = before + incl - c;
+    acc += all;
+  }
+  if (threadIdx.x == 0) *tot = acc;
+}
+
+// grid as k_pts_count; off = the scanned cnt.  Writes exactly the pixels k_pts_count counted.
+__global__ void __launch_bounds__(kPtsCols) k_pts_fill(int mode, const float4* __restrict__ planes,
+                                                       const uint8_t* __restrict__ weak, const uint8_t* __restrict__ bgr,
+                                                       DpeCamera cam, int w, int h, int nseg, float dmin, float dmax,
+                                                       const int* __restrict__ off, TatPoint* __restrict__ out) {
+  const int c = blockIdx.x * kPtsCols + threadIdx.x;
+  if (c >= w) return;
+  const int seg = blockIdx.y;
+  const int j0 = seg * kPtsSeg, j1 = min(h, j0 + kPtsSeg);
+  int a = off[(size_t)c * nseg + seg];
+  for (int j = j0; j < j1; ++j) {
+    const size_t p = (size_t)j * w + c;
+    const float d = pts_depth(mode, planes, weak, p);
+    if (!pts_valid(d, dmin, dmax)) continue;
+    const FP3 X = fz_world(c, j, d, cam);
+    const uint8_t* col = bgr + 3 * p;
+    out[a++] = TatPoint{X.x, X.y, X.z, (float)col[0], (float)col[1], (float)col[2]};
+  }
+}
+
+}  // namespace dpe

@@ -1,10 +1,12 @@
 // cli.cpp — the `dpe` command line, same positional arguments as the reference's `DPE` binary
 // (main.cpp:602-635):
 //
-//     dpe dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge] [fusion_mode]
+//     dpe dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge] [fusion_mode] [point_cloud]
 //
 // fusion_mode (an addition: the reference calls RunFusion and has to be rebuilt for the others):
 // eth3d (0, the default), tat_intermediate (1) or tat_advanced (2).
+// point_cloud (an addition: the reference's call is commented out, main.cpp:456-466): off (0, the
+// default), all (1) or strong (2): point_<it>.ply per image after the last pass of every round.
 //
 // One process per GPU: launched under torchrun (or any launcher that sets RANK / WORLD_SIZE /
 // LOCAL_RANK), each rank takes a contiguous block of reference images on GPU LOCAL_RANK and the
@@ -94,9 +96,13 @@ bool rccl_init(Rccl& r, int rank, int world, int device) {
 
 }  // namespace
 
+const char* const kUsage =
+    "USAGE: DPE dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge]"
+    " [fusion_mode: eth3d | tat_intermediate | tat_advanced] [point_cloud: off | all | strong]\n";
+
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "USAGE: DPE dense_folder\n");
+    std::fprintf(stderr, "%s", kUsage);
     return EXIT_FAILURE;
   }
   DpePipelineOptions o;
@@ -114,6 +120,15 @@ int main(int argc, char** argv) {
     o.fusion_mode = m == "eth3d" ? DPE_FUSION_ETH3D : m == "tat_intermediate" ? DPE_FUSION_TAT_INTERMEDIATE
                   : m == "tat_advanced" ? DPE_FUSION_TAT_ADVANCED
                   : (m.size() == 1 && m[0] >= '0' && m[0] <= '9') ? m[0] - '0' : -1;   // the pipeline refuses the rest
+  }
+  if (argc >= 12) {   // not in the reference either: 0 | off, 1 | all, 2 | strong
+    const std::string m = argv[11];
+    o.point_cloud = (m == "off" || m == "0") ? 0 : (m == "all" || m == "1") ? DPE_POINTS_ALL
+                  : (m == "strong" || m == "2") ? DPE_POINTS_STRONG : -1;
+    if (o.point_cloud < 0) {
+      std::fprintf(stderr, "bad point_cloud '%s'\n%s", argv[11], kUsage);
+      return EXIT_FAILURE;
+    }
   }
   const char* ws = std::getenv("WORLD_SIZE");
   Rccl rccl;

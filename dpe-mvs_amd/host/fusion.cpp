@@ -253,14 +253,15 @@ FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const f
 }
 
 // ExportPointCloud (DPE.cpp:532-572): binary little-endian PLY, xyz float + BGR uchar
-bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& cloud, std::string& err) {
+bool export_point_cloud(const std::string& path, const FusedPoint* cloud, size_t n, std::string& err) {
   std::ofstream out(path, std::ios::binary);
   if (!out) { err = "cannot write " + path; return false; }
-  out << "ply\n" << "format binary_little_endian 1.0\n" << "element vertex " << int(cloud.size()) << "\n"
+  out << "ply\n" << "format binary_little_endian 1.0\n" << "element vertex " << int(n) << "\n"
       << "property float x\n" << "property float y\n" << "property float z\n"
       << "property uchar diffuse_blue\n" << "property uchar diffuse_green\n" << "property uchar diffuse_red\n"
       << "end_header\n";
-  for (const FusedPoint& p : cloud) {
+  for (size_t i = 0; i < n; ++i) {
+    const FusedPoint& p = cloud[i];
     const float xyz[3] = {p.x, p.y, p.z};
     const uint8_t px[3] = {static_cast<uint8_t>(p.b), static_cast<uint8_t>(p.g), static_cast<uint8_t>(p.r)};
     out.write(reinterpret_cast<const char*>(xyz), sizeof(xyz));
@@ -268,6 +269,9 @@ bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& 
   }
   if (!out) { err = "write failed: " + path; return false; }
   return true;
+}
+bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& cloud, std::string& err) {
+  return export_point_cloud(path, cloud.data(), cloud.size(), err);
 }
 
 }  // namespace dpe_host

@@ -101,7 +101,15 @@ using FusedPoint = DpeFusedPoint;   // x, y, z, b, g, r
 bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
                 std::string& err);
 FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const float* bgr);
+bool export_point_cloud(const std::string& path, const FusedPoint* cloud, size_t n, std::string& err);
 bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& cloud, std::string& err);
+// points.cpp: RescaleImageAndCamera (DPE.cpp:1123-1144) and ExportDepthImagePointCloud (DPE.cpp:1691-1724)
+void scale_intrinsics(DpeCamera& cam, float sx, float sy);   // K of an image resized by (sx, sy)
+// `img` resized to w x h per channel (resize_u8) into `bgr`, and cam's intrinsics scaled with it
+void resize_bgr_and_camera(const ColorImage& img, int w, int h, DpeCamera& cam, std::vector<uint8_t>& bgr);
+// the serial double loop, columns outside: the number of points, or -1 when `cap` is too small
+long long depth_point_cloud(int mode, int w, int h, const float* depth, const uint8_t* weak, const DpeCamera& cam,
+                            const uint8_t* bgr, float depth_min, float depth_max, FusedPoint* out, size_t cap);
 // fusion_tat.cpp: RunFusion_TAT_Intermediate / RunFusion_TAT_advanced (DPE.cpp:1372-1689), `mode` =
 // DPE_FUSION_TAT_*.  ctx == nullptr: the reference's serial loops on the host; else every image on
 // the device (the serial loops still run when a reference is among its own sources or an id repeats).

@@ -30,12 +30,21 @@
 // while the following passes run.  With a runner hook the state is on the host and the same
 // pictures come from viz.cpp / jpeg_enc.cpp, byte for byte the same files.
 //
+// point_cloud = 1 / 2 writes the reference's per-image point clouds (ExportDepthImagePointCloud, whose
+// call is the commented block at main.cpp:456-466): point_<it>.ply after the last pass of every
+// resolution round, from the post-epilogue state, 2 = STRONG pixels only (main.cpp:464).  An option of
+// its own here (the reference nests it under the medium results).  With the default runner the points
+// are computed from the HBM-resident state (dpe_state_point_cloud) and only they come back, into two
+// pinned buffers that a host thread (PointCloudWriter) encodes and writes while the following passes
+// run; with a runner hook dpe_host_depth_point_cloud's loop runs on the host state.  Same files.
+//
 // run() at the end of the file is the table of contents: the phases of a run in order, each a
 // member of PipelineRun.  The rule every phase keeps with several ranks is in rank_group.h.
 #include "host.h"
 #include "parallel.h"
 #include "rank_group.h"
 #include "viz_writer.h"
+#include "point_writer.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
@@ -96,8 +105,6 @@ int std_round(float v) { return (int)std::round(v); }   // std::round: half away
 
 std::string image_path(const std::string& dense, int id) { return (fs::path(dense) / "images" / (fmt_index(id) + ".jpg")).string(); }
 std::string cam_path(const std::string& dense, int id) { return (fs::path(dense) / "cams" / (fmt_index(id) + "_cam.txt")).string(); }
-// the intrinsics of an image resized by (sx, sy) (DPE.cpp:812-815, 1139-1142)
-void scale_intrinsics(DpeCamera& cam, float sx, float sy) { cam.K[0] *= sx; cam.K[2] *= sx; cam.K[4] *= sy; cam.K[5] *= sy; }
 
 bool generate_sample_list(const std::string& dense, std::vector<Problem>& probs, std::string& err) {   // main.cpp:264-308
   std::ifstream f(fs::path(dense) / "pair.txt");
@@ -391,18 +398,8 @@ bool load_fusion_view(const Problem& p, const ImageState& st, bool use_block, Fu
   if (!read_camera(cam_path(p.dense_folder, p.ref_image_id), cam, err)) return false;
   ColorImage img;
   if (!read_bgr(image_path(p.dense_folder, p.ref_image_id), img, err)) return false;
-  if (img.w != st.w || img.h != st.h) {   // RescaleImageAndCamera (DPE.cpp:1123-1144), per channel
-    std::vector<uint8_t> ch((size_t)img.w * img.h), och((size_t)st.w * st.h);
-    v.bgr.assign((size_t)st.w * st.h * 3, 0);
-    for (int k = 0; k < 3; ++k) {
-      for (size_t q = 0; q < ch.size(); ++q) ch[q] = img.bgr[3 * q + k];
-      resize_u8(ch.data(), img.w, img.h, och.data(), st.w, st.h);
-      for (size_t q = 0; q < och.size(); ++q) v.bgr[3 * q + k] = och[q];
-    }
-    scale_intrinsics(cam, st.w / (float)img.w, st.h / (float)img.h);
-  } else {
-    v.bgr = std::move(img.bgr);
-  }
+  if (img.w != st.w || img.h != st.h) resize_bgr_and_camera(img, st.w, st.h, cam, v.bgr);   // RescaleImageAndCamera (DPE.cpp:1123-1144)
+  else v.bgr = std::move(img.bgr);
   cam.width = st.w; cam.height = st.h;
   if (use_block) {
     GrayImage b;
@@ -439,6 +436,8 @@ struct PipelineRun {
   bool resident = false;
   Runner runner;
   std::unique_ptr<VizWriter> viz;   // declared after `runner`: joined before the context goes
+  std::unique_ptr<PointCloudWriter> points;   // (the same)
+  std::map<int, ColorImage> colour;      // point_cloud: the colour images of this rank's references, decoded once
   int w0 = 0, h0 = 0;               // the full image size (CheckImages: all the same)
   int round_num = 0, iteration_index = 0;
   std::map<int, ImageState> states;      // final states; with a runner hook also every pass's prior
@@ -547,6 +546,29 @@ struct PipelineRun {
     return !single_rank_failed();
   }
 
+  // ExportDepthImagePointCloud's inputs (DPE.cpp:1702-1708) for the W x H state of problem `p`: the
+  // camera and the colour image (decoded once per run) through RescaleImageAndCamera.  *px: the pixels.
+  bool point_cloud_inputs(const Problem& p, int W, int H, DpeCamera& cam, std::vector<uint8_t>& scaled, const uint8_t** px,
+                          std::string& perr) {
+    if (!read_camera(cam_path(p.dense_folder, p.ref_image_id), cam, perr)) return false;
+    auto it = colour.find(p.ref_image_id);
+    if (it == colour.end()) {
+      ColorImage img;
+      if (!read_bgr(image_path(p.dense_folder, p.ref_image_id), img, perr)) return false;
+      it = colour.emplace(p.ref_image_id, std::move(img)).first;
+    }
+    const ColorImage& img = it->second;
+    if (img.w != W || img.h != H) { resize_bgr_and_camera(img, W, H, cam, scaled); *px = scaled.data(); }
+    else *px = img.bgr.data();
+    cam.width = W; cam.height = H;
+    return true;
+  }
+  // main.cpp:456: after the last pass of a resolution round
+  bool point_cloud_due(const Problem& p) const { return opt.point_cloud != 0 && (p.iteration + 1) % 4 == 0; }
+  static std::string point_cloud_path(const Problem& p) {
+    return (fs::path(p.result_folder) / ("point_" + std::to_string(p.iteration) + ".ply")).string();
+  }
+
   // stage, execute and save in HBM; nothing comes back unless the intermediate maps are asked for
   bool run_resident_pass(const Problem& p, const PassInput& pi, std::string& perr) {
     int rc = dpe_pm_stage_resident(runner.ctx, &pi.in, p.ref_image_id);
@@ -562,6 +584,15 @@ struct PipelineRun {
       for (int kind = 0; kind < 3; ++kind)
         if (!viz->submit(p.ref_image_id, kind, p.params.depth_min, p.params.depth_max, pi.W, pi.H, viz_path(p, kind), perr))
           return false;
+    if (point_cloud_due(p)) {   // main.cpp:456-466, from the saved state as well
+      DpeCamera cam;
+      std::vector<uint8_t> scaled;
+      const uint8_t* px = nullptr;
+      if (!point_cloud_inputs(p, pi.W, pi.H, cam, scaled, &px, perr)) return false;
+      if (!points->submit(p.ref_image_id, opt.point_cloud, cam, px, p.params.depth_min, p.params.depth_max,
+                          point_cloud_path(p), perr))
+        return false;
+    }
     return true;
   }
 
@@ -622,6 +653,17 @@ struct PipelineRun {
         viz_render(kind, W, H, s.depth.data(), s.normal.data(), s.weak.data(), P.depth_min, P.depth_max, bgr.data());
         if (!write_jpeg(viz_path(p, kind), bgr.data(), W, H, 3, kVizQuality, perr)) return false;
       }
+    }
+    if (point_cloud_due(p)) {   // main.cpp:456-466 on the host
+      DpeCamera cam;
+      std::vector<uint8_t> scaled;
+      const uint8_t* px = nullptr;
+      if (!point_cloud_inputs(p, W, H, cam, scaled, &px, perr)) return false;
+      std::vector<FusedPoint> cloud(L);
+      const long long n = depth_point_cloud(opt.point_cloud, W, H, s.depth.data(), s.weak.data(), cam, px, P.depth_min,
+                                            P.depth_max, cloud.data(), cloud.size());
+      if (n < 0) { perr = "point cloud failed"; return false; }
+      if (!export_point_cloud(point_cloud_path(p), cloud.data(), (size_t)n, perr)) return false;
     }
     states[p.ref_image_id] = std::move(s);
     return true;
@@ -742,6 +784,10 @@ struct PipelineRun {
   void finish_viz() {   // the pictures still being coded or written; their errors
     std::string verr;
     if (viz && !viz->finish(verr)) ranks.fail(verr);
+  }
+  void finish_points() {   // the point clouds still being copied or written; their errors
+    std::string perr;
+    if (points && !points->finish(perr)) ranks.fail(perr);
   }
 
   void collect_final_states() {   // the final states come back from HBM once
@@ -868,6 +914,10 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
     err = "bad fusion_mode " + std::to_string(opt.fusion_mode) + " (0 = ETH3D, 1 = TAT intermediate, 2 = TAT advanced)";
     return 1;
   }
+  if (opt.point_cloud != 0 && opt.point_cloud != DPE_POINTS_ALL && opt.point_cloud != DPE_POINTS_STRONG) {
+    err = "bad point_cloud " + std::to_string(opt.point_cloud) + " (0 = off, 1 = all pixels, 2 = STRONG pixels only)";
+    return 1;
+  }
   PipelineRun r(dense_folder, opt, err);
   RankGroup& ranks = r.ranks;
   if (!r.load_problems()) return 1;
@@ -880,11 +930,13 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
   if (!r.edge_prepass()) return 1;
   lap(kTimeEdges);
   if (opt.viz && r.resident) r.viz.reset(new VizWriter(r.runner.ctx, r.w0, r.h0));
+  if (opt.point_cloud != 0 && r.resident) r.points.reset(new PointCloudWriter(r.runner.ctx, r.w0, r.h0));
   for (int i = 0; i < r.round_num; ++i)
     for (int j = -1; j < 3; ++j)
       if (!r.run_pass_round(i, j)) return 1;
   lap(kTimePasses);
   r.finish_viz();
+  r.finish_points();
   r.collect_final_states();
   r.write_all_outputs();
   // every rank learns here whether any rank failed after its last exchange (a rank returning alone

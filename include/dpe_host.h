@@ -27,6 +27,9 @@
  *   ShowWeakImage             DPE.cpp:475-502    dpe_host_viz_render(DPE_VIZ_WEAK)    state, dpe_state_render*)
  *   cv::imwrite(".jpg")       DPE.cpp:446, main.cpp:363  dpe_host_write_jpeg (libjpeg's defaults: quality 95,
  *                                                baseline, 4:2:0 / grey, Annex K Huffman tables)
+ *   ExportDepthImagePointCloud DPE.cpp:1691      dpe_host_depth_point_cloud (point_cloud = 1 / 2: on the GPU
+ *     (call commented out, main.cpp:456-466)     from the resident state, dpe_state_point_cloud)
+ *   RescaleImageAndCamera     DPE.cpp:1123       dpe_host_rescale_image_and_camera
  *
  * Additions for the one-process-per-GPU deployment: a pass runner hook (default: the HIP library
  * on `gpu_index`) and an all-gather hook for the depth maps (RCCL in the CLI, torch.distributed
@@ -92,6 +95,11 @@ typedef struct DpePipelineOptions {
                                variants (DPE.cpp:1372-1689), whole image on the GPU; with a fusion_runner
                                hook (no GPU) their serial loops run on the host and the hook is not called.
                                Any other value fails */
+  int point_cloud;          /* 0 (the default): off.  DPE_POINTS_ALL (1) / DPE_POINTS_STRONG (2): after the last
+                               pass of every resolution round ((iteration + 1) % 4 == 0, main.cpp:456) every
+                               reference image's point_<iteration>.ply goes into its result folder
+                               (ExportDepthImagePointCloud; 2: STRONG pixels only, main.cpp:464).  Independent
+                               of `viz`, under which the reference nests it.  Any other value fails */
 } DpePipelineOptions;
 
 void dpe_pipeline_default_options(DpePipelineOptions* opt);
@@ -200,6 +208,26 @@ long long dpe_host_fusion_tat_run(int mode, const DpeHostTatView* views, int n, 
                                   size_t cap);
 int dpe_host_fusion_tat_thresholds(float* D, int n);
 int dpe_host_fusion_tat_angle_test(float dot, int k);
+
+/*
+ * ExportDepthImagePointCloud (DPE.cpp:1691-1724) as the reference writes it: the serial double loop,
+ * columns outside and rows inside, over HOST arrays that are already at the map size (depth f32 [h][w],
+ * weak u8 [h][w] PixelState, NULL allowed in DPE_POINTS_ALL, bgr u8 [h][w][3]).  `mode`, the test and the
+ * point are dpe_state_point_cloud's (dpe_mvs.h), whose yardstick this is, and what point_cloud runs
+ * without a GPU.  Writes up to `cap` points; returns their number, or -1 for a bad argument or when
+ * `cap` is too small.
+ *   dpe_host_rescale_image_and_camera  RescaleImageAndCamera (DPE.cpp:1123-1144): the src_w x src_h BGR
+ *                                   image resized to w x h per channel (dpe_host_resize_u8) into
+ *                                   `out_bgr`, and cam->K[0], K[2] *= w / (float)src_w, K[4], K[5] *=
+ *                                   h / (float)src_h; equal sizes copy the image and leave K alone.
+ *   dpe_host_write_point_cloud      ExportPointCloud (DPE.cpp:532-572): binary little-endian PLY, xyz
+ *                                   float + BGR uchar.  0 on success.
+ */
+long long dpe_host_depth_point_cloud(int mode, int w, int h, const float* depth, const uint8_t* weak, const DpeCamera* cam,
+                                     const uint8_t* bgr, float depth_min, float depth_max, DpeFusedPoint* out, size_t cap);
+int dpe_host_rescale_image_and_camera(const uint8_t* bgr, int src_w, int src_h, int w, int h, DpeCamera* cam,
+                                      uint8_t* out_bgr);
+int dpe_host_write_point_cloud(const char* path, const DpeFusedPoint* points, size_t n);
 
 #ifdef __cplusplus
 }

@@ -380,6 +380,41 @@ int dpe_jpeg_blocks_device(DpeContext* ctx, const uint8_t* host_bgr, int w, int 
                            size_t cap);
 long long dpe_viz_launches(void);
 
+/*
+ * ExportDepthImagePointCloud (DPE.cpp:1691-1724; its call is the commented block at main.cpp:456-466):
+ * one image's depth map back-projected into coloured points, from the HBM-resident state after
+ * dpe_state_save (csrc/pass_points.h).  Bit-identical to dpe_host_depth_point_cloud (dpe_host.h).
+ *
+ * A pixel is skipped when `depth < depth_min || depth > depth_max || isnan(depth)` (both ends kept,
+ * NaN tested on the bit pattern).  `mode` DPE_POINTS_ALL: the depth as it is; DPE_POINTS_STRONG
+ * (main.cpp:464): a pixel whose state is not DPE_STRONG has its depth replaced by 0 BEFORE the test
+ * (with depth_min <= 0 it is emitted at depth 0).  The points come in the reference's order: columns
+ * outside, rows inside.  A point is Get3DPointonWorld(column, row, depth, cam) and the colour image's
+ * (B, G, R) at that pixel as floats.
+ *
+ * dpe_state_point_cloud:  image_id's state; `cam` and `host_bgr` (u8 [h][w][3]) are already at the map
+ *                    size (RescaleImageAndCamera).  Uploads the colours, runs the kernels on `stream`
+ *                    (NULL = the context's) and waits for them: *n is the number of points on return
+ *                    (more than `cap` is DPE_ERR_ARG and copies nothing).  Only the n points are then
+ *                    copied into the HOST buffer `out` (pin it with dpe_host_pin for an asynchronous
+ *                    copy); the copy is complete at dpe_sync, or when dpe_state_point_cloud_wait(ctx, out),
+ *                    which any host thread may call, returns.  DPE_ERR_STATE for an unknown id, and in
+ *                    DPE_POINTS_STRONG for a depth-only (imported) state; DPE_ERR_ARG for a bad mode.
+ * dpe_point_cloud_arrays: the diagnostic twin (tests) over caller HOST arrays (depth f32 [h][w], weak u8
+ *                    [h][w], NULL allowed in DPE_POINTS_ALL, bgr u8 [h][w][3]) through the same kernels.
+ *                    Synchronous.
+ * dpe_points_launches: kernels of this section launched by the process so far (a run without point
+ *                    clouds launches none).
+ */
+enum { DPE_POINTS_ALL = 1, DPE_POINTS_STRONG = 2 };
+int dpe_state_point_cloud(DpeContext* ctx, int image_id, int mode, const DpeCamera* cam, const uint8_t* host_bgr,
+                          float depth_min, float depth_max, DpeFusedPoint* out, size_t cap, size_t* n, void* stream);
+int dpe_state_point_cloud_wait(DpeContext* ctx, const DpeFusedPoint* out);
+int dpe_point_cloud_arrays(DpeContext* ctx, int mode, int w, int h, const float* depth, const uint8_t* weak,
+                           const DpeCamera* cam, const uint8_t* bgr, float depth_min, float depth_max, DpeFusedPoint* out,
+                           size_t cap, size_t* n);
+long long dpe_points_launches(void);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);
