@@ -80,22 +80,6 @@ struct DevBufs {
 #ifndef DPE_DIAG
 #define DPE_DIAG 0
 #endif
-// DPE_UNCLAMPED=0 (A/B only): every fast Old-NCC patch keeps its tap clamps (taps_unclamped unused)
-#ifndef DPE_UNCLAMPED
-#define DPE_UNCLAMPED 1
-#endif
-// DPE_AB_OFF=<bits> (A/B only, same results): the set-up work outside the tap loops as it was before
-//   1  baseline lengths per pixel (not PassConst::base_len)     2  spatial weight term per tap (not ::spat36)
-//   4  the strong sweep's slot list, selected-view list and refinement hypotheses on one lane per pixel
-//   8  LocalRefine's hypothesis depths divided again on lane 0 of DepthToWeak (not read from its lanes)
-//  16  the strong pools' last rounds split as before: cost vectors up to 16 jobs, refinement never
-//  32  the fast taps' texel offset in four instructions (tex_addr.h tex_offset4), not two (tex_offset2)
-//  64  (unused: the same offset in the weak sweep's sample_quad8 was measured and not adopted)
-// 128  the Old NCC's centre test always with the IEEE division and before the patch's reciprocal-range
-//      test, not after it with the 3-op exact reciprocal where the range holds
-#ifndef DPE_AB_OFF
-#define DPE_AB_OFF 0
-#endif
 #define DPE_POOL_STATS (((DPE_DIAG) >> 4) & 1)
 #define DPE_PHASE_PROF ((DPE_DIAG) & 1)
 #define DPE_LINE_STATS (((DPE_DIAG) >> 1) & 1)
@@ -325,6 +309,56 @@ DEV float4 perturbed_normal_vd(const float4& vd, const float4& normal, const flo
 }
 DEV float4 perturbed_normal_from(const DpeCamera& c, int px, int py, const float4& normal, const float* sc) {
   return perturbed_normal_vd(view_direction(c, px, py, 1.0f), normal, sc);
+}
+
+// ---- steps the strong and the weak sweep share (pass_sweep.h)
+// The draws as the sweeps stage them, 12 floats per pixel `rnd`: [0] u_depth, [1..3] the pre-flip
+// normal, [4] u_pert, [5..10] (sin, cos) of the three angles.  Lane c = 1 of a pixel writes [0..4],
+// lanes c = 2..4 one angle each; the stream is at the view sampling's start (the draws are words 15..).
+DEV void refine_draws_lane(const Rng& rs, int c, float* rnd) {
+  const float pert = (float)(0.02f * 3.14159265358979323846);
+  const RefineDraws d = refine_draws(rs, 15u);
+  if (c == 1) { rnd[0] = d.u_depth; rnd[1] = d.n[0]; rnd[2] = d.n[1]; rnd[3] = d.n[2]; rnd[4] = d.u_pert; }
+  else refine_angle(rs, d.w_angles, c - 2, pert, &rnd[5 + 2 * (c - 2)], &rnd[6 + 2 * (c - 2)]);
+}
+// The five hypotheses of PlaneHypothesisRefinement (DPE.cu:1081-1095) on one lane, from the accepted
+// plane `pnow` at depth `depth_now` and the staged draws: (normal, depth) = (now, rand), (rand, now),
+// (rand, rand), (perturbed, now), (now, perturbed).
+DEV void refine_hypotheses(const DpeCamera& c0, int x, int y, float dmin, float dmax, const float4& pnow, float depth_now,
+                           const float* rnd, float4* hyp) {
+  const float depth_rand = rnd[0] * (dmax - dmin) + dmin;
+  const float4 prand = random_normal_from(c0, x, y, rnd + 1, depth_now);
+  const float dminp = (1 - 0.02f) * depth_now, dmaxp = (1 + 0.02f) * depth_now;
+  const float depth_perturbed = rnd[4] * (dmaxp - dminp) + dminp;
+  const float4 ppert = perturbed_normal_from(c0, x, y, pnow, rnd + 5);
+  float4 h0 = pnow, h1 = prand, h2 = prand, h3 = ppert, h4 = pnow;
+  h0.w = dist2origin(c0, x, y, depth_rand, h0);
+  h1.w = dist2origin(c0, x, y, depth_now, h1);
+  h2.w = dist2origin(c0, x, y, depth_rand, h2);
+  h3.w = dist2origin(c0, x, y, depth_now, h3);
+  h4.w = dist2origin(c0, x, y, depth_perturbed, h4);
+  hyp[0] = h0; hyp[1] = h1; hyp[2] = h2; hyp[3] = h3; hyp[4] = h4;
+}
+// two planes with the same bits (the alias searches: such planes share one cost vector)
+DEV bool same_plane_bits(const float4& a, const float4& b) {
+  return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) &&
+         __float_as_uint(a.z) == __float_as_uint(b.z) && __float_as_uint(a.w) == __float_as_uint(b.w);
+}
+// A plane's cost over the pixel's selected views (DPE.cu:1140-1150): the view weights vwl times
+// val(k, view) for the k-th selected view, summed in list order, over the weight norm.
+template <class ValF>
+DEV float sel_weighted_cost(const uint8_t* vwl, const int* sel_list, int nsel, float wnorm, ValF val) {
+  float tc = 0.0f;
+  for (int k = 0; k < nsel; ++k) tc += vwl[sel_list[k]] * val(k, sel_list[k]);
+  return tc / wnorm;
+}
+// The sequential acceptance of a hypothesis (DPE.cu:1097-1117): plane `cand` of depth db and cost tc
+// replaces the accepted one if its depth is in range and it is cheaper.
+DEV bool accept_if_better(const float4& cand, float db, float tc, float dmin, float dmax, float& depth_now, float4& pnow,
+                          float& cost_now) {
+  if (!(db >= dmin && db <= dmax && tc < cost_now)) return false;
+  depth_now = db; pnow = cand; cost_now = tc;
+  return true;
 }
 
 // ------------------------------------------------------------------------------ homography
@@ -608,9 +642,9 @@ DEV void line_stat(int T, const void* p) {
 // Fast-path tap constants of one (view, homography): the t clamps of the two axes and the texel
 // offset's two constants (tex_addr.h): the row coefficient `coef` of the layout (wave-uniform) and the
 // view's byte offset `vadj`, biased so that the t encodings index texels directly.  Layout T takes the
-// two-instruction offset unless it is TEX_F16W (frames too wide for it) or DPE_AB_OFF & 32.
+// two-instruction offset unless it is TEX_F16W (frames too wide for it).
 DEV f2v tex_tmax2(int W, int H) { return (f2v){tex_tmax(W), tex_tmax(H)}; }
-template <int T> constexpr bool tap_packed() { return !((DPE_AB_OFF) & 32) && T != TEX_F16W; }
+template <int T> constexpr bool tap_packed() { return T != TEX_F16W; }
 template <int T> DEV uint32_t tap_coef(uint32_t stride) { return tap_packed<T>() ? tex_coef<T>(stride) : stride; }
 template <int T> DEV uint32_t tap_vadj(uint32_t vofs, uint32_t stride) {
   return tap_packed<T>() ? tex_vadj2<T>(vofs, stride) : tex_vadj<T>(vofs, stride);
@@ -709,8 +743,6 @@ DEV float bilateral_weight(int i, int j, float pix, float cpix, float ss, float 
 // spatial term -sd / (2 ss ss) comes from the pass table, the same bits (pass_tables.h)
 DEV float bilateral_weight36(const PassConst& pc, int k, float pix, float cpix) {
   const float sc = pc.P.sigma_color;
-  if constexpr ((DPE_AB_OFF) & 2)
-    return bilateral_weight(-5 + 2 * (k / 6), -5 + 2 * (k % 6), pix, cpix, pc.P.sigma_spatial, sc);
   const float cd = __builtin_fabsf(pix - cpix);
   return d_expf(pc.spat36[k] - cd / (2.0f * sc * sc));
 }
@@ -810,20 +842,14 @@ DEV bool center_outside(const PassConst& pc, int v, const Homog& H, int px, int 
   return pt.x >= (float)sc.width || pt.x < 0.0f || pt.y >= (float)sc.height || pt.y < 0.0f;
 }
 
-// center_outside of the centre of a 5/2 patch together with the patch's reciprocal-range test `ok`
-// (left unset when the centre is outside and DPE_AB_OFF & 128).  The range test first: where it holds,
+// center_outside of the centre of a 5/2 patch together with the patch's reciprocal-range test `ok`.
+// The range test first: where it holds,
 // the centre's denominator, one of the box's, has a biased exponent in [1, 252], so the 3-op
 // reciprocal is the IEEE quotient bit for bit (d_rcp_fast) and the test's outcome is the same.
 DEV bool center_outside_patch(const PassConst& pc, int v, const Homog& H, int px, int py, bool& ok) {
-  if constexpr ((DPE_AB_OFF) & 128) {
-    if (center_outside(pc, v, H, px, py)) return true;
-    ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
-    return false;
-  } else {
-    ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
-    if (__builtin_expect(ok, 1)) return center_outside<true>(pc, v, H, px, py);   // a branch: the division stays rare
-    return center_outside<false>(pc, v, H, px, py);
-  }
+  ok = rcp_range_ok(H, (float)(px - 5), (float)(px + 5), (float)(py - 5), (float)(py + 5));
+  if (__builtin_expect(ok, 1)) return center_outside<true>(pc, v, H, px, py);   // a branch: the division stays rare
+  return center_outside<false>(pc, v, H, px, py);
 }
 
 // ComputeBilateralNCCOld (DPE.cu:692-778), weights per tap.

@@ -207,7 +207,7 @@ DEV float ncc_old_lds(const float* pw, float s_ref, float s_rr, float s_w, int p
     atomicAdd(&g_pool[6][2], ncl ? 0ull : 1ull);
     atomicAdd(&g_pool[7][0], 1ull);
 #endif
-    if (DPE_UNCLAMPED && U8 != TEX_F32 && __all(ncl)) {
+    if (U8 != TEX_F32 && __all(ncl)) {
 #if DPE_POOL_STATS
       atomicAdd(&g_pool[7][1], 1ull);
 #endif
@@ -229,19 +229,12 @@ DEV float ncc_old_any(bool fast, const float* pw, float s_ref, float s_rr, float
 // Baseline part of DPE.cu:2629-2648 (without the cost, which DepthToWeak never uses).
 DEV void baseline_and_weights(const PassConst& pc, uint32_t sel, const uint8_t* vw, float& base_line, float& weight_normal,
                               int& valid) {
-  const DpeCamera& c0 = pc.cams[0];
   base_line = 0.0f; weight_normal = 0.0f; valid = 0;
   for (int si = 1; si < pc.N; ++si) {
     const int vi = si - 1;
     if (isSet(sel, vi)) {
       weight_normal += vw[vi];
-      if constexpr ((DPE_AB_OFF) & 1) {
-        const DpeCamera& cs = pc.cams[si];
-        const float d0 = c0.c[0] - cs.c[0], d1 = c0.c[1] - cs.c[1], d2 = c0.c[2] - cs.c[2];
-        const float tv = d0 * d0 + d1 * d1 + d2 * d2;
-        base_line += __builtin_sqrtf(tv);
-      } else
-        base_line += pc.base_len[si];              // the same sqrtf, once per pass (pass_tables.h)
+      base_line += pc.base_len[si];                // |c0 - c_si|, once per pass (pass_tables.h)
       valid++;
     }
   }
@@ -401,7 +394,7 @@ __global__ void __launch_bounds__(64 * kBwD2W, kTapWaves) k_depth_to_weak(const 
   // LocalRefine's choice (DPE.cu:2807-2834): the in-range hypothesis of least cost in pd order
   float min_cost = 2.0f, best_depth = od;
   for (int pd = -5; pd <= 5; ++pd) {
-    const float p_depth = ((DPE_AB_OFF) & 8) ? c0.K[0] * base_line / (disp + (float)pd) : s_ld[wave][pd + 5];
+    const float p_depth = s_ld[wave][pd + 5];
     if (p_depth < pc.P.depth_min || p_depth > pc.P.depth_max) continue;
     const float tcv = s_lr[wave][pd + 5];
     if (tcv < min_cost) { min_cost = tcv; best_depth = p_depth; }

@@ -377,6 +377,39 @@ template <int P, int C> using StrongCarveT = lds::StrongCarve<P, C, kTailJobs>;
 __host__ __device__ inline int strong_lds_per_wave(int P, int C, int nv) {
   return P == 4 && C == 16 ? StrongCarveT<4, 16>::total(nv) : StrongCarveT<8, 8>::total(nv);
 }
+// A wave's block of that carve: typed pointers to pixel q's part of each region (q = 0..P-1; a lane's
+// own pixel and, in the job pools, any other).  Holds the block's base and nv, nothing else: every
+// address is computed from the layout's offsets where it is used.
+template <int P, int C>
+struct StrongWave {
+  using SC = StrongCarveT<P, C>;
+  float* wl;
+  int nv;
+  DEV float4* hyp(int q) const { return (float4*)(wl + SC::hyp()) + q * 5; }                 // [5] refinement hypotheses
+  DEV float* patch(int q) const { return wl + SC::patch() + q * SC::kPatch; }                // [108] reference patch
+  DEV float* cost(int q) const { return wl + SC::cost(nv) + q * (C + 1) * nv; }              // [C + 1][nv]; slot C = the current plane
+  DEV float* sp(int q) const { return wl + SC::sp(nv) + q * nv; }                            // [nv] view probabilities
+  DEV float* ref(int q) const { return wl + SC::ref(nv) + q * 5 * nv; }                      // [5][nv] refinement NCCs (+ sampling counts)
+  DEV int* sample_counts(int q) const { return (int*)ref(q); }                                // [nv] view_sample_coop's counts (over ref)
+  DEV float* fc(int q) const { return wl + SC::fc(nv) + q * 8; }                             // [8] final costs
+  DEV float* sums(int q) const { return wl + SC::sums(nv) + q * 4; }                         // patch sums s_ref, s_rr, s_w; wnorm
+  DEV uint8_t* vw(int q) const { return (uint8_t*)(wl + SC::vw(nv)) + q * 32; }              // [32] view weights
+  DEV int* ib(int q) const { return (int*)(wl + SC::ib(nv)) + q * SC::ib_ints(nv); }
+  DEV int* pos(int q) const { return ib(q) + SC::IB_POS; }                                   // [C] candidate positions (-1 = none)
+  DEV int* fin(int q) const { return ib(q) + SC::IB_FIN; }                                   // [8] final slot of direction d (-1 = zero vector)
+  DEV int* misc(int q) const { return ib(q) + SC::IB_MISC; }                                 // [8] MI_* slots
+  DEV int* sel_list(int q) const { return ib(q) + SC::IB_SEL; }                              // [nv] selected views
+  DEV int* slots(int q) const { return ib(q) + SC::ib_slots(nv); }                           // [C + 1] cost-vector jobs: candidate slots, then C
+  DEV float4* cpl(int q) const { return (float4*)(wl + SC::cpl(nv)) + q * (C + 1); }         // [C + 1] candidate planes, slot C = current
+  DEV int* alias(int q) const { return (int*)(wl + SC::alias(nv)) + q * (C + 1); }           // [C + 1]
+  DEV float* rnd(int q) const { return wl + SC::rnd(nv) + q * 12; }                          // [12] refinement draws
+  DEV float* tail() const { return wl + SC::tail(nv); }                                      // the split last rounds' row sums
+  DEV int& nsel(int q) const { return misc(q)[SC::MI_NSEL]; }                                // selected views
+  DEV int& jobs(int q) const { return misc(q)[SC::MI_JOBS]; }                                // cost-vector job slots (candidates + current)
+  DEV float& wnorm(int q) const { return sums(q)[3]; }
+  DEV float depth(int q, int h) const { return __int_as_float(misc(q)[SC::MI_DEPTH + h]); }  // depth of hypothesis h
+  DEV void set_depth(int q, int h, float d) const { misc(q)[SC::MI_DEPTH + h] = __float_as_int(d); }
+};
 
 // Job pools of a wave: the NCCs of all its pixels are dealt round-robin over the 64 lanes, so a
 // lane's work does not depend on how many candidates / selected views its own pixel has.
@@ -455,6 +488,230 @@ DEV void pool_tail_split(int tail, int lane, float* tb, const PassConst& pc, con
   }
 }
 
+// ---- the strong sweep's per-pixel phases.  None holds a barrier: k_strong_coop puts one after each.
+// Those that say "converged" use a ballot or a shuffle, so every lane of the wave calls them.
+
+// 31-bit hash of a plane's bits
+DEV int plane_hash(const float4& p) {
+  uint32_t h = __float_as_uint(p.x) * 0x9E3779B1u;
+  h = (h ^ (h >> 15) ^ __float_as_uint(p.y)) * 0x85EBCA77u;
+  h = (h ^ (h >> 13) ^ __float_as_uint(p.z)) * 0xC2B2AE3Du;
+  h = (h ^ (h >> 16) ^ __float_as_uint(p.w)) * 0x27D4EB2Fu;
+  return (int)((h ^ (h >> 15)) & 0x7FFFFFFFu);
+}
+// phase 1: lane c's candidate position, its plane and the plane's hash; lane 0 adds the current plane
+template <bool EDGE, int P, int C>
+DEV void strong_candidate(const StrongWave<P, C>& sw, int ps, int c, const PassConst& pc, const DevBufs& B, int x, int y,
+                          int center, int iter, bool on_edge) {
+  const float4* __restrict__ planes_s = B.planes_snap;
+  int pos;
+  if constexpr (EDGE) {
+    const int d = c & 7, kind = c >> 3;
+    pos = (kind == 1 && on_edge) ? -1 : edge_candidate(pc, B, B.costs_snap, x, y, center, iter, d, kind, on_edge);
+  } else {
+    pos = acmh_candidate(pc, B.costs_snap, x, y, center, c);
+  }
+  sw.pos(ps)[c] = pos;
+  if (pos >= 0) { const float4 pl = planes_s[pos]; sw.cpl(ps)[c] = pl; sw.alias(ps)[c] = plane_hash(pl); }
+  else sw.alias(ps)[c] = (int)(0x80000000u | (uint32_t)c);
+  if (c == 0) { const float4 pl = planes_s[center]; sw.cpl(ps)[C] = pl; sw.alias(ps)[C] = plane_hash(pl); }
+}
+// phase 1b: bitwise-identical planes among the candidates and the current plane (a third of the
+// candidates in a converged map: propagation copies planes) share one cost vector.  alias[] holds
+// the 31-bit hash of each valid slot's plane (absent slots: a unique value with the top bit set); the
+// earliest equal-hash slot is confirmed bit by bit.  al[r]: the alias of slot c + r C (-1: absent).
+template <int P, int C>
+DEV void strong_alias_search(const StrongWave<P, C>& sw, int ps, int c, int (&al)[2]) {
+  const int* alias = sw.alias(ps);
+  const float4* cpl = sw.cpl(ps);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int sl = c + r * C;
+    if (sl > C || (sl < C && sw.pos(ps)[sl] < 0)) continue;
+    const float4 me = cpl[sl];
+    const uint32_t h = (uint32_t)alias[sl];
+    uint32_t m = 0;
+#pragma unroll
+    for (int t = 0; t < C; ++t) m |= ((uint32_t)alias[t] == h && t < sl) ? (1u << t) : 0u;
+    int a = sl;
+    while (m) {
+      const int t = __builtin_ctz(m);
+      if (same_plane_bits(cpl[t], me)) { a = t; break; }
+      m &= m - 1;
+    }
+    al[r] = a;
+  }
+}
+// The cost-vector job slots (k with alias[k] == k, ascending) and, on lane 0, the patch sums.
+// SPREAD (converged): lane c owns slot c, and its place in the list is the number of owners below it
+// among the pixel's lanes; slot C (the current plane) goes last.  Otherwise lane 0 scans the slots.
+template <bool SPREAD, int P, int C>
+DEV void strong_slot_list(const StrongWave<P, C>& sw, int ps, int c, int lane, bool active, bool fast) {
+  const int* alias = sw.alias(ps);
+  int* slots = sw.slots(ps);
+  int n = 0;
+  if constexpr (SPREAD) {
+    const bool own = active && alias[c] == c;
+    const uint32_t bits = (uint32_t)(__ballot(own) >> (lane - c)) & ((1u << C) - 1u);
+    if (own) slots[__popc(bits & ((1u << c) - 1u))] = c;
+    n = __popc(bits);
+  }
+  if (c == 0) {
+    if (active) {
+      if constexpr (SPREAD) { if (alias[C] == C) slots[n++] = C; }
+      else for (int k = 0; k <= C; ++k) if (alias[k] == k) slots[n++] = k;
+      float* sums = sw.sums(ps);
+      if (fast) patch_lds_pre(sw.patch(ps), sums[0], sums[1], sums[2]);
+    }
+    sw.jobs(ps) = n;
+  }
+}
+// duplicates take their original's cost vector
+template <int P, int C>
+DEV void strong_copy_aliased(const StrongWave<P, C>& sw, int ps, int c) {
+  float* cost = sw.cost(ps);
+  const int nv = sw.nv;
+  for (int sl = c; sl <= C; sl += C) {
+    const int a = sw.alias(ps)[sl];
+    if (a >= 0 && a != sl)
+      for (int v = 0; v < nv; ++v) cost[sl * nv + v] = cost[a * nv + v];
+  }
+}
+// phase 3: the final slot of direction d: in edge mode the arbitration of its two candidates
+// (DPE.cu:1323-1342)
+template <bool EDGE, int P, int C>
+DEV void strong_arbitrate(const StrongWave<P, C>& sw, int ps, int d, int iter, bool on_edge) {
+  const int* posl = sw.pos(ps);
+  if constexpr (EDGE) {
+    const float* cost = sw.cost(ps);
+    const int nv = sw.nv;
+    const bool hasA = posl[d] >= 0, hasB = !on_edge && posl[8 + d] >= 0;
+    int f = hasA ? d : -1;
+    if (hasB) {
+      const float good_threshold = 0.8f * d_expf((float)(iter * iter) / (-90.0f));
+      int g0 = 0, g1 = 0, b0 = 0, b1 = 0;
+      for (int j = 0; j < nv; ++j) {
+        // slot A as the reference sees it: its vector, or the zero-initialised row
+        const float v0 = hasA ? cost[d * nv + j] : ((d == 0 && j == 0) ? 2.0f : 0.0f);
+        if (v0 < good_threshold) g0++;
+        if (v0 > 1.2f) b0++;
+        const float v1 = cost[(8 + d) * nv + j];
+        if (v1 < good_threshold) g1++;
+        if (v1 > 1.2f) b1++;
+      }
+      if (!hasA || g1 > g0 || (g1 == g0 && b1 < b0)) f = 8 + d;
+    }
+    sw.fin(ps)[d] = f;
+  } else {
+    sw.fin(ps)[d] = posl[d] >= 0 ? d : -1;
+  }
+}
+// cost of (direction j, view i) as the reference's cost_array holds it
+template <int P, int C>
+DEV float strong_dir_cost(const StrongWave<P, C>& sw, int ps, int j, int i) {
+  const int f = sw.fin(ps)[j];
+  return f >= 0 ? sw.cost(ps)[f * sw.nv + i] : ((j == 0 && i == 0) ? 2.0f : 0.0f);
+}
+// phase 4: per-view sampling probabilities with the 4-neighbour priors (DPE.cu:1552-1590)
+template <int P, int C>
+DEV void strong_view_probs(const StrongWave<P, C>& sw, int ps, int c, const PassConst& pc, const DevBufs& B, int center,
+                           int iter) {
+  const int W = pc.W, nv = sw.nv;
+  const int* fin = sw.fin(ps);
+  float* sp = sw.sp(ps);
+  const float cost_threshold = (float)(0.8 * (double)d_expf((float)(iter * iter) / (-90.0f)));
+  const long Lp = (long)W * pc.H;
+  uint32_t nsv[4];
+  bool nfl[4];
+  const long npos[4] = {(long)center - W, (long)center + W, (long)center - 1, (long)center + 1};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    nfl[i] = fin[2 * i] >= 0;
+    nsv[i] = (nfl[i] && npos[i] >= 0 && npos[i] < Lp) ? B.sel_snap[npos[i]] : 0u;
+  }
+  for (int v = c; v < nv; v += C) {
+    float prior = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (nfl[i]) prior += isSet(nsv[i], v) == 1 ? 0.9f : 0.1f;
+    sp[v] = view_prob_raw([&](int j, int i) { return strong_dir_cost(sw, ps, j, i); }, v, cost_threshold) * prior;
+  }
+}
+// The selected views (vw > 0) as a mask, a list and the weight norm, after the sampling.  SPREAD
+// (converged): C views per ballot, view v's place in the list is the number of selected views below
+// it, and wnorm adds integers below 2^24: exact, so the order is free.  Otherwise lane 0 scans them.
+// tsv and wnorm are lane 0's; the lane's stream is left after the 15 sampling words.
+template <bool SPREAD, int P, int C>
+DEV void strong_selected_views(const StrongWave<P, C>& sw, int ps, int c, int lane, bool active, Rng& rs, uint32_t& tsv,
+                               float& wnorm) {
+  const int nv = sw.nv;
+  const uint8_t* vwl = sw.vw(ps);
+  int* sel_list = sw.sel_list(ps);
+  if constexpr (SPREAD) {
+    for (int v0 = 0; v0 < nv; v0 += C) {
+      const bool on = active && v0 + c < nv && vwl[v0 + c] > 0;
+      tsv |= ((uint32_t)(__ballot(on) >> (lane - c)) & ((1u << C) - 1u)) << v0;
+    }
+    for (int v = c; v < nv; v += C)
+      if (isSet(tsv, v)) sel_list[__popc(tsv & ((1u << v) - 1u))] = v;
+  }
+  if (c == 0) {
+    int ns = 0;
+    if (active) {
+      rng_seek(rs, 15);
+      if constexpr (SPREAD) {
+        int wi = 0;
+        for (int i = 0; i < nv; ++i) wi += vwl[i];
+        wnorm = (float)wi;
+      } else {
+        for (int i = 0; i < nv; ++i) if (vwl[i] > 0) { setBit(tsv, i); wnorm += vwl[i]; sel_list[ns++] = i; }
+      }
+      sw.wnorm(ps) = wnorm;
+    }
+    sw.nsel(ps) = SPREAD ? __popc(tsv) : ns;
+  }
+}
+// phase 5: the final cost of direction d over the sampled views
+template <int P, int C>
+DEV void strong_final_cost(const StrongWave<P, C>& sw, int ps, int d) {
+  const int nv = sw.nv;
+  const uint8_t* vwl = sw.vw(ps);
+  float wn = 0.0f;
+  for (int i = 0; i < nv; ++i) wn += vwl[i];   // == weight_norm (same order: sum of vw > 0)
+  float f = 0.0f;
+  for (int j = 0; j < nv; ++j) { const int w = vwl[j]; if (w > 0) f += w * strong_dir_cost(sw, ps, d, j); }
+  sw.fc(ps)[d] = f / wn;
+}
+// The five hypotheses on lanes 0..4 of the pixel, one each, from lane 0's accepted plane and depth
+// (converged): (normal, depth) = (now, rand), (rand, now), (rand, rand), (perturbed, now),
+// (now, perturbed).  Lanes 1..3 share one view_direction call (at depth_now, or at 1 for the
+// perturbed normal).
+template <int P, int C>
+DEV void strong_hypotheses_spread(const StrongWave<P, C>& sw, int ps, int c, int lane, bool active, const PassConst& pc,
+                                  int x, int y, const float4& pnow, float depth_now) {
+  const DpeCamera& c0 = pc.cams[0];
+  const float* rnd = sw.rnd(ps);
+  const int l0 = lane - c;
+  const float4 pn = make_float4(__shfl(pnow.x, l0), __shfl(pnow.y, l0), __shfl(pnow.z, l0), __shfl(pnow.w, l0));
+  const float dn = __shfl(depth_now, l0);
+  if (active && c < 5) {
+    float4 h = pn;
+    if (c >= 1 && c <= 3) {
+      const float4 vd = view_direction(c0, x, y, c == 3 ? 1.0f : dn);
+      h = c == 3 ? perturbed_normal_vd(vd, pn, rnd + 5) : random_normal_vd(vd, rnd + 1);
+    }
+    float dep = dn;
+    if (c == 0 || c == 2) {
+      const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
+      dep = rnd[0] * (dmax - dmin) + dmin;
+    } else if (c == 4) {
+      const float dminp = (1 - 0.02f) * dn, dmaxp = (1 + 0.02f) * dn;
+      dep = rnd[4] * (dmaxp - dminp) + dminp;
+    }
+    h.w = dist2origin(c0, x, y, dep, h);
+    sw.hyp(ps)[c] = h;
+  }
+}
+
 // waves per workgroup: 2 (4 before round 5's end; 2 fits the first half-sweep beside GenNeighbours
 // better: wall -0.6 ms together with DepthToWeak at 1, profiles/r05ao_ab_wgsize2.log)
 constexpr int kBwStrong = 2;
@@ -469,10 +726,10 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
   // the sections that used to run on one lane per pixel (slot list, selected-view list, refinement
   // hypotheses) spread over the pixel's lanes.  Not in the f32-texel instantiation, which has no
   // registers to spare: its edge-mode kernel went from 0 to 8 B/lane of scratch with them.
-  constexpr bool kSpread = !((DPE_AB_OFF) & 4) && U8 != TEX_F32;
+  constexpr bool kSpread = U8 != TEX_F32;
   // likewise the wider pool tails (last rounds of 17..32 jobs split, and the refinement pool's split
   // at all): 8 B/lane of scratch in the same kernel
-  constexpr bool kWideTails = !((DPE_AB_OFF) & 16) && U8 != TEX_F32;
+  constexpr bool kWideTails = U8 != TEX_F32;
   const PassConst& pc = *pcp;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int ps = lane / C, c = lane % C;
@@ -484,125 +741,32 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
   const bool active = gi < nlist;
   const int center = active ? list[gi] : 0;
   const int x = center % W, y = center / W;
-  // ---- LDS carve (per wave, lds_layout.h; arrays indexed by pixel q where another pixel's data is read)
-  using SC = StrongCarveT<P, C>;
-  float* wl = lds + (size_t)wave * SC::total(nv);
-  float4* hyp_all = (float4*)(wl + SC::hyp());           // [P][5] float4
-  float* pw_all = wl + SC::patch();                      // [P][108] patch
-  float* cost_all = wl + SC::cost(nv);                   // [P][C + 1][nv]; slot C = the current plane
-  float* sp = wl + SC::sp(nv) + ps * nv;                 // [P][nv]
-  float* ref_all = wl + SC::ref(nv);                     // [P][5][nv] refinement NCCs
-  float* fc = wl + SC::fc(nv) + ps * 8;                  // [P][8]  final costs
-  float* sums_all = wl + SC::sums(nv);                   // [P][4]  patch sums s_ref, s_rr, s_w; wnorm
-  uint8_t* vwl = (uint8_t*)(wl + SC::vw(nv)) + ps * 32;  // [P][32] view weights
-  int* ib_all = (int*)(wl + SC::ib(nv));
-  const int ibs = SC::ib_ints(nv);                       // ints per pixel
-  int* ib = ib_all + ps * ibs;
-  int* posl = ib + SC::IB_POS;                           // [C] candidate positions (-1 = none)
-  int* fin = ib + SC::IB_FIN;                            // [8] final slot of direction d (-1 = zero vector)
-  int* misc = ib + SC::IB_MISC;                          // [8] 0: nsel, 1: job slots (candidates + current)
-  int* sel_list = ib + SC::IB_SEL;                       // [nv]
-  int* slots = ib + SC::ib_slots(nv);                    // [C + 1] cost-vector jobs: candidate slots, then C
-  float4* cpl_all = (float4*)(wl + SC::cpl(nv));         // [P][C + 1] candidate planes, slot C = current
-  int* alias_all = (int*)(wl + SC::alias(nv));           // [P][C + 1]
-  float* rnd = wl + SC::rnd(nv) + ps * 12;               // [P][12] refinement draws
-  float4* cpl = cpl_all + ps * (C + 1);
-  int* alias = alias_all + ps * (C + 1);
-  float4* hyp = hyp_all + ps * 5;
-  float* pw = pw_all + ps * 108;
-  float* cost = cost_all + ps * (C + 1) * nv;
-  float* ref = ref_all + ps * 5 * nv;
-
-  const float* __restrict__ costs_s = B.costs_snap;
-  const float4* __restrict__ planes_s = B.planes_snap;
+  // the wave's LDS carve (lds_layout.h): pixel ps is the lane's own, the pools read any pixel q
+  const StrongWave<P, C> sw{lds + (size_t)wave * StrongCarveT<P, C>::total(nv), nv};
   const bool fast = FAST_PATCH(pc);
+  const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
   bool on_edge = false;
   PHASE_BEGIN();
   // ---- phase 1: reference patch + candidate scans
   if (active) {
-    if (fast) patch_lds_build<C>(pw, pc, B, x, y, c);
+    if (fast) patch_lds_build<C>(sw.patch(ps), pc, B, x, y, c);
     PHASE(14);
-    int pos;
-    if constexpr (EDGE) {
-      on_edge = B.edge[center] != 0;
-      const int d = c & 7, kind = c >> 3;
-      pos = (kind == 1 && on_edge) ? -1 : edge_candidate(pc, B, costs_s, x, y, center, iter, d, kind, on_edge);
-    } else {
-      pos = acmh_candidate(pc, costs_s, x, y, center, c);
-    }
-    posl[c] = pos;
-    auto phash = [](const float4& p) -> int {
-      uint32_t h = __float_as_uint(p.x) * 0x9E3779B1u;
-      h = (h ^ (h >> 15) ^ __float_as_uint(p.y)) * 0x85EBCA77u;
-      h = (h ^ (h >> 13) ^ __float_as_uint(p.z)) * 0xC2B2AE3Du;
-      h = (h ^ (h >> 16) ^ __float_as_uint(p.w)) * 0x27D4EB2Fu;
-      return (int)((h ^ (h >> 15)) & 0x7FFFFFFFu);
-    };
-    if (pos >= 0) { const float4 pl = planes_s[pos]; cpl[c] = pl; alias[c] = phash(pl); }
-    else alias[c] = (int)(0x80000000u | (uint32_t)c);
-    if (c == 0) { const float4 pl = planes_s[center]; cpl[C] = pl; alias[C] = phash(pl); }
+    if constexpr (EDGE) on_edge = B.edge[center] != 0;
+    strong_candidate<EDGE>(sw, ps, c, pc, B, x, y, center, iter, on_edge);
   }
   wave_sync();
   PHASE(0);
-  // ---- phase 1b: bitwise-identical planes among the candidates and the current plane (a third of
-  // the candidates in a converged map: propagation copies planes) share one cost vector.  alias[]
-  // first holds a 31-bit hash of each valid slot's plane (absent slots: a unique value with the top
-  // bit set); the earliest equal-hash slot is then confirmed bit by bit.
-  auto same = [](const float4& a, const float4& b) {
-    return __float_as_uint(a.x) == __float_as_uint(b.x) && __float_as_uint(a.y) == __float_as_uint(b.y) &&
-           __float_as_uint(a.z) == __float_as_uint(b.z) && __float_as_uint(a.w) == __float_as_uint(b.w);
-  };
+  // ---- phase 1b: slots with bitwise-identical planes share one cost vector
   int al[2] = {-1, -1};
-  if (active) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int sl = c + r * C;
-      if (sl > C || (sl < C && posl[sl] < 0)) continue;
-      const float4 me = cpl[sl];
-      const uint32_t h = (uint32_t)alias[sl];
-      uint32_t m = 0;
-#pragma unroll
-      for (int t = 0; t < C; ++t) m |= ((uint32_t)alias[t] == h && t < sl) ? (1u << t) : 0u;
-      int a = sl;
-      while (m) {
-        const int t = __builtin_ctz(m);
-        if (same(cpl[t], me)) { a = t; break; }
-        m &= m - 1;
-      }
-      al[r] = a;
-    }
-  }
+  if (active) strong_alias_search(sw, ps, c, al);
   wave_sync();
   if (active) {
-    alias[c] = al[0];
-    if (c == 0) alias[C] = al[1];
+    sw.alias(ps)[c] = al[0];
+    if (c == 0) sw.alias(ps)[C] = al[1];
   }
   wave_sync();
   PHASE(1);
-  if constexpr (!kSpread) {
-    if (c == 0) {
-      int n = 0;
-      if (active) {
-        for (int k = 0; k <= C; ++k) if (alias[k] == k) slots[n++] = k;
-        if (fast) patch_lds_pre(pw, sums_all[ps * 4 + 0], sums_all[ps * 4 + 1], sums_all[ps * 4 + 2]);
-      }
-      misc[SC::MI_JOBS] = n;
-    }
-  } else {
-    // the job slots (k with alias[k] == k, ascending): lane c owns slot c, and its place in the list
-    // is the number of owners below it among the pixel's lanes; slot C (the current plane) goes last
-    const bool own = active && alias[c] == c;
-    const uint32_t bits = (uint32_t)(__ballot(own) >> (lane - c)) & ((1u << C) - 1u);
-    if (own) slots[__popc(bits & ((1u << c) - 1u))] = c;
-    if (c == 0) {
-      int n = __popc(bits);
-      if (active) {
-        if (alias[C] == C) slots[n++] = C;
-        if (fast) patch_lds_pre(pw, sums_all[ps * 4 + 0], sums_all[ps * 4 + 1], sums_all[ps * 4 + 2]);
-      }
-      misc[SC::MI_JOBS] = n;
-    }
-  }
+  strong_slot_list<kSpread>(sw, ps, c, lane, active, fast);
   wave_sync();
   PHASE(2);
   // ---- phase 2: cost vectors of every candidate and of the current plane, one flat pool
@@ -610,7 +774,7 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     // view-major order: the lanes of one round gather from the same source image (cache locality)
     int cnt[P], S = 0;
 #pragma unroll
-    for (int q = 0; q < P; ++q) { cnt[q] = ib_all[q * ibs + SC::IB_MISC + 1]; S += cnt[q]; }
+    for (int q = 0; q < P; ++q) { cnt[q] = sw.jobs(q); S += cnt[q]; }
     int q, r;
     const int total = S * nv, tail = total & 63;
     // a last round of at most kTailMaxJobs jobs is split by patch rows (pool_tail_split)
@@ -620,216 +784,85 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     if (tail > 0) TAIL_STAT(0, split ? tail_lanes_per_job(tail) : 1);
     const int jend = split ? total - tail : total;
     // cost-vector job j as the split last round sees it: slot list entry j % S of view j / S + 1
+    // (the whole rounds below spell the same job out: through cv_job the ACMH quarter-integer kernel
+    // spills 8 B/lane)
     auto cv_job = [&](int j) {
       job_decode<P>(cnt, j % S, q, r);
-      const int slot = ib_all[q * ibs + SC::ib_slots(nv) + r], v = j / S + 1;
+      const int slot = sw.slots(q)[r], v = j / S + 1;
       const int cq = list[wbase + q];
-      return TailJob{pw_all + q * 108, sums_all + q * 4, cost_all + (q * (C + 1) + slot) * nv + v - 1,
-                     cq % W, cq / W, v, cpl_all[q * (C + 1) + slot]};
+      return TailJob{sw.patch(q), sw.sums(q), sw.cost(q) + slot * nv + v - 1, cq % W, cq / W, v, sw.cpl(q)[slot]};
     };
     for (int j = lane; j < jend; j += 64) {
       job_decode<P>(cnt, j % S, q, r);
-      const int* iq = ib_all + q * ibs;
-      const int slot = iq[SC::ib_slots(nv) + r], v = j / S + 1;
+      const int slot = sw.slots(q)[r], v = j / S + 1;
       const int cq = list[wbase + q];
-      const int qx = cq % W, qy = cq / W;
-      const float4 pl = cpl_all[q * (C + 1) + slot];
-      const float* sm = sums_all + q * 4;
-      cost_all[(q * (C + 1) + slot) * nv + v - 1] =
-          ncc_old_any<U8>(fast, pw_all + q * 108, sm[0], sm[1], sm[2], qx, qy, pc, B, v, pl);
+      const float* sm = sw.sums(q);
+      sw.cost(q)[slot * nv + v - 1] =
+          ncc_old_any<U8>(fast, sw.patch(q), sm[0], sm[1], sm[2], cq % W, cq / W, pc, B, v, sw.cpl(q)[slot]);
     }
-    if (split) pool_tail_split<U8>(tail, lane, wl + SC::tail(nv), pc, B, [&](int t) { return cv_job(jend + t); });
+    if (split) pool_tail_split<U8>(tail, lane, sw.tail(), pc, B, [&](int t) { return cv_job(jend + t); });
   }
   wave_sync();
   PHASE(3);
-  if (active) {                                          // duplicates take their original's vector
-    for (int sl = c; sl <= C; sl += C) {
-      const int a = alias[sl];
-      if (a >= 0 && a != sl)
-        for (int v = 0; v < nv; ++v) cost[sl * nv + v] = cost[a * nv + v];
-    }
-  }
+  if (active) strong_copy_aliased(sw, ps, c);
   wave_sync();
   PHASE(4);
   // ---- phase 3: arbitration of the two candidates of each direction (edge mode, DPE.cu:1323-1342)
-  if (active && c < 8) {
-    if constexpr (EDGE) {
-      const int d = c;
-      const bool hasA = posl[d] >= 0, hasB = !on_edge && posl[8 + d] >= 0;
-      int f = hasA ? d : -1;
-      if (hasB) {
-        const float good_threshold = 0.8f * d_expf((float)(iter * iter) / (-90.0f));
-        int g0 = 0, g1 = 0, b0 = 0, b1 = 0;
-        for (int j = 0; j < nv; ++j) {
-          // slot A as the reference sees it: its vector, or the zero-initialised row
-          const float v0 = hasA ? cost[d * nv + j] : ((d == 0 && j == 0) ? 2.0f : 0.0f);
-          if (v0 < good_threshold) g0++;
-          if (v0 > 1.2f) b0++;
-          const float v1 = cost[(8 + d) * nv + j];
-          if (v1 < good_threshold) g1++;
-          if (v1 > 1.2f) b1++;
-        }
-        if (!hasA || g1 > g0 || (g1 == g0 && b1 < b0)) f = 8 + d;
-      }
-      fin[d] = f;
-    } else {
-      fin[c] = posl[c] >= 0 ? c : -1;
-    }
-  }
+  if (active && c < 8) strong_arbitrate<EDGE>(sw, ps, c, iter, on_edge);
   wave_sync();
   PHASE(5);
-  // cost of (direction j, view i) as the reference's cost_array holds it
-  auto cst = [&](int j, int i) -> float {
-    const int f = fin[j];
-    return f >= 0 ? cost[f * nv + i] : ((j == 0 && i == 0) ? 2.0f : 0.0f);
-  };
-  const float cost_threshold = (float)(0.8 * (double)d_expf((float)(iter * iter) / (-90.0f)));
   // ---- phase 4: per-view sampling probabilities with the 4-neighbour priors (DPE.cu:1552-1590)
-  if (active) {
-    const long Lp = (long)W * pc.H;
-    uint32_t nsv[4];
-    bool nfl[4];
-    const long npos[4] = {(long)center - W, (long)center + W, (long)center - 1, (long)center + 1};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      nfl[i] = fin[2 * i] >= 0;
-      nsv[i] = (nfl[i] && npos[i] >= 0 && npos[i] < Lp) ? B.sel_snap[npos[i]] : 0u;
-    }
-    for (int v = c; v < nv; v += C) {
-      float prior = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (nfl[i]) prior += isSet(nsv[i], v) == 1 ? 0.9f : 0.1f;
-      sp[v] = view_prob_raw(cst, v, cost_threshold) * prior;
-    }
-  }
+  if (active) strong_view_probs(sw, ps, c, pc, B, center, iter);
   wave_sync();
   PHASE(6);
-  // ---- samples + view weights (cooperative), then the selected-view list on lane 0
+  // ---- samples + view weights (cooperative), then the selected-view list
   Rng rs;
   rng_init(rs, (uint32_t)center, pc.seed32, STREAM_ITER_BASE + 4 * iter + 0, pc.salt);
-  view_sample_coop(sp, (int*)ref, nv, c, C, active, rs, vwl, B.vw + (size_t)center * DPE_MAX_IMAGES);
+  view_sample_coop(sw.sp(ps), sw.sample_counts(ps), nv, c, C, active, rs, sw.vw(ps), B.vw + (size_t)center * DPE_MAX_IMAGES);
   PHASE(12);
   uint32_t tsv = 0; float wnorm = 0.0f;
-  if constexpr (!kSpread) {
-    if (c == 0) {
-      int ns = 0;
-      if (active) {
-        rng_seek(rs, 15);
-        for (int i = 0; i < nv; ++i) if (vwl[i] > 0) { setBit(tsv, i); wnorm += vwl[i]; sel_list[ns++] = i; }
-        sums_all[ps * 4 + 3] = wnorm;
-      }
-      misc[SC::MI_NSEL] = ns;
-    }
-  } else {
-    // selected views (vw > 0), C views per ballot; view v's place in sel_list is the number of
-    // selected views below it.  wnorm adds integers below 2^24: exact, so the order is free.
-    for (int v0 = 0; v0 < nv; v0 += C) {
-      const bool on = active && v0 + c < nv && vwl[v0 + c] > 0;
-      tsv |= ((uint32_t)(__ballot(on) >> (lane - c)) & ((1u << C) - 1u)) << v0;
-    }
-    for (int v = c; v < nv; v += C)
-      if (isSet(tsv, v)) sel_list[__popc(tsv & ((1u << v) - 1u))] = v;
-    if (c == 0) {
-      if (active) {
-        rng_seek(rs, 15);
-        int wi = 0;
-        for (int i = 0; i < nv; ++i) wi += vwl[i];
-        wnorm = (float)wi;
-        sums_all[ps * 4 + 3] = wnorm;
-      }
-      misc[SC::MI_NSEL] = __popc(tsv);
-    }
-  }
+  strong_selected_views<kSpread>(sw, ps, c, lane, active, rs, tsv, wnorm);
   wave_sync();
   PHASE(7);
-  const int nsel = active ? misc[SC::MI_NSEL] : 0;
+  const int nsel = active ? sw.nsel(ps) : 0;
   // ---- phase 5: final costs of the 8 directions
-  if (active && c < 8) {
-    float wn = 0.0f;
-    for (int i = 0; i < nv; ++i) wn += vwl[i];   // == weight_norm (same order: sum of vw > 0)
-    float f = 0.0f;
-    for (int j = 0; j < nv; ++j) { const int w = vwl[j]; if (w > 0) f += w * cst(c, j); }
-    fc[c] = f / wn;
-  }
+  if (active && c < 8) strong_final_cost(sw, ps, c);
   wave_sync();
   PHASE(8);
   // ---- serial: propagation acceptance + refinement hypotheses (DPE.cu:1617-1654, 1065-1095)
   float cost_now = 0.0f, cost_written = 0.0f, depth_now = 0.0f;
   float4 pnow = make_float4(0, 0, 0, 0);
-  const float pert = (float)(0.02f * 3.14159265358979323846);
-  // lanes 1..4 evaluate the refinement draws (refine_draws: stream words 15.. after the view
-  // sampling) while lane 0 runs the acceptance; lane 0 then finishes the hypotheses from them
-  if (active && c >= 1 && c <= 4) {
-    const RefineDraws d = refine_draws(rs, 15u);
-    if (c == 1) { rnd[0] = d.u_depth; rnd[1] = d.n[0]; rnd[2] = d.n[1]; rnd[3] = d.n[2]; rnd[4] = d.u_pert; }
-    else refine_angle(rs, d.w_angles, c - 2, pert, &rnd[5 + 2 * (c - 2)], &rnd[6 + 2 * (c - 2)]);
-  }
+  // lanes 1..4 evaluate the refinement draws while lane 0 runs the acceptance; the hypotheses are
+  // then finished from them
+  if (active && c >= 1 && c <= 4) refine_draws_lane(rs, c, sw.rnd(ps));
   if (active && c == 0) {
+    const float* fc = sw.fc(ps);
     int mi = 0; float mcost = fc[0];
     for (int i = 1; i < 8; ++i) if (fc[i] <= mcost) { mcost = fc[i]; mi = i; }
-    const float4 curp = planes_s[center];
-    for (int k = 0; k < nsel; ++k) cost_now += vwl[sel_list[k]] * cost[C * nv + sel_list[k]];
-    cost_now /= wnorm;
+    const float4 curp = B.planes_snap[center];
+    const float* cur_cost = sw.cost(ps) + C * nv;
+    cost_now = sel_weighted_cost(sw.vw(ps), sw.sel_list(ps), nsel, wnorm, [&](int, int v) { return cur_cost[v]; });
     cost_written = cost_now;
     B.costs[center] = cost_now;
     depth_now = depth_from_plane(c0, curp, x, y);
     pnow = curp;
-    const int f = fin[mi];
+    const int f = sw.fin(ps)[mi];
     if (f >= 0) {
-      const float4 cand = planes_s[posl[f]];
-      const float db = depth_from_plane(c0, cand, x, y);
-      if (db >= pc.P.depth_min && db <= pc.P.depth_max && fc[mi] < cost_now) {
-        depth_now = db; pnow = cand; cost_now = fc[mi]; B.sel[center] = tsv;
-      }
+      const float4 cand = B.planes_snap[sw.pos(ps)[f]];
+      if (accept_if_better(cand, depth_from_plane(c0, cand, x, y), fc[mi], dmin, dmax, depth_now, pnow, cost_now))
+        B.sel[center] = tsv;
     }
   }
   wave_sync();
-  if constexpr (kSpread) {
-    // lanes 0..4 of the pixel build one hypothesis each from lane 0's accepted plane and depth:
-    // (normal, depth) = (now, rand), (rand, now), (rand, rand), (perturbed, now), (now, perturbed).
-    // Lanes 1..3 share one view_direction call (at depth_now, or at 1 for the perturbed normal).
-    const int l0 = lane - c;
-    const float4 pn = make_float4(__shfl(pnow.x, l0), __shfl(pnow.y, l0), __shfl(pnow.z, l0), __shfl(pnow.w, l0));
-    const float dn = __shfl(depth_now, l0);
-    if (active && c < 5) {
-      float4 h = pn;
-      if (c >= 1 && c <= 3) {
-        const float4 vd = view_direction(c0, x, y, c == 3 ? 1.0f : dn);
-        h = c == 3 ? perturbed_normal_vd(vd, pn, rnd + 5) : random_normal_vd(vd, rnd + 1);
-      }
-      float dep = dn;
-      if (c == 0 || c == 2) {
-        const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
-        dep = rnd[0] * (dmax - dmin) + dmin;
-      } else if (c == 4) {
-        const float dminp = (1 - 0.02f) * dn, dmaxp = (1 + 0.02f) * dn;
-        dep = rnd[4] * (dmaxp - dminp) + dminp;
-      }
-      h.w = dist2origin(c0, x, y, dep, h);
-      hyp[c] = h;
-    }
-  } else if (active && c == 0) {
-    const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
-    const float depth_rand = rnd[0] * (dmax - dmin) + dmin;
-    const float4 prand = random_normal_from(c0, x, y, rnd + 1, depth_now);
-    const float dminp = (1 - 0.02f) * depth_now, dmaxp = (1 + 0.02f) * depth_now;
-    const float depth_perturbed = rnd[4] * (dmaxp - dminp) + dminp;
-    const float4 ppert = perturbed_normal_from(c0, x, y, pnow, rnd + 5);
-    float4 h0 = pnow, h1 = prand, h2 = prand, h3 = ppert, h4 = pnow;
-    h0.w = dist2origin(c0, x, y, depth_rand, h0);
-    h1.w = dist2origin(c0, x, y, depth_now, h1);
-    h2.w = dist2origin(c0, x, y, depth_rand, h2);
-    h3.w = dist2origin(c0, x, y, depth_now, h3);
-    h4.w = dist2origin(c0, x, y, depth_perturbed, h4);
-    hyp[0] = h0; hyp[1] = h1; hyp[2] = h2; hyp[3] = h3; hyp[4] = h4;
-  }
+  if constexpr (kSpread) strong_hypotheses_spread(sw, ps, c, lane, active, pc, x, y, pnow, depth_now);
+  else if (active && c == 0) refine_hypotheses(c0, x, y, dmin, dmax, pnow, depth_now, sw.rnd(ps), sw.hyp(ps));
   wave_sync();
   PHASE(9);
   // ---- phase 6: refinement NCCs, one flat pool of (pixel, hypothesis, selected view)
   {
     int cnt[P];
 #pragma unroll
-    for (int q = 0; q < P; ++q) cnt[q] = 5 * ib_all[q * ibs + SC::IB_MISC];
+    for (int q = 0; q < P; ++q) cnt[q] = 5 * sw.nsel(q);
     POOL_STAT(1, [&] { int t = 0; for (int q = 0; q < P; ++q) t += cnt[q]; return t; }());
     int q, r;
     // a last round of at most kTailMaxJobs jobs is split by patch rows, as in the cost-vector pool
@@ -841,43 +874,33 @@ __global__ void __launch_bounds__(64 * kBwStrong, kTapWaves) k_strong_coop(const
     const bool split = kWideTails && fast && tail > 0 && tail <= kTailMaxJobs;
     if (tail > 0) TAIL_STAT(1, split ? tail_lanes_per_job(tail) : 1);
     const int jend = split ? total - tail : total;
-    for (int j = lane; j < jend && job_decode<P>(cnt, j, q, r); j += 64) {
-      const int* iq = ib_all + q * ibs;
-      const int h = r % 5, k = r / 5;                      // the 5 hypotheses of one view adjacent
+    // refinement job (q, r): hypothesis r % 5 in the pixel's selected view r / 5 (the 5 hypotheses of
+    // one view adjacent)
+    auto ref_job = [&]() {
+      const int h = r % 5, k = r / 5;
       const int cq = list[wbase + q];
-      const float* sm = sums_all + q * 4;
-      ref_all[(q * 5 + h) * nv + k] = ncc_old_any<U8>(fast, pw_all + q * 108, sm[0], sm[1], sm[2], cq % W, cq / W, pc,
-                                                      B, iq[SC::IB_SEL + k] + 1, hyp_all[q * 5 + h]);
+      return TailJob{sw.patch(q), sw.sums(q), sw.ref(q) + h * nv + k, cq % W, cq / W, sw.sel_list(q)[k] + 1, sw.hyp(q)[h]};
+    };
+    for (int j = lane; j < jend && job_decode<P>(cnt, j, q, r); j += 64) {
+      const TailJob J = ref_job();
+      *J.out = ncc_old_any<U8>(fast, J.pw, J.sm[0], J.sm[1], J.sm[2], J.qx, J.qy, pc, B, J.v, J.pl);
     }
     if (split)
-      pool_tail_split<U8>(tail, lane, wl + SC::tail(nv), pc, B, [&](int t) {
-        job_decode<P>(cnt, jend + t, q, r);
-        const int h = r % 5, k = r / 5;
-        const int cq = list[wbase + q];
-        return TailJob{pw_all + q * 108, sums_all + q * 4, ref_all + (q * 5 + h) * nv + k,
-                       cq % W, cq / W, ib_all[q * ibs + SC::IB_SEL + k] + 1, hyp_all[q * 5 + h]};
-      });
+      pool_tail_split<U8>(tail, lane, sw.tail(), pc, B, [&](int t) { job_decode<P>(cnt, jend + t, q, r); return ref_job(); });
   }
   wave_sync();
   PHASE(10);
   // ---- hypothesis costs and depths (one lane each), then sequential acceptance + write-back on
   // lane 0 (DPE.cu:1097-1117, 1656-1665)
   if (active && c < 5) {
-    const int h = c;
-    float tc = 0.0f;
-    for (int k = 0; k < nsel; ++k) tc += vwl[sel_list[k]] * ref[h * nv + k];
-    tc /= sums_all[ps * 4 + 3];
-    fc[h] = tc;
-    misc[SC::MI_DEPTH + h] = __float_as_int(depth_from_plane(c0, hyp[h], x, y));
+    const float* ref = sw.ref(ps) + c * nv;
+    sw.fc(ps)[c] = sel_weighted_cost(sw.vw(ps), sw.sel_list(ps), nsel, sw.wnorm(ps), [&](int k, int) { return ref[k]; });
+    sw.set_depth(ps, c, depth_from_plane(c0, sw.hyp(ps)[c], x, y));
   }
   wave_sync();
   PHASE(13);
   if (active && c == 0) {
-    const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
-    for (int h = 0; h < 5; ++h) {
-      const float tc = fc[h], db = __int_as_float(misc[SC::MI_DEPTH + h]);
-      if (db >= dmin && db <= dmax && tc < cost_now) { depth_now = db; pnow = hyp[h]; cost_now = tc; }
-    }
+    for (int h = 0; h < 5; ++h) accept_if_better(sw.hyp(ps)[h], sw.depth(ps, h), sw.fc(ps)[h], dmin, dmax, depth_now, pnow, cost_now);
     if (pc.P.state == DPE_REFINE_INIT) {
       if ((double)cost_now < (double)cost_written - 0.1) { B.costs[center] = cost_now; B.planes[center] = pnow; }
     } else {
@@ -1074,18 +1097,306 @@ DEV float ncc_new_tab(const PassConst& pc, const DevBufs& B, const WeakTab& T, i
 
 // LDS floats per weak pixel (lds_layout.h WeakCarve: fixed part, then [8][nv] costs, [nv] sampling
 // probabilities, [nv] selected views, [7][nv] hypothesis values; multiple of 4).  At 9 source views a
-// pixel takes 636 floats, so four 4-wave workgroups (4 x 40.7 KB) fit a CU's LDS.
-using WC = lds::WeakCarveT<true>;
+// pixel takes 640 floats, so four 4-wave workgroups (4 x 40 KB, the whole budget) fit a CU's LDS.
+using WC = lds::WeakCarve;
 constexpr int kWeakFixed = WC::FIXED;
 __host__ __device__ inline int weak_lds_per_pixel(int nv) { return WC::per_pixel(nv); }
+// The patch geometries of a weak pixel: the centre patch's radius is the pixel's (RANSAC radius map),
+// the neighbour patches' the pass's; n = the side in taps.  A patch of side <= 6 (centre) or <= 3
+// (neighbours) is tabulated; rc = the pixel's grey level, the bilateral weights' centre.
+struct WeakSides {
+  int rad_c, inc_c, n_c, rad_n, inc_n, n_n;
+  bool tab_c, tab_n;
+  float rc;
+  // phase 1 by patch rows (the common case: centre side <= 6, 3x3 neighbour patches)
+  DEV bool by_rows() const { return tab_c && tab_n && n_n == 3; }
+};
+// A pixel's block of that carve: typed pointers to its regions, for the lane's own pixel and, in the
+// pooled phases, for any pixel of the workgroup.  Holds the block's base and nv, nothing else.
+struct WeakPixel {
+  float* b;
+  int nv;
+  DEV float* pw() const { return b + WC::PW; }                                   // [108] Old-NCC patch (patch_lds_build)
+  DEV float* tc() const { return b + WC::TC; }                                   // centre patch table, pairs [36][2]
+  DEV float* tn() const { return b + WC::TN; }                                   // neighbour patch tables, pairs [8][9][2]
+  DEV float* sums() const { return b + WC::SUMS; }                               // [9][3] ncc_pre of each tabulated patch
+  DEV float* osum() const { return b + WC::OSUM; }                               // [3] Old-NCC patch sums
+  DEV float4* cpl() const { return (float4*)(b + WC::CPL); }                     // [8] candidate planes
+  DEV float4* hyp() const { return (float4*)(b + WC::HYP); }                     // [5] hypotheses, then:
+  DEV float4& final_plane() const { return hyp()[5]; }
+  DEV float4& fit_plane() const { return hyp()[6]; }
+  DEV float* rsum(int row) const { return b + WC::RSUM + 3 * row; }              // phases 1-1b: row sums of the centre patch
+  DEV float* fc() const { return b + WC::FC; }                                   // [8] final candidate costs
+  DEV int* misc() const { return (int*)(b + WC::MISC); }                         // WC::M_* slots
+  DEV int* flags() const { return misc() + WC::M_FLAGS; }                        // [8] neighbour i + 1 is strong: a candidate
+  DEV short2* nbl() const { return (short2*)(b + WC::NBL); }                     // [9] neighbour pixels ([0] = the pixel itself)
+  DEV uint32_t* nsv() const { return (uint32_t*)(b + WC::NSV); }                 // [9] selected views of the neighbours
+  DEV int* alias() const { return (int*)(b + WC::ALIAS); }                       // [8] earlier row with a bitwise-identical plane
+  DEV uint8_t* vwl() const { return (uint8_t*)(b + WC::VWL); }                   // [32] view weights
+  DEV float* rnd() const { return b + WC::RND; }                                 // [12] refinement draws (over alias)
+  DEV float* cost() const { return b + WC::cost(nv); }                           // [8][nv]
+  DEV float* sp() const { return b + WC::sp(nv); }                               // [nv]
+  DEV int* sel_list() const { return (int*)(b + WC::sel(nv)); }                  // [nv]
+  DEV float* hv(int row) const { return b + WC::hv(nv) + row * nv; }             // [7][nv] plane x selected-view values
+  DEV int* sample_counts() const { return (int*)hv(0); }                         // [nv] view_sample_coop's counts (over hv)
+  DEV int& nsel() const { return misc()[WC::M_NSEL]; }
+  DEV int& pool_jobs() const { return misc()[WC::M_POOL]; }                      // the pixel's jobs in the next pool
+  DEV int& cmask() const { return misc()[WC::M_CMASK]; }                         // candidates with a cost vector of their own
+  DEV float wnorm() const { return __int_as_float(misc()[WC::M_WNORM]); }
+  DEV void set_wnorm(float w) const { misc()[WC::M_WNORM] = __float_as_int(w); }
+  // the header the pooled phases read: the centre patch's geometry, the grey level, the box of the
+  // neighbour patches (nb3: they are tabulated 3x3 and the box is set)
+  DEV void set_header(int rad_c, int inc_c, int n_c, bool nb3, const float* nbox, float rc) const {
+    misc()[WC::M_RADC] = rad_c; misc()[WC::M_INCC] = inc_c; misc()[WC::M_NC] = n_c; misc()[WC::M_NB3] = nb3 ? 1 : 0;
+    b[WC::NBOX_A] = nbox[0]; b[WC::NBOX_A + 1] = nbox[1]; b[WC::NBOX_A + 2] = nbox[2]; b[WC::NBOX_B] = nbox[3];
+    b[WC::RC] = rc;
+  }
+  // the tables of the pixel as ncc_new_tab takes them; the neighbour patches' geometry is the pass's,
+  // so any pixel's `g` serves
+  DEV WeakTab tab(const WeakSides& g) const {
+    const int* h = misc();
+    WeakTab t;
+    t.rad_c = h[WC::M_RADC]; t.inc_c = h[WC::M_INCC]; t.n_c = h[WC::M_NC]; t.nb3 = h[WC::M_NB3] != 0;
+    t.rad_n = g.rad_n; t.inc_n = g.inc_n; t.n_n = g.n_n; t.tab_n = g.tab_n;
+    t.tab_c = t.n_c >= 1 && t.n_c <= 6;
+    t.rc = b[WC::RC];
+    t.nbox[0] = b[WC::NBOX_A]; t.nbox[1] = b[WC::NBOX_A + 1]; t.nbox[2] = b[WC::NBOX_A + 2]; t.nbox[3] = b[WC::NBOX_B];
+    t.tc = tc(); t.tn = tn(); t.sums = sums();
+    t.nbl = nbl(); t.nsv = nsv();
+    return t;
+  }
+};
+
+// ---- the weak sweep's per-pixel phases (no barrier inside: k_weak_coop puts one after each)
+// phase 1, by_rows(): the tables by patch rows with their reference sums (the order of
+// weak_table_sums): lanes 0..n_c-1 a centre row each (row sums to rsum, added in row order by
+// weak_centre_sums), lanes 8..15 a 3x3 neighbour patch each (sums complete); a lane's texel loads
+// are issued together
+DEV void weak_tables_by_rows(const WeakPixel& me, int c, const PassConst& pc, const DevBufs& B, const short2* nbg,
+                             const WeakSides& g) {
+  const int W = pc.W, Hh = pc.H;
+  const float ss = pc.P.sigma_spatial, sc = pc.P.sigma_color;
+  const int rad_c = g.rad_c, inc_c = g.inc_c, n_c = g.n_c, rad_n = g.rad_n, inc_n = g.inc_n;
+  if (c < n_c) {
+    const short2 np = nbg[0];
+    if (!(np.x == -1 || np.y == -1)) {
+      const int i = -rad_c + c * inc_c;
+      float rp[6];
+#pragma unroll
+      for (int b = 0; b < 6; ++b) rp[b] = b < n_c ? ref_texel(B.ref, W, Hh, np.x + i, np.y - rad_c + b * inc_c) : 0.0f;
+      float* tcp = me.tc();
+      float r_ref = 0, r_rr = 0, r_w = 0;
+#pragma unroll
+      for (int b = 0; b < 6; ++b) {
+        if (b >= n_c) break;
+        const float w = bilateral_weight(i, -rad_c + b * inc_c, rp[b], g.rc, ss, sc);
+        const float wr = w * rp[b];
+        tcp[2 * (c * n_c + b)] = w; tcp[2 * (c * n_c + b) + 1] = wr;
+        r_ref = r_ref + wr;
+        r_rr = __builtin_fmaf(wr, rp[b], r_rr);
+        r_w = r_w + w;
+      }
+      float* rs3 = me.rsum(c);
+      rs3[0] = r_ref; rs3[1] = r_rr; rs3[2] = r_w;
+    }
+  } else if (c >= 8) {
+    const int k = c - 7;
+    const short2 np = nbg[k];
+    if (!(np.x == -1 || np.y == -1)) {
+      float rp[9];
+#pragma unroll
+      for (int t = 0; t < 9; ++t) rp[t] = ref_texel(B.ref, W, Hh, np.x - rad_n + (t / 3) * inc_n, np.y - rad_n + (t % 3) * inc_n);
+      float* tp = me.tn() + (k - 1) * 18;
+      float a_ref = 0, a_rr = 0, a_w = 0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        float r_ref = 0, r_rr = 0, r_w = 0;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const float w = bilateral_weight(-rad_n + a * inc_n, -rad_n + b * inc_n, rp[a * 3 + b], g.rc, ss, sc);
+          const float wr = w * rp[a * 3 + b];
+          tp[2 * (a * 3 + b)] = w; tp[2 * (a * 3 + b) + 1] = wr;
+          r_ref = r_ref + wr;
+          r_rr = __builtin_fmaf(wr, rp[a * 3 + b], r_rr);
+          r_w = r_w + w;
+        }
+        a_ref += r_ref; a_rr += r_rr; a_w += r_w;
+      }
+      float* sm = me.sums() + 3 * k;
+      ncc_pre(a_ref, a_rr, a_w, sm[0], sm[1], sm[2]);
+    }
+  }
+}
+// phase 1 otherwise: the taps of the tabulated patches dealt over the pixel's C lanes
+DEV void weak_tables_by_taps(const WeakPixel& me, int c, int C, const PassConst& pc, const DevBufs& B, const short2* nbg,
+                             const WeakSides& g) {
+  const float ss = pc.P.sigma_spatial, sc = pc.P.sigma_color;
+  const int rad_c = g.rad_c, inc_c = g.inc_c, n_c = g.n_c, rad_n = g.rad_n, inc_n = g.inc_n, n_n = g.n_n;
+  const int ntc = g.tab_c ? n_c * n_c : 0, ntn = g.tab_n ? n_n * n_n : 0;
+  for (int t = c; t < ntc + 8 * ntn; t += C) {
+    int k, tt, n, rad, inc;
+    if (t < ntc) { k = 0; tt = t; n = n_c; rad = rad_c; inc = inc_c; }
+    else { k = 1 + (t - ntc) / ntn; tt = (t - ntc) % ntn; n = n_n; rad = rad_n; inc = inc_n; }
+    const short2 np = nbg[k];
+    if (np.x == -1 || np.y == -1) continue;
+    const int i = -rad + (tt / n) * inc, j = -rad + (tt % n) * inc;
+    const float rp = ref_texel(B.ref, pc.W, pc.H, np.x + i, np.y + j);
+    const float w = bilateral_weight(i, j, rp, g.rc, ss, sc);
+    float* dst = k == 0 ? me.tc() + 2 * tt : me.tn() + 2 * ((k - 1) * 9 + tt);
+    dst[0] = w; dst[1] = w * rp;
+  }
+}
+// phase 1: the neighbours with their selected views
+DEV void weak_neighbours(const WeakPixel& me, int c, int C, const PassConst& pc, const DevBufs& B, const short2* nbg) {
+  for (int k = c; k < 9; k += C) {
+    const short2 np = nbg[k];
+    me.nbl()[k] = np;
+    me.nsv()[k] = (np.x == -1 || np.y == -1) ? 0u : B.sel[np.x + np.y * pc.W];
+  }
+}
+// phase 1: the candidate rows: neighbour i + 1 is a candidate if it is strong (its plane to cpl),
+// otherwise its cost row is the reference's zero row
+DEV void weak_candidate_rows(const WeakPixel& me, int c, int C, const PassConst& pc, const DevBufs& B, const short2* nbg) {
+  const int W = pc.W, nv = me.nv;
+  for (int i = c; i < 8; i += C) {
+    const short2 np = nbg[i + 1];
+    const bool fl = !(np.x == -1 || np.y == -1) && B.weak[np.x + np.y * W] == DPE_STRONG;
+    me.flags()[i] = fl ? 1 : 0;
+    if (fl) me.cpl()[i] = B.planes[np.x + np.y * W];
+    else for (int v = 0; v < nv; ++v) me.cost()[i * nv + v] = (i == 0 && v == 0) ? 2.0f : 0.0f;
+  }
+}
+// phase 1b, one lane: the header, with the union box of the neighbour patches (k = 1..8) for the
+// one-check fast path of ncc_new_tab
+DEV void weak_header(const WeakPixel& me, const WeakSides& g) {
+  const int rad_n = g.rad_n;
+  bool nb3 = false;
+  float nbox[4];
+  if (g.tab_n && g.n_n == 3) {
+    int x0 = 0x7FFFFFFF, x1 = -0x7FFFFFFF, y0 = 0x7FFFFFFF, y1 = -0x7FFFFFFF;
+    for (int k = 1; k < DPE_NEIGHBOUR_NUM; ++k) {
+      const short2 np = me.nbl()[k];
+      if (np.x == -1 || np.y == -1) continue;
+      x0 = min(x0, (int)np.x); x1 = max(x1, (int)np.x); y0 = min(y0, (int)np.y); y1 = max(y1, (int)np.y);
+    }
+    if (x0 <= x1) {
+      nb3 = true;
+      nbox[0] = (float)(x0 - rad_n); nbox[1] = (float)(x1 + rad_n);
+      nbox[2] = (float)(y0 - rad_n); nbox[3] = (float)(y1 + rad_n);
+    }
+  }
+  me.set_header(g.rad_c, g.inc_c, g.n_c, nb3, nbox, g.rc);
+}
+// phase 1b, by_rows(), one lane: the centre patch's row sums added in row order
+DEV void weak_centre_sums(const WeakPixel& me, int n_c) {
+  const short2 np = me.nbl()[0];
+  if (np.x == -1 || np.y == -1) return;
+  float a_ref = 0, a_rr = 0, a_w = 0;
+  for (int a = 0; a < n_c; ++a) {
+    const float* rs3 = me.rsum(a);
+    a_ref += rs3[0]; a_rr += rs3[1]; a_w += rs3[2];
+  }
+  float* sm = me.sums();
+  ncc_pre(a_ref, a_rr, a_w, sm[0], sm[1], sm[2]);
+}
+// phase 1b otherwise: the reference sums of every tabulated patch (tap order of patch_ncc_generic),
+// one patch per lane
+DEV void weak_table_sums(const WeakPixel& me, int c, int C, const PassConst& pc, const DevBufs& B, const WeakSides& g) {
+  const int rad_c = g.rad_c, inc_c = g.inc_c, n_c = g.n_c, rad_n = g.rad_n, inc_n = g.inc_n, n_n = g.n_n;
+  const bool tab_c = g.tab_c, tab_n = g.tab_n;
+  for (int k = c; k < 9; k += C) {
+    const short2 np = me.nbl()[k];
+    if (np.x == -1 || np.y == -1 || !(k == 0 ? tab_c : tab_n)) continue;
+    const int n = k == 0 ? n_c : n_n, rad = k == 0 ? rad_c : rad_n, inc = k == 0 ? inc_c : inc_n;
+    const float* tp = k == 0 ? me.tc() : me.tn() + (k - 1) * 18;
+    float a_ref = 0, a_rr = 0, a_w = 0;
+    for (int a = 0; a < n; ++a) {
+      float r_ref = 0, r_rr = 0, r_w = 0;
+      for (int b = 0; b < n; ++b) {
+        const float rp = ref_texel(B.ref, pc.W, pc.H, np.x - rad + a * inc, np.y - rad + b * inc);
+        const float w = tp[2 * (a * n + b)], wr = tp[2 * (a * n + b) + 1];
+        r_ref = r_ref + wr;
+        r_rr = __builtin_fmaf(wr, rp, r_rr);
+        r_w = r_w + w;
+      }
+      a_ref += r_ref; a_rr += r_rr; a_w += r_w;
+    }
+    float* sm = me.sums() + 3 * k;
+    ncc_pre(a_ref, a_rr, a_w, sm[0], sm[1], sm[2]);
+  }
+}
+// phase 1b: bitwise-identical neighbour planes share one cost vector: alias = first earlier flagged
+// row with the same plane (lanes 8..15; lanes 0..8 build the sums)
+DEV void weak_alias_rows(const WeakPixel& me, int c, int C) {
+  for (int i = c - 8; i >= 0 && i < 8; i += C) {
+    int a = i;
+    if (me.flags()[i]) {
+      const float4 pl = me.cpl()[i];
+      for (int t = 0; t < i; ++t)
+        if (me.flags()[t] && same_plane_bits(me.cpl()[t], pl)) { a = t; break; }
+    }
+    me.alias()[i] = a;
+  }
+}
+// phase 3: per-view probabilities with the deformable-neighbour priors (DPE.cu:1768-1790)
+DEV void weak_view_probs(const WeakPixel& me, int c, int C, int iter) {
+  const int nv = me.nv;
+  const float* cost = me.cost();
+  const float cost_threshold = (float)(0.8 * (double)d_expf((float)(iter * iter) / (-90.0f)));
+  auto cst = [&](int j, int i) -> float { return cost[j * nv + i]; };
+  for (int v = c; v < nv; v += C) {
+    float prior = 0.0f;
+    for (int i = 0; i < 8; ++i) {
+      const short2 np = me.nbl()[i + 1];
+      if (np.x == -1 || np.y == -1) continue;
+      prior += isSet(me.nsv()[i + 1], v) == 1 ? 0.9f : 0.1f;
+    }
+    me.sp()[v] = view_prob_raw(cst, v, cost_threshold) * prior;
+  }
+}
+// the final cost of candidate i over the sampled views, with the geometric term (DPE.cu:1792-1810)
+DEV void weak_final_cost(const WeakPixel& me, int i, const PassConst& pc, const DevBufs& B, int x, int y, float wn) {
+  const int nv = me.nv;
+  const bool geom = pc.P.geom_consistency;
+  const float gf = pc.P.geom_factor;
+  const float* cost = me.cost();
+  const uint8_t* vwl = me.vwl();
+  const bool fl = me.flags()[i] != 0;
+  const float3 fwi = (geom && fl) ? geom_point(pc, x, y, me.cpl()[i]) : make_float3(0.0f, 0.0f, 0.0f);
+  float f = 0.0f;
+  for (int j = 0; j < nv; ++j) {
+    const int w = vwl[j];
+    if (w > 0) {
+      if (geom) {
+        if (fl) f += w * (cost[i * nv + j] + gf * geom_cost_at(pc, B, x, y, j + 1, fwi));
+        else f += w * (cost[i * nv + j] + gf * 3.0f);
+      } else {
+        f += w * cost[i * nv + j];
+      }
+    }
+  }
+  me.fc()[i] = f / wn;
+}
 
 // CheckerboardPropagationWeak (DPE.cu:1668-1862) + PlaneHypothesisRefinementWeak (:1120-1212).
-// C lanes per pixel, 64/C pixels per wave, blockDim.x/64 waves per workgroup.
+// C = 16 lanes per pixel, 4 pixels per wave, blockDim.x/64 waves per workgroup.
+//
+// Pooled phases: the NCCs of all the workgroup's pixels are dealt round-robin over its lanes, so a
+// job carries its pixel q (0..npx-1, the workgroup's pixels in list order) and pix(q) is that pixel's
+// LDS block.  A pool's jobs fill whole waves first, so a wave with no job left skips the round and
+// its SIMD issues other waves (pools over one wave's 4 pixels left 27-46 of 64 lanes idle in the
+// current-plane, refinement and final-cost rounds).  Each pixel's job count sits in its pool_jobs();
+// a job index is decoded by a scan over the pool's pixels.  The barriers around a pool are
+// workgroup-wide.
 template <int U8, int C>
 __global__ void __launch_bounds__(256, kTapWaves) k_weak_coop(const PassConst* __restrict__ pcp, DevBufs B, int iter,
                                                    const int* __restrict__ list, const int* __restrict__ nlist_p) {
   extern __shared__ float4 lds4[];
-  static_assert(C == 16 || C == 32, "the per-pixel phases give lanes 0..8 the patch sums and lanes 8..15 the alias rows");
+  // (a local: with `(float*)lds4` written into pix() below, the first job pool of every instantiation
+  // grows by 240 instructions, scalar values kept in VGPR lanes and their wait states, and the weak
+  // class by 0.2 ms per pass; profiles/sweep_cleanup_ab.md)
+  float* lds = (float*)lds4;
+  static_assert(C == 16, "the per-pixel phases give lanes 0..8 the patch sums and lanes 8..15 the alias rows");
   constexpr int P = 64 / C;
   const PassConst& pc = *pcp;
   const int nlist = *nlist_p;
@@ -1094,444 +1405,210 @@ __global__ void __launch_bounds__(256, kTapWaves) k_weak_coop(const PassConst* _
   const int ps = lane / C, c = lane % C;
   const int W = pc.W, Hh = pc.H, nv = pc.N - 1;
   const DpeCamera& c0 = pc.cams[0];
-  const int wgbase = xcd_remap(blockIdx.x, gridDim.x, B.xcd_rows * 16) * wpb * P;
-  const int wbase = wgbase + wave * P;
-  constexpr bool WGP = true;   // workgroup-wide job pools (false: each wave's own 4 pixels)
-  if ((WGP ? wgbase : wbase) >= nlist) return;           // workgroup- (wave-) uniform tail
-  const int gi = wbase + ps;
+  const int wgbase = xcd_remap(blockIdx.x, gridDim.x, B.xcd_rows * 16) * wpb * P;   // list index of the pool's pixel 0
+  if (wgbase >= nlist) return;                           // workgroup-uniform tail
+  const int gi = wgbase + wave * P + ps;
   const bool active = gi < nlist;
   const int center = active ? list[gi] : 0;
   const int x = center % W, y = center / W;
-  // ---- LDS carve (per pixel, floats; lds_layout.h WeakCarve)
+  // the LDS carve (lds_layout.h WeakCarve): one block per pixel, `me` the lane's own
   const int S = weak_lds_per_pixel(nv);
-  float* pb = (float*)lds4 + (size_t)(wave * P + ps) * S;
-  float* pw = pb + WC::PW;                               // [108] Old-NCC patch (patch_lds_build)
-  float* tcp = pb + WC::TC;                              // centre patch table, pairs [36][2]
-  float* tnp = pb + WC::TN;                              // neighbour patch tables, pairs [8][9][2]
-  float* sums = pb + WC::SUMS;                           // [9][3]
-  float* osum = pb + WC::OSUM;                           // [3] Old-NCC patch sums
-  float4* cpl = (float4*)(pb + WC::CPL);                 // [8] candidate planes
-  float4* hyp = (float4*)(pb + WC::HYP);                 // [7] refinement hypotheses / final plane
-  float* fc = pb + WC::FC;                               // [8] final candidate costs
-  int* misc = (int*)(pb + WC::MISC);                     // WC::M_* slots (nsel, header, wnorm, candidate mask, flags)
-  short2* nbl = (short2*)(pb + WC::NBL);                 // [9]
-  uint32_t* nsv = (uint32_t*)(pb + WC::NSV);             // [9]
-  int* alias = (int*)(pb + WC::ALIAS);                   // [8] earlier row with a bitwise-identical plane
-  uint8_t* vwl = (uint8_t*)(pb + WC::VWL);               // [32] view weights
-  // the pixel's header, read by the lanes of other pixels in the pooled phases: misc[M_RADC / M_INCC /
-  // M_NC / M_NB3], the grey level at RC, nbox at NBOX_A[0..2] and NBOX_B; fit plane in hyp[6]
-  float* cost = pb + WC::cost(nv);                       // [8][nv]
-  float* sp = pb + WC::sp(nv);                           // [nv]
-  int* sel_list = (int*)(pb + WC::sel(nv));              // [nv]
-  float* hv = pb + WC::hv(nv);                           // [7][nv] hypothesis x selected-view values
+  auto pix = [&](int q) { return WeakPixel{lds + (size_t)q * S, nv}; };
+  const WeakPixel me = pix(wave * P + ps);
+  const int npx = wpb * P;
 
   const bool geom = pc.P.geom_consistency;
   const float gf = pc.P.geom_factor;
   const bool fast_old = pc.P.strong_radius == 5 && pc.P.strong_increment == 2;
-  WeakTab T;
-  T.rad_c = pc.P.strong_radius; T.inc_c = pc.P.strong_increment;
-  if (pc.P.use_radius && active) { T.rad_c = B.radius[center]; T.inc_c = MAXo(2, d2i(2.0 * T.rad_c / 5.0)); }
-  T.rad_n = pc.P.weak_radius; T.inc_n = pc.P.weak_increment;
-  T.n_c = T.rad_c >= 0 ? (2 * T.rad_c) / T.inc_c + 1 : 0;
-  T.n_n = T.rad_n >= 0 ? (2 * T.rad_n) / T.inc_n + 1 : 0;
-  T.tab_c = T.n_c >= 1 && T.n_c <= 6;
-  T.tab_n = T.n_n >= 1 && T.n_n <= 3;
-  // plain copies (round 5): references to T's fields under the selects below kept T in scratch
-  // (32 B/lane); with the round-5 phase 1 and workgroup pools the copies are as fast and 0 B
-  const int rad_c = T.rad_c, inc_c = T.inc_c, n_c = T.n_c, rad_n = T.rad_n, inc_n = T.inc_n, n_n = T.n_n;
-  const bool tab_c = T.tab_c, tab_n = T.tab_n;
-  T.rc = active ? ref_texel(B.ref, W, Hh, x, y) : 0.0f;
-  T.tc = tcp; T.tn = tnp; T.sums = sums; T.nbl = nbl; T.nsv = nsv;
+  WeakSides g;
+  g.rad_c = pc.P.strong_radius; g.inc_c = pc.P.strong_increment;
+  if (pc.P.use_radius && active) { g.rad_c = B.radius[center]; g.inc_c = MAXo(2, d2i(2.0 * g.rad_c / 5.0)); }
+  g.rad_n = pc.P.weak_radius; g.inc_n = pc.P.weak_increment;
+  g.n_c = g.rad_c >= 0 ? (2 * g.rad_c) / g.inc_c + 1 : 0;
+  g.n_n = g.rad_n >= 0 ? (2 * g.rad_n) / g.inc_n + 1 : 0;
+  g.tab_c = g.n_c >= 1 && g.n_c <= 6;
+  g.tab_n = g.n_n >= 1 && g.n_n <= 3;
+  g.rc = active ? ref_texel(B.ref, W, Hh, x, y) : 0.0f;
   const short2* nbg = B.nb + (size_t)center * 9;
-  // pooled phases: the NCCs of all the workgroup's pixels are dealt round-robin over its lanes, so
-  // a job carries its pixel q (0..npx-1, the workgroup's pixels in list order) and pix(q) is that
-  // pixel's LDS block.  A pool's jobs fill whole waves first, so a wave with no job left skips
-  // the round and its SIMD issues other waves (pools over one wave's 4 pixels left 27-46 of 64
-  // lanes idle in the current-plane, refinement and final-cost rounds).  Each pixel's job count
-  // sits in its misc[M_POOL]; a job index is decoded by a scan over the pool's pixels.
-  const int npx = WGP ? wpb * P : P;
-  float* const pool0 = (float*)lds4 + (size_t)(WGP ? 0 : wave * P) * S;
-  const int pbase = WGP ? wgbase : wbase;                // list index of the pool's pixel 0
-  const int pl_lane = WGP ? (int)threadIdx.x : lane, pl_n = WGP ? (int)blockDim.x : 64;
-  auto pool_sync = [&]() { if constexpr (WGP) __syncthreads(); else wave_sync(); };
-  auto pix = [&](int q) -> float* { return pool0 + (size_t)q * S; };
-  auto pool_cnt = [&](int q) -> int { return ((const int*)(pix(q) + WC::MISC))[WC::M_POOL]; };
-  auto pool_total = [&]() -> int { int t = 0; for (int q = 0; q < npx; ++q) t += pool_cnt(q); return t; };
-  auto pool_decode = [&](int j, int& q, int& r) { q = 0; for (int cc; j >= (cc = pool_cnt(q)); ++q) j -= cc; r = j; };
+  auto pool_total = [&]() -> int { int t = 0; for (int q = 0; q < npx; ++q) t += pix(q).pool_jobs(); return t; };
+  auto pool_decode = [&](int j, int& q, int& r) { q = 0; for (int cc; j >= (cc = pix(q).pool_jobs()); ++q) j -= cc; r = j; };
   auto pool_stat_g = [&](int k, int jobs) {   // DPE_DIAG & 16: jobs, wave rounds with a job, waves
 #if DPE_POOL_STATS
-    if (pl_lane == 0) {
+    if (threadIdx.x == 0) {
       atomicAdd(&g_pool[k][0], (unsigned long long)jobs);
       atomicAdd(&g_pool[k][1], (unsigned long long)((jobs + 63) / 64));
-      atomicAdd(&g_pool[k][2], (unsigned long long)(pl_n / 64));
+      atomicAdd(&g_pool[k][2], (unsigned long long)(blockDim.x / 64));
     }
 #else
     (void)k; (void)jobs;
 #endif
   };
-  auto tab_of = [&](int q) -> WeakTab {
-    const float* qb = pix(q);
-    const int* h = (const int*)(qb + WC::MISC);
-    WeakTab t;
-    t.rad_c = h[WC::M_RADC]; t.inc_c = h[WC::M_INCC]; t.n_c = h[WC::M_NC]; t.nb3 = h[WC::M_NB3] != 0;
-    t.rad_n = T.rad_n; t.inc_n = T.inc_n; t.n_n = T.n_n; t.tab_n = T.tab_n;
-    t.tab_c = t.n_c >= 1 && t.n_c <= 6;
-    t.rc = qb[WC::RC];
-    t.nbox[0] = qb[WC::NBOX_A]; t.nbox[1] = qb[WC::NBOX_A + 1]; t.nbox[2] = qb[WC::NBOX_A + 2]; t.nbox[3] = qb[WC::NBOX_B];
-    t.tc = qb + WC::TC; t.tn = qb + WC::TN; t.sums = qb + WC::SUMS;
-    t.nbl = (const short2*)(qb + WC::NBL); t.nsv = (const uint32_t*)(qb + WC::NSV);
-    return t;
-  };
-  // phase 1 by patch rows (the common case: centre side <= 6, 3x3 neighbour patches, C = 16)
-  const bool rows1 = C == 16 && tab_c && tab_n && n_n == 3;
+  const bool rows1 = g.by_rows();
 
   PHASE_BEGIN();
   // ---- phase 1: neighbours, weight tables, Old-NCC patch, candidate rows
   if (active) {
-    if (fast_old) patch_lds_build<C>(pw, pc, B, x, y, c);
-    for (int k = c; k < 9; k += C) {
-      const short2 np = nbg[k];
-      nbl[k] = np;
-      nsv[k] = (np.x == -1 || np.y == -1) ? 0u : B.sel[np.x + np.y * W];
-    }
-    const float ss = pc.P.sigma_spatial, sc = pc.P.sigma_color;
-    if (rows1) {
-      // the tables by patch rows with their reference sums (the order of phase 1b's loop): lanes
-      // 0..n_c-1 a centre row each (row sums to RSUM, added in row order in phase 1b), lanes 8..15
-      // a 3x3 neighbour patch each (sums complete); a lane's texel loads are issued together
-      if (c < n_c) {
-        const short2 np = nbg[0];
-        if (!(np.x == -1 || np.y == -1)) {
-          const int i = -rad_c + c * inc_c;
-          float rp[6];
-#pragma unroll
-          for (int b = 0; b < 6; ++b) rp[b] = b < n_c ? ref_texel(B.ref, W, Hh, np.x + i, np.y - rad_c + b * inc_c) : 0.0f;
-          float r_ref = 0, r_rr = 0, r_w = 0;
-#pragma unroll
-          for (int b = 0; b < 6; ++b) {
-            if (b >= n_c) break;
-            const float w = bilateral_weight(i, -rad_c + b * inc_c, rp[b], T.rc, ss, sc);
-            const float wr = w * rp[b];
-            tcp[2 * (c * n_c + b)] = w; tcp[2 * (c * n_c + b) + 1] = wr;
-            r_ref = r_ref + wr;
-            r_rr = __builtin_fmaf(wr, rp[b], r_rr);
-            r_w = r_w + w;
-          }
-          float* rs3 = pb + WC::RSUM + 3 * c;
-          rs3[0] = r_ref; rs3[1] = r_rr; rs3[2] = r_w;
-        }
-      } else if (c >= 8) {
-        const int k = c - 7;
-        const short2 np = nbg[k];
-        if (!(np.x == -1 || np.y == -1)) {
-          float rp[9];
-#pragma unroll
-          for (int t = 0; t < 9; ++t) rp[t] = ref_texel(B.ref, W, Hh, np.x - rad_n + (t / 3) * inc_n, np.y - rad_n + (t % 3) * inc_n);
-          float* tp = tnp + (k - 1) * 18;
-          float a_ref = 0, a_rr = 0, a_w = 0;
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            float r_ref = 0, r_rr = 0, r_w = 0;
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-              const float w = bilateral_weight(-rad_n + a * inc_n, -rad_n + b * inc_n, rp[a * 3 + b], T.rc, ss, sc);
-              const float wr = w * rp[a * 3 + b];
-              tp[2 * (a * 3 + b)] = w; tp[2 * (a * 3 + b) + 1] = wr;
-              r_ref = r_ref + wr;
-              r_rr = __builtin_fmaf(wr, rp[a * 3 + b], r_rr);
-              r_w = r_w + w;
-            }
-            a_ref += r_ref; a_rr += r_rr; a_w += r_w;
-          }
-          ncc_pre(a_ref, a_rr, a_w, sums[3 * k], sums[3 * k + 1], sums[3 * k + 2]);
-        }
-      }
-    }
-    const int ntc = tab_c && !rows1 ? n_c * n_c : 0, ntn = tab_n && !rows1 ? n_n * n_n : 0;
-    for (int t = c; t < ntc + 8 * ntn; t += C) {
-      int k, tt, n, rad, inc;
-      if (t < ntc) { k = 0; tt = t; n = n_c; rad = rad_c; inc = inc_c; }
-      else { k = 1 + (t - ntc) / ntn; tt = (t - ntc) % ntn; n = n_n; rad = rad_n; inc = inc_n; }
-      const short2 np = nbg[k];
-      if (np.x == -1 || np.y == -1) continue;
-      const int i = -rad + (tt / n) * inc, j = -rad + (tt % n) * inc;
-      const float rp = ref_texel(B.ref, W, Hh, np.x + i, np.y + j);
-      const float w = bilateral_weight(i, j, rp, T.rc, ss, sc);
-      float* dst = k == 0 ? tcp + 2 * tt : tnp + 2 * ((k - 1) * 9 + tt);
-      dst[0] = w; dst[1] = w * rp;
-    }
-    for (int i = c; i < 8; i += C) {
-      const short2 np = nbg[i + 1];
-      const bool fl = !(np.x == -1 || np.y == -1) && B.weak[np.x + np.y * W] == DPE_STRONG;
-      misc[WC::M_FLAGS + i] = fl ? 1 : 0;
-      if (fl) cpl[i] = B.planes[np.x + np.y * W];
-      else for (int v = 0; v < nv; ++v) cost[i * nv + v] = (i == 0 && v == 0) ? 2.0f : 0.0f;
-    }
+    if (fast_old) patch_lds_build<C>(me.pw(), pc, B, x, y, c);
+    weak_neighbours(me, c, C, pc, B, nbg);
+    if (rows1) weak_tables_by_rows(me, c, pc, B, nbg, g);
+    else weak_tables_by_taps(me, c, C, pc, B, nbg, g);
+    weak_candidate_rows(me, c, C, pc, B, nbg);
   }
   wave_sync();
   PHASE(0);
-  // union box of the neighbour patches (k = 1..8) for the one-check fast path of ncc_new_tab
-  T.nb3 = false;
-  if (active && T.tab_n && T.n_n == 3) {
-    int x0 = 0x7FFFFFFF, x1 = -0x7FFFFFFF, y0 = 0x7FFFFFFF, y1 = -0x7FFFFFFF;
-    for (int k = 1; k < DPE_NEIGHBOUR_NUM; ++k) {
-      const short2 np = nbl[k];
-      if (np.x == -1 || np.y == -1) continue;
-      x0 = min(x0, (int)np.x); x1 = max(x1, (int)np.x); y0 = min(y0, (int)np.y); y1 = max(y1, (int)np.y);
-    }
-    if (x0 <= x1) {
-      T.nb3 = true;
-      T.nbox[0] = (float)(x0 - T.rad_n); T.nbox[1] = (float)(x1 + T.rad_n);
-      T.nbox[2] = (float)(y0 - T.rad_n); T.nbox[3] = (float)(y1 + T.rad_n);
-    }
-  }
-  // ---- phase 1b: reference sums of every tabulated patch (tap order of patch_ncc_generic)
+  // ---- phase 1b: the header, the reference sums of every tabulated patch, the alias rows
   if (active) {
-    if (c == C - 2) {
-      misc[WC::M_RADC] = T.rad_c; misc[WC::M_INCC] = T.inc_c; misc[WC::M_NC] = T.n_c; misc[WC::M_NB3] = T.nb3 ? 1 : 0;
-      pb[WC::NBOX_A] = T.nbox[0]; pb[WC::NBOX_A + 1] = T.nbox[1]; pb[WC::NBOX_A + 2] = T.nbox[2]; pb[WC::NBOX_B] = T.nbox[3];
-      pb[WC::RC] = T.rc;
-    }
-    if (rows1 && c == 0) {   // the centre patch's row sums in row order
-      const short2 np = nbl[0];
-      if (!(np.x == -1 || np.y == -1)) {
-        float a_ref = 0, a_rr = 0, a_w = 0;
-        for (int a = 0; a < n_c; ++a) {
-          const float* rs3 = pb + WC::RSUM + 3 * a;
-          a_ref += rs3[0]; a_rr += rs3[1]; a_w += rs3[2];
-        }
-        ncc_pre(a_ref, a_rr, a_w, sums[0], sums[1], sums[2]);
-      }
-    }
-    for (int k = c; k < 9; k += C) {
-      const short2 np = nbl[k];
-      if (rows1 || np.x == -1 || np.y == -1 || !(k == 0 ? tab_c : tab_n)) continue;
-      const int n = k == 0 ? n_c : n_n, rad = k == 0 ? rad_c : rad_n, inc = k == 0 ? inc_c : inc_n;
-      const float* tp = k == 0 ? tcp : tnp + (k - 1) * 18;
-      float a_ref = 0, a_rr = 0, a_w = 0;
-      for (int a = 0; a < n; ++a) {
-        float r_ref = 0, r_rr = 0, r_w = 0;
-        for (int b = 0; b < n; ++b) {
-          const float rp = ref_texel(B.ref, W, Hh, np.x - rad + a * inc, np.y - rad + b * inc);
-          const float w = tp[2 * (a * n + b)], wr = tp[2 * (a * n + b) + 1];
-          r_ref = r_ref + wr;
-          r_rr = __builtin_fmaf(wr, rp, r_rr);
-          r_w = r_w + w;
-        }
-        a_ref += r_ref; a_rr += r_rr; a_w += r_w;
-      }
-      ncc_pre(a_ref, a_rr, a_w, sums[3 * k], sums[3 * k + 1], sums[3 * k + 2]);
-    }
-    if (c == C - 1 && fast_old) patch_lds_pre(pw, osum[0], osum[1], osum[2]);
-    // bitwise-identical neighbour planes share one cost vector: alias = first earlier flagged row
-    // with the same plane (lanes 8..15; lanes 0..8 build the sums above)
-    for (int i = c - 8; i >= 0 && i < 8; i += C) {
-      int a = i;
-      if (misc[WC::M_FLAGS + i]) {
-        const float4 me = cpl[i];
-        for (int t = 0; t < i; ++t)
-          if (misc[WC::M_FLAGS + t] && __float_as_uint(cpl[t].x) == __float_as_uint(me.x) &&
-              __float_as_uint(cpl[t].y) == __float_as_uint(me.y) && __float_as_uint(cpl[t].z) == __float_as_uint(me.z) &&
-              __float_as_uint(cpl[t].w) == __float_as_uint(me.w)) { a = t; break; }
-      }
-      alias[i] = a;
-    }
+    if (c == C - 2) weak_header(me, g);
+    if (!rows1) weak_table_sums(me, c, C, pc, B, g);
+    else if (c == 0) weak_centre_sums(me, g.n_c);
+    if (c == C - 1 && fast_old) { float* os = me.osum(); patch_lds_pre(me.pw(), os[0], os[1], os[2]); }
+    weak_alias_rows(me, c, C);
   }
   wave_sync();
   PHASE(1);
   // ---- phase 2: candidate cost vectors, jobs (unique flagged neighbour plane, view)
   if (active && c == 0) {
     uint32_t um = 0;
-    for (int i = 0; i < 8; ++i) if (misc[WC::M_FLAGS + i] && alias[i] == i) um |= 1u << i;
-    misc[WC::M_CMASK] = (int)um;
-    misc[WC::M_POOL] = __builtin_popcount(um);
+    for (int i = 0; i < 8; ++i) if (me.flags()[i] && me.alias()[i] == i) um |= 1u << i;
+    me.cmask() = (int)um;
+    me.pool_jobs() = __builtin_popcount(um);
   }
-  if (!active && c == 0) misc[WC::M_POOL] = 0;
-  pool_sync();
+  if (!active && c == 0) me.pool_jobs() = 0;
+  __syncthreads();
   {
     const int Sj = pool_total();
     int q, r;
     pool_stat_g(2, Sj * nv);
     // view-major: the lanes of one round gather from the same source images
-    for (int j = pl_lane; j < Sj * nv; j += pl_n) {
+    for (int j = threadIdx.x; j < Sj * nv; j += blockDim.x) {
       pool_decode(j % Sj, q, r);
       const int v = j / Sj + 1;
-      float* qb = pix(q);
-      uint32_t m = (uint32_t)((const int*)(qb + WC::MISC))[WC::M_CMASK];
+      const WeakPixel px = pix(q);
+      uint32_t m = (uint32_t)px.cmask();
       for (; r > 0; --r) m &= m - 1;
       const int i = __builtin_ctz(m);
-      const int cq = list[pbase + q];
-      (qb + WC::cost(nv))[i * nv + v - 1] = ncc_new_tab<U8>(pc, B, tab_of(q), cq % W, cq / W, v, ((const float4*)(qb + WC::CPL))[i]);
+      const int cq = list[wgbase + q];
+      px.cost()[i * nv + v - 1] = ncc_new_tab<U8>(pc, B, px.tab(g), cq % W, cq / W, v, px.cpl()[i]);
     }
   }
-  pool_sync();
+  __syncthreads();
   PHASE(2);
   if (active)
     for (int i = c; i < 8; i += C)
-      if (misc[WC::M_FLAGS + i] && alias[i] != i)
-        for (int v = 0; v < nv; ++v) cost[i * nv + v] = cost[alias[i] * nv + v];
+      if (me.flags()[i] && me.alias()[i] != i)
+        for (int v = 0; v < nv; ++v) me.cost()[i * nv + v] = me.cost()[me.alias()[i] * nv + v];
   wave_sync();
   PHASE(3);
   // ---- phase 3: per-view probabilities with the deformable-neighbour priors (DPE.cu:1768-1790)
-  const float cost_threshold = (float)(0.8 * (double)d_expf((float)(iter * iter) / (-90.0f)));
-  if (active) {
-    auto cst = [&](int j, int i) -> float { return cost[j * nv + i]; };
-    for (int v = c; v < nv; v += C) {
-      float prior = 0.0f;
-      for (int i = 0; i < 8; ++i) {
-        const short2 np = nbl[i + 1];
-        if (np.x == -1 || np.y == -1) continue;
-        prior += isSet(nsv[i + 1], v) == 1 ? 0.9f : 0.1f;
-      }
-      sp[v] = view_prob_raw(cst, v, cost_threshold) * prior;
-    }
-  }
+  if (active) weak_view_probs(me, c, C, iter);
   wave_sync();
   PHASE(4);
   Rng rs;
   rng_init(rs, (uint32_t)center, pc.seed32, STREAM_ITER_BASE + 4 * iter + 2, pc.salt);
-  view_sample_coop(sp, (int*)hv, nv, c, C, active, rs, vwl, B.vw + (size_t)center * DPE_MAX_IMAGES);
+  view_sample_coop(me.sp(), me.sample_counts(), nv, c, C, active, rs, me.vwl(), B.vw + (size_t)center * DPE_MAX_IMAGES);
   uint32_t tsv = 0; float wnorm = 0.0f;
   if (active && c == 0) {
     rng_seek(rs, 15);
     int ns = 0;
-    for (int i = 0; i < nv; ++i) if (vwl[i] > 0) { setBit(tsv, i); wnorm += vwl[i]; sel_list[ns++] = i; }
-    misc[WC::M_NSEL] = ns;
-    misc[WC::M_WNORM] = __float_as_int(wnorm);
+    for (int i = 0; i < nv; ++i) if (me.vwl()[i] > 0) { setBit(tsv, i); wnorm += me.vwl()[i]; me.sel_list()[ns++] = i; }
+    me.nsel() = ns;
+    me.set_wnorm(wnorm);
     const float4 f6 = B.fit_plane[center];
-    hyp[6] = f6;
-    misc[WC::M_POOL] = ((f6.x == 0 && f6.y == 0 && f6.z == 0) ? 1 : 2) * ns;   // current (+ fit) plane jobs
+    me.fit_plane() = f6;
+    me.pool_jobs() = ((f6.x == 0 && f6.y == 0 && f6.z == 0) ? 1 : 2) * ns;   // current (+ fit) plane jobs
   }
-  if (!active && c == 0) misc[WC::M_POOL] = 0;
-  pool_sync();
+  if (!active && c == 0) me.pool_jobs() = 0;
+  __syncthreads();
   PHASE(5);
-  const int nsel = active ? misc[WC::M_NSEL] : 0;
-  const float wn = active ? __int_as_float(misc[WC::M_WNORM]) : 1.0f;
+  const int nsel = active ? me.nsel() : 0;
+  const float wn = active ? me.wnorm() : 1.0f;
   const float4 cur = active ? B.planes[center] : make_float4(0, 0, 0, 1);
   const float4 fp = active ? B.fit_plane[center] : make_float4(0, 0, 0, 0);
   const bool has_fit = !(fp.x == 0 && fp.y == 0 && fp.z == 0);
-  // ---- phase 4: current plane and fit plane over the selected views; final candidate costs
-  // pixel q's hyp_cost term (DPE.cu:1140-1150) (view v, plane pl) into its hv row
-  auto hyp_val_q = [&](int q, int v, const float4& pl) __attribute__((always_inline)) -> float {
-    const int cq = list[pbase + q];
+  // pixel q's hyp_cost term (DPE.cu:1140-1150) of plane pl in view v.  Its two pools below are two
+  // loops: as one loop over a plane functor they cost the f32-texel kernel 16 B/lane of scratch.
+  auto hyp_val_q = [&](const WeakPixel& px, int q, int v, const float4& pl) __attribute__((always_inline)) -> float {
+    const int cq = list[wgbase + q];
     const int qx = cq % W, qy = cq / W;
-    const float cn = ncc_new_tab<U8>(pc, B, tab_of(q), qx, qy, v, pl);
+    const float cn = ncc_new_tab<U8>(pc, B, px.tab(g), qx, qy, v, pl);
     return geom ? cn + gf * geom_cost(pc, B, qx, qy, v, pl) : cn;
   };
+  // ---- phase 4: current plane and fit plane over the selected views; final candidate costs
   {
     const int tot = pool_total();
     pool_stat_g(3, tot);
     int q, r;
-    for (int j = pl_lane; j < tot; j += pl_n) {
+    for (int j = threadIdx.x; j < tot; j += blockDim.x) {
       pool_decode(j, q, r);
-      float* qb = pix(q);
-      const int ns = ((const int*)(qb + WC::MISC))[WC::M_NSEL];
+      const WeakPixel px = pix(q);
+      const int ns = px.nsel();
       const int h = r / ns, k = r % ns;
-      const int v = ((const int*)(qb + WC::sel(nv)))[k] + 1;
-      (qb + WC::hv(nv))[h * nv + k] = hyp_val_q(q, v, h ? ((const float4*)(qb + WC::HYP))[6] : B.planes[list[pbase + q]]);
+      const int v = px.sel_list()[k] + 1;
+      px.hv(h)[k] = hyp_val_q(px, q, v, h ? px.fit_plane() : B.planes[list[wgbase + q]]);
     }
   }
   PHASE(12);   // (phase 6 from here: the final candidate costs)
-  if (active) {
-    for (int i = c; i < 8; i += C) {
-      const bool fl = misc[WC::M_FLAGS + i] != 0;
-      const float3 fwi = (geom && fl) ? geom_point(pc, x, y, cpl[i]) : make_float3(0.0f, 0.0f, 0.0f);
-      float f = 0.0f;
-      for (int j = 0; j < nv; ++j) {
-        const int w = vwl[j];
-        if (w > 0) {
-          if (geom) {
-            if (fl) f += w * (cost[i * nv + j] + gf * geom_cost_at(pc, B, x, y, j + 1, fwi));
-            else f += w * (cost[i * nv + j] + gf * 3.0f);
-          } else {
-            f += w * cost[i * nv + j];
-          }
-        }
-      }
-      fc[i] = f / wn;
-    }
-  }
-  pool_sync();   // the current / fit-plane values of every pool pixel are in
+  if (active)
+    for (int i = c; i < 8; i += C) weak_final_cost(me, i, pc, B, x, y, wn);
+  __syncthreads();   // the current / fit-plane values of every pool pixel are in
   PHASE(6);
   // ---- serial: propagation acceptance, fit plane, refinement hypotheses (DPE.cu:1792-1843, 1120-1170)
   float cost_now = 0.0f, cost_written = 0.0f, depth_now = 0.0f;
   float4 pnow = cur;
   const float dmin = pc.P.depth_min, dmax = pc.P.depth_max;
-  const float pert = (float)(0.02f * 3.14159265358979323846);
-  // lanes 1..4 evaluate the refinement draws (refine_draws: stream words 15.. after the view
-  // sampling) while lane 0 runs the acceptance; lane 0 then finishes the hypotheses from them
-  float* rnd = pb + WC::RND;
-  if (active && has_fit && c >= 1 && c <= 4) {
-    const RefineDraws d = refine_draws(rs, 15u);
-    if (c == 1) { rnd[0] = d.u_depth; rnd[1] = d.n[0]; rnd[2] = d.n[1]; rnd[3] = d.n[2]; rnd[4] = d.u_pert; }
-    else refine_angle(rs, d.w_angles, c - 2, pert, &rnd[5 + 2 * (c - 2)], &rnd[6 + 2 * (c - 2)]);
-  }
+  // the cost of the plane whose values are in row `row` of hv
+  auto row_cost = [&](int row) {
+    const float* hv = me.hv(row);
+    return sel_weighted_cost(me.vwl(), me.sel_list(), nsel, wnorm, [&](int k, int) { return hv[k]; });
+  };
+  // lanes 1..4 evaluate the refinement draws while lane 0 runs the acceptance; lane 0 then finishes
+  // the hypotheses from them
+  if (active && has_fit && c >= 1 && c <= 4) refine_draws_lane(rs, c, me.rnd());
   if (active && c == 0) {
+    const float* fc = me.fc();
     int mi = 0; float mcost = fc[0];
     for (int i = 1; i < 8; ++i) if (fc[i] <= mcost) { mcost = fc[i]; mi = i; }
-    for (int k = 0; k < nsel; ++k) cost_now += vwl[sel_list[k]] * hv[k];
-    cost_now /= wnorm;
+    cost_now = row_cost(0);
     cost_written = cost_now;
     depth_now = depth_from_plane(c0, cur, x, y);
-    if (misc[WC::M_FLAGS + mi]) {
-      const float4 cand_pl = cpl[mi];
-      const float db = depth_from_plane(c0, cand_pl, x, y);
-      if (db >= dmin && db <= dmax && fc[mi] < cost_now) {
-        depth_now = db; pnow = cand_pl; cost_now = fc[mi]; B.sel[center] = tsv;
-      }
+    if (me.flags()[mi]) {
+      const float4 cand_pl = me.cpl()[mi];
+      if (accept_if_better(cand_pl, depth_from_plane(c0, cand_pl, x, y), fc[mi], dmin, dmax, depth_now, pnow, cost_now))
+        B.sel[center] = tsv;
     }
     if (has_fit) {
-      float tc = 0.0f;
-      for (int k = 0; k < nsel; ++k) tc += vwl[sel_list[k]] * hv[nv + k];
-      tc /= wnorm;
-      const float db = depth_from_plane(c0, fp, x, y);
-      if (db >= dmin && db <= dmax && tc < cost_now) { depth_now = db; pnow = fp; cost_now = tc; }
+      const float tc = row_cost(1);
+      accept_if_better(fp, depth_from_plane(c0, fp, x, y), tc, dmin, dmax, depth_now, pnow, cost_now);
     }
   }
   wave_sync();
-  if (active && c == 0 && has_fit) {
-    const float depth_rand = rnd[0] * (dmax - dmin) + dmin;
-    const float4 prand = random_normal_from(c0, x, y, rnd + 1, depth_now);
-    const float dminp = (1 - 0.02f) * depth_now, dmaxp = (1 + 0.02f) * depth_now;
-    const float depth_perturbed = rnd[4] * (dmaxp - dminp) + dminp;
-    const float4 ppert = perturbed_normal_from(c0, x, y, pnow, rnd + 5);
-    float4 h0 = pnow, h1 = prand, h2 = prand, h3 = ppert, h4 = pnow;
-    h0.w = dist2origin(c0, x, y, depth_rand, h0);
-    h1.w = dist2origin(c0, x, y, depth_now, h1);
-    h2.w = dist2origin(c0, x, y, depth_rand, h2);
-    h3.w = dist2origin(c0, x, y, depth_now, h3);
-    h4.w = dist2origin(c0, x, y, depth_perturbed, h4);
-    hyp[0] = h0; hyp[1] = h1; hyp[2] = h2; hyp[3] = h3; hyp[4] = h4;
-  }
-  if (c == 0) misc[WC::M_POOL] = active && has_fit ? 5 * nsel : 0;
-  pool_sync();
+  if (active && c == 0 && has_fit) refine_hypotheses(c0, x, y, dmin, dmax, pnow, depth_now, me.rnd(), me.hyp());
+  if (c == 0) me.pool_jobs() = active && has_fit ? 5 * nsel : 0;
+  __syncthreads();
   PHASE(7);
   // ---- phase 5: refinement NCCs, jobs (hypothesis, selected view)
   {
     const int tot = pool_total();
     pool_stat_g(4, tot);
     int q, r;
-    for (int j = pl_lane; j < tot; j += pl_n) {
+    for (int j = threadIdx.x; j < tot; j += blockDim.x) {
       pool_decode(j, q, r);
-      float* qb = pix(q);
-      const int ns = ((const int*)(qb + WC::MISC))[WC::M_NSEL];
+      const WeakPixel px = pix(q);
+      const int ns = px.nsel();
       const int h = r / ns, k = r % ns;
-      const int v = ((const int*)(qb + WC::sel(nv)))[k] + 1;
-      (qb + WC::hv(nv))[(2 + h) * nv + k] = hyp_val_q(q, v, ((const float4*)(qb + WC::HYP))[h]);
+      const int v = px.sel_list()[k] + 1;
+      px.hv(2 + h)[k] = hyp_val_q(px, q, v, px.hyp()[h]);
     }
   }
-  pool_sync();
+  __syncthreads();
   PHASE(8);
   // ---- serial: sequential acceptance + write-back (DPE.cu:1190-1207, 1831-1843)
   if (active && c == 0) {
     if (has_fit) {
       for (int h = 0; h < 5; ++h) {
-        const float4 tp = hyp[h];
-        float tc = 0.0f;
-        for (int k = 0; k < nsel; ++k) tc += vwl[sel_list[k]] * hv[(2 + h) * nv + k];
-        tc /= wnorm;
-        const float db = depth_from_plane(c0, tp, x, y);
-        if (db >= dmin && db <= dmax && tc < cost_now) { depth_now = db; pnow = tp; cost_now = tc; }
+        const float4 tp = me.hyp()[h];
+        const float tc = row_cost(2 + h);
+        accept_if_better(tp, depth_from_plane(c0, tp, x, y), tc, dmin, dmax, depth_now, pnow, cost_now);
       }
     }
     float4 fin = cur;
@@ -1541,32 +1618,28 @@ __global__ void __launch_bounds__(256, kTapWaves) k_weak_coop(const PassConst* _
       fin = pnow;
       B.planes[center] = pnow;
     }
-    hyp[5] = fin;
+    me.final_plane() = fin;
   }
-  if (c == 0) misc[WC::M_POOL] = active ? nsel : 0;
-  pool_sync();
+  if (c == 0) me.pool_jobs() = active ? nsel : 0;
+  __syncthreads();
   PHASE(9);
   // ---- phase 6: the stored cost is the Old NCC of the final plane (DPE.cu:1845-1861)
   {
     const int tot = pool_total();
     pool_stat_g(5, tot);
     int q, r;
-    for (int j = pl_lane; j < tot; j += pl_n) {
+    for (int j = threadIdx.x; j < tot; j += blockDim.x) {
       pool_decode(j, q, r);
-      float* qb = pix(q);
-      const int cq = list[pbase + q];
-      const int v = ((const int*)(qb + WC::sel(nv)))[r] + 1;
-      (qb + WC::hv(nv))[r] = ncc_old_any<U8>(fast_old, qb + WC::PW, qb[WC::OSUM], qb[WC::OSUM + 1], qb[WC::OSUM + 2], cq % W,
-                                                   cq / W, pc, B, v, ((const float4*)(qb + WC::HYP))[5]);
+      const WeakPixel px = pix(q);
+      const int cq = list[wgbase + q];
+      const int v = px.sel_list()[r] + 1;
+      const float* os = px.osum();
+      px.hv(0)[r] = ncc_old_any<U8>(fast_old, px.pw(), os[0], os[1], os[2], cq % W, cq / W, pc, B, v, px.final_plane());
     }
   }
-  pool_sync();
+  __syncthreads();
   PHASE(10);
-  if (active && c == 0) {
-    float c2 = 0.0f;
-    for (int k = 0; k < nsel; ++k) c2 += vwl[sel_list[k]] * hv[k];
-    B.costs[center] = c2 / wnorm;
-  }
+  if (active && c == 0) B.costs[center] = row_cost(0);
   PHASE(11);
   PHASE_END(1);
 }

@@ -6,7 +6,9 @@ CPU oracle's bit for bit: the oracle keeps the per-pixel, one-thread form of all
 
 The view counts 2..10 give the job pools last rounds of many sizes and the view ballots many fill
 levels (10 images = 9 source views: more views than the 8 lanes an ACMH pixel has), 57x43 leaves
-ragged waves and rows, and both candidate schemes run (edge: 16 lanes per pixel, ACMH: 8)."""
+ragged waves and rows, and both candidate schemes run (edge: 16 lanes per pixel, ACMH: 8).  The f32
+cases (images that are neither 8-bit nor quarter-integer) run the f32-texel instantiations, where the
+strong sweep builds its slot list and refinement hypotheses on one lane and its tails stay narrow."""
 import numpy as np
 import pytest
 
@@ -50,18 +52,26 @@ def _assert_same(g, o, what):
             pytest.fail(f"{what}: {k} differs at {len(ys)} pixels, first ({ys[0]}, {xs[0]})")
 
 
-def _run(ctx, W, H, N, p, what):
+def _run(ctx, W, H, N, p, what, tex="u8"):
     sc = synthetic.make_scene(W, H, N)
+    if tex == "f32":                     # grey levels off the 1/4 grid, as test_gpu_non_integer_images makes them
+        sc["images"] = [(im * np.float32(0.73) + np.float32(0.31)).astype(np.float32) for im in sc["images"]]
     st = synthetic.gt_state(sc, seed=W + H)
     inp = synthetic.pass_input(sc, p, depths=synthetic.src_depths(sc), seed=W * 7 + N)
     _assert_same(ctx.run(inp, st), oracle.run_pass(inp, st), what)
+    if tex == "f32":
+        assert ctx.last_stat(_abi.DPE_STAT_TEX_CLASS) == 0, f"{what}: not the f32-texel kernels"
 
 
-@pytest.mark.parametrize("N", [2, 3, 4, 6, 10])
-@pytest.mark.parametrize("W,H", [(64, 48), (57, 43)])
-@pytest.mark.parametrize("kind", ["refine_iter", "acmh_geom"])
-def test_setup_paths_match_oracle(ctx, kind, W, H, N):
-    _run(ctx, W, H, N, _params(kind), f"{W}x{H}x{N} {kind}")
+_CASES = [pytest.param(kind, W, H, N, "u8", id=f"{kind}-{W}-{H}-{N}")
+          for kind in ("refine_iter", "acmh_geom") for W, H in ((64, 48), (57, 43)) for N in (2, 3, 4, 6, 10)]
+_CASES += [pytest.param(kind, 57, 43, N, "f32", id=f"{kind}-57-43-{N}-f32")
+           for kind in ("refine_iter", "acmh_geom") for N in (3, 10)]
+
+
+@pytest.mark.parametrize("kind,W,H,N,tex", _CASES)
+def test_setup_paths_match_oracle(ctx, kind, W, H, N, tex):
+    _run(ctx, W, H, N, _params(kind), f"{W}x{H}x{N} {kind} {tex}", tex)
 
 
 def test_spatial_table_follows_sigma(ctx):
