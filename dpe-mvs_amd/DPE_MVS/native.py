@@ -27,6 +27,7 @@ EXPORTED = [
     "dpe_state_render", "dpe_state_render_jpeg_blocks", "dpe_state_render_wait", "dpe_viz_render_arrays",
     "dpe_jpeg_blocks_device", "dpe_viz_launches", "dpe_live_device_bytes",
     "dpe_state_point_cloud", "dpe_state_point_cloud_wait", "dpe_point_cloud_arrays", "dpe_points_launches",
+    "dpe_fusion_consistency", "dpe_consistency_launches",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -74,6 +75,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_fusion_stage.restype = C.c_int
     lib.dpe_fusion_candidates.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.dpe_fusion_candidates.restype = C.c_int
+    lib.dpe_fusion_consistency.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+    lib.dpe_fusion_consistency.restype = C.c_int
+    lib.dpe_consistency_launches.argtypes = []
+    lib.dpe_consistency_launches.restype = C.c_longlong
     lib.dpe_fusion_tat_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.dpe_fusion_tat_begin.restype = C.c_int
     lib.dpe_fusion_tat_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -254,6 +259,28 @@ class PatchMatchContext:
         return {name: {"ncc": int(buf[4 * i]), "taps": int(buf[4 * i + 1]), "geom": int(buf[4 * i + 2]),
                        "launches": int(buf[4 * i + 3])} for i, name in enumerate(CLASSES)}
 
+    def fusion_stage(self, views):
+        """Uploads views = [(depth f32 [H, W], normal f32 [H, W, 3], DpeCamera)] (dpe_fusion_stage); they stay
+        resident for fusion_consistency."""
+        arr, keep = fusion_view_array(views)
+        _check(_LIB.dpe_fusion_stage(self._ctx, arr, len(views)), "dpe_fusion_stage")
+        self._staged_sizes = [(v.width, v.height) for v in arr]
+
+    def fusion_consistency(self, ref: int, src, dot_threshold: float, min_views: int, want_count: bool = True,
+                           want_depth: bool = True) -> tuple:
+        """The consistency maps of staged view `ref` against the staged views `src` on the GPU
+        (dpe_fusion_consistency): (count u8 [H, W], depth_filtered f32 [H, W]); an output that is not
+        wanted is passed as NULL and returned as None.  `dot_threshold`: pipeline.consistency_dot_threshold()."""
+        sizes = getattr(self, "_staged_sizes", [])
+        w, h = sizes[ref] if 0 <= ref < len(sizes) else (1, 1)
+        s = np.ascontiguousarray(src, np.int32)
+        count = np.empty((h, w), np.uint8) if want_count else None
+        depth = np.empty((h, w), np.float32) if want_depth else None
+        _check(_LIB.dpe_fusion_consistency(self._ctx, int(ref), s.ctypes.data if len(s) else None, len(s), float(dot_threshold),
+                                           int(min_views), None if count is None else count.ctypes.data,
+                                           None if depth is None else depth.ctypes.data), "dpe_fusion_consistency")
+        return count, depth
+
     def fusion_candidates(self, views, ref: int, src) -> tuple:
         """RunFusion's projection tests on the GPU (dpe_fusion_stage + dpe_fusion_candidates) for
         views = [(depth, normal, DpeCamera)]: (idx int32 [L*ns], val f32 [L*ns*3])."""
@@ -393,6 +420,11 @@ def points_launches() -> int:
     return int(_LIB.dpe_points_launches())
 
 
+def consistency_launches() -> int:
+    """Kernels of the consistency maps launched by this process so far."""
+    return int(_LIB.dpe_consistency_launches())
+
+
 def live_device_bytes() -> int:
     """Device bytes the library's contexts in this process hold at the moment."""
     return int(_LIB.dpe_live_device_bytes())
@@ -416,4 +448,4 @@ def param_struct(**overrides) -> _abi.DpePatchMatchParams:
 
 Context = PatchMatchContext
 
-__all__ = ["PatchMatchContext", "Context", "viz_launches", "points_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]
+__all__ = ["PatchMatchContext", "Context", "viz_launches", "points_launches", "consistency_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]

@@ -47,6 +47,7 @@ class DpePipelineOptions(C.Structure):
         ("abort_collectives", C.c_void_p), ("abort_user", C.c_void_p),
         ("fusion_mode", C.c_int),
         ("point_cloud", C.c_int),
+        ("consistency", C.c_int),
     ]
 
 
@@ -114,6 +115,9 @@ def lib() -> C.CDLL:
         L.dpe_host_rescale_image_and_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                         C.POINTER(_abi.DpeCamera), C.c_void_p]
         L.dpe_host_write_point_cloud.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+        L.dpe_host_consistency.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.dpe_host_consistency_dot_threshold.argtypes = [C.POINTER(C.c_float)]
+        L.dpe_host_consistency_angle_test.argtypes = [C.c_float]
         _lib = L
     return _lib
 
@@ -327,6 +331,41 @@ def write_point_cloud(path: str, points: np.ndarray) -> None:
         raise PipelineError(f"cannot write {path}")
 
 
+# ------------------------------------------------------------------------------ consistency maps (C++, consistency.cpp)
+def consistency(views, ref: int, src, min_views: int):
+    """The consistency maps of reference view `ref` on the host (dpe_host_consistency): views =
+    [(depth f32 [H, W], normal f32 [H, W, 3], DpeCamera)], src = indices into views.  Returns (count u8 [H, W]:
+    the source views that pass RunFusion's reprojection, depth and angle tests at the pixel, without its masks,
+    depth_filtered f32 [H, W]: the depth where count >= min_views, else 0)."""
+    arr = (_abi.DpeFusionView * len(views))()
+    keep = []
+    for k, (d, n, cam) in enumerate(views):
+        d = np.ascontiguousarray(d, np.float32)
+        n = np.ascontiguousarray(n, np.float32)
+        keep += [d, n]
+        arr[k] = _abi.DpeFusionView(d.shape[1], d.shape[0], cam, d.ctypes.data, n.ctypes.data)
+    s = np.ascontiguousarray(src, np.int32)
+    h, w = (arr[ref].height, arr[ref].width) if 0 <= ref < len(views) else (1, 1)
+    count, filtered = np.empty((h, w), np.uint8), np.empty((h, w), np.float32)
+    if lib().dpe_host_consistency(arr, len(views), int(ref), s.ctypes.data, len(s), int(min_views), count.ctypes.data,
+                                  filtered.ctypes.data) != 0:
+        raise PipelineError("consistency: bad argument")
+    return count, filtered
+
+
+def consistency_dot_threshold() -> float:
+    """D: the smallest float dot product in [-1, 1] whose GetAngle is below 0.174533 (the device's angle test)."""
+    D = C.c_float()
+    if lib().dpe_host_consistency_dot_threshold(C.byref(D)) != 0:
+        raise PipelineError("the consistency angle threshold does not verify")
+    return D.value
+
+
+def consistency_angle_test(dot: float) -> bool:
+    """The host loop's angle test: GetAngle(dot) < 0.174533f."""
+    return bool(lib().dpe_host_consistency_angle_test(float(dot)))
+
+
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)
 def _u8(img: np.ndarray) -> np.ndarray:
     a = np.ascontiguousarray(img)
@@ -511,7 +550,7 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
                      edge: bool = False, schedule: str = "reference", dist=None, runner=None,
                      base_seed: int = 0x5EED, keep_intermediate: bool = False, fusion_runner=None,
                      max_iterations: int = 0, photometric_only: bool = False, allgather_device=None,
-                     fusion_mode="eth3d", point_cloud=0) -> int:
+                     fusion_mode="eth3d", point_cloud=0, consistency: int = 0) -> int:
     """RunDPEPipeline (main.cpp:474) through libdpe_host.  `dist`: an initialised torch.distributed
     (one process per GPU; problems split in contiguous blocks, depth maps all-gathered per pass).
     `runner`: (C function pointer, user pointer) of a dpe_pass_runner_fn; default the HIP library.
@@ -524,11 +563,16 @@ def run_dpe_pipeline(dense_folder: str, gpu_index: int = 0, verbose: bool = True
     image at a time on the GPU; with a `fusion_runner` their serial loops on the host), or the integer
     of DpePipelineOptions.fusion_mode.  `point_cloud`: 0 / "off" (the default), 1 / "all" or 2 / "strong":
     every reference image's point_<it>.ply (ExportDepthImagePointCloud) after the last pass of every
-    resolution round; "strong" keeps the STRONG pixels only (main.cpp:464)."""
+    resolution round; "strong" keeps the STRONG pixels only (main.cpp:464).  `consistency`: 0 (the default)
+    off, or min_views 1..255: every reference image's consistency.npy (u8 [H, W]: the source views that pass
+    RunFusion's reprojection, depth and angle tests at the pixel, without its masks and blocks) and
+    depth_filtered.npy (f32 [H, W]: the final depth where that count >= min_views, else 0); on the GPU, or
+    with a `fusion_runner` on host threads; any other value raises PipelineError."""
     o = DpePipelineOptions()
     lib().dpe_pipeline_default_options(C.byref(o))
     o.fusion_mode = _fusion_mode(fusion_mode)
     o.point_cloud = _point_cloud_mode(point_cloud)
+    o.consistency = int(consistency)
     o.gpu_index = gpu_index
     o.verbose, o.fusion, o.viz, o.depth, o.normal, o.weak, o.edge = verbose, fusion, viz, depth, normal, weak, edge
     o.schedule = {"reference": SCHEDULE_REFERENCE, "jacobi": SCHEDULE_JACOBI}[schedule]

@@ -159,7 +159,7 @@ struct EdgeScratch {
   DevArr<short> stab;
 };
 
-// the views of a fusion (dpe_fusion.hip: dpe_fusion_stage / dpe_fusion_candidates)
+// the views of a fusion (dpe_fusion.hip: dpe_fusion_stage / dpe_fusion_candidates / dpe_fusion_consistency)
 struct FusionStage {
   std::vector<DevArr<float>> depth, normal;
   std::vector<FusionViewDev> host;
@@ -168,6 +168,8 @@ struct FusionStage {
   DevArr<int> src;
   DevArr<int32_t> idx;
   DevArr<float> val;
+  DevArr<uint8_t> cons_count;        // dpe_fusion_consistency: the reference view's consistency count
+  DevArr<float> cons_depth;          //   and its filtered depth map
   int n = 0;
 };
 

@@ -1,13 +1,16 @@
 // dpe_fusion.hip -- the fusions of include/dpe_mvs.h on the GPU: dpe_fusion_stage and
 // dpe_fusion_candidates (pass_fusion.h), and the two Tanks-and-Temples fusions dpe_fusion_tat_*
-// (pass_fusion_tat.h) over the staged views.  A unit of libdpe_mvs.so.  The calls use the context's
+// (pass_fusion_tat.h) and the consistency maps dpe_fusion_consistency (pass_consistency.h) over the
+// staged views.  A unit of libdpe_mvs.so.  The calls use the context's
 // stream and synchronise it before they return; the one copy dpe_fusion_tat_image leaves in flight
 // is described with the concurrency contract in dpe_mvs.hip.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <vector>
 
 #include "pass_fusion.h"
 #include "pass_fusion_tat.h"
+#include "pass_consistency.h"
 #include "dpe_entry.h"
 #include "dpe_context.h"
 
@@ -58,6 +61,39 @@ extern "C" int dpe_fusion_candidates(DpeContext* c, int ref, const int* src, int
   HIPC(hipMemcpyAsync(idx, fz.idx.p, L * ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPC(hipMemcpyAsync(val, fz.val.p, L * ns * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
+  return DPE_OK;
+}
+
+static std::atomic<long long> g_consistency_launches{0};
+
+extern "C" long long dpe_consistency_launches(void) { return g_consistency_launches.load(); }
+
+extern "C" int dpe_fusion_consistency(DpeContext* c, int ref, const int* src, int ns, float dot_threshold, int min_views,
+                                      uint8_t* count, float* depth_filtered) {
+  TRY(enter(c, ns >= 0 && (ns == 0 || src), "dpe_fusion_consistency: bad argument"));
+  if (ns > kConsistencyMaxSrc) { g_err = "dpe_fusion_consistency: more than 255 source views"; return DPE_ERR_ARG; }
+  if (min_views < 1 || min_views > 255) { g_err = "dpe_fusion_consistency: min_views outside 1..255"; return DPE_ERR_ARG; }
+  FusionStage& fz = c->fz;
+  if (fz.n < 1) { g_err = "dpe_fusion_consistency: nothing staged"; return DPE_ERR_STATE; }
+  if (ref < 0 || ref >= fz.n) { g_err = "dpe_fusion_consistency: bad reference view"; return DPE_ERR_ARG; }
+  for (int j = 0; j < ns; ++j) {
+    if (src[j] < 0 || src[j] >= fz.n) { g_err = "dpe_fusion_consistency: bad source view"; return DPE_ERR_ARG; }
+    if (src[j] == ref) { g_err = "dpe_fusion_consistency: the reference view is among its sources"; return DPE_ERR_ARG; }
+  }
+  const size_t L = (size_t)fz.host[ref].w * fz.host[ref].h;
+  if (L >= (size_t)1 << 31) { g_err = "dpe_fusion_consistency: view too large"; return DPE_ERR_ARG; }   // the kernel's int pixel index
+  HIPC(host_wait(c));   // the buffers below may grow, and the results are read on the host
+  HIPC(fz.src.ensure(ns > 0 ? ns : 1));
+  HIPC(fz.cons_count.ensure(L));
+  HIPC(fz.cons_depth.ensure(L));
+  if (ns > 0) HIPC(hipMemcpyAsync(fz.src.p, src, ns * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  k_consistency<<<(unsigned)((L + 255) / 256), 256, 0, c->stream>>>(fz.cams.p, fz.views.p, ref, fz.src.p, ns, dot_threshold,
+                                                                   min_views, fz.cons_count.p, fz.cons_depth.p);
+  HIPC(hipGetLastError());
+  g_consistency_launches += 1;
+  if (count) HIPC(hipMemcpyAsync(count, fz.cons_count.p, L, hipMemcpyDeviceToHost, c->stream));
+  if (depth_filtered) HIPC(hipMemcpyAsync(depth_filtered, fz.cons_depth.p, L * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));   // also before the caller's `src` goes out of scope
   return DPE_OK;
 }
 

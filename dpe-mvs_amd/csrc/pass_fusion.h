@@ -16,12 +16,24 @@
 
 namespace dpe {
 
+// The source pixel (src_c, src_r) = (int(x + 0.5f), int(y + 0.5f)) of the projection of X into view S
+// (DPE.cpp:1318-1321), taken only for x + 0.5, y + 0.5 in (-1, size): the in-range test on the float,
+// so NaN / huge projections are rejected the same way as on the reference's host (where they convert
+// to INT_MIN).  False when the projection lies outside.  The one copy of this test: the candidates
+// below, the Tanks-and-Temples hit (pass_fusion_tat.h) and the consistency count (pass_consistency.h).
+__device__ inline bool fz_pixel(const FP3& X, const FusionViewDev& S, const DpeCamera& sc, int& src_c, int& src_r) {
+  float px, py, pd;
+  fz_project(X, sc, px, py, pd);
+  const float fx = px + 0.5f, fy = py + 0.5f;
+  if (!(fx > -1.0f && fx < (float)S.w && fy > -1.0f && fy < (float)S.h)) return false;
+  src_c = (int)fx; src_r = (int)fy;
+  return true;
+}
+
 // idx[p*ns + j]: source pixel (row-major) when the projection of reference pixel p lands inside
 // source view src[j] on a positive depth with reprojection error < 2 and relative depth difference
 // < 0.01, else -1.  val[(p*ns + j)*3 + {0, 1, 2}] = (reprojection error, relative depth difference,
-// normal dot product) of those candidates.  `int(v + 0.5f)` of the reference is taken only for
-// v + 0.5 in (-1, size): the in-range test on the float, so NaN / huge projections are rejected
-// the same way as on the reference's host (where they convert to INT_MIN).
+// normal dot product) of those candidates.
 __global__ void __launch_bounds__(256) k_fusion_candidates(const DpeCamera* __restrict__ cams,
                                                           const FusionViewDev* __restrict__ views, int ref,
                                                           const int* __restrict__ src, int ns,
@@ -47,11 +59,8 @@ __global__ void __launch_bounds__(256) k_fusion_candidates(const DpeCamera* __re
     const int s = src[j];
     const FusionViewDev S = views[s];
     const DpeCamera& sc = cams[s];
-    float px, py, pd;
-    fz_project(X, sc, px, py, pd);
-    const float fx = px + 0.5f, fy = py + 0.5f;
-    if (fx > -1.0f && fx < (float)S.w && fy > -1.0f && fy < (float)S.h) {
-      const int src_c = (int)fx, src_r = (int)fy;
+    int src_c, src_r;
+    if (fz_pixel(X, S, sc, src_c, src_r)) {
       const int sp = src_r * S.w + src_c;
       const float sd = S.depth[sp];
       if (sd > 0.0f) {

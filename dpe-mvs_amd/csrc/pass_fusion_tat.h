@@ -46,13 +46,11 @@ __device__ inline bool tat_active(const FusionViewDev& R, const uint8_t* block, 
 }
 
 // DPE.cpp:1481-1489: source pixel of the projection when it lies inside the view, is not masked and
-// has a depth; else -1.  The in-range test on the float as in k_fusion_candidates.
+// has a depth; else -1.  The in-range test on the float (fz_pixel).
 __device__ inline int tat_hit(const FP3& X, const FusionViewDev& S, const DpeCamera& sc, const uint8_t* smask) {
-  float px, py, pd;
-  fz_project(X, sc, px, py, pd);
-  const float fx = px + 0.5f, fy = py + 0.5f;
-  if (!(fx > -1.0f && fx < (float)S.w && fy > -1.0f && fy < (float)S.h)) return -1;
-  const int sp = (int)fy * S.w + (int)fx;
+  int src_c, src_r;
+  if (!fz_pixel(X, S, sc, src_c, src_r)) return -1;
+  const int sp = src_r * S.w + src_c;
   if (smask[sp] == 1) return -1;
   if (S.depth[sp] <= 0.0f) return -1;
   return sp;

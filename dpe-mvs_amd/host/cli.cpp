@@ -2,11 +2,14 @@
 // (main.cpp:602-635):
 //
 //     dpe dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge] [fusion_mode] [point_cloud]
+//         [consistency]
 //
 // fusion_mode (an addition: the reference calls RunFusion and has to be rebuilt for the others):
 // eth3d (0, the default), tat_intermediate (1) or tat_advanced (2).
 // point_cloud (an addition: the reference's call is commented out, main.cpp:456-466): off (0, the
 // default), all (1) or strong (2): point_<it>.ply per image after the last pass of every round.
+// consistency (an addition): 0 (off, the default) or min_views 1..255: consistency.npy (how many source
+// views pass RunFusion's three tests at each pixel, without its masks) and depth_filtered.npy per image.
 //
 // One process per GPU: launched under torchrun (or any launcher that sets RANK / WORLD_SIZE /
 // LOCAL_RANK), each rank takes a contiguous block of reference images on GPU LOCAL_RANK and the
@@ -98,7 +101,8 @@ bool rccl_init(Rccl& r, int rank, int world, int device) {
 
 const char* const kUsage =
     "USAGE: DPE dense_folder [gpu_index] [verbose] [viz] [fusion] [depth] [normal] [weak] [edge]"
-    " [fusion_mode: eth3d | tat_intermediate | tat_advanced] [point_cloud: off | all | strong]\n";
+    " [fusion_mode: eth3d | tat_intermediate | tat_advanced] [point_cloud: off | all | strong]"
+    " [consistency: 0 = off | min_views 1..255]\n";
 
 int main(int argc, char** argv) {
   if (argc < 2) {
@@ -129,6 +133,15 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "bad point_cloud '%s'\n%s", argv[11], kUsage);
       return EXIT_FAILURE;
     }
+  }
+  if (argc >= 13) {   // nor this: 0 = off, 1..255 = min_views (the pipeline refuses the rest)
+    char* end = nullptr;
+    const long v = std::strtol(argv[12], &end, 10);
+    if (end == argv[12] || *end != '\0' || v < 0 || v > 255) {
+      std::fprintf(stderr, "bad consistency '%s'\n%s", argv[12], kUsage);
+      return EXIT_FAILURE;
+    }
+    o.consistency = (int)v;
   }
   const char* ws = std::getenv("WORLD_SIZE");
   Rccl rccl;

@@ -24,10 +24,6 @@
 #include <unordered_map>
 
 namespace dpe_host {
-namespace {
-
-const float kAngleBase = 0.06981317007977318f;   // 4 degree (DPE.cpp:1380)
-const float kAngleGrad = 0.05235987755982988f;   // 3 degree (DPE.cpp:1381)
 
 // GetAngle (DPE.cpp:1208-1217) from the dot product
 float get_angle(float dot_product) {
@@ -35,9 +31,6 @@ float get_angle(float dot_product) {
   if (angle != angle) return 0.0f;
   return angle;
 }
-float angle_threshold(int k) { return k * kAngleGrad + kAngleBase; }   // DPE.cpp:1508
-
-struct F3 { float x, y, z; };
 
 F3 world_point(int x, int y, float depth, const DpeCamera& cam) {   // Get3DPointonWorld (DPE.cpp:1170-1194)
   const float zero[3] = {0.0f, 0.0f, 0.0f};
@@ -53,6 +46,13 @@ void project_camera(const F3& X, const DpeCamera& cam, float& px, float& py, flo
   px = (cam.K[0] * tx + cam.K[1] * ty + cam.K[2] * tz) / depth;
   py = (cam.K[3] * tx + cam.K[4] * ty + cam.K[5] * tz) / depth;
 }
+
+namespace {
+
+const float kAngleBase = 0.06981317007977318f;   // 4 degree (DPE.cpp:1380)
+const float kAngleGrad = 0.05235987755982988f;   // 3 degree (DPE.cpp:1381)
+
+float angle_threshold(int k) { return k * kAngleGrad + kAngleBase; }   // DPE.cpp:1508
 
 // The problems as indices into `views`, with the reference's imageIdToindexMap (emplace keeps the
 // first of equal ids, operator[] gives 0 for an unknown one).
@@ -223,19 +223,6 @@ void tat_advanced_serial(std::vector<FusionView>& views, const Plan& pl, std::ve
   }
 }
 
-// floats in value order as unsigned keys (for the bisection below)
-uint32_t key_of(float f) {
-  uint32_t b;
-  std::memcpy(&b, &f, 4);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-float float_of(uint32_t k) {
-  const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-
 // the default path: every image on the device, in order
 bool tat_device(std::vector<FusionView>& views, const Plan& pl, int mode, DpeContext* ctx, std::vector<FusedPoint>& cloud,
                 std::string& err) {
@@ -277,26 +264,44 @@ bool tat_device(std::vector<FusionView>& views, const Plan& pl, int mode, DpeCon
   return ok;
 }
 
+// floats in value order as unsigned keys (for the bisection below)
+uint32_t key_of(float f) {
+  uint32_t b;
+  std::memcpy(&b, &f, 4);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+float float_of(uint32_t k) {
+  const uint32_t b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+  float f;
+  std::memcpy(&f, &b, 4);
+  return f;
+}
 }  // namespace
 
-// D[k], k = 2..n-1: the smallest float x in [-1, 1] with get_angle(x) < angle_threshold(k), found by
-// bisection on the float's bits; exact when acosf is monotonic on [-1, 1], and verified at the result
-// and at its predecessor, so a wrong table is an error, never a result.
+// The smallest float x in [-1, 1] with get_angle(x) < T, found by bisection on the float's bits; exact
+// when acosf is monotonic on [-1, 1], and verified at the result and at its predecessor, so a wrong
+// threshold is an error, never a result.
+DotThreshold angle_dot_threshold(float T, float& D) {
+  auto pass = [T](float x) { return get_angle(x) < T; };
+  if (!pass(1.0f)) return DotThreshold::kNonePasses;
+  if (pass(-1.0f)) { D = -1.0f; return DotThreshold::kOk; }
+  uint32_t lo = key_of(-1.0f), hi = key_of(1.0f);   // pass(lo) false, pass(hi) true
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (pass(float_of(mid))) hi = mid; else lo = mid;
+  }
+  D = float_of(hi);
+  const float prev = std::nextafter(D, -2.0f);
+  return get_angle(D) < T && T <= get_angle(prev) ? DotThreshold::kOk : DotThreshold::kUnverified;
+}
+
+// D[k], k = 2..n-1: angle_dot_threshold of the Intermediate angle threshold at k
 bool tat_thresholds(float* D, int n, std::string& err) {
   for (int k = 0; k < n && k < 2; ++k) D[k] = 0.0f;
   for (int k = 2; k < n; ++k) {
-    const float T = angle_threshold(k);
-    auto pass = [T](float x) { return get_angle(x) < T; };
-    if (!pass(1.0f)) { err = "fusion: no dot product passes the angle test at k = " + std::to_string(k); return false; }
-    if (pass(-1.0f)) { D[k] = -1.0f; continue; }
-    uint32_t lo = key_of(-1.0f), hi = key_of(1.0f);   // pass(lo) false, pass(hi) true
-    while (hi - lo > 1) {
-      const uint32_t mid = lo + (hi - lo) / 2;
-      if (pass(float_of(mid))) hi = mid; else lo = mid;
-    }
-    D[k] = float_of(hi);
-    const float prev = std::nextafter(D[k], -2.0f);
-    if (!(get_angle(D[k]) < T && T <= get_angle(prev))) {
+    const DotThreshold r = angle_dot_threshold(angle_threshold(k), D[k]);
+    if (r == DotThreshold::kNonePasses) { err = "fusion: no dot product passes the angle test at k = " + std::to_string(k); return false; }
+    if (r == DotThreshold::kUnverified) {
       err = "fusion: the angle threshold table does not verify at k = " + std::to_string(k);
       return false;
     }

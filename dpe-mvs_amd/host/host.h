@@ -117,5 +117,22 @@ bool run_fusion_tat(std::vector<FusionView>& views, int mode, DpeContext* ctx, s
                     std::string& err);
 // D[k], k = 2..n-1: smallest dot product in [-1, 1] that passes the Intermediate angle test at k
 bool tat_thresholds(float* D, int n, std::string& err);
+// what every fusion loop is written with (fusion_tat.cpp): Get3DPointonWorld, ProjectCamera and GetAngle
+// from the dot product (DPE.cpp:1170-1217), and the smallest float D in [-1, 1] with get_angle(D) < T
+// (bisection on the float's bits, verified at D and at its predecessor)
+struct F3 { float x, y, z; };
+F3 world_point(int x, int y, float depth, const DpeCamera& cam);
+void project_camera(const F3& X, const DpeCamera& cam, float& px, float& py, float& depth);
+float get_angle(float dot_product);
+enum class DotThreshold { kOk, kNonePasses, kUnverified };
+DotThreshold angle_dot_threshold(float T, float& D);
+// consistency.cpp: the consistency maps (RunFusion's view loop, DPE.cpp:1312-1343, without the masks and
+// the blocks): the serial double loop over reference view `ref` of `views`, src = indices into `views`.
+// count u8 [H][W] and filtered f32 [H][W] may be null.
+void consistency_image(const DpeFusionView* views, int ref, const int* src, int ns, int min_views, uint8_t* count,
+                       float* filtered);
+bool consistency_dot_threshold(float& D, std::string& err);
+// the arguments dpe_host_consistency refuses, as dpe_fusion_consistency does (the message into err)
+bool consistency_args_ok(int n_views, int ref, const int* src, int ns, int min_views, std::string& err);
 
 }  // namespace dpe_host

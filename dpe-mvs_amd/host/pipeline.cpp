@@ -38,6 +38,14 @@
 // pinned buffers that a host thread (PointCloudWriter) encodes and writes while the following passes
 // run; with a runner hook dpe_host_depth_point_cloud's loop runs on the host state.  Same files.
 //
+// consistency = min_views (1..255) writes, for every reference image, consistency.npy (how many source
+// views of its pair.txt line pass RunFusion's reprojection, depth and angle tests at each pixel, without
+// RunFusion's order-dependent masks and without the blocks) and depth_filtered.npy (the final depth where
+// that count reaches min_views).  It reads what fusion reads, the final maps of every image, so the same
+// gather feeds it, and then every rank filters its own images: on the GPU (dpe_fusion_consistency over
+// the staged views, which ETH3D fusion in the same context reuses; 5 bytes per pixel come back), or, with
+// a fusion_runner hook, dpe_host_consistency on host threads.  Same files.  Only cameras are read for it.
+//
 // run() at the end of the file is the table of contents: the phases of a run in order, each a
 // member of PipelineRun.  The rule every phase keeps with several ranks is in rank_group.h.
 #include "host.h"
@@ -77,10 +85,11 @@ enum TimeSlot {
   kTimeExchange,   // (multi-rank) the depth exchanges alone
   kTimePassWork,   // the pass work alone
   kTimeFusion,     // RunFusion alone (rank 0, incl. the normal/weak exchange that feeds it)
+  kTimeConsistency,   // the consistency maps alone (incl. that exchange when there is no fusion)
   kNumTimes
 };
-static_assert(kNumTimes == 8, "include/dpe_host.h documents entries [0]..[7]");
-double g_times[kNumTimes] = {0, 0, 0, 0, 0, 0, 0, 0};
+static_assert(kNumTimes == 9, "include/dpe_host.h documents entries [0]..[8]");
+double g_times[kNumTimes] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Problem {   // main.h:108-118
@@ -248,19 +257,24 @@ int native_runner(void* user, const DpePassInput* in, const DpePassState* st) {
 struct NativeFusion {
   DpeContext* ctx = nullptr;
   bool own = false;
-  const DpeFusionView* staged = nullptr;
+  std::vector<DpeFusionView> staged;   // what the context holds: the same views (sizes, cameras, maps) stage once
   std::string err;   // the library's message of a failed call (run_fusion calls from a worker thread,
                      // and dpe_last_error() is per thread)
   ~NativeFusion() { if (own && ctx) dpe_destroy(ctx); }
+  int stage(const DpeFusionView* views, int n) {
+    static_assert(sizeof(DpeFusionView) == 2 * sizeof(int) + sizeof(DpeCamera) + 2 * sizeof(void*), "compared as bytes");
+    if ((int)staged.size() == n && std::memcmp(staged.data(), views, (size_t)n * sizeof(DpeFusionView)) == 0) return DPE_OK;
+    staged.clear();
+    const int r = dpe_fusion_stage(ctx, views, n);
+    if (r != DPE_OK) { err = dpe_last_error(); return r; }
+    staged.assign(views, views + n);
+    return DPE_OK;
+  }
 };
 int native_fusion(void* user, const DpeFusionView* views, int n, int ref, const int* src, int ns, int32_t* idx,
                   float* val) {
   NativeFusion* f = static_cast<NativeFusion*>(user);
-  if (f->staged != views) {
-    const int r = dpe_fusion_stage(f->ctx, views, n);
-    if (r != DPE_OK) { f->err = dpe_last_error(); return r; }
-    f->staged = views;
-  }
+  if (const int r = f->stage(views, n); r != DPE_OK) return r;
   const int r = dpe_fusion_candidates(f->ctx, ref, src, ns, idx, val);
   if (r != DPE_OK) f->err = dpe_last_error();
   return r;
@@ -389,28 +403,41 @@ bool write_outputs(const Problem& p, const ImageState& s, const DpePipelineOptio
   return true;
 }
 
-// One fusion view: camera, colour image (decode + RescaleImageAndCamera) and block mask of problem
-// `p` at the size of its final state `st`, whose maps the view borrows.
+// The maps of problem `p`'s final state `st` (borrowed) and its camera at their size: ReadCamera, with
+// the intrinsics scaled as RescaleImageAndCamera (DPE.cpp:1123-1144) scales them for a src_w x src_h
+// image.  No image is read: all the consistency maps need of a view.
+bool map_view(const Problem& p, const ImageState& st, int src_w, int src_h, DpeFusionView& view, std::string& err) {
+  DpeCamera cam;
+  if (!read_camera(cam_path(p.dense_folder, p.ref_image_id), cam, err)) return false;
+  if (src_w != st.w || src_h != st.h) scale_intrinsics(cam, st.w / (float)src_w, st.h / (float)src_h);
+  cam.width = st.w; cam.height = st.h;
+  view.width = st.w; view.height = st.h;
+  view.cam = cam;
+  view.depth = st.depth.data();
+  view.normal = st.normal.data();
+  return true;
+}
+
+// One fusion view: map_view, the colour image (decode + RescaleImageAndCamera) and the block mask of
+// problem `p` at the size of its final state `st`.
 bool load_fusion_view(const Problem& p, const ImageState& st, bool use_block, FusionView& v, std::string& err) {
   v.image_id = p.ref_image_id;
   v.src_ids = p.src_image_ids;
-  DpeCamera cam;
-  if (!read_camera(cam_path(p.dense_folder, p.ref_image_id), cam, err)) return false;
   ColorImage img;
   if (!read_bgr(image_path(p.dense_folder, p.ref_image_id), img, err)) return false;
-  if (img.w != st.w || img.h != st.h) resize_bgr_and_camera(img, st.w, st.h, cam, v.bgr);   // RescaleImageAndCamera (DPE.cpp:1123-1144)
-  else v.bgr = std::move(img.bgr);
-  cam.width = st.w; cam.height = st.h;
+  if (!map_view(p, st, img.w, img.h, v.view, err)) return false;
+  if (img.w != st.w || img.h != st.h) {   // RescaleImageAndCamera's image half (map_view has scaled the camera)
+    DpeCamera scratch = v.view.cam;
+    resize_bgr_and_camera(img, st.w, st.h, scratch, v.bgr);
+  } else {
+    v.bgr = std::move(img.bgr);
+  }
   if (use_block) {
     GrayImage b;
     if (!read_gray((fs::path(p.dense_folder) / "blocks" / ("mask_" + std::to_string(p.ref_image_id) + ".jpg")).string(), b, err)) return false;
     if (b.w != st.w || b.h != st.h) { err = "block mask size differs from the depth map"; return false; }
     v.block = std::move(b.px);
   }
-  v.view.width = st.w; v.view.height = st.h;
-  v.view.cam = cam;
-  v.view.depth = st.depth.data();
-  v.view.normal = st.normal.data();
   v.weak = st.weak.data();
   return true;
 }
@@ -443,6 +470,7 @@ struct PipelineRun {
   std::map<int, ImageState> states;      // final states; with a runner hook also every pass's prior
   std::map<int, DepthMap> depth_cur;     // runner hook: the current depth map of every image of the run
   std::map<int, ImageState> fusion_states;   // what RunFusion reads: this rank's states and the gathered ones
+  NativeFusion nf;                           // the device side of fusion and of the consistency maps
 
   Problem& problem_of(int rank, size_t k) { return problems[ranks.block(rank)[k]]; }
   // one rank has nobody to wait for: its first failure ends the run
@@ -867,17 +895,92 @@ struct PipelineRun {
     return true;
   }
 
+  // the context of the device fusion and the device consistency maps: the runner's, or (runner hook) one of its own
+  bool open_fusion_context() {
+    if (nf.ctx) return true;
+    nf.ctx = runner.ctx;
+    if (!nf.ctx) {
+      nf.ctx = dpe_create(opt.gpu_index);
+      if (!nf.ctx) { err = std::string("dpe_create: ") + dpe_last_error(); return false; }
+      nf.own = true;
+    }
+    return true;
+  }
+
+  // consistency.npy / depth_filtered.npy of this rank's images against the gathered final states.  The
+  // problems as indices into the views with RunFusion's imageIdToindexMap (the first of equal ids, 0 for an
+  // unknown one).  fusion_runner == NULL: every image on the device, the views staged once (and left for
+  // ETH3D fusion); else dpe_host_consistency's loop on host threads, one image each.
+  bool write_consistency_maps() {
+    const int n = (int)problems.size();
+    std::vector<DpeFusionView> cv(n);
+    std::map<int, int> index;
+    for (int i = 0; i < n; ++i) {
+      const Problem& p = problems[i];
+      if (!map_view(p, fusion_states.at(p.ref_image_id), w0, h0, cv[i], err)) return false;
+      index.emplace(p.ref_image_id, i);
+    }
+    auto idx_of = [&](int id) { auto it = index.find(id); return it == index.end() ? 0 : it->second; };
+    const std::vector<int>& mine = ranks.mine();
+    std::vector<int> refs(mine.size());
+    std::vector<std::vector<int>> srcs(mine.size());
+    for (size_t k = 0; k < mine.size(); ++k) {
+      const Problem& p = problems[mine[k]];
+      refs[k] = idx_of(p.ref_image_id);
+      for (int id : p.src_image_ids) srcs[k].push_back(idx_of(id));
+      std::string aerr;
+      if (!consistency_args_ok(n, refs[k], srcs[k].data(), (int)srcs[k].size(), opt.consistency, aerr)) {
+        err = aerr + " (image " + std::to_string(p.ref_image_id) + ")";
+        return false;
+      }
+    }
+    auto write_maps = [&](size_t k, const uint8_t* count, const float* filtered, std::string& werr) {
+      const DpeFusionView& R = cv[refs[k]];
+      const fs::path rf(problems[mine[k]].result_folder);
+      const std::vector<int64_t> hw{R.height, R.width};
+      return write_npy((rf / "consistency.npy").string(), count, hw, "|u1", 1, werr) &&
+             write_npy((rf / "depth_filtered.npy").string(), filtered, hw, "<f4", 4, werr);
+    };
+    if (opt.fusion_runner) {
+      const int nt = std::max(1, std::min<int>(host_threads(), (int)mine.size()));
+      std::vector<std::string> terr(mine.size());
+      run_on_threads(nt, [&](int t) {
+        for (size_t k = t; k < mine.size(); k += nt) {
+          const size_t L = (size_t)cv[refs[k]].width * cv[refs[k]].height;
+          std::vector<uint8_t> count(L);
+          std::vector<float> filtered(L);
+          consistency_image(cv.data(), refs[k], srcs[k].data(), (int)srcs[k].size(), opt.consistency, count.data(),
+                            filtered.data());
+          if (!write_maps(k, count.data(), filtered.data(), terr[k]) && terr[k].empty()) terr[k] = "write failed";
+        }
+      });
+      for (auto& e : terr) if (!e.empty()) { err = e; return false; }
+      return true;
+    }
+    float D = 0.0f;
+    if (!consistency_dot_threshold(D, err)) return false;
+    if (!open_fusion_context()) return false;
+    if (nf.stage(cv.data(), n) != DPE_OK) { err = "dpe_fusion_stage: " + nf.err; return false; }
+    std::vector<uint8_t> count;
+    std::vector<float> filtered;
+    for (size_t k = 0; k < mine.size(); ++k) {
+      const size_t L = (size_t)cv[refs[k]].width * cv[refs[k]].height;
+      count.resize(L); filtered.resize(L);
+      if (dpe_fusion_consistency(nf.ctx, refs[k], srcs[k].data(), (int)srcs[k].size(), D, opt.consistency, count.data(),
+                                 filtered.data()) != DPE_OK) {
+        err = std::string("dpe_fusion_consistency: ") + dpe_last_error();
+        return false;
+      }
+      if (!write_maps(k, count.data(), filtered.data(), err)) return false;
+    }
+    return true;
+  }
+
   bool fuse_and_export(std::vector<FusionView>& views) {   // RunFusion + ExportPointCloud (main.cpp:578-580)
-    NativeFusion nf;
     dpe_fusion_fn ffn = opt.fusion_runner;
     void* fuser = opt.fusion_user;
     if (!ffn) {
-      nf.ctx = runner.ctx;
-      if (!nf.ctx) {
-        nf.ctx = dpe_create(opt.gpu_index);
-        if (!nf.ctx) { err = std::string("dpe_create: ") + dpe_last_error(); return false; }
-        nf.own = true;
-      }
+      if (!open_fusion_context()) return false;
       ffn = native_fusion; fuser = &nf;
     }
     std::vector<FusedPoint> cloud;
@@ -918,6 +1021,10 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
     err = "bad point_cloud " + std::to_string(opt.point_cloud) + " (0 = off, 1 = all pixels, 2 = STRONG pixels only)";
     return 1;
   }
+  if (opt.consistency < 0 || opt.consistency > 255) {
+    err = "bad consistency " + std::to_string(opt.consistency) + " (0 = off, 1..255 = min_views)";
+    return 1;
+  }
   PipelineRun r(dense_folder, opt, err);
   RankGroup& ranks = r.ranks;
   if (!r.load_problems()) return 1;
@@ -943,12 +1050,21 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
   // would leave the others' next collective, or their success, inconsistent with it)
   if (ranks.multi() && !ranks.status_exchange(err)) return 1;
   if (ranks.failed()) { err = ranks.first_error(); return 1; }
+  if (opt.fusion || opt.consistency) {   // both read every rank's final states (a collective: the options are the run's)
+    const double t_gather0 = now_s();
+    if (!r.gather_states_for_fusion()) return 1;
+    g_times[opt.fusion ? kTimeFusion : kTimeConsistency] = now_s() - t_gather0;
+  }
+  if (opt.consistency) {   // every rank, its own images; before fusion, which finds the views staged
+    const double t_cons0 = now_s();
+    if (!r.write_consistency_maps()) return 1;
+    g_times[kTimeConsistency] += now_s() - t_cons0;
+  }
   if (opt.fusion) {   // RunFusion (main.cpp:578-580) on rank 0, over every rank's final states
     const double t_fusion0 = now_s();
-    if (!r.gather_states_for_fusion()) return 1;
     std::vector<FusionView> views;
     if (ranks.rank() == 0 && !(r.load_fusion_views(views) && r.fuse_and_export(views))) return 1;
-    g_times[kTimeFusion] = now_s() - t_fusion0;
+    g_times[kTimeFusion] += now_s() - t_fusion0;
   }
   if (!opt.keep_intermediate) r.remove_intermediate_maps();
   if (opt.verbose && ranks.rank() == 0) std::cout << "All done" << std::endl;

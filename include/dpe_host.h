@@ -30,6 +30,9 @@
  *   ExportDepthImagePointCloud DPE.cpp:1691      dpe_host_depth_point_cloud (point_cloud = 1 / 2: on the GPU
  *     (call commented out, main.cpp:456-466)     from the resident state, dpe_state_point_cloud)
  *   RescaleImageAndCamera     DPE.cpp:1123       dpe_host_rescale_image_and_camera
+ *   (RunFusion's view loop without its masks,    dpe_host_consistency (consistency = min_views: per-image
+ *     DPE.cpp:1312-1343; no such output there)   consistency.npy / depth_filtered.npy, on the GPU by
+ *                                                dpe_fusion_consistency)
  *
  * Additions for the one-process-per-GPU deployment: a pass runner hook (default: the HIP library
  * on `gpu_index`) and an all-gather hook for the depth maps (RCCL in the CLI, torch.distributed
@@ -100,6 +103,14 @@ typedef struct DpePipelineOptions {
                                reference image's point_<iteration>.ply goes into its result folder
                                (ExportDepthImagePointCloud; 2: STRONG pixels only, main.cpp:464).  Independent
                                of `viz`, under which the reference nests it.  Any other value fails */
+  int consistency;          /* 0 (the default): off.  1..255 = min_views: every reference image's result folder gets
+                               consistency.npy (|u1 [H][W]: the source views of its pair.txt line that pass
+                               RunFusion's reprojection, depth and angle tests at the pixel, without RunFusion's
+                               masks and blocks) and depth_filtered.npy (<f4 [H][W]: the final depth where that
+                               count >= min_views, else 0), from the final maps, independent of the depth / normal
+                               flags; each rank writes its own images.  On the GPU (dpe_fusion_consistency), or
+                               with a fusion_runner hook on host threads (dpe_host_consistency): the same files.
+                               Must be the same on every rank.  Any other value fails */
 } DpePipelineOptions;
 
 void dpe_pipeline_default_options(DpePipelineOptions* opt);
@@ -111,8 +122,10 @@ const char* dpe_pipeline_last_error(void);
  * [4] outputs + fusion, [5] the depth exchanges alone (multi-rank: status all-gather, export,
  * all-gather, import, summed over the pass rounds; 0 for one rank), [6] the pass work alone (each
  * pass round up to its GPU work's end, on one rank too), [7] RunFusion (part of [4]; with several
- * ranks it includes the exchange of the final normals / pixel states; 0 without fusion).  Returns
- * the number of entries written (<= n, at most 8). */
+ * ranks it includes the exchange of the final normals / pixel states; 0 without fusion), [8] the
+ * consistency maps (part of [4]: views, filter and files of this rank's images; with several ranks and
+ * no fusion it includes that exchange; 0 without `consistency`).  Returns the number of entries
+ * written (<= n, at most 9). */
 int dpe_pipeline_last_timings(double* out, int n);
 
 /* Grey-level decode of a JPEG (baseline/extended, luma plane) or binary PGM.  Writes up to `cap`
@@ -228,6 +241,23 @@ long long dpe_host_depth_point_cloud(int mode, int w, int h, const float* depth,
 int dpe_host_rescale_image_and_camera(const uint8_t* bgr, int src_w, int src_h, int w, int h, DpeCamera* cam,
                                       uint8_t* out_bgr);
 int dpe_host_write_point_cloud(const char* path, const DpeFusedPoint* points, size_t n);
+
+/*
+ * The consistency maps (DpePipelineOptions.consistency) on the host: the yardstick of
+ * dpe_fusion_consistency (dpe_mvs.h, which states the tests) and what the option runs without a GPU.
+ *   dpe_host_consistency                the serial double loop over reference view `ref` of views[0..n_views-1]
+ *                                       against src[0..ns-1] (indices into views), calling acosf itself:
+ *                                       count u8 [H][W], depth_filtered f32 [H][W] (either may be NULL).
+ *                                       0, or nonzero for what dpe_fusion_consistency refuses.
+ *   dpe_host_consistency_dot_threshold  *D = the smallest float in [-1, 1] whose acosf is below 0.174533f
+ *                                       (what the device test `dot >= D` needs), found and verified as
+ *                                       dpe_host_fusion_tat_thresholds does.  0, or nonzero when it does not verify.
+ *   dpe_host_consistency_angle_test     the loop's own test: GetAngle(dot) < 0.174533f.
+ */
+int dpe_host_consistency(const DpeFusionView* views, int n_views, int ref, const int* src, int ns, int min_views,
+                         uint8_t* count, float* depth_filtered);
+int dpe_host_consistency_dot_threshold(float* D);
+int dpe_host_consistency_angle_test(float dot);
 
 #ifdef __cplusplus
 }

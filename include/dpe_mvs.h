@@ -340,6 +340,30 @@ int dpe_fusion_tat_image(DpeContext* ctx, int mode, int ref, const int* src, int
 int dpe_fusion_tat_wait(DpeContext* ctx);
 int dpe_fusion_tat_mask(DpeContext* ctx, int view, uint8_t* mask);
 
+/*
+ * Consistency maps of one reference view (csrc/pass_consistency.h), after dpe_fusion_stage: for
+ * reference view `ref`, its source views src[0..ns-1] (indices into the staged views, none equal to
+ * `ref`, ns <= 255) and pixel p (row-major),
+ *   count[p]          = the number of j for which RunFusion's view loop (DPE.cpp:1312-1343) reaches
+ *                       num_consistent++ with its masks[...] tests and the blocks test removed: reference
+ *                       depth > 0, projection inside view src[j] (x + 0.5, y + 0.5 in (-1, size), tested on
+ *                       the float) on a depth > 0, reprojection error < 2.0f (squares, sum and root in
+ *                       double, rounded once), relative depth difference < 0.01f, and the angle test
+ *                       `!(dot >= -1 && dot <= 1) || dot >= dot_threshold`, which is
+ *                       GetAngle(n_ref, n_src) < 0.174533f when dot_threshold comes from
+ *                       dpe_host_consistency_dot_threshold (dpe_host.h);
+ *   depth_filtered[p] = count[p] >= min_views ? depth_ref[p] : 0.0f.
+ * RunFusion's dynamic_consistency weight is not part of this.  Bit-identical to dpe_host_consistency.
+ * HOST output buffers of W*H uint8 / floats of the reference view; either may be NULL (no copy).
+ * Synchronous.  ns = 0 gives all zeros.  DPE_ERR_ARG: ns < 0 or > 255, min_views outside 1..255, an
+ * index outside the staged views, `ref` among `src`; DPE_ERR_STATE: nothing staged.
+ * dpe_consistency_launches: kernels of this section launched by the process so far (a run without the
+ * option launches none).
+ */
+int dpe_fusion_consistency(DpeContext* ctx, int ref, const int* src, int ns, float dot_threshold, int min_views,
+                           uint8_t* count, float* depth_filtered);
+long long dpe_consistency_launches(void);
+
 /* Page-locks (pins) / releases a caller's host buffer so that device -> host copies into it run at
  * full PCIe rate (hipHostRegister; the host fusion pins its candidate buffers).  Nonzero when the
  * runtime refuses (no device, limits): the buffer then stays pageable and every call still works. */

@@ -10,7 +10,12 @@ host/fusion_tat.cpp) against the device path the pipeline takes (dpe_fusion_tat_
 two `--reps` times after one untimed device run, and checks that both give the same points.  Each time
 is a host clock around one whole fusion (the device one includes its context, the uploads of depths,
 normals, colours and the copy-out of the points).
-Usage: python tools/fusion_prof.py [n_images] [width] [height] [--mode M] [--reps R]"""
+
+--consistency N: the pipeline run also writes the consistency maps with min_views = N, and the line it
+prints carries dpe_pipeline_last_timings [8] (views, staging, one kernel and 5 B/px back per image, the
+two .npy files) beside [7] (RunFusion, whose candidates path brings 16 * ns B/px back): the filter's cost
+against the candidates path on the same folder, in the same run.
+Usage: python tools/fusion_prof.py [n_images] [width] [height] [--mode M] [--reps R] [--consistency N]"""
 import argparse
 import os
 import shutil
@@ -30,6 +35,7 @@ ap.add_argument("W", nargs="?", type=int, default=1920)
 ap.add_argument("H", nargs="?", type=int, default=1080)
 ap.add_argument("--mode", choices=["eth3d", "tat_intermediate", "tat_advanced", "both"], default="eth3d")
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--consistency", type=int, default=0, metavar="N")
 a = ap.parse_args()
 n, W, H = a.n, a.W, a.H
 
@@ -59,11 +65,22 @@ try:
     del sc
     print("scene written", flush=True)
     t0 = time.perf_counter()
-    pipeline.run_dpe_pipeline(folder, gpu_index=0, verbose=False, fusion=True, keep_intermediate=a.mode != "eth3d")
+    pipeline.run_dpe_pipeline(folder, gpu_index=0, verbose=False, fusion=True, keep_intermediate=a.mode != "eth3d",
+                              consistency=a.consistency)
     import ctypes
-    ph = (ctypes.c_double * 8)()
-    pipeline.lib().dpe_pipeline_last_timings(ph, 8)
-    print(f"{n} x {W}x{H}: wall {time.perf_counter() - t0:.2f} s, passes {ph[6]:.2f} s, fusion {ph[7]:.2f} s", flush=True)
+    ph = (ctypes.c_double * 9)()
+    pipeline.lib().dpe_pipeline_last_timings(ph, 9)
+    print(f"{n} x {W}x{H}: wall {time.perf_counter() - t0:.2f} s, passes {ph[6]:.2f} s, fusion {ph[7]:.2f} s" +
+          (f", consistency maps (min_views {a.consistency}) {ph[8]:.3f} s" if a.consistency else ""), flush=True)
+    if a.consistency:   # what the maps say, so that the time above is the time of a real answer
+        hist, kept = np.zeros(256, np.int64), 0
+        for i in range(n):
+            rf = os.path.join(folder, pipeline.OUT_NAME, f"{i:08d}")
+            hist += np.bincount(np.load(os.path.join(rf, "consistency.npy")).ravel(), minlength=256)
+            kept += np.count_nonzero(np.load(os.path.join(rf, "depth_filtered.npy")))
+        top = int(np.nonzero(hist)[0].max())
+        print(f"consistency: {kept} of {n * W * H} pixels kept ({100.0 * kept / (n * W * H):.1f} %), "
+              f"count histogram 0..{top}: {hist[:top + 1].tolist()}", flush=True)
     if a.mode != "eth3d":
         views = final_views(folder)
         for mode in (["tat_intermediate", "tat_advanced"] if a.mode == "both" else [a.mode]):
