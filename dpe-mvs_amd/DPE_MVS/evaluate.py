@@ -1,0 +1,40 @@
+"""python -m DPE_MVS.evaluate recon.ply gt.ply --tau T [T ...] [--radius R] [--gpu N] [--json FILE]
+
+Precision, recall and F-score of a reconstructed PLY (DPE/DPE.ply of a run with fusion) against a
+ground-truth PLY: pipeline.evaluate_clouds over the two files, the table and numbers of bin/dpe_eval.  Without
+--gpu the distances run on host threads; with it on that device: the same numbers.  The clouds are taken as
+they are (no registration, cropping or down-sampling).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+
+from . import pipeline
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m DPE_MVS.evaluate", description=__doc__.split("\n\n")[1])
+    ap.add_argument("recon")
+    ap.add_argument("gt")
+    ap.add_argument("--tau", type=float, nargs="+", required=True, help="distance thresholds (1 to 16)")
+    ap.add_argument("--radius", type=float, default=None, help="truncation radius (default: the largest tau)")
+    ap.add_argument("--gpu", type=int, default=-1, help="device of the distances (default: host threads)")
+    ap.add_argument("--json", default=None, help="also write the result to this file")
+    a = ap.parse_args(argv)
+    try:
+        e = pipeline.evaluate_clouds(pipeline.read_point_cloud(a.recon), pipeline.read_point_cloud(a.gt), a.tau, a.radius, a.gpu)
+    except pipeline.PipelineError as err:
+        print(f"evaluate: {err}", file=sys.stderr)
+        return 1
+    sys.stdout.write(pipeline.format_cloud_eval(e))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(e, n_tau=len(e["tau"])), f)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

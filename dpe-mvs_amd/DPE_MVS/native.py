@@ -28,6 +28,7 @@ EXPORTED = [
     "dpe_jpeg_blocks_device", "dpe_viz_launches", "dpe_live_device_bytes",
     "dpe_state_point_cloud", "dpe_state_point_cloud_wait", "dpe_point_cloud_arrays", "dpe_points_launches",
     "dpe_fusion_consistency", "dpe_consistency_launches",
+    "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -132,6 +133,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_point_cloud_arrays.restype = C.c_int
     lib.dpe_points_launches.argtypes = []
     lib.dpe_points_launches.restype = C.c_longlong
+    lib.dpe_cloud_nn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
+    lib.dpe_cloud_nn.restype = C.c_int
+    lib.dpe_cloud_nn_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]
+    lib.dpe_cloud_nn_pair.restype = C.c_int
+    lib.dpe_cloud_launches.argtypes = []
+    lib.dpe_cloud_launches.restype = C.c_longlong
+    lib.dpe_cloud_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+    lib.dpe_cloud_last_timings.restype = C.c_int
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
@@ -150,6 +159,16 @@ def fusion_view_array(views):
         keep += [d, n]
         arr[k] = _abi.DpeFusionView(d.shape[1], d.shape[0], cam, d.ctypes.data, n.ctypes.data)
     return arr, keep
+
+
+def as_cloud(points) -> np.ndarray:
+    """A cloud as the C-ABI takes it: contiguous f32 [k, 3] (its memory is valid for k = 0 too)."""
+    a = np.ascontiguousarray(points, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        if a.size:
+            raise ValueError("expected points of shape [k, 3]")
+        a = np.empty((0, 3), np.float32)
+    return a
 
 
 _LIB = load_library()
@@ -403,6 +422,30 @@ class PatchMatchContext:
                "dpe_point_cloud_arrays")
         return out[:n.value].copy()
 
+    # cloud evaluation (include/dpe_mvs.h: dpe_cloud_nn)
+    def cloud_nn(self, query, target, radius: float) -> np.ndarray:
+        """out[i] = min(R*R, min_j d2(query[i], target[j])) on the device: f32 [n] SQUARED distances, the bits of
+        a serial float loop (pipeline.cloud_nn gives the same on host threads).  Clouds: f32 [k, 3]."""
+        q, t = as_cloud(query), as_cloud(target)
+        out = np.empty(len(q), np.float32)
+        _check(_LIB.dpe_cloud_nn(self._ctx, q.ctypes.data, len(q), t.ctypes.data, len(t), float(radius), out.ctypes.data),
+               "dpe_cloud_nn")
+        return out
+
+    def cloud_nn_pair(self, a, b, radius: float) -> tuple:
+        """Both directions with each cloud staged once: (a_to_b f32 [n], b_to_a f32 [m])."""
+        a, b = as_cloud(a), as_cloud(b)
+        ab, ba = np.empty(len(a), np.float32), np.empty(len(b), np.float32)
+        _check(_LIB.dpe_cloud_nn_pair(self._ctx, a.ctypes.data, len(a), b.ctypes.data, len(b), float(radius), ab.ctypes.data,
+                                      ba.ctypes.data), "dpe_cloud_nn_pair")
+        return ab, ba
+
+    def cloud_timings(self) -> dict:
+        """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}."""
+        buf = (C.c_float * 4)()
+        n = _LIB.dpe_cloud_last_timings(self._ctx, buf, 4)
+        return {k: float(buf[i]) for i, k in enumerate(("stage", "build", "query", "download")) if i < n}
+
     def device_planes(self) -> int:
         return int(_LIB.dpe_pm_device_planes(self._ctx) or 0)
 
@@ -423,6 +466,11 @@ def points_launches() -> int:
 def consistency_launches() -> int:
     """Kernels of the consistency maps launched by this process so far."""
     return int(_LIB.dpe_consistency_launches())
+
+
+def cloud_launches() -> int:
+    """Kernels of the cloud evaluation launched by this process so far."""
+    return int(_LIB.dpe_cloud_launches())
 
 
 def live_device_bytes() -> int:
@@ -448,4 +496,4 @@ def param_struct(**overrides) -> _abi.DpePatchMatchParams:
 
 Context = PatchMatchContext
 
-__all__ = ["PatchMatchContext", "Context", "viz_launches", "points_launches", "consistency_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]
+__all__ = ["PatchMatchContext", "Context", "viz_launches", "points_launches", "consistency_launches", "cloud_launches", "live_device_bytes", "run_pass", "param_struct", "DpeError", "LIB_PATH", "EXPORTED", "np"]

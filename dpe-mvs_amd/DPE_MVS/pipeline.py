@@ -68,6 +68,17 @@ class DpeHostTatView(C.Structure):   # include/dpe_host.h
                 ("bgr", C.c_void_p), ("block", C.c_void_p), ("mask", C.c_void_p)]
 
 
+CLOUD_MAX_TAU = 16
+
+
+class DpeCloudEval(C.Structure):   # include/dpe_host.h
+    _fields_ = [("n_tau", C.c_int), ("radius", C.c_float), ("tau", C.c_float * CLOUD_MAX_TAU),
+                ("precision", C.c_double * CLOUD_MAX_TAU), ("recall", C.c_double * CLOUD_MAX_TAU),
+                ("fscore", C.c_double * CLOUD_MAX_TAU), ("mean_accuracy_truncated", C.c_double),
+                ("mean_completeness_truncated", C.c_double), ("n_recon", C.c_ulonglong), ("n_gt", C.c_ulonglong),
+                ("dropped_recon", C.c_ulonglong), ("dropped_gt", C.c_ulonglong)]
+
+
 class PipelineError(RuntimeError):
     pass
 
@@ -118,6 +129,10 @@ def lib() -> C.CDLL:
         L.dpe_host_consistency.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.dpe_host_consistency_dot_threshold.argtypes = [C.POINTER(C.c_float)]
         L.dpe_host_consistency_angle_test.argtypes = [C.c_float]
+        L.dpe_host_cloud_nn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]
+        L.dpe_host_read_point_cloud.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dpe_host_cloud_eval.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
+                                          C.c_int, C.POINTER(DpeCloudEval)]
         _lib = L
     return _lib
 
@@ -364,6 +379,73 @@ def consistency_dot_threshold() -> float:
 def consistency_angle_test(dot: float) -> bool:
     """The host loop's angle test: GetAngle(dot) < 0.174533f."""
     return bool(lib().dpe_host_consistency_angle_test(float(dot)))
+
+
+# ------------------------------------------------------------------------------ cloud evaluation (C++, cloud_eval.cpp, ply_read.cpp)
+def _last_error() -> str:
+    return lib().dpe_pipeline_last_error().decode(errors="replace")
+
+
+def _as_cloud(points) -> np.ndarray:
+    a = np.ascontiguousarray(points, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        if a.size:
+            raise ValueError("expected points of shape [k, 3]")
+        a = np.empty((0, 3), np.float32)
+    return a
+
+
+def read_point_cloud(path: str) -> np.ndarray:
+    """The vertex positions f32 [n, 3] of a PLY (ascii or binary little-endian; x, y, z float or double at any
+    position of the vertex element).  PipelineError with the reader's message for what it refuses."""
+    n = C.c_size_t()
+    if lib().dpe_host_read_point_cloud(os.fsencode(path), None, 0, C.byref(n)) != 0:
+        raise PipelineError(_last_error())
+    out = np.empty((n.value, 3), np.float32)
+    if lib().dpe_host_read_point_cloud(os.fsencode(path), out.ctypes.data, n.value, C.byref(n)) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def cloud_nn(query, target, radius: float) -> np.ndarray:
+    """out[i] = min(R*R, min_j d2(query[i], target[j])) on host threads (dpe_host_cloud_nn): f32 [n] SQUARED
+    distances, the bits of a serial float loop and of the device path (native.PatchMatchContext.cloud_nn)."""
+    q, t = _as_cloud(query), _as_cloud(target)
+    out = np.empty(len(q), np.float32)
+    if lib().dpe_host_cloud_nn(q.ctypes.data, len(q), t.ctypes.data, len(t), float(radius), out.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int = -1) -> dict:
+    """Precision, recall and F-score of cloud `recon` against cloud `gt` (f32 [k, 3]) at the thresholds `taus`
+    (1 to 16, each 0 < tau <= radius; radius None: the largest tau), from the truncated nearest-neighbour
+    distances in both directions (dpe_host_cloud_eval).  gpu_index < 0: on host threads, else on that device:
+    equal dicts.  Keys: tau, precision, recall, fscore (lists), radius, mean_accuracy_truncated,
+    mean_completeness_truncated (means of the distances truncated at the radius), n_recon, n_gt, dropped_recon,
+    dropped_gt (points with a non-finite coordinate; they still count in the denominators)."""
+    a, b = _as_cloud(recon), _as_cloud(gt)
+    t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
+    e = DpeCloudEval()
+    if lib().dpe_host_cloud_eval(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t),
+                                 0.0 if radius is None else float(radius), int(gpu_index), C.byref(e)) != 0:
+        raise PipelineError(_last_error())
+    k = e.n_tau
+    return dict(tau=[float(v) for v in e.tau[:k]], precision=list(e.precision[:k]), recall=list(e.recall[:k]),
+                fscore=list(e.fscore[:k]), radius=float(e.radius), mean_accuracy_truncated=e.mean_accuracy_truncated,
+                mean_completeness_truncated=e.mean_completeness_truncated, n_recon=int(e.n_recon), n_gt=int(e.n_gt),
+                dropped_recon=int(e.dropped_recon), dropped_gt=int(e.dropped_gt))
+
+
+def format_cloud_eval(e: dict) -> str:
+    """The table bin/dpe_eval prints, from evaluate_clouds' dict."""
+    rows = ["recon %d points (%d dropped), gt %d points (%d dropped), radius %.9g"
+            % (e["n_recon"], e["dropped_recon"], e["n_gt"], e["dropped_gt"], e["radius"]),
+            "%14s %10s %10s %10s" % ("tau", "precision", "recall", "fscore")]
+    rows += ["%14.9g %10.6f %10.6f %10.6f" % v for v in zip(e["tau"], e["precision"], e["recall"], e["fscore"])]
+    rows += ["mean accuracy (truncated at the radius) %.9g" % e["mean_accuracy_truncated"],
+             "mean completeness (truncated at the radius) %.9g" % e["mean_completeness_truncated"]]
+    return "\n".join(rows) + "\n"
 
 
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)

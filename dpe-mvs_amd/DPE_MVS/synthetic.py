@@ -250,6 +250,20 @@ def src_depths(scene: dict, seed: int = 11, noise: float = 0.01) -> list:
     return out
 
 
+def gt_point_cloud(scene: dict, stride: int = 1) -> np.ndarray:
+    """The scene's ground-truth surface as points f32 [k, 3]: every view's finite ground-truth depth at every
+    `stride`-th pixel of both axes, back-projected with that view's K, R, C (X = C + d * R^T K^-1 (x, y, 1),
+    in double, rounded once)."""
+    out = []
+    for v in scene["views"]:
+        d = v["depth"][::stride, ::stride].astype(np.float64)
+        ys, xs = np.mgrid[0:scene["H"]:stride, 0:scene["W"]:stride].astype(np.float64)
+        ok = np.isfinite(d)
+        rays = np.stack([xs[ok], ys[ok], np.ones(int(ok.sum()))], -1) @ np.linalg.inv(v["K"]).T
+        out.append((v["C"] + d[ok][:, None] * (rays @ v["R"])).astype(np.float32))
+    return np.concatenate(out) if out else np.empty((0, 3), np.float32)
+
+
 def pass_input(scene: dict, params, depths=None, seed: int = 1, pass_salt: int = 0) -> dict:
     params.depth_min = float(np.float32(scene["cams"][0].depth_min) * np.float32(0.6))    # DPE.cpp:788
     params.depth_max = float(np.float32(scene["cams"][0].depth_max) * np.float32(1.2))    # DPE.cpp:789

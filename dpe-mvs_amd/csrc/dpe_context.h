@@ -1,7 +1,7 @@
 // dpe_context.h -- what a DpeContext (include/dpe_mvs.h) holds: device arrays, streams and events that
 // own their HIP resources, the cached images, the resident states and the context itself, its members
 // grouped by the unit that owns them.  Internal to the library and shared by its units (dpe_mvs.hip,
-// dpe_state.hip, dpe_edges.hip, dpe_viz.hip, dpe_fusion.hip, dpe_points.hip): every type here is an ordinary named
+// dpe_state.hip, dpe_edges.hip, dpe_viz.hip, dpe_fusion.hip, dpe_points.hip, dpe_cloud.hip): every type here is an ordinary named
 // type and the byte counter has one definition in the process.  Includes no kernel header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,11 +218,24 @@ struct PointsScratch {
   DevArr<uint8_t> weak;
 };
 
+// cloud evaluation (dpe_cloud.hip: dpe_cloud_nn / dpe_cloud_nn_pair): scratch, allocated on first use and
+// grown on demand.  `ev` is declared first and so outlives the buffers.
+struct CloudScratch {
+  std::vector<Event> ev;             // timing (dpe_set_timing): start, staged, then (build, query, download) per direction
+  float ms[4] = {0, 0, 0, 0};        // dpe_cloud_last_timings: stage, build, query, download of the last call
+  bool timed = false;
+  DevArr<float> pts[2];              // the two clouds as the caller packs them, f32 [k][3]
+  DevArr<uint32_t> bounds;           // per cloud 8 words: k_cloud_bounds' keys and the finite count
+  DevArr<float4> st, sq;             // target / query points in bucket order: (x, y, z, original index)
+  DevArr<int> tcnt, qcnt;            // per bucket: counts -> starts -> ends
+  DevArr<float> out;                 // the distances, by original index
+};
+
 }  // namespace dpe
 
 // Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
 // reverse order: the streams and events are declared first and so outlive every buffer (the events of
-// one group alone, tat.ev, viz.ev and points.ev, are the first members of their group).
+// one group alone, tat.ev, viz.ev, points.ev and cloud.ev, are the first members of their group).
 struct DpeContext {
   int device = 0;
   dpe::Stream stream;
@@ -243,4 +256,5 @@ struct DpeContext {
   dpe::TatFusion tat;
   dpe::VizScratch viz;
   dpe::PointsScratch points;
+  dpe::CloudScratch cloud;
 };

@@ -135,4 +135,16 @@ bool consistency_dot_threshold(float& D, std::string& err);
 // the arguments dpe_host_consistency refuses, as dpe_fusion_consistency does (the message into err)
 bool consistency_args_ok(int n_views, int ref, const int* src, int ns, int min_views, std::string& err);
 
+// pipeline.cpp: the message dpe_pipeline_last_error returns on this thread (the helpers of cloud_eval.cpp and
+// ply_read.cpp report through it)
+void set_last_error(const std::string& msg);
+// cloud_eval.cpp: the truncated nearest-neighbour distance of dpe_cloud_nn (dpe_mvs.h) over the same grid
+// (csrc/cloud_dist.h) on host threads, and the evaluation built on it (gpu_index < 0: that path, else
+// dpe_cloud_nn_pair in a context of its own; the counts and means on the host either way)
+bool cloud_nn(const float* query, size_t n, const float* target, size_t m, float radius, float* out, std::string& err);
+bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                int gpu_index, DpeCloudEval* out, std::string& err);
+// ply_read.cpp: the vertex positions of an ascii / binary little-endian PLY; xyz == nullptr: *n only
+bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n, std::string& err);
+
 }  // namespace dpe_host

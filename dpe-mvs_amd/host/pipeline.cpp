@@ -1076,6 +1076,10 @@ int run(const char* dense_folder, const DpePipelineOptions& opt) {
 }  // namespace
 }  // namespace dpe_host
 
+namespace dpe_host {
+void set_last_error(const std::string& msg) { g_err = msg; }
+}  // namespace dpe_host
+
 extern "C" {
 
 void dpe_pipeline_default_options(DpePipelineOptions* o) {

@@ -259,6 +259,47 @@ int dpe_host_consistency(const DpeFusionView* views, int n_views, int ref, const
 int dpe_host_consistency_dot_threshold(float* D);
 int dpe_host_consistency_angle_test(float dot);
 
+/*
+ * Cloud evaluation: precision, recall and F-score of a reconstructed cloud against a ground-truth cloud.
+ * No counterpart in the reference.  The numbers are those of the two clouds as given: no registration,
+ * cropping or down-sampling, so they are not a benchmark's leaderboard figures.
+ *   dpe_host_cloud_nn          the contract of dpe_cloud_nn (dpe_mvs.h: d2, truncation at R2 = R*R, non-finite
+ *                              points) over the same grid on host threads (at most 16): the same bits.  The
+ *                              yardstick of the device path and the path used without a GPU.
+ *   dpe_host_read_point_cloud  the vertex positions of a PLY, `ascii` or `binary_little_endian 1.0`: scalar
+ *                              properties x, y, z of the `vertex` element at any position, float or double
+ *                              (rounded to float); other scalar properties are skipped by their size, later
+ *                              elements ignored.  Writes up to `cap` points into xyz f32 [cap][3] and their
+ *                              number into *n (xyz = NULL: the number only).  A list property inside `vertex`,
+ *                              a big-endian file, a truncated body, a count above 2^31 - 1 and a missing
+ *                              coordinate fail.  Reads what dpe_host_write_point_cloud writes.
+ *   dpe_host_cloud_eval        a = out(recon -> gt), c = out(gt -> recon) at radius R (0: the largest tau);
+ *                              1 <= n_tau <= 16, every tau finite with 0 < tau <= R.
+ *                                precision[k] = #{ i : a[i] < tau[k]*tau[k] } / n_recon   (product in float,
+ *                                recall[k]    = the same from c over n_gt                  division in double;
+ *                                fscore[k]    = 2 p r / (p + r), 0 when p + r = 0          0 for an empty cloud)
+ *                                mean_*_truncated = sum of sqrt((double)a[i]) / n in index order: means of
+ *                                distances truncated at R, not of the distances themselves.
+ *                              Points with a non-finite coordinate are counted in dropped_* and still count in
+ *                              the denominators.  gpu_index < 0: dpe_host_cloud_nn; else dpe_cloud_nn_pair in a
+ *                              context of its own on that device.  The counts and means are taken on the host
+ *                              from the distance arrays on both paths: equal structs.
+ * Each returns 0, or nonzero with the message in dpe_pipeline_last_error().
+ */
+#define DPE_CLOUD_MAX_TAU 16
+typedef struct DpeCloudEval {
+  int n_tau;
+  float radius;                         /* the R that was used */
+  float tau[DPE_CLOUD_MAX_TAU];
+  double precision[DPE_CLOUD_MAX_TAU], recall[DPE_CLOUD_MAX_TAU], fscore[DPE_CLOUD_MAX_TAU];
+  double mean_accuracy_truncated, mean_completeness_truncated;
+  unsigned long long n_recon, n_gt, dropped_recon, dropped_gt;
+} DpeCloudEval;
+int dpe_host_cloud_nn(const float* query, size_t n, const float* target, size_t m, float radius, float* d2_out);
+int dpe_host_read_point_cloud(const char* path, float* xyz, size_t cap, size_t* n);
+int dpe_host_cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                        int gpu_index, DpeCloudEval* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -439,6 +439,38 @@ int dpe_point_cloud_arrays(DpeContext* ctx, int mode, int w, int h, const float*
                            size_t cap, size_t* n);
 long long dpe_points_launches(void);
 
+/*
+ * Cloud evaluation: the exact truncated nearest-neighbour distance between two point clouds, the measurement
+ * behind precision / recall / F-score of a PLY (dpe_host_cloud_eval, dpe_host.h).  No counterpart in the
+ * reference, which publishes no accuracy figure.
+ *
+ * Clouds are packed f32 [k][3] HOST arrays; radius R is a finite float > 0; n, m <= 2^31 - 1; anything else
+ * is DPE_ERR_ARG.  All in float, every operation rounded, no contraction:
+ *   d2(q, t):  dx = q.x - t.x; dy = q.y - t.y; dz = q.z - t.z;  s = dx*dx; s = s + dy*dy; s = s + dz*dz
+ *   out[i] = min(R2, min_j d2(Q[i], T[j])),  R2 = R*R            (the SQUARED distance, f32 [n])
+ * A target point with a non-finite coordinate is skipped; a query point with one gets R2; m = 0 gives all R2.
+ * The result is a minimum over a set: the bits of a serial loop over the target, whatever the schedule
+ * (dpe_host_cloud_nn gives the same bits on host threads).  A hashed uniform grid of edge R * (1 + 2^-10)
+ * over the target and a 27-cell query; csrc/cloud_dist.h states why that covers every t with d2 < R2.
+ * A target whose extent over that edge reaches 2^30 cells on an axis is DPE_ERR_ARG ("radius too small for
+ * the cloud's extent").
+ *   dpe_cloud_nn            one direction.  Synchronous: d2_out is complete when it returns.
+ *   dpe_cloud_nn_pair       both directions, each cloud staged once: a_to_b f32 [n], b_to_a f32 [m].
+ *   dpe_cloud_launches      kernels of this section launched by the process so far (a run that never asks
+ *                           for an evaluation launches none).
+ *   dpe_cloud_last_timings  with dpe_set_timing on: device milliseconds of the last call's parts, [0] stage
+ *                           (upload), [1] grid build, [2] query, [3] download, summed over the directions;
+ *                           returns the number of entries written (<= n, at most 4; 0 when none was timed).
+ * The buffers belong to the context, grow on demand, are freed by dpe_destroy and count in
+ * dpe_live_device_bytes.
+ */
+int dpe_cloud_nn(DpeContext* ctx, const float* query, size_t n, const float* target, size_t m, float radius,
+                 float* d2_out);
+int dpe_cloud_nn_pair(DpeContext* ctx, const float* a, size_t n, const float* b, size_t m, float radius, float* a_to_b,
+                      float* b_to_a);
+long long dpe_cloud_launches(void);
+int dpe_cloud_last_timings(DpeContext* ctx, float* ms, int n);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);
