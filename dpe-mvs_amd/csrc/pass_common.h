@@ -497,7 +497,8 @@ DEV float tex_frac(float t, uint32_t bits) {
   return __builtin_amdgcn_fractf(t);
 }
 // The taps' numerators Q = 256 q: the column coefficients h1, h4 scaled by 256 here, the row terms
-// (h0 x + h2, h3 x + h5) scaled after their FMA (the oracle's OracleSampleQ caller does the same).
+// (h0 x + h2, h3 x + h5) scaled after their FMA.  kTexUnit is 1 since round 3: Q = q, and the oracle's
+// PatchNCC takes the same unscaled numerators (a 256-scaled one overflows for |q| >= 2^120).
 DEV Homog scale_cols(const Homog& H) {
   Homog S = H;
   S.h[1] = H.h[1] * kTexUnit;

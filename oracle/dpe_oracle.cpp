@@ -35,7 +35,7 @@
 //     weight are not evaluated when the product is provably +0 (cost vectors feeding only
 //     `view_weights[j] * c` sums).
 //  7. Bilinear taps: the fixed-point coordinate of the texture unit is RN(256 (q / qz) + 256), rounded
-//     once from the 256-scaled homography numerator and the tap reciprocal iz (OracleSampleQ);
+//     once from the homography numerator q and the tap reciprocal iz (OracleSampleQ);
 //     the reference's hardware conversion is unspecified beyond "8 fractional bits".
 //  8. (round 5) The tap reciprocal iz is gfx950's v_rcp_f32, not the correctly rounded 1 / qz
 //     (oracle_math.h o_rcp_tap: the instruction's table for biased exponents 1..252, IEEE outside);
@@ -107,13 +107,36 @@ struct Pass {
   std::vector<int> radius;                 // [L]
 };
 
+// Tap-path class counts of the last pass (TEST INFRASTRUCTURE, oracle_last_tap_stats; they change no
+// output).  Which branch the HIP kernels would take for each patch and tap, measured on the
+// restatement's own values (tests/test_scaled_camera_inputs.py):
+//   [0] patch NCC evaluations (PatchNCC calls: the centre projected inside the source image)
+//   [1] of [0], patches whose box fails the kernels' whole-patch reciprocal range test (RcpRangeClass)
+//   [2] of [0], patches whose box passes it with a negative denominator everywhere
+//   [3] taps whose denominator qz has a biased exponent outside 1..252 (IEEE reciprocal)
+//   [4] taps with a NaN coordinate t before the clamp (either axis)
+//   [5] taps clamped at either end of the range (either axis; NaN taps not included)
+// Each thread sums its own and adds them to the totals once, when its rows are done.
+constexpr int kTapStats = 6;
+static std::atomic<uint64_t> g_tap_stats[kTapStats];
+static thread_local uint64_t t_tap_stats[kTapStats];
+static void tap_stats_flush() {
+  for (int k = 0; k < kTapStats; ++k) {
+    if (t_tap_stats[k]) g_tap_stats[k].fetch_add(t_tap_stats[k], std::memory_order_relaxed);
+    t_tap_stats[k] = 0;
+  }
+}
+static void tap_stats_reset() {
+  for (int k = 0; k < kTapStats; ++k) { t_tap_stats[k] = 0; g_tap_stats[k].store(0, std::memory_order_relaxed); }
+}
+
 template <class F>
 static void parallel_rows(int H, int nthreads, F f) {
   if (nthreads <= 1) { for (int y = 0; y < H; ++y) f(y); return; }
   std::atomic<int> next(0);
   std::vector<std::thread> th;
   for (int t = 0; t < nthreads; ++t)
-    th.emplace_back([&]() { for (int y; (y = next.fetch_add(1)) < H;) f(y); });
+    th.emplace_back([&]() { for (int y; (y = next.fetch_add(1)) < H;) f(y); tap_stats_flush(); });
   for (auto& t : th) t.join();
 }
 
@@ -262,18 +285,21 @@ static inline float RefTexel(const Pass& S, const std::vector<float>& im, int x,
   return im[(size_t)y * S.W + x];
 }
 // tex2D<float>(img, sx + 0.5f, sy + 0.5f), linear filter, clamp addressing (DPE.cpp:927-933).
-// Texture model (restatement choice 7): the tap's homography numerators are scaled by 256
-// (Q = fma(256 h1, y, 256 fma(h0, x, h2)) = 256 q, exact) and the coordinate s + 1 = q / qz + 1 is converted to fixed point with 8
-// fractional bits by ONE round-to-nearest-even, U = RN(Q * iz + 256) with iz = 1 / qz, evaluated
-// as t = fma(Q, iz, 1.5*2^23 + 256) on the unit grid of [2^23, 2^24) so that U = t - 1.5*2^23;
-// U is clamped to [0, 256 lim + 256] (clamp addressing: beyond that the filtered value is the
-// border texel's), NaN -> 0.  Texel index i = (U >> 8) - 1, weight a = (U & 255) / 256.
-static const float kTexMagic = 12582912.0f;   // 1.5 * 2^23
-static inline uint32_t TexU(float Q, float iz, int lim) {
-  const float t = fmaf(Q, iz, kTexMagic + 256.0f);
-  const float tc = fminf(fmaxf(t, kTexMagic), kTexMagic + 256.0f * (float)(lim + 1));
+// Texture model (restatement choice 7): from the tap's homography numerator q = fma(h1, y, fma(h0, x, h2))
+// the coordinate s + 1 = q / qz + 1 is converted to fixed point with 8 fractional bits by ONE
+// round-to-nearest-even, U = RN(256 (q * iz) + 256) with iz = 1 / qz, evaluated as
+// t = fma(q, iz, 1.5*2^15 + 1) on the 1/256 grid of [2^15, 2^16), so that U is the difference of the
+// encodings of t and 1.5*2^15; U is clamped to [0, 256 lim + 256] (clamp addressing: beyond that the
+// filtered value is the border texel's), NaN -> 0.  Texel index i = (U >> 8) - 1, weight a = (U & 255) / 256.
+// (Until the scaled-camera tests this scaled the numerator first, Q = 256 q and t = fma(Q, iz, 1.5*2^23 + 256)
+// on the unit grid: the same U bit for bit while 256 q is finite, but |q| >= 2^120 overflowed to an inf
+// coordinate where the kernels, and the reference's q / qz, have a finite one.)
+static const float kTexMagic = 49152.0f;   // 1.5 * 2^15
+static inline uint32_t TexU(float q, float iz, int lim) {
+  const float t = fmaf(q, iz, kTexMagic + 1.0f);
+  const float tc = fminf(fmaxf(t, kTexMagic), kTexMagic + (float)(lim + 1));
   uint32_t u; std::memcpy(&u, &tc, 4);
-  return u - 0x4B400000u;
+  return u - 0x47400000u;
 }
 static inline float OracleSampleU(const Pass& S, const std::vector<float>& im, uint32_t ux, uint32_t uy) {
   const float ax = (float)(ux & 255u) * 0.00390625f;
@@ -430,13 +456,44 @@ static inline float BilateralWeight(const Pass& S, int i, int j, float pix, floa
   return o_expf(-sd / (2.0f * ss * ss) - cd / (2.0f * sc * sc));
 }
 
+// The kernels' whole-patch reciprocal range test (csrc/pass_common.h rcp_range_ok) over the box
+// [x0, x1] x [y0, y1], in float32 with the same FMAs: 0 = fails (per-tap range test), 1 = passes with
+// qz > 0, 2 = passes with qz < 0.  Counted only (tap_stats); the restatement's arithmetic has no such split.
+static inline int RcpRangeClass(const Homog& H, float x0, float x1, float y0, float y1) {
+  const float b0 = fmaf(H.h[6], x0, H.h[8]), b1 = fmaf(H.h[6], x1, H.h[8]);
+  const float q00 = fmaf(H.h[7], y0, b0), q01 = fmaf(H.h[7], y1, b0);
+  const float q10 = fmaf(H.h[7], y0, b1), q11 = fmaf(H.h[7], y1, b1);
+  const float mn = fminf(fminf(q00, q01), fminf(q10, q11));
+  const float mx = fmaxf(fmaxf(q00, q01), fmaxf(q10, q11));
+  const float amax = fmaxf(fmaxf(fabsf(b0), fabsf(b1)), fmaxf(fabsf(mn), fabsf(mx)));
+  const float lo = mn > 0.0f ? mn : -mx;
+  const bool ok = (mn > 0.0f || mx < 0.0f) && lo > amax * 9.5367431640625e-07f && lo > 7.888609052210118e-31f &&
+                  amax < 1.2676506002282294e+30f;
+  return !ok ? 0 : (mn > 0.0f ? 1 : 2);
+}
+// Classes of one tap for tap_stats [3..5]: denominator qz, numerators (Qx, Qy), reciprocal iz.
+static inline void TapClass(const Pass& S, float qz, float Qx, float Qy, float iz, uint64_t* n) {
+  uint32_t zb; std::memcpy(&zb, &qz, 4);
+  if (((zb >> 23) & 0xFFu) - 1u >= 252u) ++n[0];
+  const float tx = fmaf(Qx, iz, kTexMagic + 1.0f), ty = fmaf(Qy, iz, kTexMagic + 1.0f);
+  if (tx != tx || ty != ty) { ++n[1]; return; }
+  if (tx < kTexMagic || ty < kTexMagic || tx > kTexMagic + (float)(S.W + 1) || ty > kTexMagic + (float)(S.H + 1)) ++n[2];
+}
+
 // Bilateral-weighted NCC of one patch (body shared by ComputeBilateralNCCOld :715-775 and the
 // per-point body of ComputeBilateralNCCNew :609-668).
 static inline float PatchNCC(const Pass& S, const std::vector<float>& src, const Homog& H, int cx, int cy,
                              float ref_center_pix, int radius, int increment) {
   const std::vector<float>& ref = S.img[0];
-  const float h1s = H.h[1] * 256.0f, h4s = H.h[4] * 256.0f;   // tap numerators Q = 256 q (choice 7)
   float s_ref = 0, s_rr = 0, s_src = 0, s_ss = 0, s_rs = 0, s_w = 0;
+  uint64_t taps[3] = {0, 0, 0};
+  {
+    const int cls = RcpRangeClass(H, (float)(cx - radius), (float)(cx + radius), (float)(cy - radius), (float)(cy + radius));
+    uint64_t* ts = t_tap_stats;
+    ++ts[0];
+    if (cls == 0) ++ts[1];
+    if (cls == 2) ++ts[2];
+  }
   for (int i = -radius; i <= radius; i += increment) {
     float r_ref = 0, r_src = 0, r_rr = 0, r_ss = 0, r_rs = 0, r_w = 0;
     for (int j = -radius; j <= radius; j += increment) {
@@ -444,14 +501,15 @@ static inline float PatchNCC(const Pass& S, const std::vector<float>& src, const
       const float rp = RefTexel(S, ref, x, y);
       const float xf = (float)x, yf = (float)y;
 #if ORACLE_LITERAL
-      (void)h1s; (void)h4s;
       const float2_ st = Project(H, xf, yf);
       const float sp = OracleSampleU(S, src, TexULiteral(st.x, S.W), TexULiteral(st.y, S.H));
 #else
-      const float Qx = fmaf(h1s, yf, fmaf(H.h[0], xf, H.h[2]) * 256.0f);
-      const float Qy = fmaf(h4s, yf, fmaf(H.h[3], xf, H.h[5]) * 256.0f);
-      const float iz = o_rcp_tap(fmaf(H.h[7], yf, fmaf(H.h[6], xf, H.h[8])));   // choice 8
+      const float Qx = fmaf(H.h[1], yf, fmaf(H.h[0], xf, H.h[2]));   // tap numerators (choice 7)
+      const float Qy = fmaf(H.h[4], yf, fmaf(H.h[3], xf, H.h[5]));
+      const float qz = fmaf(H.h[7], yf, fmaf(H.h[6], xf, H.h[8]));
+      const float iz = o_rcp_tap(qz);   // choice 8
       const float sp = OracleSampleQ(S, src, Qx, Qy, iz);
+      TapClass(S, qz, Qx, Qy, iz, taps);
 #endif
       const float w = BilateralWeight(S, i, j, rp, ref_center_pix);
       const float wr = w * rp;
@@ -465,6 +523,7 @@ static inline float PatchNCC(const Pass& S, const std::vector<float>& src, const
     }
     s_ref += r_ref; s_rr += r_rr; s_src += r_src; s_ss += r_ss; s_rs += r_rs; s_w += r_w;
   }
+  if (taps[0] | taps[1] | taps[2]) { uint64_t* ts = t_tap_stats; ts[3] += taps[0]; ts[4] += taps[1]; ts[5] += taps[2]; }
   const float inv = 1.0f / s_w;
   s_ref *= inv; s_rr *= inv; s_src *= inv; s_ss *= inv; s_rs *= inv;
   const float var_ref = s_rr - s_ref * s_ref;
@@ -1839,9 +1898,15 @@ void oracle_rcp_tap(const float* z, float* out, long n) {
   for (long i = 0; i < n; ++i) out[i] = o_rcp_tap(z[i]);
 }
 
+// The tap-path class counts of the last oracle_pm_run (tap_stats above): test infrastructure.
+void oracle_last_tap_stats(uint64_t out[6]) {
+  for (int k = 0; k < kTapStats; ++k) out[k] = g_tap_stats[k].load(std::memory_order_relaxed);
+}
+
 // Runs one pass on the CPU.  Same structs and in/out semantics as dpe_pm_run (include/dpe_mvs.h).
 int oracle_pm_run(const DpePassInput* in, const DpePassState* st, int nthreads) {
   g_err[0] = 0;
+  tap_stats_reset();
   if (!in || !st || !st->planes || !st->weak_info || !st->selected_views) { snprintf(g_err, sizeof g_err, "null arg"); return DPE_ERR_ARG; }
   if (in->num_images > DPE_MAX_IMAGES) { snprintf(g_err, sizeof g_err, "too many images"); return DPE_ERR_TOO_MANY; }
   if (in->num_images < 2 || in->width <= 0 || in->height <= 0) { snprintf(g_err, sizeof g_err, "bad shape"); return DPE_ERR_ARG; }
@@ -1889,6 +1954,7 @@ int oracle_pm_run(const DpePassInput* in, const DpePassState* st, int nthreads) 
   S.label_boundary.assign(L * 8, mk_s2(-1, -1));
   S.radius.assign(L, 0);
   RunPass(S);
+  tap_stats_flush();   // rows run on the calling thread (nthreads 1)
   std::memcpy(st->planes, S.planes.data(), L * sizeof(float4_));
   std::memcpy(st->weak_info, S.weak.data(), L);
   std::memcpy(st->selected_views, S.sel.data(), L * sizeof(uint32_t));
@@ -2047,7 +2113,7 @@ void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
 float oracle_sample(const float* img, int W, int H, float sx, float sy) {
   Pass S; S.W = W; S.H = H;
   std::vector<float> im(img, img + (size_t)W * H);
-  return OracleSampleQ(S, im, sx * 256.0f, sy * 256.0f, 1.0f);   // the coordinate itself (iz = 1)
+  return OracleSampleQ(S, im, sx, sy, 1.0f);   // the coordinate itself (iz = 1)
 }
 
 // dpe_pass_runner_fn (include/dpe_host.h) over the restatement, so tests can drive the C++ host

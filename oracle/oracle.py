@@ -39,6 +39,8 @@ def _load(path: str = LIB):
     lib.oracle_ncc_old.restype = C.c_float
     lib.oracle_rcp_tap.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
     lib.oracle_rcp_tap.restype = None
+    lib.oracle_last_tap_stats.argtypes = [C.POINTER(C.c_uint64)]
+    lib.oracle_last_tap_stats.restype = None
     lib.oracle_expf.argtypes = [C.c_float]
     lib.oracle_expf.restype = C.c_float
     lib.oracle_sinf.argtypes = [C.c_float]
@@ -138,6 +140,18 @@ def run_pass(pass_input: dict, state: dict, threads: int = 0, library=None) -> d
     if rc != 0:
         raise RuntimeError("oracle_pm_run: " + L.oracle_last_error().decode())
     return {k: v.copy() for k, v in b.outputs().items()}
+
+
+TAP_STATS = ("patches", "patches_slow", "patches_negative", "taps_ieee_rcp", "taps_nan", "taps_clamped")
+
+
+def last_tap_stats(library=None) -> dict:
+    """Tap-path class counts of the last run_pass (dpe_oracle.cpp tap_stats): patch NCC evaluations, those
+    whose box fails the kernels' whole-patch reciprocal range test, those that pass it with a negative
+    denominator, and the taps with an out-of-range denominator exponent, a NaN coordinate, a clamped one."""
+    out = (C.c_uint64 * len(TAP_STATS))()
+    (library or lib()).oracle_last_tap_stats(out)
+    return dict(zip(TAP_STATS, (int(v) for v in out)))
 
 
 def ncc_old(pass_input: dict, x: int, y: int, view: int, plane) -> float:
