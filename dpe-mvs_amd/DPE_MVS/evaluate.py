@@ -1,9 +1,11 @@
-"""python -m DPE_MVS.evaluate recon.ply gt.ply --tau T [T ...] [--radius R] [--gpu N] [--json FILE]
+"""python -m DPE_MVS.evaluate recon.ply gt.ply --tau T [T ...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1]
+                              [--gpu N | --cpu] [--json FILE]
 
 Precision, recall and F-score of a reconstructed PLY (DPE/DPE.ply of a run with fusion) against a
 ground-truth PLY: pipeline.evaluate_clouds over the two files, the table and numbers of bin/dpe_eval.  Without
 --gpu the distances run on host threads; with it on that device: the same numbers.  The clouds are taken as
-they are (no registration, cropping or down-sampling).
+they are (no registration) unless --crop keeps the points inside a box and --voxel down-samples both clouds to
+one point per voxel first (pipeline.evaluate_clouds' crop and voxel).
 """
 from __future__ import annotations
 
@@ -21,10 +23,16 @@ def main(argv=None) -> int:
     ap.add_argument("--tau", type=float, nargs="+", required=True, help="distance thresholds (1 to 16)")
     ap.add_argument("--radius", type=float, default=None, help="truncation radius (default: the largest tau)")
     ap.add_argument("--gpu", type=int, default=-1, help="device of the distances (default: host threads)")
+    ap.add_argument("--cpu", action="store_true", help="host threads (the default)")
+    ap.add_argument("--voxel", type=float, default=None, help="down-sample both clouds to one point per voxel of this edge first")
+    ap.add_argument("--crop", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="keep the points of both clouds inside this box first")
     ap.add_argument("--json", default=None, help="also write the result to this file")
     a = ap.parse_args(argv)
     try:
-        e = pipeline.evaluate_clouds(pipeline.read_point_cloud(a.recon), pipeline.read_point_cloud(a.gt), a.tau, a.radius, a.gpu)
+        crop = None if a.crop is None else (a.crop[:3], a.crop[3:])
+        e = pipeline.evaluate_clouds(pipeline.read_point_cloud(a.recon), pipeline.read_point_cloud(a.gt), a.tau, a.radius,
+                                     -1 if a.cpu else a.gpu, voxel=a.voxel, crop=crop)
     except pipeline.PipelineError as err:
         print(f"evaluate: {err}", file=sys.stderr)
         return 1

@@ -28,7 +28,7 @@ EXPORTED = [
     "dpe_jpeg_blocks_device", "dpe_viz_launches", "dpe_live_device_bytes",
     "dpe_state_point_cloud", "dpe_state_point_cloud_wait", "dpe_point_cloud_arrays", "dpe_points_launches",
     "dpe_fusion_consistency", "dpe_consistency_launches",
-    "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings",
+    "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings", "dpe_cloud_voxel",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -141,6 +141,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_cloud_launches.restype = C.c_longlong
     lib.dpe_cloud_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
     lib.dpe_cloud_last_timings.restype = C.c_int
+    lib.dpe_cloud_voxel.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.dpe_cloud_voxel.restype = C.c_int
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
@@ -440,8 +443,29 @@ class PatchMatchContext:
                                       ba.ctypes.data), "dpe_cloud_nn_pair")
         return ab, ba
 
+    def cloud_voxel(self, points, voxel: float, colors=None) -> tuple:
+        """One record per non-empty voxel of edge `voxel` (include/dpe_mvs.h, dpe_cloud_voxel): (xyz f32 [k, 3],
+        colours u8 [k, 3] or None, first i32 [k], count i32 [k]) in ascending `first`, the bits of the serial host
+        loop (pipeline.voxel_down_sample).  points f32 [n, 3]; colors u8 [n, 3] or None."""
+        p = as_cloud(points)
+        n = len(p)
+        c = None
+        if colors is not None:
+            c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+            if len(c) != n:
+                raise ValueError("expected one colour per point")
+        xyz, first, count = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.int32)
+        rgb = None if c is None else np.empty((n, 3), np.uint8)
+        k = C.c_size_t()
+        _check(_LIB.dpe_cloud_voxel(self._ctx, p.ctypes.data, n, None if c is None else c.ctypes.data, float(voxel),
+                                    xyz.ctypes.data, None if rgb is None else rgb.ctypes.data, first.ctypes.data,
+                                    count.ctypes.data, n, C.byref(k)), "dpe_cloud_voxel")
+        k = k.value
+        return xyz[:k].copy(), (None if rgb is None else rgb[:k].copy()), first[:k].copy(), count[:k].copy()
+
     def cloud_timings(self) -> dict:
-        """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}."""
+        """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}.  After
+        cloud_voxel the four slots are, in this order, stage, cells + insert, emit and download."""
         buf = (C.c_float * 4)()
         n = _LIB.dpe_cloud_last_timings(self._ctx, buf, 4)
         return {k: float(buf[i]) for i, k in enumerate(("stage", "build", "query", "download")) if i < n}

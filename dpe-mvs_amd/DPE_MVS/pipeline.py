@@ -79,6 +79,11 @@ class DpeCloudEval(C.Structure):   # include/dpe_host.h
                 ("dropped_recon", C.c_ulonglong), ("dropped_gt", C.c_ulonglong)]
 
 
+class DpeCloudPrep(C.Structure):   # include/dpe_host.h
+    _fields_ = [("voxel", C.c_float), ("use_crop", C.c_int), ("crop_lo", C.c_float * 3), ("crop_hi", C.c_float * 3),
+                ("n_recon_in", C.c_ulonglong), ("n_gt_in", C.c_ulonglong)]
+
+
 class PipelineError(RuntimeError):
     pass
 
@@ -133,6 +138,15 @@ def lib() -> C.CDLL:
         L.dpe_host_read_point_cloud.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.dpe_host_cloud_eval.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
                                           C.c_int, C.POINTER(DpeCloudEval)]
+        L.dpe_host_cloud_voxel.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dpe_host_cloud_crop.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        L.dpe_host_cloud_crop.restype = C.c_size_t
+        L.dpe_host_read_point_cloud_rgb.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_int)]
+        L.dpe_host_cloud_eval_prep.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
+                                               C.c_int, C.POINTER(DpeCloudPrep), C.POINTER(DpeCloudEval)]
         _lib = L
     return _lib
 
@@ -417,20 +431,104 @@ def cloud_nn(query, target, radius: float) -> np.ndarray:
     return out
 
 
-def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int = -1) -> dict:
+def _as_colors(colors, n: int):
+    if colors is None:
+        return None
+    c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    if len(c) != n:
+        raise ValueError("expected one colour per point")
+    return c
+
+
+def read_point_cloud_colors(path: str):
+    """(positions f32 [n, 3], colours u8 [n, 3] as (b, g, r) or None) of a PLY: read_point_cloud plus the three uchar
+    colour properties a PLY of ours carries (diffuse_blue / green / red, or blue / green / red)."""
+    n, has = C.c_size_t(), C.c_int()
+    if lib().dpe_host_read_point_cloud_rgb(os.fsencode(path), None, None, 0, C.byref(n), C.byref(has)) != 0:
+        raise PipelineError(_last_error())
+    xyz, rgb = np.empty((n.value, 3), np.float32), np.zeros((n.value, 3), np.uint8)
+    if lib().dpe_host_read_point_cloud_rgb(os.fsencode(path), xyz.ctypes.data, rgb.ctypes.data, n.value, C.byref(n), C.byref(has)) != 0:
+        raise PipelineError(_last_error())
+    return xyz, (rgb if has.value else None)
+
+
+def crop_cloud(points, lo, hi, colors=None):
+    """(points, colours or None, original indices i32) of the finite points with lo <= p <= hi on every axis,
+    compared as floats, both ends inclusive, in their order (dpe_host_cloud_crop)."""
+    p = _as_cloud(points)
+    c = _as_colors(colors, len(p))
+    lo3, hi3 = np.ascontiguousarray(lo, np.float32).reshape(3), np.ascontiguousarray(hi, np.float32).reshape(3)
+    xyz, idx = np.empty((len(p), 3), np.float32), np.empty(len(p), np.int32)
+    rgb = None if c is None else np.empty((len(p), 3), np.uint8)
+    k = lib().dpe_host_cloud_crop(p.ctypes.data, len(p), None if c is None else c.ctypes.data, lo3.ctypes.data, hi3.ctypes.data,
+                                  xyz.ctypes.data, None if rgb is None else rgb.ctypes.data, idx.ctypes.data)
+    return xyz[:k].copy(), (None if rgb is None else rgb[:k].copy()), idx[:k].copy()
+
+
+def voxel_down_sample(points, voxel: float, colors=None, gpu_index: int = -1):
+    """One record per non-empty voxel of edge `voxel` (include/dpe_mvs.h, dpe_cloud_voxel, states the contract):
+    (xyz f32 [k, 3] lattice centroids, colours u8 [k, 3] means rounded half up or None, first i32 [k] lowest
+    original index, count i32 [k]), in ascending `first`.  gpu_index < 0: the serial host loop
+    (dpe_host_cloud_voxel), else native.PatchMatchContext.cloud_voxel on that device: the same bits."""
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            return ctx.cloud_voxel(points, voxel, colors)
+        finally:
+            ctx.close()
+    p = _as_cloud(points)
+    c = _as_colors(colors, len(p))
+    n = len(p)
+    xyz, first, count = np.empty((n, 3), np.float32), np.empty(n, np.int32), np.empty(n, np.int32)
+    rgb = None if c is None else np.empty((n, 3), np.uint8)
+    k = C.c_size_t()
+    if lib().dpe_host_cloud_voxel(p.ctypes.data, n, None if c is None else c.ctypes.data, float(voxel), xyz.ctypes.data,
+                                  None if rgb is None else rgb.ctypes.data, first.ctypes.data, count.ctypes.data, n, C.byref(k)) != 0:
+        raise PipelineError(_last_error())
+    k = k.value
+    return xyz[:k].copy(), (None if rgb is None else rgb[:k].copy()), first[:k].copy(), count[:k].copy()
+
+
+def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int = -1, voxel: float | None = None,
+                    crop=None) -> dict:
     """Precision, recall and F-score of cloud `recon` against cloud `gt` (f32 [k, 3]) at the thresholds `taus`
     (1 to 16, each 0 < tau <= radius; radius None: the largest tau), from the truncated nearest-neighbour
     distances in both directions (dpe_host_cloud_eval).  gpu_index < 0: on host threads, else on that device:
     equal dicts.  Keys: tau, precision, recall, fscore (lists), radius, mean_accuracy_truncated,
     mean_completeness_truncated (means of the distances truncated at the radius), n_recon, n_gt, dropped_recon,
-    dropped_gt (points with a non-finite coordinate; they still count in the denominators)."""
+    dropped_gt (points with a non-finite coordinate; they still count in the denominators).
+    `crop` = (lo, hi) keeps the points of both clouds inside that box first, `voxel` then down-samples both to one
+    point per voxel (voxel_down_sample; on the device too when gpu_index >= 0) before they are scored
+    (dpe_host_cloud_eval_prep).  With either the dict also has voxel (or None), crop ([lo, hi] or None), n_recon_in and
+    n_gt_in (the counts before the preparation; n_recon and n_gt are those after it)."""
     a, b = _as_cloud(recon), _as_cloud(gt)
     t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
     e = DpeCloudEval()
-    if lib().dpe_host_cloud_eval(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t),
-                                 0.0 if radius is None else float(radius), int(gpu_index), C.byref(e)) != 0:
+    prep = None
+    if voxel is not None or crop is not None:
+        prep = DpeCloudPrep()
+        prep.voxel = 0.0 if voxel is None else float(voxel)
+        if voxel is not None and not prep.voxel > 0.0:
+            raise PipelineError("cloud_eval: the voxel edge is not a finite positive number")
+        if crop is not None:
+            prep.use_crop = 1
+            for k in range(3):
+                prep.crop_lo[k], prep.crop_hi[k] = float(crop[0][k]), float(crop[1][k])
+    if lib().dpe_host_cloud_eval_prep(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t),
+                                      0.0 if radius is None else float(radius), int(gpu_index),
+                                      None if prep is None else C.byref(prep), C.byref(e)) != 0:
         raise PipelineError(_last_error())
     k = e.n_tau
+    out = _cloud_eval_dict(e, k)
+    if prep is not None:
+        out.update(voxel=(float(prep.voxel) if voxel is not None else None),
+                   crop=([[float(v) for v in prep.crop_lo], [float(v) for v in prep.crop_hi]] if crop is not None else None),
+                   n_recon_in=int(prep.n_recon_in), n_gt_in=int(prep.n_gt_in))
+    return out
+
+
+def _cloud_eval_dict(e: DpeCloudEval, k: int) -> dict:
     return dict(tau=[float(v) for v in e.tau[:k]], precision=list(e.precision[:k]), recall=list(e.recall[:k]),
                 fscore=list(e.fscore[:k]), radius=float(e.radius), mean_accuracy_truncated=e.mean_accuracy_truncated,
                 mean_completeness_truncated=e.mean_completeness_truncated, n_recon=int(e.n_recon), n_gt=int(e.n_gt),
@@ -439,7 +537,12 @@ def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int
 
 def format_cloud_eval(e: dict) -> str:
     """The table bin/dpe_eval prints, from evaluate_clouds' dict."""
-    rows = ["recon %d points (%d dropped), gt %d points (%d dropped), radius %.9g"
+    rows = []
+    if "n_recon_in" in e:
+        box = "none" if e["crop"] is None else "[%.9g %.9g %.9g] to [%.9g %.9g %.9g]" % tuple(e["crop"][0] + e["crop"][1])
+        rows.append("prepared: voxel %.9g, crop %s, from recon %d points, gt %d points"
+                    % (e["voxel"] or 0.0, box, e["n_recon_in"], e["n_gt_in"]))
+    rows += ["recon %d points (%d dropped), gt %d points (%d dropped), radius %.9g"
             % (e["n_recon"], e["dropped_recon"], e["n_gt"], e["dropped_gt"], e["radius"]),
             "%14s %10s %10s %10s" % ("tau", "precision", "recall", "fscore")]
     rows += ["%14.9g %10.6f %10.6f %10.6f" % v for v in zip(e["tau"], e["precision"], e["recall"], e["fscore"])]

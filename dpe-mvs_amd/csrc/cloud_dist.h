@@ -104,4 +104,63 @@ inline bool cloud_grid_make(const float lo[3], const float hi[3], size_t m, floa
   return true;
 }
 
+// ---- voxel down-sampling (dpe_cloud_voxel of include/dpe_mvs.h, which states the contract; the kernels are
+// pass_voxel.h's, the serial loop host/cloud_voxel.cpp's).  A voxel is a cell of edge h = (double)v over the
+// origin o = the per-axis minimum of the finite points.  Everything a record holds is a sum, a minimum or a
+// count over the voxel's points in integers, so it does not depend on the order in which they are met.
+
+// the voxel grid of a cloud; filled by the host from the cloud's bounds (voxel_grid_make)
+struct VoxelGrid {
+  double o[3];      // origin: per-axis minimum of the finite points
+  double h;         // voxel edge
+};
+
+// The grid of a cloud with finite bounds lo[3] <= hi[3] (float).  False: the extent reaches kCloudMaxCell
+// voxels on an axis (decided on the double, as cloud_grid_make does).
+inline bool voxel_grid_make(const float lo[3], const float hi[3], float v, VoxelGrid* g) {
+  g->h = (double)v;
+  for (int a = 0; a < 3; ++a) {
+    g->o[a] = (double)lo[a];
+    const double u = ((double)hi[a] - (double)lo[a]) / g->h;
+    if (!(u < kCloudMaxCell)) return false;
+  }
+  return true;
+}
+
+// Slots of the open-addressing table for m finite points: the power of two at or above 2 m, 64 at least and
+// 2^31 at most (a slot index is kept in an int; m < 2^31, so even then the table is never full).
+inline uint64_t voxel_slot_count(size_t m) {
+  uint64_t s = 64;
+  while (s < (1ull << 31) && s < 2 * (uint64_t)m) s <<= 1;
+  return s;
+}
+
+// One axis of a finite point of the cloud the grid was made from: u = (x - o) / h in [0, 2^30) (cloud_cell's
+// arithmetic, never clamped), *c = floor(u), and the return value q = (uint64)((u - c) * 2^32) truncated: the
+// point's place inside the voxel on a lattice of 2^32 steps.  u - c is exact and lies in [0, 1), so q < 2^32.
+DPE_CHD uint32_t voxel_cell_frac(float x, double origin, double h, int32_t* c) {
+  const double u = ((double)x - origin) / h;
+  const long long t = (long long)u;
+  const long long fl = (double)t > u ? t - 1 : t;
+  *c = (int32_t)fl;
+  const double f = u - (double)fl;
+  return (uint32_t)(unsigned long long)(f * 4294967296.0);
+}
+
+// The coordinate of a voxel's record on one axis from the integer sum S of its points' q: every operation a
+// rounded double operation in this order, then one rounding to float.
+DPE_CHD float voxel_coord(double origin, double h, int32_t c, unsigned long long S, int32_t count) {
+  const double mean = (double)S / (double)count;
+  const double t = mean * 0x1p-32;
+  const double u = (double)c + t;
+  const double w = u * h;
+  return (float)(origin + w);
+}
+
+// The colour channel of a voxel's record from the 64-bit sum of its points' channel: the mean rounded half up.
+DPE_CHD uint8_t voxel_colour(unsigned long long sum, int32_t count) {
+  const unsigned long long n = (unsigned long long)count;
+  return (uint8_t)((2ull * sum + n) / (2ull * n));
+}
+
 }  // namespace dpe

@@ -229,6 +229,18 @@ struct CloudScratch {
   DevArr<float4> st, sq;             // target / query points in bucket order: (x, y, z, original index)
   DevArr<int> tcnt, qcnt;            // per bucket: counts -> starts -> ends
   DevArr<float> out;                 // the distances, by original index
+  // dpe_cloud_voxel (pass_voxel.h); the cloud is staged in pts[0], its bounds in bounds[0..7]
+  DevArr<uint8_t> vrgb;              // the colours as the caller packs them, u8 [n][3]
+  DevArr<int4> vcell;                // per point: cell and valid flag
+  DevArr<uint32_t> vfrac;            // per point: the three lattice fractions
+  DevArr<int> vowner, vcount;        // the table, per slot
+  DevArr<uint32_t> vfirst;
+  DevArr<unsigned long long> vsum, vcsum;   // per slot and axis / channel
+  DevArr<int> vslot_at, vbcnt;       // per point: the slot it is the first point of, or -1; per block: marked -> offsets
+  DevArr<uint32_t> verr;             // the insert kernel's error word
+  DevArr<float> vout_xyz;            // the records
+  DevArr<uint8_t> vout_rgb;
+  DevArr<int> vout_first, vout_count;
 };
 
 }  // namespace dpe

@@ -132,8 +132,9 @@ void cloud_stats(const float* d2, size_t n, const float* tau, int n_tau, double*
 
 }  // namespace
 
-bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
-                int gpu_index, DpeCloudEval* out, std::string& err) {
+// what cloud_eval refuses before any work, and the radius R it uses
+static bool cloud_eval_args(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                            const DpeCloudEval* out, float* R_out, std::string& err) {
   if (!out || !tau || n_tau < 1 || n_tau > DPE_CLOUD_MAX_TAU) { err = "cloud_eval: 1 to 16 thresholds expected"; return false; }
   if (n > (size_t)INT_MAX || m > (size_t)INT_MAX || (!recon && n) || (!gt && m)) { err = "cloud_eval: bad cloud"; return false; }
   float tmax = 0.0f;
@@ -144,16 +145,20 @@ bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const f
   const float R = radius == 0.0f ? tmax : radius;
   if (!cloud_radius_ok(R)) { err = "cloud_eval: the radius is not a finite positive number"; return false; }
   if (tmax > R) { err = "cloud_eval: a threshold exceeds the radius"; return false; }
+  *R_out = R;
+  return true;
+}
+
+bool cloud_eval_in(DpeContext* ctx, const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau,
+                   float radius, DpeCloudEval* out, std::string& err) {
+  float R = 0.0f;
+  if (!cloud_eval_args(recon, n, gt, m, tau, n_tau, radius, out, &R, err)) return false;
   std::vector<float> a(n), c(m);
-  if (gpu_index < 0) {
+  if (!ctx) {
     if (!cloud_nn(recon, n, gt, m, R, a.data(), err) || !cloud_nn(gt, m, recon, n, R, c.data(), err)) return false;
-  } else {
-    DpeContext* ctx = dpe_create(gpu_index);
-    if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
-    const int rc = dpe_cloud_nn_pair(ctx, recon, n, gt, m, R, a.data(), c.data());
-    if (rc != 0) err = std::string("cloud_eval: ") + dpe_last_error();
-    dpe_destroy(ctx);
-    if (rc != 0) return false;
+  } else if (dpe_cloud_nn_pair(ctx, recon, n, gt, m, R, a.data(), c.data()) != 0) {
+    err = std::string("cloud_eval: ") + dpe_last_error();
+    return false;
   }
   *out = DpeCloudEval{};
   out->n_tau = n_tau;
@@ -170,6 +175,18 @@ bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const f
     out->fscore[k] = p + r > 0.0 ? 2.0 * p * r / (p + r) : 0.0;
   }
   return true;
+}
+
+bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                int gpu_index, DpeCloudEval* out, std::string& err) {
+  if (gpu_index < 0) return cloud_eval_in(nullptr, recon, n, gt, m, tau, n_tau, radius, out, err);
+  float R = 0.0f;
+  if (!cloud_eval_args(recon, n, gt, m, tau, n_tau, radius, out, &R, err)) return false;   // before a context is made
+  DpeContext* ctx = dpe_create(gpu_index);
+  if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
+  const bool ok = cloud_eval_in(ctx, recon, n, gt, m, tau, n_tau, radius, out, err);
+  dpe_destroy(ctx);
+  return ok;
 }
 
 }  // namespace dpe_host

@@ -1,6 +1,8 @@
 // eval_cli.cpp — bin/dpe_eval: precision, recall and F-score of a reconstructed PLY against a ground-truth
 // PLY (dpe_host_cloud_eval, include/dpe_host.h).
-//   dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--gpu N | --cpu] [--json FILE]
+//   dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1] [--gpu N | --cpu] [--json FILE]
+// --voxel V down-samples both clouds to one point per voxel of edge V before they are scored, --crop keeps the
+// points inside the box first (dpe_host_cloud_eval_prep); with either the table gets a first line naming them.
 // --gpu N (the default, N = 0) runs the distances on that device, --cpu on host threads: the same numbers.
 // Prints one table; --json also writes the struct.  `python -m DPE_MVS.evaluate` prints the same table.
 #include <cstdio>
@@ -12,7 +14,8 @@
 #include "../../include/dpe_host.h"
 
 static int usage() {
-  std::fprintf(stderr, "usage: dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--gpu N | --cpu] [--json FILE]\n");
+  std::fprintf(stderr, "usage: dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1]"
+                       " [--gpu N | --cpu] [--json FILE]\n");
   return 2;
 }
 
@@ -33,16 +36,29 @@ int main(int argc, char** argv) {
   float radius = 0.0f;
   int gpu = 0;
   const char* json = nullptr;
+  DpeCloudPrep prep{};
+  bool prepared = false, have_voxel = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--cpu") gpu = -1;
     else if (a == "--gpu" && i + 1 < argc) gpu = std::atoi(argv[++i]);
     else if (a == "--radius" && i + 1 < argc) radius = std::strtof(argv[++i], nullptr);
     else if (a == "--json" && i + 1 < argc) json = argv[++i];
+    else if (a == "--voxel" && i + 1 < argc) { prep.voxel = std::strtof(argv[++i], nullptr); prepared = have_voxel = true; }
+    else if (a == "--crop" && i + 6 < argc) {
+      for (int k = 0; k < 3; ++k) prep.crop_lo[k] = std::strtof(argv[++i], nullptr);
+      for (int k = 0; k < 3; ++k) prep.crop_hi[k] = std::strtof(argv[++i], nullptr);
+      prep.use_crop = 1;
+      prepared = true;
+    }
     else if (a.rfind("--", 0) == 0) return usage();
     else pos.push_back(argv[i]);
   }
   if (pos.size() < 3) return usage();
+  if (have_voxel && !(prep.voxel > 0.0f)) {   // 0 means "none" in the block; asked for on the command line it is an error
+    std::fprintf(stderr, "dpe_eval: cloud_eval: the voxel edge is not a finite positive number\n");
+    return 1;
+  }
   std::vector<float> tau;
   for (size_t k = 2; k < pos.size(); ++k) {
     char* end = nullptr;
@@ -53,9 +69,19 @@ int main(int argc, char** argv) {
   size_t n = 0, m = 0;
   DpeCloudEval e;
   if (!read_cloud(pos[0], recon, n) || !read_cloud(pos[1], gt, m) ||
-      dpe_host_cloud_eval(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu, &e) != 0) {
+      dpe_host_cloud_eval_prep(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu, prepared ? &prep : nullptr,
+                               &e) != 0) {
     std::fprintf(stderr, "dpe_eval: %s\n", dpe_pipeline_last_error());
     return 1;
+  }
+  if (prepared) {
+    std::printf("prepared: voxel %.9g, crop", (double)prep.voxel);
+    if (prep.use_crop)
+      std::printf(" [%.9g %.9g %.9g] to [%.9g %.9g %.9g]", (double)prep.crop_lo[0], (double)prep.crop_lo[1], (double)prep.crop_lo[2],
+                  (double)prep.crop_hi[0], (double)prep.crop_hi[1], (double)prep.crop_hi[2]);
+    else
+      std::printf(" none");
+    std::printf(", from recon %llu points, gt %llu points\n", prep.n_recon_in, prep.n_gt_in);
   }
   std::printf("recon %llu points (%llu dropped), gt %llu points (%llu dropped), radius %.9g\n", e.n_recon, e.dropped_recon,
               e.n_gt, e.dropped_gt, (double)e.radius);
@@ -75,8 +101,19 @@ int main(int argc, char** argv) {
     json_array(f, "fscore", e.fscore, e.n_tau);
     std::fprintf(f, ", \"mean_accuracy_truncated\": %.17g, \"mean_completeness_truncated\": %.17g, ", e.mean_accuracy_truncated,
                  e.mean_completeness_truncated);
-    std::fprintf(f, "\"n_recon\": %llu, \"n_gt\": %llu, \"dropped_recon\": %llu, \"dropped_gt\": %llu}\n", e.n_recon, e.n_gt,
+    std::fprintf(f, "\"n_recon\": %llu, \"n_gt\": %llu, \"dropped_recon\": %llu, \"dropped_gt\": %llu", e.n_recon, e.n_gt,
                  e.dropped_recon, e.dropped_gt);
+    if (prepared) {
+      if (have_voxel) std::fprintf(f, ", \"voxel\": %.17g", (double)prep.voxel);
+      else std::fprintf(f, ", \"voxel\": null");
+      std::fprintf(f, ", \"n_recon_in\": %llu, \"n_gt_in\": %llu, \"crop\": ", prep.n_recon_in, prep.n_gt_in);
+      if (prep.use_crop)
+        std::fprintf(f, "[[%.17g, %.17g, %.17g], [%.17g, %.17g, %.17g]]", (double)prep.crop_lo[0], (double)prep.crop_lo[1],
+                     (double)prep.crop_lo[2], (double)prep.crop_hi[0], (double)prep.crop_hi[1], (double)prep.crop_hi[2]);
+      else
+        std::fprintf(f, "null");
+    }
+    std::fprintf(f, "}\n");
     std::fclose(f);
   }
   return 0;

@@ -146,5 +146,23 @@ bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const f
                 int gpu_index, DpeCloudEval* out, std::string& err);
 // ply_read.cpp: the vertex positions of an ascii / binary little-endian PLY; xyz == nullptr: *n only
 bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n, std::string& err);
+// the same with the file's three uchar colours as (b, g, r) in rgb[3 * i ...]; *has_rgb = 0 and rgb untouched for a
+// file without them
+bool read_point_cloud_rgb(const std::string& path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb,
+                          std::string& err);
+// cloud_eval.cpp: cloud_eval over a context the caller owns (nullptr: on host threads)
+bool cloud_eval_in(DpeContext* ctx, const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau,
+                   float radius, DpeCloudEval* out, std::string& err);
+// cloud_voxel.cpp: the voxel down-sampling of dpe_cloud_voxel (dpe_mvs.h) as a serial loop over the same
+// arithmetic (csrc/cloud_dist.h); false with more voxels than `cap` (*k = their number, nothing written) and
+// for what dpe_cloud_voxel refuses
+bool cloud_voxel(const float* xyz, size_t n, const uint8_t* rgb, float voxel, float* out_xyz, uint8_t* out_rgb,
+                 int32_t* out_first, int32_t* out_count, size_t cap, size_t* k, std::string& err);
+// the indices of the finite points with lo[a] <= p[a] <= hi[a] on every axis, ascending
+void cloud_crop(const float* xyz, size_t n, const float lo[3], const float hi[3], std::vector<int32_t>& keep);
+// crop (optional) and down-sampling (voxel > 0) of both clouds, then cloud_eval_in: gpu_index >= 0 runs the
+// down-sampling and the distances in one context on that device
+bool cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                     int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err);
 
 }  // namespace dpe_host

@@ -3,6 +3,8 @@
 // position; a double is rounded to float), every other scalar property skipped by its size, elements after
 // `vertex` ignored.  It reads what export_point_cloud (fusion.cpp) writes.  The file comes from outside: every
 // count and size is checked before it is used, and nothing is trusted beyond the bytes that were read.
+// dpe_host_read_point_cloud_rgb also returns the three uchar colours such a file carries (diffuse_blue / green /
+// red, or blue / green / red), as (b, g, r), and says whether the file had them.
 #include "host.h"
 
 #include <algorithm>
@@ -58,9 +60,12 @@ bool parse_count(const std::string& s, unsigned long long& v) {
 
 }  // namespace
 
-bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n, std::string& err) {
+// the reader behind read_point_cloud and read_point_cloud_rgb: rgb / has_rgb null for the positions alone
+static bool read_ply_vertices(const std::string& path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb,
+                              std::string& err) {
   if (!n) { err = "read_point_cloud: null argument"; return false; }
   *n = 0;
+  if (has_rgb) *has_rgb = 0;
   std::unique_ptr<FILE, FileCloser> file(std::fopen(path.c_str(), "rb"));
   FILE* f = file.get();
   if (!f) { err = "cannot read " + path; return false; }
@@ -117,10 +122,17 @@ bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n
   // where x, y, z sit in a vertex
   int col[3] = {-1, -1, -1}, off[3] = {0, 0, 0};
   bool dbl[3] = {false, false, false};
+  // and the three uchar colours of a PLY of ours, in the order blue, green, red
+  static const char* const kColour[3][2] = {{"diffuse_blue", "blue"}, {"diffuse_green", "green"}, {"diffuse_red", "red"}};
+  int ccol[3] = {-1, -1, -1}, coff[3] = {0, 0, 0};
   size_t stride = 0;
   for (size_t k = 0; k < V.props.size(); ++k) {
     const PlyProperty& p = V.props[k];
     if (p.list) { err = path + ": a list property inside the vertex element is not supported"; return false; }
+    for (int a = 0; a < 3; ++a) {
+      if (ccol[a] >= 0 || (p.type != "uchar" && p.type != "uint8") || (p.name != kColour[a][0] && p.name != kColour[a][1])) continue;
+      ccol[a] = (int)k; coff[a] = (int)stride;
+    }
     for (int a = 0; a < 3; ++a) {
       if (p.name != std::string(1, "xyz"[a]) || col[a] >= 0) continue;
       if (!ply_is_float(p.type) && !ply_is_double(p.type)) { err = path + ": coordinate " + p.name + " is neither float nor double"; return false; }
@@ -146,7 +158,10 @@ bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n
     }
   }
   *n = (size_t)V.count;
+  const bool colours = ccol[0] >= 0 && ccol[1] >= 0 && ccol[2] >= 0;
+  if (has_rgb) *has_rgb = colours ? 1 : 0;
   if (!xyz) return true;   // size query
+  if (!colours) rgb = nullptr;
   if (cap < *n) { err = path + ": point buffer too small"; return false; }
   if (binary) {
     const size_t kBatch = 4096;
@@ -159,6 +174,7 @@ bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n
         for (int a = 0; a < 3; ++a) {
           if (dbl[a]) { double d; std::memcpy(&d, v + off[a], 8); xyz[3 * (i0 + i) + a] = (float)d; }
           else std::memcpy(&xyz[3 * (i0 + i) + a], v + off[a], 4);
+          if (rgb) rgb[3 * (i0 + i) + a] = v[coff[a]];
         }
       }
     }
@@ -179,13 +195,31 @@ bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n
       if (end == p) { err = path + ": truncated body"; return false; }
       for (int a = 0; a < 3; ++a)
         if (col[a] == k) xyz[3 * i + a] = dbl[a] ? (float)d : std::strtof(p, nullptr);
+      for (int a = 0; a < 3; ++a)
+        if (rgb && ccol[a] == k) rgb[3 * i + a] = (uint8_t)(d >= 255.0 ? 255 : d > 0.0 ? (int)d : 0);
       p = end;
     }
   }
   return true;
 }
 
+bool read_point_cloud(const std::string& path, float* xyz, size_t cap, size_t* n, std::string& err) {
+  return read_ply_vertices(path, xyz, nullptr, cap, n, nullptr, err);
+}
+
+bool read_point_cloud_rgb(const std::string& path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb,
+                          std::string& err) {
+  return read_ply_vertices(path, xyz, rgb, cap, n, has_rgb, err);
+}
+
 }  // namespace dpe_host
+
+extern "C" int dpe_host_read_point_cloud_rgb(const char* path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb) {
+  std::string err;
+  if (path && dpe_host::read_point_cloud_rgb(path, xyz, rgb, cap, n, has_rgb, err)) return 0;
+  dpe_host::set_last_error(path ? err : "read_point_cloud: null argument");
+  return 1;
+}
 
 extern "C" int dpe_host_read_point_cloud(const char* path, float* xyz, size_t cap, size_t* n) {
   std::string err;

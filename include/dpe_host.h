@@ -262,7 +262,8 @@ int dpe_host_consistency_angle_test(float dot);
 /*
  * Cloud evaluation: precision, recall and F-score of a reconstructed cloud against a ground-truth cloud.
  * No counterpart in the reference.  The numbers are those of the two clouds as given: no registration,
- * cropping or down-sampling, so they are not a benchmark's leaderboard figures.
+ * cropping or down-sampling (dpe_host_cloud_eval_prep below adds a crop box and voxel down-sampling; registration
+ * stays out), so they are not a benchmark's leaderboard figures.
  *   dpe_host_cloud_nn          the contract of dpe_cloud_nn (dpe_mvs.h: d2, truncation at R2 = R*R, non-finite
  *                              points) over the same grid on host threads (at most 16): the same bits.  The
  *                              yardstick of the device path and the path used without a GPU.
@@ -299,6 +300,46 @@ int dpe_host_cloud_nn(const float* query, size_t n, const float* target, size_t 
 int dpe_host_read_point_cloud(const char* path, float* xyz, size_t cap, size_t* n);
 int dpe_host_cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                         int gpu_index, DpeCloudEval* out);
+
+/*
+ * Preparing clouds for the evaluation, and thinning one: crop box and voxel down-sampling.
+ *   dpe_host_cloud_voxel           the contract of dpe_cloud_voxel (dpe_mvs.h: cell, lattice centroid, colour
+ *                                  mean rounded half up, first, count, ascending `first`) as a serial loop with
+ *                                  a hash map over the same header functions (csrc/cloud_dist.h): the same
+ *                                  bits.  The yardstick of the device path and the path used without a GPU.
+ *                                  A voxel holding one point may return that point moved by one float ulp.
+ *                                  More voxels than `cap`: nonzero, *k = their number, nothing written.
+ *   dpe_host_cloud_crop            keeps the points that are finite and have lo[a] <= p[a] <= hi[a] on every
+ *                                  axis, compared as floats (both ends inclusive), in their order; colours (u8
+ *                                  [n][3], or NULL) are carried along.  Writes the kept points, colours and
+ *                                  original indices (each output may be NULL) and returns their number; the
+ *                                  outputs hold n entries at most.
+ *   dpe_host_read_point_cloud_rgb  dpe_host_read_point_cloud plus the three `uchar` colour properties a PLY of
+ *                                  ours carries, diffuse_blue / diffuse_green / diffuse_red or blue / green /
+ *                                  red, into rgb u8 [cap][3] as (b, g, r).  *has_rgb = 1 when the file has all
+ *                                  three, else 0 and rgb is left alone.  The refusals are the same.
+ *   dpe_host_cloud_eval_prep       dpe_host_cloud_eval after a preparation: both clouds are cropped to the box
+ *                                  first (use_crop != 0), then down-sampled (voxel > 0; 0 = none), then scored.
+ *                                  gpu_index >= 0 runs the down-sampling on that device in the same context as
+ *                                  the distances; both paths fill equal structs.  n_recon and n_gt of
+ *                                  DpeCloudEval are the counts AFTER the preparation; the counts before it come
+ *                                  back in prep->n_recon_in and prep->n_gt_in.  prep = NULL is
+ *                                  dpe_host_cloud_eval unchanged.
+ * dpe_host_cloud_crop returns a count; the others 0, or nonzero with the message in dpe_pipeline_last_error().
+ */
+typedef struct DpeCloudPrep {
+  float voxel;                          /* voxel edge; 0: no down-sampling */
+  int use_crop;                         /* nonzero: keep crop_lo <= p <= crop_hi */
+  float crop_lo[3], crop_hi[3];
+  unsigned long long n_recon_in, n_gt_in;   /* out: the counts before the preparation */
+} DpeCloudPrep;
+int dpe_host_cloud_voxel(const float* xyz, size_t n, const uint8_t* rgb_or_null, float voxel, float* out_xyz,
+                         uint8_t* out_rgb, int32_t* out_first, int32_t* out_count, size_t cap, size_t* k);
+size_t dpe_host_cloud_crop(const float* xyz, size_t n, const uint8_t* rgb_or_null, const float* lo, const float* hi,
+                           float* out_xyz, uint8_t* out_rgb, int32_t* out_index);
+int dpe_host_read_point_cloud_rgb(const char* path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb);
+int dpe_host_cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                             int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out);
 
 #ifdef __cplusplus
 }

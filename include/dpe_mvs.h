@@ -471,6 +471,44 @@ int dpe_cloud_nn_pair(DpeContext* ctx, const float* a, size_t n, const float* b,
 long long dpe_cloud_launches(void);
 int dpe_cloud_last_timings(DpeContext* ctx, float* ms, int n);
 
+/*
+ * Voxel down-sampling: one record per non-empty voxel of a cloud, what the ETH3D and Tanks-and-Temples tools
+ * do to both clouds before they score, and a way to thin a fused cloud.  No counterpart in the reference.
+ *
+ * Inputs (HOST arrays): n points, packed f32 [n][3], n <= 2^31 - 1; optionally n colours, u8 [n][3] (three
+ * channels in the caller's order, each treated alike); a voxel edge v, a finite float > 0.  Anything else is
+ * DPE_ERR_ARG ("bad argument").
+ * Output, k records: xyz f32 [k][3]; rgb u8 [k][3] (only when colours were given); first i32 [k]; count i32 [k].
+ *
+ * Cell of a point.  A point with a non-finite coordinate belongs to no voxel.  o[a] = the per-axis minimum of
+ * the finite points as a double, h = (double)v, u = ((double)x - o) / h, c = floor(u) (dpe_cloud_nn's cell
+ * arithmetic).  An extent (max - min) / h of 2^30 cells or more on an axis, decided on the double, is
+ * DPE_ERR_ARG ("voxel too small for the cloud's extent").
+ * Position.  The centroid is taken on a lattice of 2^32 steps per voxel edge, so that it is an exact integer
+ * sum and depends on no order: per point and axis f = u - c (exact, in [0, 1)) and q = (uint64)(f * 2^32),
+ * truncated; per voxel and axis S = sum of q in uint64 (below 2^63 for any n); the coordinate is
+ *   (float)(o + ((double)c + ((double)S / (double)count) * 2^-32) * h)
+ * every operation a rounded double operation in exactly this order, without contraction.  The lattice costs less
+ * than h * 2^-32 per coordinate against the real-number centroid.  A voxel that holds ONE point may return that
+ * point moved by one float ulp: the record is the lattice expression above, not a copy of the input.
+ * Colour.  Per channel (2 * sum + count) / (2 * count) in integers, the mean rounded half up; the sums are
+ * 64 bits wide, exact for any n.
+ * first = the lowest original index among the voxel's points, count = their number.
+ * Order.  Ascending `first`: the order in which a serial loop over the points meets the voxels.
+ * Everything in a record is a sum, a minimum or a count over a set, so the result is the serial loop's to the
+ * bit whatever the schedule (dpe_host_cloud_voxel, dpe_host.h, is that loop).
+ *
+ *   dpe_cloud_voxel  writes at most `cap` records and their number into *k.  With more voxels than `cap` it
+ *                    writes no record, stores the number of voxels in *k and returns DPE_ERR_ARG (cap = n
+ *                    always fits).  n = 0 or no finite point: *k = 0 and no kernel beyond the staging of the
+ *                    cloud.  Concurrency as dpe_cloud_nn: waits until the context is quiet, runs on its stream,
+ *                    synchronous.  An open-addressing table over the cells (csrc/pass_voxel.h); its buffers
+ *                    belong to the context like dpe_cloud_nn's, every launch counts in dpe_cloud_launches, and
+ *                    dpe_cloud_last_timings then reports [0] stage, [1] cells + insert, [2] emit, [3] download.
+ */
+int dpe_cloud_voxel(DpeContext* ctx, const float* xyz, size_t n, const uint8_t* rgb_or_null, float voxel, float* out_xyz,
+                    uint8_t* out_rgb, int32_t* out_first, int32_t* out_count, size_t cap, size_t* k);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);

@@ -12,7 +12,18 @@ same bits, which is checked on every size.
 Also runs the smallest end-to-end case (64 x 48, 4 views, fusion) and records the F-scores of DPE/DPE.ply
 against the scene's ground truth at 1, 2, 4, 8 pixel footprints.
 
-Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5]"""
+With --voxel V the tool measures the voxel down-sampling instead (dpe_cloud_voxel in a warm context against the
+serial host loop dpe_host_cloud_voxel) on the 800 x 600 pair, 1.92 million points each, at voxel edge V, and writes
+profiles/cloud_voxel.json: the device time by part (stage, cells + insert, emit, download: dpe_cloud_last_timings),
+the host loop's time, the bytes of device scratch per point, the cells + insert part on the 24 096 points of the
+tests' line cloud, whose crowd of 20 000 shares ONE voxel at edge 0.01, and on the same cloud without the crowd (what
+contention on one slot costs), and the 64 x 48 end-to-end F-scores with both clouds down-sampled at tau_max / 2.
+
+With --voxel V --ab LIB LIB... it instead compares builds of libdpe_mvs.so (tools/build_variants.sh) on the
+down-sampling, interleaved in one process: the cells + insert part and the whole call's wall time per build on the
+800 x 600 cloud and on the two line clouds, every build held to the first one's records.
+
+Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]]"""
 import argparse
 import json
 import os
@@ -27,9 +38,12 @@ import numpy as np  # noqa: E402
 from DPE_MVS import native, pipeline, synthetic  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cloud_eval.json"))
+ap.add_argument("--out", default=None)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--voxel", type=float, default=None, help="measure the voxel down-sampling at this edge instead")
+ap.add_argument("--ab", nargs="+", default=None, help="with --voxel: builds of libdpe_mvs.so to compare, interleaved")
 a = ap.parse_args()
+a.out = a.out or os.path.join(ROOT, "profiles", "cloud_eval.json" if a.voxel is None else "cloud_voxel.json")
 
 
 def best_of(fn, reps):
@@ -43,6 +57,128 @@ def best_of(fn, reps):
             best, extra = dt, x
     return best, extra
 
+
+def same_records(x, y):
+    return all((p is None and q is None) or (p.dtype == q.dtype and p.tobytes() == q.tobytes()) for p, q in zip(x, y))
+
+
+def line_cloud():
+    """The target of the tests' line cloud (tests/test_cloud_eval.py): 4 096 points along one axis and a crowd of
+    20 000 inside one cell of edge 0.01; returns (all of it, the line alone)."""
+    R = 0.01
+    rng = np.random.default_rng(9)
+    line = np.zeros((4096, 3))
+    line[:, 0] = np.sort(rng.random(4096)) * 1e4 * R
+    line[:, 1:] = rng.random((4096, 2)) * 0.5 * R
+    crowd = np.array([50.25 * R, 0.1 * R, 0.1 * R]) + rng.random((20000, 3)) * 0.4 * R
+    return np.concatenate([line, crowd]).astype(np.float32), line.astype(np.float32)
+
+
+def voxel_profile():
+    out = {"voxel": a.voxel, "clouds": []}
+    live0 = native.live_device_bytes()
+    ctx = native.PatchMatchContext(0)
+    ctx.set_timing(True)
+    sc = synthetic.make_scene(800, 600, 4)
+    A = synthetic.gt_point_cloud(sc)
+    del sc
+    rng = np.random.default_rng(3)
+    tau = 2 * 5.0 / (1.2 * 800)
+    u = rng.normal(0, 1, A.shape)
+    B = (A + 0.5 * tau * u / np.linalg.norm(u, axis=1, keepdims=True)).astype(np.float32)
+    col = rng.integers(0, 256, A.shape).astype(np.uint8)
+    for name, P, C in (("A", A, None), ("B", B, None), ("A with colours", A, col)):
+        host_s, h = best_of(lambda: pipeline.voxel_down_sample(P, a.voxel, C), max(1, a.reps // 2))
+
+        def device():
+            r = ctx.cloud_voxel(P, a.voxel, C)
+            return r, ctx.cloud_timings()
+        dev_s, (d, parts) = best_of(device, a.reps)
+        parts = dict(zip(("stage", "cells_insert", "emit", "download"), parts.values()))
+        row = {"cloud": name, "points": int(len(P)), "voxels": int(len(d[0])), "largest_voxel": int(d[3].max()),
+               "host_seconds": host_s, "device_seconds": dev_s, "device_parts_ms": parts, "identical": same_records(h, d)}
+        out["clouds"].append(row)
+        print(json.dumps(row), flush=True)
+    out["scratch_bytes_per_point_with_colours"] = (native.live_device_bytes() - live0) / len(A)
+    full, line = line_cloud()
+    for name, P in (("line cloud, 20 000 points in one voxel", full), ("line cloud without that voxel", line)):
+
+        def device():
+            r = ctx.cloud_voxel(P, 0.01)
+            return r, ctx.cloud_timings()
+        dev_s, (d, parts) = best_of(device, a.reps)
+        parts = dict(zip(("stage", "cells_insert", "emit", "download"), parts.values()))
+        row = {"cloud": name, "points": int(len(P)), "voxels": int(len(d[0])), "largest_voxel": int(d[3].max()),
+               "device_seconds": dev_s, "device_parts_ms": parts, "identical": same_records(pipeline.voxel_down_sample(P, 0.01), d)}
+        out["clouds"].append(row)
+        print(json.dumps(row), flush=True)
+    ctx.close()
+    folder = tempfile.mkdtemp(prefix="dpe_cloud_voxel_prof_")
+    try:
+        sc = synthetic.write_dense_folder(folder, 64, 48, 4)
+        pipeline.run_dpe_pipeline(folder, gpu_index=0, verbose=False, fusion=True)
+        recon = pipeline.read_point_cloud(os.path.join(folder, pipeline.OUT_NAME, "DPE.ply"))
+        foot = 5.0 / (1.2 * 64)
+        e = pipeline.evaluate_clouds(recon, synthetic.gt_point_cloud(sc), [foot, 2 * foot, 4 * foot, 8 * foot], gpu_index=0, voxel=4 * foot)
+        out["end_to_end_64x48x4_voxel_half_tau_max"] = {k: e[k] for k in ("tau", "voxel", "precision", "recall", "fscore", "n_recon_in", "n_gt_in",
+                                                                          "n_recon", "n_gt")}
+        print(json.dumps(out["end_to_end_64x48x4_voxel_half_tau_max"]), flush=True)
+    finally:
+        shutil.rmtree(folder, ignore_errors=True)
+    return out
+
+
+def voxel_ab(paths):
+    import ctypes as C
+    sc = synthetic.make_scene(800, 600, 4)
+    A = synthetic.gt_point_cloud(sc)
+    del sc
+    col = np.random.default_rng(3).integers(0, 256, A.shape).astype(np.uint8)
+    full, line = line_cloud()
+    clouds = (("A", A, None, a.voxel), ("A with colours", A, col, a.voxel), ("line cloud, 20 000 points in one voxel", full, None, 0.01),
+              ("line cloud without that voxel", line, None, 0.01))
+    libs = [(p, native.load_library(p)) for p in paths]
+    ctxs = [(p, L, L.dpe_create(0)) for p, L in libs]
+    for _, L, c in ctxs:
+        L.dpe_set_timing(c, 1)
+    out = {"voxel": a.voxel, "rounds": a.reps, "builds": paths, "clouds": []}
+    for name, P, Cc, v in clouds:
+        n = len(P)
+        xyz, rgb, first, count = np.empty((n, 3), np.float32), np.empty((n, 3), np.uint8), np.empty(n, np.int32), np.empty(n, np.int32)
+        k, ms = C.c_size_t(), (C.c_float * 4)()
+        ref, rows = None, {p: {"cells_insert_ms": [], "wall_ms": []} for p in paths}
+        for rnd in range(a.reps + 1):                      # round 0 warms up
+            for p, L, c in ctxs:
+                t = time.perf_counter()
+                rc = L.dpe_cloud_voxel(c, P.ctypes.data, n, None if Cc is None else Cc.ctypes.data, v, xyz.ctypes.data,
+                                       None if Cc is None else rgb.ctypes.data, first.ctypes.data, count.ctypes.data, n, C.byref(k))
+                dt = time.perf_counter() - t
+                assert rc == 0, (p, L.dpe_last_error())
+                got = b"".join(x[:k.value].tobytes() for x in ((xyz, first, count) if Cc is None else (xyz, rgb, first, count)))
+                ref = ref or got
+                assert got == ref, f"{p}: records differ from {paths[0]}"
+                L.dpe_cloud_last_timings(c, ms, 4)
+                if rnd:
+                    rows[p]["cells_insert_ms"].append(float(ms[1]))
+                    rows[p]["wall_ms"].append(dt * 1e3)
+        row = {"cloud": name, "points": n, "voxels": int(k.value)}
+        for p in paths:
+            row[os.path.basename(p)] = {key: {"min": min(vals), "median": float(np.median(vals))} for key, vals in rows[p].items()}
+        out["clouds"].append(row)
+        print(json.dumps(row), flush=True)
+    for _, L, c in ctxs:
+        L.dpe_destroy(c)
+    return out
+
+
+if a.voxel is not None:
+    result = voxel_ab(a.ab) if a.ab else voxel_profile()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("written", a.out)
+    sys.exit(0)
 
 result = {"host_threads": min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 16)), "sizes": []}
 ctx = native.PatchMatchContext(0)
