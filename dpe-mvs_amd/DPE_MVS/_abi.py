@@ -39,6 +39,10 @@ class DpeFusionView(C.Structure):   # include/dpe_mvs.h (RunFusion's projection 
                 ("depth", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class DpeIcpSums(C.Structure):   # include/dpe_mvs.h (one ICP step: the matched count and the 16 pairwise sums)
+    _fields_ = [("matched", C.c_longlong), ("d2", C.c_double), ("a", C.c_double * 3), ("b", C.c_double * 3), ("ab", C.c_double * 9)]
+
+
 class DpePatchMatchParams(C.Structure):
     _fields_ = [
         ("max_iterations", C.c_int),

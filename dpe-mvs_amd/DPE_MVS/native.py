@@ -29,6 +29,7 @@ EXPORTED = [
     "dpe_state_point_cloud", "dpe_state_point_cloud_wait", "dpe_point_cloud_arrays", "dpe_points_launches",
     "dpe_fusion_consistency", "dpe_consistency_launches",
     "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings", "dpe_cloud_voxel",
+    "dpe_cloud_nn_index", "dpe_cloud_icp_stage", "dpe_cloud_icp_step",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -144,12 +145,21 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_cloud_voxel.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     lib.dpe_cloud_voxel.restype = C.c_int
+    lib.dpe_cloud_nn_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]
+    lib.dpe_cloud_nn_index.restype = C.c_int
+    lib.dpe_cloud_icp_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float]
+    lib.dpe_cloud_icp_stage.restype = C.c_int
+    lib.dpe_cloud_icp_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DpeIcpSums)]
+    lib.dpe_cloud_icp_step.restype = C.c_int
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
     lib.dpe_live_device_bytes.argtypes = []
     lib.dpe_live_device_bytes.restype = C.c_longlong
     return lib
+
+
+DpeIcpSums = _abi.DpeIcpSums
 
 
 def fusion_view_array(views):
@@ -462,6 +472,33 @@ class PatchMatchContext:
                                     count.ctypes.data, n, C.byref(k)), "dpe_cloud_voxel")
         k = k.value
         return xyz[:k].copy(), (None if rgb is None else rgb[:k].copy()), first[:k].copy(), count[:k].copy()
+
+    # registration (include/dpe_mvs.h: dpe_cloud_nn_index, dpe_cloud_icp_stage, dpe_cloud_icp_step)
+    def cloud_nn_index(self, query, target, radius: float) -> tuple:
+        """(d2 f32 [n], idx i32 [n]): cloud_nn's distances and the index of the nearest target point, the j that
+        minimises (d2, j) lexicographically, -1 where nothing is within the radius (pipeline.cloud_nn_index gives the
+        same on host threads)."""
+        q, t = as_cloud(query), as_cloud(target)
+        d2, idx = np.empty(len(q), np.float32), np.empty(len(q), np.int32)
+        _check(_LIB.dpe_cloud_nn_index(self._ctx, q.ctypes.data, len(q), t.ctypes.data, len(t), float(radius), d2.ctypes.data,
+                                       idx.ctypes.data), "dpe_cloud_nn_index")
+        return d2, idx
+
+    def cloud_icp_stage(self, src, tgt, radius: float) -> None:
+        """Uploads both clouds and builds the target's grid for `radius`; they stay resident for cloud_icp_step until
+        the next cloud call of the context."""
+        p, g = as_cloud(src), as_cloud(tgt)
+        _check(_LIB.dpe_cloud_icp_stage(self._ctx, p.ctypes.data, len(p), g.ctypes.data, len(g), float(radius)), "dpe_cloud_icp_stage")
+
+    def cloud_icp_step(self, T) -> dict:
+        """One ICP step over the staged pair under T (12 numbers, 3 rows of 4): the matched count and the 16 pairwise
+        sums as a dict (pipeline.cloud_icp_step gives the same bits on the host)."""
+        t = np.ascontiguousarray(T, np.float64).reshape(-1)
+        if t.size != 12:
+            raise ValueError("expected a transform of 12 numbers (3 rows of 4)")
+        s = DpeIcpSums()
+        _check(_LIB.dpe_cloud_icp_step(self._ctx, t.ctypes.data, C.byref(s)), "dpe_cloud_icp_step")
+        return dict(matched=int(s.matched), d2=s.d2, a=list(s.a), b=list(s.b), ab=list(s.ab))
 
     def cloud_timings(self) -> dict:
         """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}.  After

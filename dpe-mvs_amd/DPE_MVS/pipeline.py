@@ -84,6 +84,23 @@ class DpeCloudPrep(C.Structure):   # include/dpe_host.h
                 ("n_recon_in", C.c_ulonglong), ("n_gt_in", C.c_ulonglong)]
 
 
+CLOUD_MAX_RADII = 4
+
+
+DpeIcpSums = _abi.DpeIcpSums   # include/dpe_mvs.h
+
+
+class DpeCloudRegOptions(C.Structure):   # include/dpe_host.h
+    _fields_ = [("radius", C.c_float * CLOUD_MAX_RADII), ("n_radii", C.c_int), ("max_iters", C.c_int), ("tol", C.c_double),
+                ("use_init", C.c_int), ("init", C.c_double * 12)]
+
+
+class DpeCloudReg(C.Structure):   # include/dpe_host.h
+    _fields_ = [("T", C.c_double * 12), ("stages", C.c_int), ("iters", C.c_int * CLOUD_MAX_RADII),
+                ("matched", C.c_longlong * CLOUD_MAX_RADII), ("rms", C.c_double * CLOUD_MAX_RADII),
+                ("converged", C.c_int * CLOUD_MAX_RADII)]
+
+
 class PipelineError(RuntimeError):
     pass
 
@@ -147,6 +164,16 @@ def lib() -> C.CDLL:
                                                     C.POINTER(C.c_int)]
         L.dpe_host_cloud_eval_prep.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
                                                C.c_int, C.POINTER(DpeCloudPrep), C.POINTER(DpeCloudEval)]
+        L.dpe_host_cloud_nn_index.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]
+        L.dpe_host_cloud_icp_step.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p,
+                                              C.POINTER(DpeIcpSums)]
+        L.dpe_host_cloud_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dpe_host_cloud_solve.argtypes = [C.POINTER(DpeIcpSums), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dpe_host_cloud_register.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(DpeCloudRegOptions), C.c_int,
+                                              C.POINTER(DpeCloudReg)]
+        L.dpe_host_cloud_eval_reg.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
+                                              C.c_int, C.POINTER(DpeCloudPrep), C.POINTER(DpeCloudRegOptions),
+                                              C.POINTER(DpeCloudReg), C.POINTER(DpeCloudEval)]
         _lib = L
     return _lib
 
@@ -490,8 +517,97 @@ def voxel_down_sample(points, voxel: float, colors=None, gpu_index: int = -1):
     return xyz[:k].copy(), (None if rgb is None else rgb[:k].copy()), first[:k].copy(), count[:k].copy()
 
 
+# ------------------------------------------------------------------------------ registration (C++, cloud_register.cpp)
+def cloud_nn_index(query, target, radius: float):
+    """(d2 f32 [n], idx i32 [n]) on host threads (dpe_host_cloud_nn_index): cloud_nn's distances and the index of the
+    nearest target point, the j that minimises (d2, j) lexicographically, -1 where nothing is within the radius: the
+    bits of the device path (native.PatchMatchContext.cloud_nn_index)."""
+    q, t = _as_cloud(query), _as_cloud(target)
+    d2, idx = np.empty(len(q), np.float32), np.empty(len(q), np.int32)
+    if lib().dpe_host_cloud_nn_index(q.ctypes.data, len(q), t.ctypes.data, len(t), float(radius), d2.ctypes.data, idx.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return d2, idx
+
+
+def _as_transform(T) -> np.ndarray:
+    t = np.ascontiguousarray(T, np.float64).reshape(-1)
+    if t.size != 12:
+        raise ValueError("expected a transform of 12 numbers (3 rows of 4)")
+    return t
+
+
+def icp_sums_dict(s: DpeIcpSums) -> dict:
+    return dict(matched=int(s.matched), d2=s.d2, a=list(s.a), b=list(s.b), ab=list(s.ab))
+
+
+def cloud_icp_step(src, tgt, radius: float, T) -> dict:
+    """One ICP step on the host (dpe_host_cloud_icp_step; include/dpe_mvs.h states it): the matched count and the 16
+    pairwise sums d2, a[3], b[3], ab[9] as a dict, the bits of the device step."""
+    p, g, t = _as_cloud(src), _as_cloud(tgt), _as_transform(T)
+    s = DpeIcpSums()
+    if lib().dpe_host_cloud_icp_step(p.ctypes.data, len(p), g.ctypes.data, len(g), float(radius), t.ctypes.data, C.byref(s)) != 0:
+        raise PipelineError(_last_error())
+    return icp_sums_dict(s)
+
+
+def cloud_solve(sums: dict, o_s, o_t) -> np.ndarray:
+    """The transform f64 [3, 4] of the original source points from one step's sums (dpe_host_cloud_solve); o_s and
+    o_t are the per-axis minima of the finite points of the source and the target."""
+    s = DpeIcpSums(int(sums["matched"]), float(sums["d2"]), (C.c_double * 3)(*sums["a"]), (C.c_double * 3)(*sums["b"]),
+                   (C.c_double * 9)(*sums["ab"]))
+    a, b = np.ascontiguousarray(o_s, np.float64).reshape(3), np.ascontiguousarray(o_t, np.float64).reshape(3)
+    T = np.empty(12, np.float64)
+    if lib().dpe_host_cloud_solve(C.byref(s), a.ctypes.data, b.ctypes.data, T.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return T.reshape(3, 4)
+
+
+def transform_cloud(T, points) -> np.ndarray:
+    """points f32 [n, 3] under T (3 rows of 4, [R | t]) in the step's own expression (dpe_host_cloud_transform):
+    (float)(((T0 x + T1 y) + T2 z) + T3) per row in double; a non-finite point becomes NaN."""
+    p, t = _as_cloud(points), _as_transform(T)
+    out = np.empty_like(p)
+    if lib().dpe_host_cloud_transform(t.ctypes.data, p.ctypes.data, len(p), out.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def _reg_options(radii, max_iters: int = 50, tol: float = 1e-6, init=None) -> DpeCloudRegOptions:
+    o = DpeCloudRegOptions()
+    r = [float(v) for v in np.atleast_1d(radii)]
+    o.n_radii = len(r)
+    for k, v in enumerate(r[:CLOUD_MAX_RADII]):
+        o.radius[k] = v
+    o.max_iters, o.tol = int(max_iters), float(tol)
+    if init is not None:
+        o.use_init = 1
+        o.init[:] = list(_as_transform(init))
+    return o
+
+
+def _reg_dict(r: DpeCloudReg, o: DpeCloudRegOptions) -> dict:
+    return dict(T=[[r.T[4 * i + j] for j in range(4)] for i in range(3)],
+                stages=[dict(radius=float(o.radius[k]), iters=int(r.iters[k]), matched=int(r.matched[k]), rms=r.rms[k],
+                             converged=int(r.converged[k])) for k in range(r.stages)])
+
+
+def register_clouds(src, tgt, radii, max_iters: int = 50, tol: float = 1e-6, init=None, gpu_index: int = -1) -> dict:
+    """Rigid registration of cloud `src` onto cloud `tgt` by point-to-point ICP (dpe_host_cloud_register;
+    include/dpe_host.h states the loop): `radii` is one match radius or 1 to 4 of them, coarse to fine, each run for
+    at most `max_iters` steps; `init` a starting transform (3 rows of 4; default the identity).  gpu_index < 0: the
+    host step, else the device step on that device: equal dicts.  Returns T (3 rows of 4, to be applied with
+    transform_cloud) and per stage radius, iters, matched, rms and converged (2: a fixed point, 1: rms within tol,
+    0: max_iters)."""
+    p, g = _as_cloud(src), _as_cloud(tgt)
+    o = _reg_options(radii, max_iters, tol, init)
+    r = DpeCloudReg()
+    if lib().dpe_host_cloud_register(p.ctypes.data, len(p), g.ctypes.data, len(g), C.byref(o), int(gpu_index), C.byref(r)) != 0:
+        raise PipelineError(_last_error())
+    return _reg_dict(r, o)
+
+
 def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int = -1, voxel: float | None = None,
-                    crop=None) -> dict:
+                    crop=None, register=None) -> dict:
     """Precision, recall and F-score of cloud `recon` against cloud `gt` (f32 [k, 3]) at the thresholds `taus`
     (1 to 16, each 0 < tau <= radius; radius None: the largest tau), from the truncated nearest-neighbour
     distances in both directions (dpe_host_cloud_eval).  gpu_index < 0: on host threads, else on that device:
@@ -501,7 +617,11 @@ def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int
     `crop` = (lo, hi) keeps the points of both clouds inside that box first, `voxel` then down-samples both to one
     point per voxel (voxel_down_sample; on the device too when gpu_index >= 0) before they are scored
     (dpe_host_cloud_eval_prep).  With either the dict also has voxel (or None), crop ([lo, hi] or None), n_recon_in and
-    n_gt_in (the counts before the preparation; n_recon and n_gt are those after it)."""
+    n_gt_in (the counts before the preparation; n_recon and n_gt are those after it).
+    `register` = a radius, a list of radii or a dict of register_clouds' options (radii, max_iters, tol, init) first
+    moves the reconstruction onto the ground truth (dpe_host_cloud_eval_reg: the down-sampled copies are registered,
+    the ground truth cropped, then the whole reconstruction is transformed and scored as above); the dict then has
+    `registration`, register_clouds' dict."""
     a, b = _as_cloud(recon), _as_cloud(gt)
     t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
     e = DpeCloudEval()
@@ -515,12 +635,21 @@ def evaluate_clouds(recon, gt, taus, radius: float | None = None, gpu_index: int
             prep.use_crop = 1
             for k in range(3):
                 prep.crop_lo[k], prep.crop_hi[k] = float(crop[0][k]), float(crop[1][k])
-    if lib().dpe_host_cloud_eval_prep(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t),
-                                      0.0 if radius is None else float(radius), int(gpu_index),
-                                      None if prep is None else C.byref(prep), C.byref(e)) != 0:
+    R = 0.0 if radius is None else float(radius)
+    if register is None:
+        rc = lib().dpe_host_cloud_eval_prep(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t), R, int(gpu_index),
+                                            None if prep is None else C.byref(prep), C.byref(e))
+    else:
+        ropt = _reg_options(**register) if isinstance(register, dict) else _reg_options(register)
+        reg = DpeCloudReg()
+        rc = lib().dpe_host_cloud_eval_reg(a.ctypes.data, len(a), b.ctypes.data, len(b), t.ctypes.data, len(t), R, int(gpu_index),
+                                           None if prep is None else C.byref(prep), C.byref(ropt), C.byref(reg), C.byref(e))
+    if rc != 0:
         raise PipelineError(_last_error())
     k = e.n_tau
     out = _cloud_eval_dict(e, k)
+    if register is not None:
+        out["registration"] = _reg_dict(reg, ropt)
     if prep is not None:
         out.update(voxel=(float(prep.voxel) if voxel is not None else None),
                    crop=([[float(v) for v in prep.crop_lo], [float(v) for v in prep.crop_hi]] if crop is not None else None),
@@ -538,6 +667,10 @@ def _cloud_eval_dict(e: DpeCloudEval, k: int) -> dict:
 def format_cloud_eval(e: dict) -> str:
     """The table bin/dpe_eval prints, from evaluate_clouds' dict."""
     rows = []
+    if "registration" in e:
+        st = e["registration"]["stages"]
+        rows.append("registered: radii %s, rms %.9g" % (" ".join("%.9g" % s["radius"] for s in st), st[-1]["rms"]))
+        rows += ["T %.17g %.17g %.17g %.17g" % tuple(row) for row in e["registration"]["T"]]
     if "n_recon_in" in e:
         box = "none" if e["crop"] is None else "[%.9g %.9g %.9g] to [%.9g %.9g %.9g]" % tuple(e["crop"][0] + e["crop"][1])
         rows.append("prepared: voxel %.9g, crop %s, from recon %d points, gt %d points"

@@ -1,6 +1,7 @@
-// dpe_cloud.hip -- the cloud evaluation's distances (dpe_cloud_nn, dpe_cloud_nn_pair) and the voxel
-// down-sampling (dpe_cloud_voxel) of include/dpe_mvs.h: the kernels of pass_cloud.h and pass_voxel.h over the
-// context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
+// dpe_cloud.hip -- the cloud evaluation's distances (dpe_cloud_nn, dpe_cloud_nn_pair), the voxel
+// down-sampling (dpe_cloud_voxel) and the registration's device half (dpe_cloud_nn_index, dpe_cloud_icp_stage,
+// dpe_cloud_icp_step) of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h and pass_register.h over
+// the context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
 // contract is dpe_mvs.hip's (dpe_entry.h): these calls wait until the context is quiet, use its stream and
 // return with it synchronised.
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 
 #include "pass_cloud.h"
 #include "pass_voxel.h"
+#include "pass_register.h"
 #include "dpe_entry.h"
 #include "dpe_context.h"
 
@@ -36,6 +38,17 @@ float cloud_unkey(uint32_t k) {
   return f;
 }
 
+// the timing events of this section, made at the first timed call
+int cloud_events(DpeContext* c) {
+  CloudScratch& v = c->cloud;
+  while (v.ev.size() < 8) {
+    Event e;
+    HIPC(e.create(hipEventDefault));
+    v.ev.push_back(std::move(e));
+  }
+  return DPE_OK;
+}
+
 unsigned cloud_blocks(size_t n) { return (unsigned)((n + kCloudBlock - 1) / kCloudBlock); }
 
 // stages cloud `which` (n points) and enqueues the reduction of its bounds into slot `which`
@@ -50,6 +63,18 @@ int cloud_stage(DpeContext* c, int which, const float* pts, size_t n) {
   k_cloud_bounds<<<grid, kCloudBlock, 0, c->stream>>>(v.pts[which].p, (int)n, v.bounds.p + 8 * which);
   HIPC(hipGetLastError());
   g_cloud_launches += 1;
+  return DPE_OK;
+}
+
+// the bounds of the two staged clouds, on the host when it returns
+int cloud_bounds_fetch(DpeContext* c, CloudBounds bd[2]) {
+  uint32_t raw[16];
+  HIPC(hipMemcpyAsync(raw, c->cloud.bounds.p, sizeof raw, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  for (int w = 0; w < 2; ++w) {
+    bd[w].finite = raw[8 * w + 6];
+    for (int k = 0; k < 3; ++k) { bd[w].lo[k] = cloud_unkey(~raw[8 * w + k]); bd[w].hi[k] = cloud_unkey(raw[8 * w + 3 + k]); }
+  }
   return DPE_OK;
 }
 
@@ -70,14 +95,16 @@ int cloud_build(DpeContext* c, const float* pts, size_t n, const CloudGrid& g, i
 }
 
 // out[0..n) = the distances of staged cloud `qi` to staged cloud `ti` (bounds tb), on the host when it returns.
+// idx (or null): the matches' indices as well (k_cloud_match instead of k_cloud_query).
 // ev: the three timing events of this direction (end of build, query, download), or null.
 int cloud_direction(DpeContext* c, int qi, size_t n, int ti, size_t m, const CloudBounds& tb, float radius, float* out,
-                    Event* ev, const char* who) {
+                    int32_t* idx, Event* ev, const char* who) {
   if (n == 0) return DPE_OK;
   CloudScratch& v = c->cloud;
   if (tb.finite == 0) {   // nothing to find: no launch
     const float r2 = radius * radius;
     for (size_t i = 0; i < n; ++i) out[i] = r2;
+    if (idx) for (size_t i = 0; i < n; ++i) idx[i] = -1;
     if (ev) for (int k = 0; k < 3; ++k) HIPC(hipEventRecord(ev[k], c->stream));
     return DPE_OK;
   }
@@ -89,14 +116,17 @@ int cloud_direction(DpeContext* c, int qi, size_t n, int ti, size_t m, const Clo
   HIPC(v.st.ensure(tb.finite));
   HIPC(v.sq.ensure(n));
   HIPC(v.out.ensure(n));
+  if (idx) HIPC(v.idx.ensure(n));
   TRY(cloud_build(c, v.pts[ti].p, m, g, 0, v.tcnt, v.st.p));
   TRY(cloud_build(c, v.pts[qi].p, n, g, 1, v.qcnt, v.sq.p));
   if (ev) HIPC(hipEventRecord(ev[0], c->stream));
-  k_cloud_query<<<cloud_blocks(n), kCloudBlock, 0, c->stream>>>(v.sq.p, (int)n, v.st.p, v.tcnt.p, g, v.out.p);
+  if (idx) k_cloud_match<<<cloud_blocks(n), kCloudBlock, 0, c->stream>>>(v.sq.p, (int)n, v.st.p, v.tcnt.p, g, v.out.p, v.idx.p);
+  else k_cloud_query<<<cloud_blocks(n), kCloudBlock, 0, c->stream>>>(v.sq.p, (int)n, v.st.p, v.tcnt.p, g, v.out.p);
   HIPC(hipGetLastError());
   g_cloud_launches += 1;
   if (ev) HIPC(hipEventRecord(ev[1], c->stream));
   HIPC(hipMemcpyAsync(out, v.out.p, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (idx) HIPC(hipMemcpyAsync(idx, v.idx.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (ev) HIPC(hipEventRecord(ev[2], c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   return DPE_OK;
@@ -108,34 +138,23 @@ bool cloud_args_ok(const float* a, size_t n, const float* b, size_t m, float rad
          (!need_b_out || b_out || m == 0) && std::isfinite(radius) && radius > 0.0f;
 }
 
-// the two clouds staged once; a_to_b always, b_to_a when it is not null
-int cloud_run(DpeContext* c, const float* a, size_t n, const float* b, size_t m, float radius, float* a_to_b, float* b_to_a,
-              const char* who) {
+// the two clouds staged once; a_to_b always (with the indices when a_idx is not null), b_to_a when it is not null
+int cloud_run(DpeContext* c, const float* a, size_t n, const float* b, size_t m, float radius, float* a_to_b, int32_t* a_idx,
+              float* b_to_a, const char* who) {
   CloudScratch& v = c->cloud;
   HIPC(host_wait(c));
   const bool timing = c->pass.timing;
   v.timed = false;
-  if (timing && v.ev.empty()) {
-    for (int k = 0; k < 8; ++k) {
-      Event e;
-      HIPC(e.create(hipEventDefault));
-      v.ev.push_back(std::move(e));
-    }
-  }
+  v.icp_staged = false;
+  if (timing) TRY(cloud_events(c));
   if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
   TRY(cloud_stage(c, 0, a, n));
   TRY(cloud_stage(c, 1, b, m));
   if (timing) HIPC(hipEventRecord(v.ev[1], c->stream));
-  uint32_t raw[16];
-  HIPC(hipMemcpyAsync(raw, v.bounds.p, sizeof raw, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
   CloudBounds bd[2];
-  for (int w = 0; w < 2; ++w) {
-    bd[w].finite = raw[8 * w + 6];
-    for (int k = 0; k < 3; ++k) { bd[w].lo[k] = cloud_unkey(~raw[8 * w + k]); bd[w].hi[k] = cloud_unkey(raw[8 * w + 3 + k]); }
-  }
-  TRY(cloud_direction(c, 0, n, 1, m, bd[1], radius, a_to_b, timing ? &v.ev[2] : nullptr, who));
-  if (b_to_a) TRY(cloud_direction(c, 1, m, 0, n, bd[0], radius, b_to_a, timing ? &v.ev[5] : nullptr, who));
+  TRY(cloud_bounds_fetch(c, bd));
+  TRY(cloud_direction(c, 0, n, 1, m, bd[1], radius, a_to_b, a_idx, timing ? &v.ev[2] : nullptr, who));
+  if (b_to_a) TRY(cloud_direction(c, 1, m, 0, n, bd[0], radius, b_to_a, nullptr, timing ? &v.ev[5] : nullptr, who));
   if (timing) {
     // [0] stage, [1] build, [2] query, [3] download; an empty direction records nothing
     const bool ran[2] = {n > 0, b_to_a && m > 0};
@@ -169,13 +188,8 @@ int voxel_run(DpeContext* c, const float* xyz, size_t n, const uint8_t* rgb, flo
   HIPC(host_wait(c));
   const bool timing = c->pass.timing;
   v.timed = false;
-  if (timing && v.ev.empty()) {
-    for (int e = 0; e < 8; ++e) {
-      Event ev;
-      HIPC(ev.create(hipEventDefault));
-      v.ev.push_back(std::move(ev));
-    }
-  }
+  v.icp_staged = false;
+  if (timing) TRY(cloud_events(c));
   if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
   TRY(cloud_stage(c, 0, xyz, n));
   if (n == 0) { HIPC(hipStreamSynchronize(c->stream)); return DPE_OK; }
@@ -269,7 +283,131 @@ int voxel_run(DpeContext* c, const float* xyz, size_t n, const uint8_t* rgb, flo
   return DPE_OK;
 }
 
+// dpe_cloud_icp_stage after its prologue: both clouds and the target's grid for `radius` resident
+int icp_stage(DpeContext* c, const float* src, size_t n, const float* tgt, size_t m, float radius) {
+  CloudScratch& v = c->cloud;
+  HIPC(host_wait(c));
+  v.timed = false;
+  v.icp_staged = false;
+  TRY(cloud_stage(c, 0, src, n));
+  TRY(cloud_stage(c, 1, tgt, m));
+  CloudBounds bd[2];
+  TRY(cloud_bounds_fetch(c, bd));
+  v.icp_n = n;
+  v.icp_m = m;
+  v.icp_tfinite = bd[1].finite;
+  for (int a = 0; a < 3; ++a) {
+    v.icp_os[a] = bd[0].finite ? (double)bd[0].lo[a] : 0.0;
+    v.icp_ot[a] = bd[1].finite ? (double)bd[1].lo[a] : 0.0;
+  }
+  if (n > 0 && bd[1].finite > 0) {
+    if (!cloud_grid_make(bd[1].lo, bd[1].hi, bd[1].finite, radius, &v.icp_grid)) {
+      g_err = "dpe_cloud_icp_stage: radius too small for the cloud's extent";
+      return DPE_ERR_ARG;
+    }
+    HIPC(v.st.ensure(bd[1].finite));
+    TRY(cloud_build(c, v.pts[1].p, m, v.icp_grid, 0, v.tcnt, v.st.p));
+    // what a step writes
+    const size_t blocks = cloud_blocks(n);
+    HIPC(v.moved.ensure(3 * n));
+    HIPC(v.sq.ensure(n));
+    HIPC(v.out.ensure(n));
+    HIPC(v.idx.ensure(n));
+    HIPC(v.part[0].ensure(blocks * kIcpTerms));
+    HIPC(v.part[1].ensure((size_t)cloud_blocks(blocks) * kIcpTerms));
+    HIPC(v.matched.ensure(1));
+    HIPC(hipStreamSynchronize(c->stream));
+  }
+  v.icp_staged = true;
+  return DPE_OK;
+}
+
+// dpe_cloud_icp_step after its prologue.  Timing events: [0] start, [1] apply + build, [2] match, [3] sums,
+// [4] download.
+int icp_step(DpeContext* c, const double* T, DpeIcpSums* out) {
+  CloudScratch& v = c->cloud;
+  HIPC(host_wait(c));
+  v.timed = false;
+  DpeIcpSums s;
+  memset(&s, 0, sizeof s);
+  const size_t n = v.icp_n;
+  if (n == 0 || v.icp_tfinite == 0) { *out = s; return DPE_OK; }   // nothing to match: no launch
+  const bool timing = c->pass.timing;
+  if (timing) TRY(cloud_events(c));
+  IcpXf xf;
+  memcpy(xf.m, T, sizeof xf.m);
+  IcpOrigins org;
+  memcpy(org.s, v.icp_os, sizeof org.s);
+  memcpy(org.t, v.icp_ot, sizeof org.t);
+  const CloudGrid& g = v.icp_grid;
+  if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
+  HIPC(hipMemsetAsync(v.matched.p, 0, sizeof(unsigned long long), c->stream));
+  k_icp_apply<<<cloud_blocks(n), kCloudBlock, 0, c->stream>>>(v.pts[0].p, (int)n, xf, v.moved.p);
+  HIPC(hipGetLastError());
+  g_cloud_launches += 1;
+  TRY(cloud_build(c, v.moved.p, n, g, 1, v.qcnt, v.sq.p));
+  if (timing) HIPC(hipEventRecord(v.ev[1], c->stream));
+  k_cloud_match<<<cloud_blocks(n), kCloudBlock, 0, c->stream>>>(v.sq.p, (int)n, v.st.p, v.tcnt.p, g, v.out.p, v.idx.p);
+  HIPC(hipGetLastError());
+  if (timing) HIPC(hipEventRecord(v.ev[2], c->stream));
+  size_t cnt = cloud_blocks(n);
+  k_icp_terms<<<(unsigned)cnt, kCloudBlock, 0, c->stream>>>(v.pts[0].p, (int)n, v.pts[1].p, v.idx.p, v.out.p, org, v.part[0].p,
+                                                            v.matched.p);
+  HIPC(hipGetLastError());
+  g_cloud_launches += 2;
+  int at = 0;   // part[at] holds the cnt partials of the level
+  while (cnt > 1) {
+    const unsigned blocks = cloud_blocks(cnt);
+    k_icp_reduce<<<blocks, kCloudBlock, 0, c->stream>>>(v.part[at].p, (int)cnt, v.part[at ^ 1].p);
+    HIPC(hipGetLastError());
+    g_cloud_launches += 1;
+    cnt = blocks;
+    at ^= 1;
+  }
+  if (timing) HIPC(hipEventRecord(v.ev[3], c->stream));
+  double sums[kIcpTerms];
+  unsigned long long matched = 0;
+  HIPC(hipMemcpyAsync(sums, v.part[at].p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(&matched, v.matched.p, sizeof matched, hipMemcpyDeviceToHost, c->stream));
+  if (timing) HIPC(hipEventRecord(v.ev[4], c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  s.matched = (long long)matched;
+  s.d2 = sums[0];
+  for (int k = 0; k < 3; ++k) { s.a[k] = sums[1 + k]; s.b[k] = sums[4 + k]; }
+  for (int k = 0; k < 9; ++k) s.ab[k] = sums[7 + k];
+  *out = s;
+  if (timing) {
+    for (int e = 0; e < 4; ++e) HIPC(hipEventElapsedTime(&v.ms[e], v.ev[e], v.ev[e + 1]));
+    v.timed = true;
+  }
+  return DPE_OK;
+}
+
 }  // namespace
+
+extern "C" int dpe_cloud_nn_index(DpeContext* c, const float* query, size_t n, const float* target, size_t m, float radius,
+                                  float* d2_out, int32_t* idx_out) {
+  const bool ok = cloud_args_ok(query, n, target, m, radius, d2_out, nullptr, false) && (idx_out || n == 0);
+  TRY(enter(c, ok, "dpe_cloud_nn_index: bad argument"));
+  int32_t none = -1;   // n == 0: no entry, and the call still stages as one with indices
+  return cloud_run(c, query, n, target, m, radius, d2_out, idx_out ? idx_out : &none, nullptr, "dpe_cloud_nn_index");
+}
+
+extern "C" int dpe_cloud_icp_stage(DpeContext* c, const float* src, size_t n, const float* tgt, size_t m, float radius) {
+  const bool ok = n <= (size_t)INT_MAX && m <= (size_t)INT_MAX && (src || n == 0) && (tgt || m == 0) && std::isfinite(radius) &&
+                  radius > 0.0f;
+  TRY(enter(c, ok, "dpe_cloud_icp_stage: bad argument"));
+  return icp_stage(c, src, n, tgt, m, radius);
+}
+
+extern "C" int dpe_cloud_icp_step(DpeContext* c, const double* T, DpeIcpSums* out) {
+  TRY(enter(c, T && out, "dpe_cloud_icp_step: bad argument"));
+  if (!c->cloud.icp_staged) {
+    g_err = "dpe_cloud_icp_step: no staged pair (dpe_cloud_icp_stage comes first)";
+    return DPE_ERR_STATE;
+  }
+  return icp_step(c, T, out);
+}
 
 extern "C" int dpe_cloud_voxel(DpeContext* c, const float* xyz, size_t n, const uint8_t* rgb, float voxel, float* out_xyz,
                                uint8_t* out_rgb, int32_t* out_first, int32_t* out_count, size_t cap, size_t* k) {
@@ -282,14 +420,14 @@ extern "C" int dpe_cloud_voxel(DpeContext* c, const float* xyz, size_t n, const 
 extern "C" int dpe_cloud_nn(DpeContext* c, const float* query, size_t n, const float* target, size_t m, float radius,
                             float* d2_out) {
   TRY(enter(c, cloud_args_ok(query, n, target, m, radius, d2_out, nullptr, false), "dpe_cloud_nn: bad argument"));
-  return cloud_run(c, query, n, target, m, radius, d2_out, nullptr, "dpe_cloud_nn");
+  return cloud_run(c, query, n, target, m, radius, d2_out, nullptr, nullptr, "dpe_cloud_nn");
 }
 
 extern "C" int dpe_cloud_nn_pair(DpeContext* c, const float* a, size_t n, const float* b, size_t m, float radius,
                                  float* a_to_b, float* b_to_a) {
   TRY(enter(c, cloud_args_ok(a, n, b, m, radius, a_to_b, b_to_a, true), "dpe_cloud_nn_pair: bad argument"));
   float none = 0.f;   // m == 0: b_to_a has no entry, and the second direction still runs as one
-  return cloud_run(c, a, n, b, m, radius, a_to_b, b_to_a ? b_to_a : &none, "dpe_cloud_nn_pair");
+  return cloud_run(c, a, n, b, m, radius, a_to_b, nullptr, b_to_a ? b_to_a : &none, "dpe_cloud_nn_pair");
 }
 
 extern "C" int dpe_cloud_last_timings(DpeContext* c, float* ms, int n) {

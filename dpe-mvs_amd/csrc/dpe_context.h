@@ -16,6 +16,7 @@
 #include "pass_common.h"
 #include "tap_launch.h"          // ImgClass
 #include "dpe_fusion_types.h"
+#include "cloud_dist.h"          // CloudGrid
 
 namespace dpe {
 
@@ -241,6 +242,16 @@ struct CloudScratch {
   DevArr<float> vout_xyz;            // the records
   DevArr<uint8_t> vout_rgb;
   DevArr<int> vout_first, vout_count;
+  // dpe_cloud_nn_index and the ICP step (pass_register.h).  A staged pair is the source in pts[0], the target in
+  // pts[1] and the target's grid in st / tcnt; every other cloud call of the context overwrites them and ends it
+  DevArr<int> idx;                   // the matches, by original index (the distances are `out`)
+  DevArr<float> moved;               // the source under the step's transform, f32 [n][3]
+  DevArr<double> part[2];            // the sums' partials, 16 per block, level by level
+  DevArr<unsigned long long> matched;
+  bool icp_staged = false;
+  size_t icp_n = 0, icp_m = 0, icp_tfinite = 0;
+  CloudGrid icp_grid;
+  double icp_os[3] = {0, 0, 0}, icp_ot[3] = {0, 0, 0};   // per-axis minima of the finite source / target points
 };
 
 }  // namespace dpe

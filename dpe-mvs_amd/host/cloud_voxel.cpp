@@ -110,12 +110,11 @@ void cloud_crop(const float* xyz, size_t n, const float lo[3], const float hi[3]
   }
 }
 
-namespace {
-
 // one cloud through the preparation: `pts` becomes what is scored
-bool prepare(DpeContext* ctx, const float* xyz, size_t n, const DpeCloudPrep& prep, std::vector<float>& pts, std::string& err) {
+bool cloud_prepare(DpeContext* ctx, const float* xyz, size_t n, const DpeCloudPrep& prep, bool crop, std::vector<float>& pts,
+                   std::string& err) {
   pts.assign(xyz, xyz + 3 * n);
-  if (prep.use_crop) {
+  if (crop) {
     std::vector<int32_t> keep;
     cloud_crop(xyz, n, prep.crop_lo, prep.crop_hi, keep);
     pts.resize(3 * keep.size());
@@ -141,30 +140,38 @@ bool prepare(DpeContext* ctx, const float* xyz, size_t n, const DpeCloudPrep& pr
   return true;
 }
 
-}  // namespace
+bool cloud_prep_args(const float* recon, size_t n, const float* gt, size_t m, const DpeCloudPrep& prep, std::string& err) {
+  if (n > (size_t)INT_MAX || m > (size_t)INT_MAX || (!recon && n) || (!gt && m)) { err = "cloud_eval: bad cloud"; return false; }
+  if (!(prep.voxel == 0.0f || (std::isfinite(prep.voxel) && prep.voxel > 0.0f))) {
+    err = "cloud_eval: the voxel edge is not a finite positive number";
+    return false;
+  }
+  if (prep.use_crop) {
+    for (int a = 0; a < 3; ++a)
+      if (!(prep.crop_lo[a] <= prep.crop_hi[a])) { err = "cloud_eval: the crop box is empty or not a number"; return false; }
+  }
+  return true;
+}
+
+bool cloud_eval_prep_in(DpeContext* ctx, const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau,
+                        float radius, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err) {
+  prep->n_recon_in = n;
+  prep->n_gt_in = m;
+  std::vector<float> a, b;
+  return cloud_prepare(ctx, recon, n, *prep, prep->use_crop != 0, a, err) && cloud_prepare(ctx, gt, m, *prep, prep->use_crop != 0, b, err) &&
+         cloud_eval_in(ctx, a.data(), a.size() / 3, b.data(), b.size() / 3, tau, n_tau, radius, out, err);
+}
 
 bool cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                      int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err) {
   if (!prep) return cloud_eval(recon, n, gt, m, tau, n_tau, radius, gpu_index, out, err);
-  if (n > (size_t)INT_MAX || m > (size_t)INT_MAX || (!recon && n) || (!gt && m)) { err = "cloud_eval: bad cloud"; return false; }
-  if (!(prep->voxel == 0.0f || (std::isfinite(prep->voxel) && prep->voxel > 0.0f))) {
-    err = "cloud_eval: the voxel edge is not a finite positive number";
-    return false;
-  }
-  if (prep->use_crop) {
-    for (int a = 0; a < 3; ++a)
-      if (!(prep->crop_lo[a] <= prep->crop_hi[a])) { err = "cloud_eval: the crop box is empty or not a number"; return false; }
-  }
-  prep->n_recon_in = n;
-  prep->n_gt_in = m;
+  if (!cloud_prep_args(recon, n, gt, m, *prep, err)) return false;
   DpeContext* ctx = nullptr;
   if (gpu_index >= 0) {
     ctx = dpe_create(gpu_index);
     if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
   }
-  std::vector<float> a, b;
-  const bool ok = prepare(ctx, recon, n, *prep, a, err) && prepare(ctx, gt, m, *prep, b, err) &&
-                  cloud_eval_in(ctx, a.data(), a.size() / 3, b.data(), b.size() / 3, tau, n_tau, radius, out, err);
+  const bool ok = cloud_eval_prep_in(ctx, recon, n, gt, m, tau, n_tau, radius, prep, out, err);
   if (ctx) dpe_destroy(ctx);
   return ok;
 }

@@ -1,8 +1,12 @@
 // eval_cli.cpp — bin/dpe_eval: precision, recall and F-score of a reconstructed PLY against a ground-truth
 // PLY (dpe_host_cloud_eval, include/dpe_host.h).
 //   dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1] [--gpu N | --cpu] [--json FILE]
+//            [--register R [R ...]] [--register-iters N] [--register-init t0 .. t11]
 // --voxel V down-samples both clouds to one point per voxel of edge V before they are scored, --crop keeps the
 // points inside the box first (dpe_host_cloud_eval_prep); with either the table gets a first line naming them.
+// --register R [R ...] (1 to 4 radii, coarse to fine: the numbers that follow it) first moves the reconstruction onto
+// the ground truth by point-to-point ICP (dpe_host_cloud_eval_reg; --register-iters: steps per radius, default 50;
+// --register-init: a starting transform, row-major 3 x 4); the table then begins with the radii, the final rms and T.
 // --gpu N (the default, N = 0) runs the distances on that device, --cpu on host threads: the same numbers.
 // Prints one table; --json also writes the struct.  `python -m DPE_MVS.evaluate` prints the same table.
 #include <cstdio>
@@ -15,7 +19,7 @@
 
 static int usage() {
   std::fprintf(stderr, "usage: dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1]"
-                       " [--gpu N | --cpu] [--json FILE]\n");
+                       " [--gpu N | --cpu] [--json FILE] [--register R [R ...]] [--register-iters N] [--register-init t0 .. t11]\n");
   return 2;
 }
 
@@ -37,7 +41,10 @@ int main(int argc, char** argv) {
   int gpu = 0;
   const char* json = nullptr;
   DpeCloudPrep prep{};
-  bool prepared = false, have_voxel = false;
+  bool prepared = false, have_voxel = false, registered = false;
+  DpeCloudRegOptions ropt{};
+  ropt.max_iters = 50;
+  ropt.tol = 1e-6;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--cpu") gpu = -1;
@@ -50,6 +57,21 @@ int main(int argc, char** argv) {
       for (int k = 0; k < 3; ++k) prep.crop_hi[k] = std::strtof(argv[++i], nullptr);
       prep.use_crop = 1;
       prepared = true;
+    }
+    else if (a == "--register") {
+      registered = true;
+      while (i + 1 < argc && ropt.n_radii < DPE_CLOUD_MAX_RADII) {   // the numbers that follow
+        char* end = nullptr;
+        const float r = std::strtof(argv[i + 1], &end);
+        if (end == argv[i + 1] || *end) break;
+        ropt.radius[ropt.n_radii++] = r;
+        ++i;
+      }
+    }
+    else if (a == "--register-iters" && i + 1 < argc) ropt.max_iters = std::atoi(argv[++i]);
+    else if (a == "--register-init" && i + 12 < argc) {
+      for (int k = 0; k < 12; ++k) ropt.init[k] = std::strtod(argv[++i], nullptr);
+      ropt.use_init = 1;
     }
     else if (a.rfind("--", 0) == 0) return usage();
     else pos.push_back(argv[i]);
@@ -68,11 +90,21 @@ int main(int argc, char** argv) {
   std::vector<float> recon, gt;
   size_t n = 0, m = 0;
   DpeCloudEval e;
+  DpeCloudReg reg{};
   if (!read_cloud(pos[0], recon, n) || !read_cloud(pos[1], gt, m) ||
-      dpe_host_cloud_eval_prep(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu, prepared ? &prep : nullptr,
-                               &e) != 0) {
+      (registered ? dpe_host_cloud_eval_reg(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu,
+                                            prepared ? &prep : nullptr, &ropt, &reg, &e)
+                  : dpe_host_cloud_eval_prep(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu,
+                                             prepared ? &prep : nullptr, &e)) != 0) {
     std::fprintf(stderr, "dpe_eval: %s\n", dpe_pipeline_last_error());
     return 1;
+  }
+  if (registered) {
+    std::printf("registered: radii");
+    for (int s = 0; s < reg.stages; ++s) std::printf(" %.9g", (double)ropt.radius[s]);
+    std::printf(", rms %.9g\n", reg.rms[reg.stages - 1]);
+    for (int r = 0; r < 3; ++r)
+      std::printf("T %.17g %.17g %.17g %.17g\n", reg.T[4 * r], reg.T[4 * r + 1], reg.T[4 * r + 2], reg.T[4 * r + 3]);
   }
   if (prepared) {
     std::printf("prepared: voxel %.9g, crop", (double)prep.voxel);
@@ -112,6 +144,16 @@ int main(int argc, char** argv) {
                      (double)prep.crop_lo[2], (double)prep.crop_hi[0], (double)prep.crop_hi[1], (double)prep.crop_hi[2]);
       else
         std::fprintf(f, "null");
+    }
+    if (registered) {
+      std::fprintf(f, ", \"registration\": {\"T\": [");
+      for (int r = 0; r < 3; ++r)
+        std::fprintf(f, "%s[%.17g, %.17g, %.17g, %.17g]", r ? ", " : "", reg.T[4 * r], reg.T[4 * r + 1], reg.T[4 * r + 2], reg.T[4 * r + 3]);
+      std::fprintf(f, "], \"stages\": [");
+      for (int s = 0; s < reg.stages; ++s)
+        std::fprintf(f, "%s{\"radius\": %.17g, \"iters\": %d, \"matched\": %lld, \"rms\": %.17g, \"converged\": %d}", s ? ", " : "",
+                     (double)ropt.radius[s], reg.iters[s], reg.matched[s], reg.rms[s], reg.converged[s]);
+      std::fprintf(f, "]}");
     }
     std::fprintf(f, "}\n");
     std::fclose(f);

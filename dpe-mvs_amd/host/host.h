@@ -164,5 +164,24 @@ void cloud_crop(const float* xyz, size_t n, const float lo[3], const float hi[3]
 // down-sampling and the distances in one context on that device
 bool cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                      int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err);
+// what cloud_eval_prep refuses in its clouds and its block before any work (the message into err)
+bool cloud_prep_args(const float* recon, size_t n, const float* gt, size_t m, const DpeCloudPrep& prep, std::string& err);
+// one cloud through the preparation (crop when `crop`, then voxel > 0) into pts; ctx or nullptr as above
+bool cloud_prepare(DpeContext* ctx, const float* xyz, size_t n, const DpeCloudPrep& prep, bool crop, std::vector<float>& pts,
+                   std::string& err);
+// cloud_eval_prep after the checks, over a context the caller owns (nullptr: on the host)
+bool cloud_eval_prep_in(DpeContext* ctx, const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau,
+                        float radius, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err);
+// cloud_eval.cpp: the nearest neighbour with its index (dpe_cloud_nn_index of dpe_mvs.h) over cloud_nn's grid
+bool cloud_radius_ok(float radius);
+bool cloud_nn_index(const float* query, size_t n, const float* target, size_t m, float radius, float* out, int32_t* idx,
+                    std::string& err);
+// cloud_register.cpp: one ICP step, the solve and the loop (dpe_host.h states them); register_in runs over a context
+// the caller owns (nullptr: the host step)
+bool cloud_icp_step(const float* src, size_t n, const float* tgt, size_t m, float radius, const double* T, DpeIcpSums* out,
+                    std::string& err);
+bool cloud_solve(const DpeIcpSums& s, const double* o_s, const double* o_t, double* T, std::string& err);
+bool cloud_register_in(DpeContext* ctx, const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions& opt,
+                       DpeCloudReg* out, std::string& err);
 
 }  // namespace dpe_host

@@ -262,8 +262,8 @@ int dpe_host_consistency_angle_test(float dot);
 /*
  * Cloud evaluation: precision, recall and F-score of a reconstructed cloud against a ground-truth cloud.
  * No counterpart in the reference.  The numbers are those of the two clouds as given: no registration,
- * cropping or down-sampling (dpe_host_cloud_eval_prep below adds a crop box and voxel down-sampling; registration
- * stays out), so they are not a benchmark's leaderboard figures.
+ * cropping or down-sampling (dpe_host_cloud_eval_prep below adds a crop box and voxel down-sampling,
+ * dpe_host_cloud_eval_reg a rigid registration before them), so they are not a benchmark's leaderboard figures.
  *   dpe_host_cloud_nn          the contract of dpe_cloud_nn (dpe_mvs.h: d2, truncation at R2 = R*R, non-finite
  *                              points) over the same grid on host threads (at most 16): the same bits.  The
  *                              yardstick of the device path and the path used without a GPU.
@@ -340,6 +340,69 @@ size_t dpe_host_cloud_crop(const float* xyz, size_t n, const uint8_t* rgb_or_nul
 int dpe_host_read_point_cloud_rgb(const char* path, float* xyz, uint8_t* rgb, size_t cap, size_t* n, int* has_rgb);
 int dpe_host_cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                              int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out);
+
+/*
+ * Rigid registration of a source cloud to a target cloud: point-to-point ICP over the nearest neighbour with
+ * index (dpe_mvs.h states both contracts).  No counterpart in the reference.
+ *   dpe_host_cloud_nn_index   the contract of dpe_cloud_nn_index over dpe_host_cloud_nn's grid on host threads
+ *                             (at most 16): the same indices and bits.
+ *   dpe_host_cloud_icp_step   one step (dpe_cloud_icp_step's contract) with the pairwise tree taken literally:
+ *                             the yardstick of the device step.
+ *   dpe_host_cloud_transform  out[i] = the image of xyz[i] under T (12 doubles, row-major 3 x 4), the x'
+ *                             expression of the step; a non-finite point becomes NaN on every axis.  out may be
+ *                             xyz.
+ *   dpe_host_cloud_solve      the absolute transform of the ORIGINAL source points from one step's sums, N =
+ *                             matched >= 3: means sum(a)/N and sum(b)/N, H = sum(ab) - sum(a) sum(b)^T / N, the
+ *                             rotation from Horn's unit quaternion (the eigenvector of the 4 x 4 symmetric matrix
+ *                             of H with the largest eigenvalue, cyclic Jacobi in double, sqrt the only libm call),
+ *                             always a proper rotation; t = (o_t + mean b) - R (o_s + mean a).  Host only, and
+ *                             what both paths of dpe_host_cloud_register call.
+ *   dpe_host_cloud_register   the loop.  radius[0 .. n_radii): 1 to 4 stages, each finite and > 0, run in the
+ *                             given order (coarse to fine); per stage at most max_iters steps (1..1000), each
+ *                             followed by the solve, so nothing is composed from step to step.  rms =
+ *                             sqrt(sum(d2) / N).  A stage ends after a step whose sums and count equal the
+ *                             previous step's bit for bit (converged = 2, a fixed point), else when
+ *                             |rms - rms_prev| <= tol * rms_prev (converged = 1; tol >= 0), else at max_iters
+ *                             (converged = 0).  Starts from init (use_init != 0) or the identity.  Fewer than 3
+ *                             matches in a step fail ("fewer than 3 matches within the radius").  gpu_index < 0:
+ *                             dpe_host_cloud_icp_step; else dpe_cloud_icp_stage / dpe_cloud_icp_step in a context
+ *                             of its own on that device: equal structs.  On failure *out is not written.
+ *   dpe_host_cloud_eval_reg   dpe_host_cloud_eval_prep after a registration of the reconstruction to the ground
+ *                             truth: with prep->voxel > 0 the voxel-down-sampled copies of both clouds are
+ *                             registered, and the ground truth is cropped first when prep has a box (the
+ *                             reconstruction is not: the box is in the ground truth's frame); then the WHOLE
+ *                             reconstruction is transformed and scored exactly as dpe_host_cloud_eval_prep scores
+ *                             it (prep may be NULL).  Everything on gpu_index runs in one context.
+ * Each returns 0, or nonzero with the message in dpe_pipeline_last_error().
+ */
+#define DPE_CLOUD_MAX_RADII 4
+typedef struct DpeCloudRegOptions {
+  float radius[DPE_CLOUD_MAX_RADII];
+  int n_radii;
+  int max_iters;
+  double tol;
+  int use_init;
+  double init[12];
+} DpeCloudRegOptions;
+typedef struct DpeCloudReg {
+  double T[12];
+  int stages;
+  int iters[DPE_CLOUD_MAX_RADII];
+  long long matched[DPE_CLOUD_MAX_RADII];
+  double rms[DPE_CLOUD_MAX_RADII];
+  int converged[DPE_CLOUD_MAX_RADII];
+} DpeCloudReg;
+int dpe_host_cloud_nn_index(const float* query, size_t n, const float* target, size_t m, float radius, float* d2_out,
+                            int32_t* idx_out);
+int dpe_host_cloud_icp_step(const float* src, size_t n, const float* tgt, size_t m, float radius, const double* T,
+                            DpeIcpSums* out);
+int dpe_host_cloud_transform(const double* T, const float* xyz, size_t n, float* out);
+int dpe_host_cloud_solve(const DpeIcpSums* sums, const double* o_s, const double* o_t, double* T);
+int dpe_host_cloud_register(const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions* opt,
+                            int gpu_index, DpeCloudReg* out);
+int dpe_host_cloud_eval_reg(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
+                            int gpu_index, DpeCloudPrep* prep_or_null, const DpeCloudRegOptions* opt, DpeCloudReg* reg,
+                            DpeCloudEval* out);
 
 #ifdef __cplusplus
 }

@@ -509,6 +509,52 @@ int dpe_cloud_last_timings(DpeContext* ctx, float* ms, int n);
 int dpe_cloud_voxel(DpeContext* ctx, const float* xyz, size_t n, const uint8_t* rgb_or_null, float voxel, float* out_xyz,
                     uint8_t* out_rgb, int32_t* out_first, int32_t* out_count, size_t cap, size_t* k);
 
+/*
+ * Rigid registration of two clouds: the nearest neighbour WITH its index, and one step of point-to-point ICP
+ * reduced to 16 sums and a count (the solve and the loop are the host's: dpe_host_cloud_register, dpe_host.h).
+ * No counterpart in the reference.  Clouds, radius and refusals are dpe_cloud_nn's.
+ *
+ * Nearest neighbour with index.  idx[i] = the j that minimises the pair (d2(Q[i], T[j]), j) lexicographically
+ * over the finite T[j] with d2 < R2; d2, R2 = R*R and the strict < are dpe_cloud_nn's, and d2_out[i] is what
+ * dpe_cloud_nn returns.  idx[i] = -1 when nothing is within R, when the query is non-finite and when the target
+ * is empty.  A lexicographic minimum over a set does not depend on the order in which the candidates are met:
+ * the result is a serial loop's to the bit (dpe_host_cloud_nn_index is that loop over the same grid).
+ *
+ * One ICP step.  Source P (n points), target G (m points), radius R, transform T: 12 doubles, row-major 3 x 4,
+ * [R | t].  Per source index i with a finite P[i]:
+ *   x' = (float)(((T[0]*x + T[1]*y) + T[2]*z) + T[3]),  y', z' from rows 1 and 2
+ * in double, every operation rounded, in this order, no contraction.  (x', y', z') is matched against G by the
+ * rule above; a non-finite P[i] or a non-finite image has no match.  A source without a match contributes +0.0
+ * to every sum.  A matched source (to G[j] at squared distance d2) contributes the 16 terms
+ *   (double)d2,  a[r] = (double)P[i][r] - o_s[r],  b[c] = (double)G[j][c] - o_t[c],  a[r] * b[c]   (r, c in 0..2)
+ * where o_s and o_t are the per-axis minima of each cloud's finite points as doubles (the centring keeps a cloud
+ * at an offset of +-1000 from cancelling in sum(ab) - sum(a) sum(b) / N) and the products are rounded doubles.
+ * Each of the 16 sums is taken by PAIRWISE SUMMATION IN INDEX ORDER: level 0 is the n terms, level l + 1 has
+ * s[k] = s_l[2k] + s_l[2k + 1] with +0.0 for a missing right operand, until one value is left.  Addition is
+ * commutative, so an xor butterfly gives these bits in every lane, and 256 consecutive leaves are a complete
+ * subtree, so blocks of 256 and further levels over the block results are the same tree.  The terms are indexed
+ * by SOURCE index, so a fixed tree over that index costs nothing to fix and plain doubles do (the voxel
+ * centroid sums per cell in an order only a sort could fix, which is why it went to an integer lattice).  The
+ * matched count is an integer.  dpe_host_cloud_icp_step (dpe_host.h) takes the tree literally: the same bits.
+ *
+ *   dpe_cloud_nn_index   one direction with indices: d2_out f32 [n], idx_out i32 [n].  Synchronous.
+ *   dpe_cloud_icp_stage  uploads both clouds, takes their bounds and builds the target's grid for `radius` once;
+ *                        clouds and grid stay resident until the next cloud call of the context.  Call it again
+ *                        for the next radius of a schedule.
+ *   dpe_cloud_icp_step   one step over what is staged: T goes up (96 bytes), DpeIcpSums comes down.  Without a
+ *                        staged pair DPE_ERR_STATE.  dpe_cloud_last_timings then reports [0] apply + build of the
+ *                        transformed source, [1] match, [2] sums, [3] download.
+ * Concurrency, error strings, dpe_cloud_launches and the buffers are dpe_cloud_nn's.
+ */
+typedef struct DpeIcpSums {
+  long long matched;
+  double d2, a[3], b[3], ab[9];         /* ab[3 * r + c] = sum of a[r] * b[c] */
+} DpeIcpSums;
+int dpe_cloud_nn_index(DpeContext* ctx, const float* query, size_t n, const float* target, size_t m, float radius,
+                       float* d2_out, int32_t* idx_out);
+int dpe_cloud_icp_stage(DpeContext* ctx, const float* src, size_t n, const float* tgt, size_t m, float radius);
+int dpe_cloud_icp_step(DpeContext* ctx, const double* T, DpeIcpSums* out);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);

@@ -23,7 +23,18 @@ With --voxel V --ab LIB LIB... it instead compares builds of libdpe_mvs.so (tool
 down-sampling, interleaved in one process: the cells + insert part and the whole call's wall time per build on the
 800 x 600 cloud and on the two line clouds, every build held to the first one's records.
 
-Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]]"""
+With --register R the tool measures the ICP step instead (dpe_cloud_icp_stage / dpe_cloud_icp_step in a warm context
+against dpe_host_cloud_icp_step) on the 800 x 600 pair, target A and source B moved by the inverse of the tests'
+(R0, t0) (4 degrees about (1, 2, 3), shift (0.03, -0.02, 0.01)), at match radius R, and writes
+profiles/cloud_register.json: the wall time of one device step and of one host step under the true transform (median
+and spread of --reps runs after a warm-up; the host step includes the build of the target's grid, which the device
+stages once), the step's device parts (apply + build, match, sums, download: dpe_cloud_last_timings), the kernels
+launched per step, and a loop driven from here, step by step with the host's solve, from a start within reach of R
+(the true transform turned by 0.02 degrees and shifted by R / 4) to the fixed point: the number of steps and every
+step's parts.  The radius of a whole-scene 4 degree error (0.35 here) is out of the grid's reach at this density, so
+the loop from the identity is not what is timed.
+
+Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]] [--register R]"""
 import argparse
 import json
 import os
@@ -42,8 +53,10 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--voxel", type=float, default=None, help="measure the voxel down-sampling at this edge instead")
 ap.add_argument("--ab", nargs="+", default=None, help="with --voxel: builds of libdpe_mvs.so to compare, interleaved")
+ap.add_argument("--register", type=float, default=None, help="measure the ICP step at this match radius instead")
 a = ap.parse_args()
-a.out = a.out or os.path.join(ROOT, "profiles", "cloud_eval.json" if a.voxel is None else "cloud_voxel.json")
+a.out = a.out or os.path.join(ROOT, "profiles", "cloud_register.json" if a.register is not None else
+                              "cloud_eval.json" if a.voxel is None else "cloud_voxel.json")
 
 
 def best_of(fn, reps):
@@ -170,6 +183,88 @@ def voxel_ab(paths):
         L.dpe_destroy(c)
     return out
 
+
+def rotation(axis, degrees):
+    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    th = np.deg2rad(degrees)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def register_profile():
+    R = a.register
+    PARTS = ("apply_build", "match", "sums", "download")
+    sc = synthetic.make_scene(800, 600, 4)
+    A = synthetic.gt_point_cloud(sc)
+    del sc
+    rng = np.random.default_rng(3)
+    tau = 2 * 5.0 / (1.2 * 800)
+    u = rng.normal(0, 1, A.shape)
+    B = (A + 0.5 * tau * u / np.linalg.norm(u, axis=1, keepdims=True)).astype(np.float32)
+    R0, t0 = rotation([1, 2, 3], 4.0), np.array([0.03, -0.02, 0.01])
+    src = ((B.astype(np.float64) - t0) @ R0).astype(np.float32)             # B under (R0, t0)^-1
+    true = np.concatenate([R0, t0[:, None]], axis=1)
+    out = {"radius": R, "points_per_cloud": int(len(A)), "host_threads": min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 16)),
+           "reps": a.reps}
+    ctx = native.PatchMatchContext(0)
+    ctx.set_timing(True)
+    t = time.perf_counter()
+    ctx.cloud_icp_stage(src, A, R)
+    out["device_stage_seconds_cold"] = time.perf_counter() - t
+    ctx.cloud_icp_step(true)                                                # warm-up
+    dev, parts, launches = [], [], []
+    for _ in range(a.reps):
+        l0 = native.cloud_launches()
+        t = time.perf_counter()
+        d = ctx.cloud_icp_step(true)
+        dev.append(time.perf_counter() - t)
+        launches.append(native.cloud_launches() - l0)
+        parts.append(dict(zip(PARTS, ctx.cloud_timings().values())))
+    pipeline.cloud_icp_step(src, A, R, true)                                # warm-up
+    host = []
+    for _ in range(max(1, a.reps)):
+        t = time.perf_counter()
+        h = pipeline.cloud_icp_step(src, A, R, true)
+        host.append(time.perf_counter() - t)
+    out["identical"] = bool(d == h)
+    out["matched"] = d["matched"]
+    out["device_step_seconds"] = {"median": float(np.median(dev)), "min": min(dev), "max": max(dev)}
+    out["host_step_seconds"] = {"median": float(np.median(host)), "min": min(host), "max": max(host)}
+    out["device_parts_ms"] = {k: {"median": float(np.median([p[k] for p in parts])), "min": min(p[k] for p in parts),
+                                  "max": max(p[k] for p in parts)} for k in PARTS}
+    out["launches_per_step"] = sorted(set(launches))
+    print(json.dumps(out), flush=True)
+    # the loop from a start within reach of R, driven step by step so that every step's parts are seen
+    fin_s, fin_t = np.isfinite(src).all(axis=1), np.isfinite(A).all(axis=1)
+    o_s, o_t = src[fin_s].astype(np.float64).min(axis=0), A[fin_t].astype(np.float64).min(axis=0)
+    near = rotation([0, 1, 0], 0.02)
+    T = np.concatenate([near @ R0, (near @ t0 + R / 4)[:, None]], axis=1)
+    prev, steps, fixed = None, [], False
+    t = time.perf_counter()
+    for it in range(1, 201):
+        s = ctx.cloud_icp_step(T)
+        steps.append(dict(zip(PARTS, ctx.cloud_timings().values()), matched=s["matched"], rms=float(np.sqrt(s["d2"] / max(1, s["matched"])))))
+        T = pipeline.cloud_solve(s, o_s, o_t)
+        fixed = s == prev
+        if fixed:
+            break
+        prev = s
+    out["loop"] = {"start": "true transform turned by 0.02 degrees about y and shifted by R / 4", "steps_to_fixed_point": it,
+                   "reached_fixed_point": fixed, "wall_seconds": time.perf_counter() - t,
+                   "final_T_minus_true_max": float(np.abs(T - true).max()), "steps": steps}
+    print(json.dumps({k: v for k, v in out["loop"].items() if k != "steps"}), flush=True)
+    ctx.close()
+    return out
+
+
+if a.register is not None:
+    result = register_profile()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("written", a.out)
+    sys.exit(0)
 
 if a.voxel is not None:
     result = voxel_ab(a.ab) if a.ab else voxel_profile()
