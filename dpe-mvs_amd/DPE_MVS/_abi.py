@@ -43,6 +43,20 @@ class DpeIcpSums(C.Structure):   # include/dpe_mvs.h (one ICP step: the matched 
     _fields_ = [("matched", C.c_longlong), ("d2", C.c_double), ("a", C.c_double * 3), ("b", C.c_double * 3), ("ab", C.c_double * 9)]
 
 
+DEPTH_MAX_TAU = 16
+DEPTH_TAU_ABS, DEPTH_TAU_REL = 0, 1
+
+
+class DpeDepthScore(C.Structure):   # include/dpe_mvs.h (one depth map against its ground truth: counts and pairwise sums)
+    _fields_ = [("n_px", C.c_longlong), ("n_gt", C.c_longlong), ("n_est", C.c_longlong), ("n_both", C.c_longlong),
+                ("within", C.c_longlong * DEPTH_MAX_TAU), ("sum_abs", C.c_double), ("sum_rel", C.c_double), ("sum_sq", C.c_double)]
+
+
+def depth_score_dict(s: DpeDepthScore, n_tau: int) -> dict:
+    return dict(n_px=int(s.n_px), n_gt=int(s.n_gt), n_est=int(s.n_est), n_both=int(s.n_both),
+                within=[int(v) for v in s.within[:n_tau]], sum_abs=s.sum_abs, sum_rel=s.sum_rel, sum_sq=s.sum_sq)
+
+
 class DpePatchMatchParams(C.Structure):
     _fields_ = [
         ("max_iterations", C.c_int),

@@ -30,6 +30,7 @@ EXPORTED = [
     "dpe_fusion_consistency", "dpe_consistency_launches",
     "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings", "dpe_cloud_voxel",
     "dpe_cloud_nn_index", "dpe_cloud_icp_stage", "dpe_cloud_icp_step",
+    "dpe_cloud_render_stage", "dpe_cloud_render_view", "dpe_depth_score",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -151,6 +152,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_cloud_icp_stage.restype = C.c_int
     lib.dpe_cloud_icp_step.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DpeIcpSums)]
     lib.dpe_cloud_icp_step.restype = C.c_int
+    lib.dpe_cloud_render_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.dpe_cloud_render_stage.restype = C.c_int
+    lib.dpe_cloud_render_view.argtypes = [C.c_void_p, C.POINTER(_abi.DpeCamera), C.c_int, C.c_void_p]
+    lib.dpe_cloud_render_view.restype = C.c_int
+    lib.dpe_depth_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                    C.POINTER(_abi.DpeDepthScore), C.c_void_p]
+    lib.dpe_depth_score.restype = C.c_int
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
@@ -500,9 +508,45 @@ class PatchMatchContext:
         _check(_LIB.dpe_cloud_icp_step(self._ctx, t.ctypes.data, C.byref(s)), "dpe_cloud_icp_step")
         return dict(matched=int(s.matched), d2=s.d2, a=list(s.a), b=list(s.b), ab=list(s.ab))
 
+    # depth-map evaluation (include/dpe_mvs.h: dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score)
+    def cloud_render_stage(self, points) -> None:
+        """Uploads a scan f32 [n, 3]; it stays resident for cloud_render_view until the next cloud call of the context."""
+        p = as_cloud(points)
+        _check(_LIB.dpe_cloud_render_stage(self._ctx, p.ctypes.data, len(p)), "dpe_cloud_render_stage")
+
+    def cloud_render_view(self, cam: _abi.DpeCamera, splat: int = 0, download: bool = True):
+        """The staged scan rendered into `cam` (at the map's size) with a z-buffer and a splat half-width of 0 to 8:
+        f32 [height, width], the minimum depth per pixel and 0 where no point falls (pipeline.render_cloud gives the
+        same bits on the host).  The map stays resident for depth_score; download=False returns None."""
+        w, h = int(cam.width), int(cam.height)
+        out = np.empty((max(h, 0), max(w, 0)), np.float32) if download else None
+        _check(_LIB.dpe_cloud_render_view(self._ctx, C.byref(cam), int(splat), None if out is None else out.ctypes.data),
+               "dpe_cloud_render_view")
+        return out
+
+    def depth_score(self, est, gt, taus, relative: bool = False, want_error: bool = False):
+        """The map `est` f32 [h, w] against `gt` (None: the last rendered map) at the thresholds `taus`: the counts and
+        the three pairwise sums as a dict (pipeline.score_depth gives the same bits on the host); with want_error
+        (dict, error map f32 [h, w])."""
+        e = np.ascontiguousarray(est, np.float32)
+        if e.ndim != 2:
+            raise ValueError("expected a map of shape [h, w]")
+        g = None if gt is None else np.ascontiguousarray(gt, np.float32)
+        if g is not None and g.shape != e.shape:
+            raise ValueError("the maps differ in shape")
+        t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
+        s = _abi.DpeDepthScore()
+        err = np.empty(e.shape, np.float32) if want_error else None
+        _check(_LIB.dpe_depth_score(self._ctx, e.ctypes.data, None if g is None else g.ctypes.data, e.shape[1], e.shape[0],
+                                    t.ctypes.data, len(t), _abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS, C.byref(s),
+                                    None if err is None else err.ctypes.data), "dpe_depth_score")
+        d = _abi.depth_score_dict(s, len(t))
+        return (d, err) if want_error else d
+
     def cloud_timings(self) -> dict:
         """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}.  After
-        cloud_voxel the four slots are, in this order, stage, cells + insert, emit and download."""
+        cloud_voxel the four slots are, in this order, stage, cells + insert, emit and download; after
+        cloud_render_stage, cloud_render_view and depth_score stage, render, score and download."""
         buf = (C.c_float * 4)()
         n = _LIB.dpe_cloud_last_timings(self._ctx, buf, 4)
         return {k: float(buf[i]) for i, k in enumerate(("stage", "build", "query", "download")) if i < n}

@@ -101,6 +101,25 @@ class DpeCloudReg(C.Structure):   # include/dpe_host.h
                 ("converged", C.c_int * CLOUD_MAX_RADII)]
 
 
+DpeDepthScore = _abi.DpeDepthScore   # include/dpe_mvs.h
+DEPTH_MAX_TAU = _abi.DEPTH_MAX_TAU
+
+
+class DpeDepthStats(C.Structure):   # include/dpe_host.h
+    _fields_ = [("accuracy", C.c_double * DEPTH_MAX_TAU), ("completeness", C.c_double * DEPTH_MAX_TAU), ("mae", C.c_double),
+                ("mre", C.c_double), ("rmse", C.c_double)]
+
+
+class DpeDepthEvalOptions(C.Structure):   # include/dpe_host.h
+    _fields_ = [("dense_folder", C.c_char_p), ("map_name", C.c_char_p), ("gt_maps_dir", C.c_char_p), ("splat", C.c_int),
+                ("mode", C.c_int), ("n_tau", C.c_int), ("tau", C.c_float * DEPTH_MAX_TAU), ("write_maps", C.c_int),
+                ("gpu_index", C.c_int)]
+
+
+class DpeDepthImage(C.Structure):   # include/dpe_host.h
+    _fields_ = [("id", C.c_int), ("width", C.c_int), ("height", C.c_int), ("score", DpeDepthScore)]
+
+
 class PipelineError(RuntimeError):
     pass
 
@@ -174,6 +193,15 @@ def lib() -> C.CDLL:
         L.dpe_host_cloud_eval_reg.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_float,
                                               C.c_int, C.POINTER(DpeCloudPrep), C.POINTER(DpeCloudRegOptions),
                                               C.POINTER(DpeCloudReg), C.POINTER(DpeCloudEval)]
+        L.dpe_host_cloud_render.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(_abi.DpeCamera), C.c_int, C.c_void_p]
+        L.dpe_host_depth_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                           C.POINTER(DpeDepthScore), C.c_void_p]
+        L.dpe_host_depth_stats.argtypes = [C.POINTER(DpeDepthScore), C.c_int, C.POINTER(DpeDepthStats)]
+        L.dpe_host_depth_stats.restype = None
+        L.dpe_host_read_npy_f32.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.dpe_host_depth_eval_list.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.dpe_host_depth_eval.argtypes = [C.POINTER(DpeDepthEvalOptions), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_size_t), C.POINTER(DpeDepthScore)]
         _lib = L
     return _lib
 
@@ -681,6 +709,146 @@ def format_cloud_eval(e: dict) -> str:
     rows += ["%14.9g %10.6f %10.6f %10.6f" % v for v in zip(e["tau"], e["precision"], e["recall"], e["fscore"])]
     rows += ["mean accuracy (truncated at the radius) %.9g" % e["mean_accuracy_truncated"],
              "mean completeness (truncated at the radius) %.9g" % e["mean_completeness_truncated"]]
+    return "\n".join(rows) + "\n"
+
+
+# ------------------------------------------------------------------------------ depth-map evaluation (C++, depth_eval.cpp)
+def read_npy_f32(path: str) -> np.ndarray:
+    """A 2-D '<f4' .npy v1.0 in C order through the host library's reader (dpe_host_read_npy_f32): f32 [h, w].
+    PipelineError with the reader's message for what it refuses (another dtype, rank or order, a body that is
+    shorter or longer than the header says)."""
+    w, h = C.c_int(), C.c_int()
+    if lib().dpe_host_read_npy_f32(os.fsencode(path), None, 0, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    out = np.empty((h.value, w.value), np.float32)
+    if lib().dpe_host_read_npy_f32(os.fsencode(path), out.ctypes.data, out.size, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def render_cloud(points, cam: _abi.DpeCamera, splat: int = 0, gpu_index: int = -1) -> np.ndarray:
+    """The scan `points` f32 [n, 3] rendered into `cam` (a camera at the map's size) with a z-buffer: f32
+    [height, width], per pixel the minimum depth of the points whose (2 splat + 1)^2 pixels cover it, 0 where none
+    does (include/dpe_mvs.h, dpe_cloud_render_view, states the contract; no occlusion test beyond the z-buffer).
+    gpu_index < 0: the host loop (dpe_host_cloud_render), else on that device: the same bits."""
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            ctx.cloud_render_stage(points)
+            return ctx.cloud_render_view(cam, splat)
+        except native.DpeError as e:
+            raise PipelineError(str(e)) from None
+        finally:
+            ctx.close()
+    p = _as_cloud(points)
+    out = np.empty((max(int(cam.height), 0), max(int(cam.width), 0)), np.float32)
+    if lib().dpe_host_cloud_render(p.ctypes.data, len(p), C.byref(cam), int(splat), out.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def depth_stats(score: dict) -> dict:
+    """What is derived from a score's counts and sums, in double (dpe_host_depth_stats, the one function both paths
+    and both programs go through): accuracy and completeness per threshold, mae, mre, rmse; 0 for an empty
+    denominator."""
+    s, d = DpeDepthScore(), DpeDepthStats()
+    k = len(score["within"])
+    for name in ("n_px", "n_gt", "n_est", "n_both", "sum_abs", "sum_rel", "sum_sq"):
+        setattr(s, name, score[name])
+    for i, v in enumerate(score["within"]):
+        s.within[i] = v
+    lib().dpe_host_depth_stats(C.byref(s), k, C.byref(d))
+    return dict(accuracy=list(d.accuracy[:k]), completeness=list(d.completeness[:k]), mae=d.mae, mre=d.mre, rmse=d.rmse)
+
+
+def _depth_dict(s: DpeDepthScore, k: int) -> dict:
+    d = _abi.depth_score_dict(s, k)
+    d.update(depth_stats(d))
+    return d
+
+
+def score_depth(est, gt, taus, relative: bool = False, gpu_index: int = -1, want_error: bool = False):
+    """The depth map `est` against the ground-truth map `gt` (f32 [h, w]) at the thresholds `taus` (1 to 16, each
+    finite and >= 0; relative: |est - gt| < tau * gt instead of < tau).  A dict of the counts n_px, n_gt, n_est,
+    n_both, within[k], the pairwise sums sum_abs, sum_rel, sum_sq (include/dpe_mvs.h, dpe_depth_score) and
+    depth_stats of them.  gpu_index < 0: the host loop (dpe_host_depth_score), else on that device: equal dicts.
+    want_error: (dict, error map f32 [h, w]: the error where both are usable, -1 where only gt is, else -2)."""
+    t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
+    e, g = np.ascontiguousarray(est, np.float32), np.ascontiguousarray(gt, np.float32)
+    if e.ndim != 2 or g.shape != e.shape:
+        raise PipelineError("depth_score: size mismatch: two maps of one shape [h, w] expected")
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            r = ctx.depth_score(e, g, t, relative, want_error)
+        except native.DpeError as x:
+            raise PipelineError(str(x)) from None
+        finally:
+            ctx.close()
+        d, err = r if want_error else (r, None)
+        d.update(depth_stats(d))
+        return (d, err) if want_error else d
+    s = DpeDepthScore()
+    err = np.empty(e.shape, np.float32) if want_error else None
+    if lib().dpe_host_depth_score(e.ctypes.data, g.ctypes.data, e.shape[1], e.shape[0], t.ctypes.data, len(t),
+                                  _abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS, C.byref(s),
+                                  None if err is None else err.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    d = _depth_dict(s, len(t))
+    return (d, err) if want_error else d
+
+
+def evaluate_depth_maps(dense_folder: str, gt, taus, relative: bool = False, splat: int = 0, map_name: str = "depth.npy",
+                        gt_maps: str | None = None, write_maps: bool = False, gpu_index: int = -1) -> dict:
+    """The depth maps DPE/%08d/<map_name> of a dense folder, in ascending image id, against the scan `gt` (f32
+    [n, 3]) rendered into each cams/%08d_cam.txt at the map's size (render_cloud, half-width `splat`), or, with
+    gt_maps = a folder, against its %08d.npy (dpe_host_depth_eval).  write_maps also writes depth_gt.npy and
+    depth_error.npy beside each map.  gpu_index < 0: on the host, else the scan is staged once on that device and
+    every view rendered and scored there: equal dicts.  Keys: map, relative, splat, tau, n_gt_points, images (a
+    list of score_depth's dicts with id, width, height) and total (the counts added, the sums added in ascending
+    id, and depth_stats of them)."""
+    t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
+    if len(t) < 1 or len(t) > DEPTH_MAX_TAU:
+        raise PipelineError("depth_score: 1 to 16 thresholds expected")
+    if gt is None and gt_maps is None:
+        raise PipelineError("depth_eval: a scan or a folder of ground-truth maps expected")
+    p = _as_cloud(np.empty((0, 3), np.float32) if gt is None else gt)
+    o = DpeDepthEvalOptions()
+    o.dense_folder, o.map_name = os.fsencode(dense_folder), os.fsencode(map_name)
+    o.gt_maps_dir = None if gt_maps is None else os.fsencode(gt_maps)
+    o.splat, o.mode, o.n_tau = int(splat), (_abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS), len(t)
+    for k, v in enumerate(t):
+        o.tau[k] = v
+    o.write_maps, o.gpu_index = int(bool(write_maps)), int(gpu_index)
+    n = C.c_size_t()
+    if lib().dpe_host_depth_eval_list(o.dense_folder, o.map_name, None, 0, C.byref(n)) != 0:
+        raise PipelineError(_last_error())
+    rows, total = (DpeDepthImage * n.value)(), DpeDepthScore()
+    if lib().dpe_host_depth_eval(C.byref(o), p.ctypes.data, len(p), rows, n.value, C.byref(n), C.byref(total)) != 0:
+        raise PipelineError(_last_error())
+    images = [dict(_depth_dict(r.score, len(t)), id=int(r.id), width=int(r.width), height=int(r.height)) for r in rows[:n.value]]
+    return dict(map=map_name, relative=bool(relative), splat=int(splat), tau=[float(v) for v in t],
+                n_gt_points=(None if gt_maps is not None else len(p)), images=images, total=_depth_dict(total, len(t)))
+
+
+def format_depth_eval(e: dict) -> str:
+    """The table bin/dpe_depth_eval prints, from evaluate_depth_maps' dict."""
+    gt = "maps" if e["n_gt_points"] is None else "cloud of %d points, splat %d" % (e["n_gt_points"], e["splat"])
+    k = len(e["tau"])
+    rows = ["map %s, ground truth %s, %s thresholds %s" % (e["map"], gt, "relative" if e["relative"] else "absolute",
+                                                           " ".join("%.9g" % v for v in e["tau"])),
+            "%8s %11s %10s %10s %10s %12s %12s %12s" % ("image", "size", "n_gt", "n_est", "n_both", "mae", "mre", "rmse")
+            + "".join(" %10s %10s" % ("acc[%d]" % i, "comp[%d]" % i) for i in range(k))]
+
+    def row(name, size, s):
+        return ("%8s %11s %10d %10d %10d %12.6g %12.6g %12.6g" % (name, size, s["n_gt"], s["n_est"], s["n_both"], s["mae"], s["mre"],
+                                                                   s["rmse"])
+                + "".join(" %10.6f %10.6f" % v for v in zip(s["accuracy"], s["completeness"])))
+
+    rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
+    rows.append(row("total", "-", e["total"]))
     return "\n".join(rows) + "\n"
 
 

@@ -1,0 +1,87 @@
+// depth_eval.h — the arithmetic of the depth-map evaluation (dpe_cloud_render_view and dpe_depth_score of
+// include/dpe_mvs.h, which states the contract) that the host (host/depth_eval.cpp) shares with the kernels
+// (pass_render.h): the projection of a scan point, its centre pixel, the test for a usable depth and what one
+// pixel contributes to a score.  Plain C++, -ffp-contract=off like everything here: every operation below is one
+// rounded single-precision operation with IEEE division, unless a double is written.
+#pragma once
+#include "../../include/dpe_mvs.h"
+#include "cloud_dist.h"   // DPE_CHD, cloud_finite3
+
+namespace dpe {
+
+constexpr int kDepthMaxSplat = 8;
+constexpr int kDepthTerms = 3;                  // e, rel, e * e
+constexpr uint32_t kDepthEmpty = 0x7F800000u;   // +inf: a pixel of the z-buffer that no point covers yet
+
+DPE_CHD uint32_t depth_bits(float v) {
+  union { float f; uint32_t u; } b;
+  b.f = v;
+  return b.u;
+}
+
+// a usable depth: positive and finite, decided on the bit pattern (a NaN, a zero of either sign and every
+// negative number fail; positive finite floats order as these integers)
+DPE_CHD bool depth_ok(float v) {
+  const uint32_t u = depth_bits(v);
+  return u > 0u && u < kDepthEmpty;
+}
+
+// ProjectCamera in the reference's order: fz_project's expression (fusion_world.h), for host and device
+DPE_CHD void depth_project(const DpeCamera& cam, float x, float y, float z, float& px, float& py, float& depth) {
+  const float tx = cam.R[0] * x + cam.R[1] * y + cam.R[2] * z + cam.t[0];
+  const float ty = cam.R[3] * x + cam.R[4] * y + cam.R[5] * z + cam.t[1];
+  const float tz = cam.R[6] * x + cam.R[7] * y + cam.R[8] * z + cam.t[2];
+  depth = cam.K[6] * tx + cam.K[7] * ty + cam.K[8] * tz;
+  px = (cam.K[0] * tx + cam.K[1] * ty + cam.K[2] * tz) / depth;
+  py = (cam.K[3] * tx + cam.K[4] * ty + cam.K[5] * tz) / depth;
+}
+
+// the centre pixel by fusion's rule (pass_fusion.h): false when the point falls outside a w x h image
+DPE_CHD bool depth_centre(float px, float py, int w, int h, int& cx, int& cy) {
+  const float fx = px + 0.5f, fy = py + 0.5f;
+  if (!(fx > -1.0f && fx < (float)w && fy > -1.0f && fy < (float)h)) return false;
+  cx = (int)fx;
+  cy = (int)fy;
+  return true;
+}
+
+// One scan point in a view: false when it renders nothing, else its centre pixel and the bits of its depth
+DPE_CHD bool depth_point(const DpeCamera& cam, float x, float y, float z, int& cx, int& cy, uint32_t& zbits) {
+  if (!cloud_finite3(x, y, z)) return false;
+  float px, py, d;
+  depth_project(cam, x, y, z, px, py, d);
+  if (!depth_ok(d)) return false;
+  zbits = depth_bits(d);
+  return depth_centre(px, py, cam.width, cam.height, cx, cy);
+}
+
+// what one pixel of (est, gt) contributes
+struct DepthPixel {
+  bool gt_ok, est_ok, both;
+  float e, rel;   // |est - gt| and e / gt; meaningful where `both`
+};
+
+DPE_CHD DepthPixel depth_pixel(float est, float gt) {
+  DepthPixel p;
+  p.gt_ok = depth_ok(gt);
+  p.est_ok = depth_ok(est);
+  p.both = p.gt_ok && p.est_ok;
+  p.e = __builtin_fabsf(est - gt);
+  p.rel = p.e / gt;
+  return p;
+}
+
+DPE_CHD bool depth_hit(const DepthPixel& p, float gt, float tau, int mode) {
+  return p.both && (mode == DPE_DEPTH_TAU_ABS ? p.e < tau : p.e < tau * gt);
+}
+
+// the three terms of the sums: +0.0 for a pixel that is not `both`, and never -0.0 (e and rel are >= +0.0)
+DPE_CHD void depth_terms(const DepthPixel& p, double* t) {
+  t[0] = p.both ? (double)p.e : 0.0;
+  t[1] = p.both ? (double)p.rel : 0.0;
+  t[2] = p.both ? (double)p.e * (double)p.e : 0.0;
+}
+
+DPE_CHD float depth_error_code(const DepthPixel& p) { return p.both ? p.e : (p.gt_ok ? -1.0f : -2.0f); }
+
+}  // namespace dpe

@@ -1,6 +1,7 @@
 // dpe_cloud.hip -- the cloud evaluation's distances (dpe_cloud_nn, dpe_cloud_nn_pair), the voxel
 // down-sampling (dpe_cloud_voxel) and the registration's device half (dpe_cloud_nn_index, dpe_cloud_icp_stage,
-// dpe_cloud_icp_step) of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h and pass_register.h over
+// dpe_cloud_icp_step) and the depth-map evaluation (dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score)
+// of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h, pass_register.h and pass_render.h over
 // the context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
 // contract is dpe_mvs.hip's (dpe_entry.h): these calls wait until the context is quiet, use its stream and
 // return with it synchronised.
@@ -14,6 +15,7 @@
 #include "pass_cloud.h"
 #include "pass_voxel.h"
 #include "pass_register.h"
+#include "pass_render.h"
 #include "dpe_entry.h"
 #include "dpe_context.h"
 
@@ -146,6 +148,7 @@ int cloud_run(DpeContext* c, const float* a, size_t n, const float* b, size_t m,
   const bool timing = c->pass.timing;
   v.timed = false;
   v.icp_staged = false;
+  v.render_staged = false;
   if (timing) TRY(cloud_events(c));
   if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
   TRY(cloud_stage(c, 0, a, n));
@@ -189,6 +192,7 @@ int voxel_run(DpeContext* c, const float* xyz, size_t n, const uint8_t* rgb, flo
   const bool timing = c->pass.timing;
   v.timed = false;
   v.icp_staged = false;
+  v.render_staged = false;
   if (timing) TRY(cloud_events(c));
   if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
   TRY(cloud_stage(c, 0, xyz, n));
@@ -289,6 +293,7 @@ int icp_stage(DpeContext* c, const float* src, size_t n, const float* tgt, size_
   HIPC(host_wait(c));
   v.timed = false;
   v.icp_staged = false;
+  v.render_staged = false;
   TRY(cloud_stage(c, 0, src, n));
   TRY(cloud_stage(c, 1, tgt, m));
   CloudBounds bd[2];
@@ -383,7 +388,177 @@ int icp_step(DpeContext* c, const double* T, DpeIcpSums* out) {
   return DPE_OK;
 }
 
+unsigned render_blocks(size_t n) { return (unsigned)((n + kRenderBlock - 1) / kRenderBlock); }
+
+// dpe_cloud_render_stage after its prologue: the scan resident in pts[0].  Timing events: [0] start, [1] staged.
+int render_stage(DpeContext* c, const float* xyz, size_t n) {
+  CloudScratch& v = c->cloud;
+  HIPC(host_wait(c));
+  const bool timing = c->pass.timing;
+  v.timed = false;
+  v.icp_staged = false;
+  v.render_staged = false;
+  if (timing) TRY(cloud_events(c));
+  if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
+  if (n > 0) {
+    HIPC(v.pts[0].ensure(3 * n));
+    HIPC(hipMemcpyAsync(v.pts[0].p, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  if (timing) HIPC(hipEventRecord(v.ev[1], c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  v.render_n = n;
+  v.render_staged = true;
+  if (timing) {
+    for (float& t : v.ms) t = 0.f;
+    HIPC(hipEventElapsedTime(&v.ms[0], v.ev[0], v.ev[1]));
+    v.timed = true;
+  }
+  return DPE_OK;
+}
+
+// dpe_cloud_render_view after its prologue.  Timing events: [0] start, [1] rendered, [2] downloaded.
+int render_view(DpeContext* c, const DpeCamera& cam, int splat, float* depth_out) {
+  CloudScratch& v = c->cloud;
+  HIPC(host_wait(c));
+  const bool timing = c->pass.timing;
+  v.timed = false;
+  if (timing) TRY(cloud_events(c));
+  const size_t npx = (size_t)cam.width * (size_t)cam.height, n = v.render_n;
+  v.rmap_w = v.rmap_h = 0;   // the old map goes with the first launch
+  HIPC(v.rmap.ensure(npx));
+  if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
+  k_render_clear<<<render_blocks(npx), kRenderBlock, 0, c->stream>>>(v.rmap.p, npx);
+  HIPC(hipGetLastError());
+  if (n > 0) {
+    k_render_splat<<<render_blocks(n), kRenderBlock, 0, c->stream>>>(v.pts[0].p, (int)n, cam, splat, v.rmap.p);
+    HIPC(hipGetLastError());
+    g_cloud_launches += 1;
+  }
+  k_render_finish<<<render_blocks(npx), kRenderBlock, 0, c->stream>>>(v.rmap.p, npx);
+  HIPC(hipGetLastError());
+  g_cloud_launches += 2;
+  if (timing) HIPC(hipEventRecord(v.ev[1], c->stream));
+  if (depth_out) HIPC(hipMemcpyAsync(depth_out, v.rmap.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (timing) HIPC(hipEventRecord(v.ev[2], c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  v.rmap_w = cam.width;
+  v.rmap_h = cam.height;
+  if (timing) {
+    for (float& t : v.ms) t = 0.f;
+    HIPC(hipEventElapsedTime(&v.ms[1], v.ev[0], v.ev[1]));
+    HIPC(hipEventElapsedTime(&v.ms[3], v.ev[1], v.ev[2]));
+    v.timed = true;
+  }
+  return DPE_OK;
+}
+
+// dpe_depth_score after its prologue; gt == nullptr: against the resident map.  Timing events: [0] start,
+// [1] uploaded, [2] scored, [3] downloaded.
+int depth_score(DpeContext* c, const float* est, const float* gt, int w, int h, const DepthTaus& T, DpeDepthScore* out,
+                float* err) {
+  CloudScratch& v = c->cloud;
+  HIPC(host_wait(c));
+  const bool timing = c->pass.timing;
+  v.timed = false;
+  if (timing) TRY(cloud_events(c));
+  const size_t npx = (size_t)w * (size_t)h;
+  size_t cnt = render_blocks(npx);
+  HIPC(v.s_est.ensure(npx));
+  if (gt) HIPC(v.s_gt.ensure(npx));
+  if (err) HIPC(v.s_err.ensure(npx));
+  HIPC(v.s_part[0].ensure(cnt * kDepthTerms));
+  HIPC(v.s_part[1].ensure((size_t)render_blocks(cnt) * kDepthTerms));
+  HIPC(v.s_cnt.ensure(kDepthCounters));
+  if (timing) HIPC(hipEventRecord(v.ev[0], c->stream));
+  HIPC(hipMemcpyAsync(v.s_est.p, est, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (gt) HIPC(hipMemcpyAsync(v.s_gt.p, gt, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemsetAsync(v.s_cnt.p, 0, kDepthCounters * sizeof(unsigned long long), c->stream));
+  if (timing) HIPC(hipEventRecord(v.ev[1], c->stream));
+  const float* g = gt ? v.s_gt.p : reinterpret_cast<const float*>(v.rmap.p);
+  k_depth_score<<<(unsigned)cnt, kRenderBlock, 0, c->stream>>>(v.s_est.p, g, npx, T, v.s_part[0].p, v.s_cnt.p,
+                                                               err ? v.s_err.p : nullptr);
+  HIPC(hipGetLastError());
+  g_cloud_launches += 1;
+  int at = 0;   // s_part[at] holds the cnt partials of the level
+  while (cnt > 1) {
+    const unsigned blocks = render_blocks(cnt);
+    k_depth_reduce<<<blocks, kRenderBlock, 0, c->stream>>>(v.s_part[at].p, cnt, v.s_part[at ^ 1].p);
+    HIPC(hipGetLastError());
+    g_cloud_launches += 1;
+    cnt = blocks;
+    at ^= 1;
+  }
+  if (timing) HIPC(hipEventRecord(v.ev[2], c->stream));
+  double sums[kDepthTerms];
+  unsigned long long counts[kDepthCounters];
+  HIPC(hipMemcpyAsync(sums, v.s_part[at].p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(counts, v.s_cnt.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+  if (err) HIPC(hipMemcpyAsync(err, v.s_err.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (timing) HIPC(hipEventRecord(v.ev[3], c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  DpeDepthScore s;
+  memset(&s, 0, sizeof s);
+  s.n_px = (long long)npx;
+  s.n_gt = (long long)counts[0];
+  s.n_est = (long long)counts[1];
+  s.n_both = (long long)counts[2];
+  for (int k = 0; k < T.n; ++k) s.within[k] = (long long)counts[3 + k];
+  s.sum_abs = sums[0];
+  s.sum_rel = sums[1];
+  s.sum_sq = sums[2];
+  *out = s;
+  if (timing) {
+    for (float& t : v.ms) t = 0.f;
+    HIPC(hipEventElapsedTime(&v.ms[0], v.ev[0], v.ev[1]));
+    HIPC(hipEventElapsedTime(&v.ms[2], v.ev[1], v.ev[2]));
+    HIPC(hipEventElapsedTime(&v.ms[3], v.ev[2], v.ev[3]));
+    v.timed = true;
+  }
+  return DPE_OK;
+}
+
 }  // namespace
+
+extern "C" int dpe_cloud_render_stage(DpeContext* c, const float* xyz, size_t n) {
+  TRY(enter(c, n <= (size_t)INT_MAX && (xyz || n == 0), "dpe_cloud_render_stage: bad argument"));
+  return render_stage(c, xyz, n);
+}
+
+extern "C" int dpe_cloud_render_view(DpeContext* c, const DpeCamera* cam, int splat, float* depth_out) {
+  const bool ok = cam && cam->width >= 1 && cam->height >= 1 && splat >= 0 && splat <= DPE_DEPTH_MAX_SPLAT;
+  TRY(enter(c, ok, "dpe_cloud_render_view: bad argument"));
+  if (!c->cloud.render_staged) {
+    g_err = "dpe_cloud_render_view: no staged cloud (dpe_cloud_render_stage comes first)";
+    return DPE_ERR_STATE;
+  }
+  return render_view(c, *cam, splat, depth_out);
+}
+
+extern "C" int dpe_depth_score(DpeContext* c, const float* est, const float* gt, int w, int h, const float* tau, int n_tau,
+                               int mode, DpeDepthScore* out, float* err) {
+  bool ok = est && w >= 1 && h >= 1 && tau && n_tau >= 1 && n_tau <= DPE_DEPTH_MAX_TAU && out &&
+            (mode == DPE_DEPTH_TAU_ABS || mode == DPE_DEPTH_TAU_REL);
+  DepthTaus T;
+  memset(&T, 0, sizeof T);
+  for (int k = 0; ok && k < n_tau; ++k) {
+    ok = std::isfinite(tau[k]) && tau[k] >= 0.0f;
+    T.tau[k] = tau[k];
+  }
+  T.n = n_tau;
+  T.mode = mode;
+  TRY(enter(c, ok, "dpe_depth_score: bad argument"));
+  if (!gt) {
+    if (c->cloud.rmap_w == 0) {
+      g_err = "dpe_depth_score: no rendered map (dpe_cloud_render_view comes first, or pass gt)";
+      return DPE_ERR_STATE;
+    }
+    if (c->cloud.rmap_w != w || c->cloud.rmap_h != h) {
+      g_err = "dpe_depth_score: the size differs from the rendered map's";
+      return DPE_ERR_ARG;
+    }
+  }
+  return depth_score(c, est, gt, w, h, T, out, err);
+}
 
 extern "C" int dpe_cloud_nn_index(DpeContext* c, const float* query, size_t n, const float* target, size_t m, float radius,
                                   float* d2_out, int32_t* idx_out) {

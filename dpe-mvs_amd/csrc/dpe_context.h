@@ -252,6 +252,15 @@ struct CloudScratch {
   size_t icp_n = 0, icp_m = 0, icp_tfinite = 0;
   CloudGrid icp_grid;
   double icp_os[3] = {0, 0, 0}, icp_ot[3] = {0, 0, 0};   // per-axis minima of the finite source / target points
+  // the depth-map evaluation (pass_render.h).  A staged scan is pts[0]; every other cloud call of the context
+  // overwrites it and ends the staging.  The rendered map and the score's buffers are its own.
+  bool render_staged = false;
+  size_t render_n = 0;
+  DevArr<uint32_t> rmap;             // the z-buffer of the last view, after k_render_finish the map f32 [h][w]
+  int rmap_w = 0, rmap_h = 0;        // 0: no map rendered yet
+  DevArr<float> s_est, s_gt, s_err;  // dpe_depth_score: the caller's maps and the error map
+  DevArr<double> s_part[2];          // the three sums' partials, level by level
+  DevArr<unsigned long long> s_cnt;  // n_gt, n_est, n_both, within[16]
 };
 
 }  // namespace dpe

@@ -6,6 +6,7 @@
 // the kernels (csrc/pass_register.h) share.  No counterpart in the reference.
 #include "host.h"
 #include "cloud_index.h"
+#include "pairwise_tree.h"
 
 #include <climits>
 #include <cmath>
@@ -19,43 +20,6 @@ namespace dpe_host {
 namespace {
 
 using dpe::kIcpTerms;
-
-// The contract's pairwise sum of 16 series at once, leaf by leaf in index order.  lvl[l] holds the finished node
-// of 2^l leaves that waits for its right sibling, exactly as a binary counter holds its digits, so push() forms
-// the nodes s[k] = s_l[2k] + s_l[2k + 1] of every complete pair and finish() pads the ragged end with +0.0 level
-// by level: the tree of the contract, node for node, without keeping its levels.
-struct PairwiseTree {
-  double lvl[40][kIcpTerms];
-  unsigned long long n = 0;
-  void push(const double* t) {
-    double carry[kIcpTerms];
-    for (int k = 0; k < kIcpTerms; ++k) carry[k] = t[k];
-    int l = 0;
-    for (unsigned long long c = n; c & 1ull; c >>= 1, ++l)
-      for (int k = 0; k < kIcpTerms; ++k) carry[k] = lvl[l][k] + carry[k];
-    for (int k = 0; k < kIcpTerms; ++k) lvl[l][k] = carry[k];
-    ++n;
-  }
-  void finish(double* out) const {
-    for (int k = 0; k < kIcpTerms; ++k) out[k] = 0.0;
-    if (n == 0) return;
-    bool have = false;   // out holds the ragged last node of the level
-    for (int l = 0;; ++l) {
-      const unsigned long long full = n >> l;             // complete nodes of 2^l leaves
-      if (full + (have ? 1 : 0) == 1) {                   // one node left: the result
-        if (!have)
-          for (int k = 0; k < kIcpTerms; ++k) out[k] = lvl[l][k];
-        return;
-      }
-      if (full & 1ull) {                                  // an odd complete node: its right is the ragged one, or +0.0
-        for (int k = 0; k < kIcpTerms; ++k) out[k] = lvl[l][k] + (have ? out[k] : 0.0);
-        have = true;
-      } else if (have) {                                  // the ragged node has no right sibling
-        for (int k = 0; k < kIcpTerms; ++k) out[k] = out[k] + 0.0;
-      }
-    }
-  }
-};
 
 void cloud_minima(const float* p, size_t n, double* o) {
   bool any = false;
@@ -86,7 +50,7 @@ void icp_step_over(const CloudIndex& ix, const float* src, size_t n, const float
   idx.resize(n);
   cloud_transform(T, src, n, moved.data());
   ix.query(moved.data(), n, d2.data(), idx.data());
-  PairwiseTree tree;
+  PairwiseTree<kIcpTerms> tree;
   long long matched = 0;
   const double zero[kIcpTerms] = {0};
   for (size_t i = 0; i < n; ++i) {

@@ -41,6 +41,9 @@ bool write_bin_mat(const std::string& path, const Mat& m, std::string& err);
 // .npy v1.0 (main.cpp:47-96); descr "<f4" / "|i1" / "|u1"
 bool write_npy(const std::string& path, const void* data, const std::vector<int64_t>& shape, const char* descr,
                size_t elem, std::string& err);
+// a 2-D '<f4' .npy v1.0 in C order, h rows of w; anything else (another version or dtype, Fortran order, another
+// rank, a body shorter or longer than the header says) is refused with a message
+bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err);
 
 bool read_camera(const std::string& path, DpeCamera& cam, std::string& err);   // DPE.cpp:341-382
 
@@ -183,5 +186,13 @@ bool cloud_icp_step(const float* src, size_t n, const float* tgt, size_t m, floa
 bool cloud_solve(const DpeIcpSums& s, const double* o_s, const double* o_t, double* T, std::string& err);
 bool cloud_register_in(DpeContext* ctx, const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions& opt,
                        DpeCloudReg* out, std::string& err);
+// depth_eval.cpp: the render of a scan into one view and the score of one map (dpe_cloud_render_view and
+// dpe_depth_score of dpe_mvs.h) as loops over the same arithmetic (csrc/depth_eval.h), what is derived from a score,
+// and total += s
+bool cloud_render(const float* xyz, size_t n, const DpeCamera& cam, int splat, float* out, std::string& err);
+bool depth_score(const float* est, const float* gt, int w, int h, const float* tau, int n_tau, int mode, DpeDepthScore* out,
+                 float* errmap, std::string& err);
+void depth_stats(const DpeDepthScore& s, int n_tau, DpeDepthStats* out);
+void depth_add(DpeDepthScore* total, const DpeDepthScore& s);
 
 }  // namespace dpe_host

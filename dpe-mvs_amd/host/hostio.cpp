@@ -1,6 +1,6 @@
 // hostio.cpp — file formats and resampling of the host pipeline.
 //   .dmb      ReadBinMat / WriteBinMat (DPE.cpp:293-339)
-//   .npy      WriteMatToNpy (main.cpp:47-96)
+//   .npy      WriteMatToNpy (main.cpp:47-96), and a reader of 2-D '<f4' files for the depth-map evaluation
 //   cams      ReadCamera (DPE.cpp:341-382)
 //   images    cv::imread(IMREAD_GRAYSCALE): JPEG luma (jpeg.cpp) or binary PGM
 //   resize    cv::resize INTER_LINEAR, float path (DPE.cpp:798-822)
@@ -78,6 +78,76 @@ bool write_npy(const std::string& path, const void* data, const std::vector<int6
   out.write(header.data(), (std::streamsize)header.size());
   out.write(reinterpret_cast<const char*>(data), (std::streamsize)(n * elem));
   if (!out) { err = "Failed while writing npy: " + path; return false; }
+  return true;
+}
+
+// The value of `key` in a .npy header dict: the text after "'key':" up to (not including) the ", " that ends it
+// at nesting depth 0.  False without the key.
+static bool npy_value(const std::string& dict, const char* key, std::string& value) {
+  const std::string k = std::string("'") + key + "'";
+  size_t at = dict.find(k);
+  if (at == std::string::npos) return false;
+  at = dict.find(':', at + k.size());
+  if (at == std::string::npos) return false;
+  ++at;
+  while (at < dict.size() && dict[at] == ' ') ++at;
+  int depth = 0;
+  size_t end = at;
+  for (; end < dict.size(); ++end) {
+    const char c = dict[end];
+    if (c == '(') ++depth;
+    else if (c == ')') --depth;
+    else if ((c == ',' || c == '}') && depth <= 0) break;
+  }
+  value = dict.substr(at, end - at);
+  while (!value.empty() && value.back() == ' ') value.pop_back();
+  return true;
+}
+
+bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err) {
+  std::ifstream in(path, std::ios::binary);
+  if (!in) { err = "cannot read npy: " + path; return false; }
+  unsigned char pre[10];
+  if (!in.read(reinterpret_cast<char*>(pre), sizeof pre) || std::memcmp(pre, "\x93NUMPY", 6) != 0) {
+    err = "not a .npy file: " + path; return false;
+  }
+  if (pre[6] != 1 || pre[7] != 0) { err = "unsupported .npy version (1.0 expected): " + path; return false; }
+  const size_t hl = (size_t)pre[8] | ((size_t)pre[9] << 8);
+  std::string dict(hl, '\0');
+  if (!in.read(&dict[0], (std::streamsize)hl)) { err = "truncated .npy header: " + path; return false; }
+  std::string descr, order, shape;
+  if (!npy_value(dict, "descr", descr) || !npy_value(dict, "fortran_order", order) || !npy_value(dict, "shape", shape)) {
+    err = "malformed .npy header: " + path; return false;
+  }
+  if (descr != "'<f4'") { err = "unsupported .npy dtype " + descr + " ('<f4' expected): " + path; return false; }
+  if (order != "False") { err = "Fortran-ordered .npy is not supported: " + path; return false; }
+  // "(h, w)": exactly two decimal numbers, each 1 .. 2^31 - 1
+  long long dim[2] = {0, 0};
+  int nd = 0;
+  bool ok = shape.size() >= 2 && shape.front() == '(' && shape.back() == ')';
+  for (size_t i = 1; ok && i + 1 < shape.size();) {
+    if (shape[i] == ' ' || shape[i] == ',') { ++i; continue; }
+    if (shape[i] < '0' || shape[i] > '9' || nd == 2) { ok = false; break; }
+    long long v = 0;
+    for (; i + 1 < shape.size() && shape[i] >= '0' && shape[i] <= '9'; ++i) {
+      v = v * 10 + (shape[i] - '0');
+      if (v > 0x7FFFFFFFll) { ok = false; break; }
+    }
+    dim[nd++] = v;
+  }
+  if (!ok || nd != 2 || dim[0] < 1 || dim[1] < 1) { err = "a 2-D .npy of at least 1 x 1 expected, shape " + shape + ": " + path; return false; }
+  const unsigned long long want = (unsigned long long)dim[0] * (unsigned long long)dim[1] * 4ull;
+  const std::streampos body = in.tellg();
+  in.seekg(0, std::ios::end);
+  const unsigned long long have = (unsigned long long)(in.tellg() - body);
+  if (have != want) {
+    err = (have < want ? "truncated .npy data: " : ".npy data longer than its header says: ") + path; return false;
+  }
+  in.seekg(body);
+  data.resize((size_t)(want / 4));
+  if (!in.read(reinterpret_cast<char*>(data.data()), (std::streamsize)want)) { err = "truncated .npy data: " + path; return false; }
+  h = (int)dim[0];
+  w = (int)dim[1];
   return true;
 }
 

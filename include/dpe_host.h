@@ -404,6 +404,58 @@ int dpe_host_cloud_eval_reg(const float* recon, size_t n, const float* gt, size_
                             int gpu_index, DpeCloudPrep* prep_or_null, const DpeCloudRegOptions* opt, DpeCloudReg* reg,
                             DpeCloudEval* out);
 
+/*
+ * Depth-map evaluation: the estimated maps DPE/%08d/depth.npy of a dense folder against a ground-truth scan
+ * rendered into each view, or against ground-truth maps.  No counterpart in the reference.  dpe_mvs.h states the
+ * contract of the render and the score (dpe_cloud_render_view, dpe_depth_score).
+ *   dpe_host_cloud_render   that render as a loop over the points on the host (csrc/depth_eval.h's arithmetic;
+ *                           large scans are split over host threads, each with a z-buffer of its own, and the
+ *                           buffers merged by minimum, which no order can change): the device path's bits.
+ *   dpe_host_depth_score    that score as a serial loop over the pixels with the pairwise tree taken literally:
+ *                           the device path's bits, struct and error map (err_or_null).
+ *   dpe_host_depth_stats    everything derived, in double, for both paths: accuracy[k] = within[k] / n_both,
+ *                           completeness[k] = within[k] / n_gt, mae = sum_abs / n_both, mre = sum_rel / n_both,
+ *                           rmse = sqrt(sum_sq / n_both); 0 where the denominator is 0.
+ *   dpe_host_read_npy_f32   a 2-D '<f4' .npy v1.0 in C order (what the pipeline writes): data == NULL gives the
+ *                           size only; another version, dtype, rank or order, a body shorter or longer than the
+ *                           header says and cap < w * h fail.
+ *   dpe_host_depth_eval_list  the image ids of `dense_folder` in ascending order: the folders DPE/%08d that hold
+ *                           `map_name` (NULL: "depth.npy").  ids == NULL or cap too small: *n only.
+ *   dpe_host_depth_eval     every listed image scored, rows[i] in ascending id, and their total (the integers add,
+ *                           the three doubles are added sequentially in that order).  gt_maps_dir ==
+ *                           NULL: the scan gt_xyz (n_gt points) is rendered into cams/%08d_cam.txt, its
+ *                           intrinsics scaled from the size of images/%08d.jpg to the map's (the arithmetic of the
+ *                           consistency maps' views), with half-width `splat`; else gt_maps_dir/%08d.npy is the
+ *                           ground truth and must have the map's size.  write_maps: depth_gt.npy and
+ *                           depth_error.npy beside each map.  gpu_index < 0: the host functions above; else
+ *                           the scan is staged once in a context of that device and every view rendered and
+ *                           scored there: equal rows.  cap < the number of images fails.
+ * All return 0, or nonzero with the message in dpe_pipeline_last_error().
+ */
+typedef struct DpeDepthStats {
+  double accuracy[DPE_DEPTH_MAX_TAU], completeness[DPE_DEPTH_MAX_TAU], mae, mre, rmse;
+} DpeDepthStats;
+typedef struct DpeDepthEvalOptions {
+  const char* dense_folder;
+  const char* map_name;       /* NULL: "depth.npy" */
+  const char* gt_maps_dir;    /* NULL: render the scan */
+  int splat, mode, n_tau;
+  float tau[DPE_DEPTH_MAX_TAU];
+  int write_maps, gpu_index;
+} DpeDepthEvalOptions;
+typedef struct DpeDepthImage {
+  int id, width, height;
+  DpeDepthScore score;
+} DpeDepthImage;
+int dpe_host_cloud_render(const float* xyz, size_t n, const DpeCamera* cam, int splat, float* depth_out);
+int dpe_host_depth_score(const float* est, const float* gt, int w, int h, const float* tau, int n_tau, int mode,
+                         DpeDepthScore* out, float* err_or_null);
+void dpe_host_depth_stats(const DpeDepthScore* s, int n_tau, DpeDepthStats* out);
+int dpe_host_read_npy_f32(const char* path, float* data, size_t cap, int* w, int* h);
+int dpe_host_depth_eval_list(const char* dense_folder, const char* map_name, int* ids, size_t cap, size_t* n);
+int dpe_host_depth_eval(const DpeDepthEvalOptions* opt, const float* gt_xyz, size_t n_gt, DpeDepthImage* rows, size_t cap,
+                        size_t* n_rows, DpeDepthScore* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -555,6 +555,66 @@ int dpe_cloud_nn_index(DpeContext* ctx, const float* query, size_t n, const floa
 int dpe_cloud_icp_stage(DpeContext* ctx, const float* src, size_t n, const float* tgt, size_t m, float radius);
 int dpe_cloud_icp_step(DpeContext* ctx, const double* T, DpeIcpSums* out);
 
+/*
+ * Depth-map evaluation: a ground-truth scan rendered into one camera with a z-buffer, and an estimated depth map
+ * compared with such a map pixel by pixel: how the ETH3D and DTU tools get per-view ground truth.  No
+ * counterpart in the reference.  All in float unless a double is written, every operation rounded, IEEE
+ * division, no contraction (csrc/depth_eval.h holds the arithmetic once, for the kernels and the host loops).
+ *
+ * Render.  A cloud f32 [n][3] (HOST array, n <= 2^31 - 1), a DpeCamera already at the map's size (width,
+ * height >= 1), a splat half-width s in 0..8; anything else is DPE_ERR_ARG.  Output f32 [height][width].
+ * Per point with three finite coordinates (decided on the bit patterns):
+ *   (px, py, z) = ProjectCamera in the reference's order (DPE.cpp:1196-1206), the expression of the fusion
+ *   kept iff 0 < bits(z) < 0x7F800000 as an integer: positive and finite, a NaN excluded by its bits
+ *   fx = px + 0.5f, fy = py + 0.5f; kept iff fx > -1 && fx < width && fy > -1 && fy < height on the floats
+ *   (the fusion's rule); cx = (int)fx, cy = (int)fy, truncated
+ *   the point covers the pixels (cx + dx, cy + dy), |dx|, |dy| <= s, that lie inside the image
+ * out[p] = the minimum z over the points that cover p, 0.0f where none does.  A minimum over a set: the bits of
+ * a serial loop whatever the schedule (on the device an integer atomic minimum on the bit pattern, since
+ * positive finite floats order as their bits).  NO OCCLUSION TEST beyond the z-buffer is made: a sparse scan
+ * lets far surfaces show between near points, and s trades that against dilated foreground edges.
+ *
+ * Score.  est and gt f32 [h][w] (w, h >= 1), 1 to 16 thresholds tau[k], each finite and >= 0, mode
+ * DPE_DEPTH_TAU_ABS or DPE_DEPTH_TAU_REL; anything else is DPE_ERR_ARG.  Per pixel in index order:
+ *   gt_ok, est_ok = the positive-finite bit test above; both = gt_ok && est_ok
+ *   e = fabsf(est - gt); rel = e / gt
+ *   hit[k] = both && (mode == ABS ? e < tau[k] : e < tau[k] * gt)          (strict, as in dpe_cloud_nn)
+ * n_px = w * h, n_gt, n_est, n_both and within[k] count the pixels; sum_abs = sum of (double)e, sum_rel = sum of
+ * (double)rel, sum_sq = sum of (double)e * (double)e, each over the `both` pixels and each by PAIRWISE SUMMATION
+ * IN PIXEL-INDEX ORDER, the tree of dpe_cloud_icp_step above: s[k] = s[2k] + s[2k + 1], +0.0 for a missing
+ * operand and for a pixel that is not `both` (so an image without a `both` pixel sums to +0.0).  The error map,
+ * when asked for: e where both, -1.0f where gt_ok only, -2.0f otherwise.  Everything derived (accuracy,
+ * completeness, means, RMSE) is the host's, in double: dpe_host_depth_stats (dpe_host.h).
+ * dpe_host_cloud_render and dpe_host_depth_score (dpe_host.h) are the serial loops: the same bits.
+ *
+ *   dpe_cloud_render_stage  uploads the cloud once; it stays resident until the next cloud call of the context
+ *                           (dpe_cloud_nn, _nn_pair, _nn_index, _voxel, _icp_stage), which ends the staging, as
+ *                           this call ends a staged ICP pair.
+ *   dpe_cloud_render_view   one view of the staged cloud (clear, one thread per point, a last pass that turns
+ *                           empty pixels into 0.0f); the map stays resident for dpe_depth_score, and comes down
+ *                           into depth_out when that is not NULL.  Without a staged cloud DPE_ERR_STATE.
+ *   dpe_depth_score         gt == NULL: against the last rendered map, whose size must be w x h (else
+ *                           DPE_ERR_ARG; DPE_ERR_STATE when no map was rendered); otherwise against the caller's
+ *                           host array.  Blocks of 256 consecutive pixels, the butterfly of the ICP step, counts
+ *                           by ballot; no float atomics.
+ * Concurrency, error strings and the buffers are dpe_cloud_nn's; every launch counts in dpe_cloud_launches, and
+ * dpe_cloud_last_timings then reports [0] stage (upload), [1] render, [2] score, [3] download of the last of
+ * these calls (the parts it does not have are 0).  A refused call leaves the context and what is resident as
+ * they were.
+ */
+#define DPE_DEPTH_MAX_TAU 16
+#define DPE_DEPTH_MAX_SPLAT 8
+#define DPE_DEPTH_TAU_ABS 0
+#define DPE_DEPTH_TAU_REL 1
+typedef struct DpeDepthScore {
+  long long n_px, n_gt, n_est, n_both, within[DPE_DEPTH_MAX_TAU];
+  double sum_abs, sum_rel, sum_sq;
+} DpeDepthScore;
+int dpe_cloud_render_stage(DpeContext* ctx, const float* xyz, size_t n);
+int dpe_cloud_render_view(DpeContext* ctx, const DpeCamera* cam, int splat, float* depth_out_or_null);
+int dpe_depth_score(DpeContext* ctx, const float* est, const float* gt_or_null, int w, int h, const float* tau, int n_tau,
+                    int mode, DpeDepthScore* out, float* err_or_null);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);

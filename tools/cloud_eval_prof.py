@@ -34,7 +34,17 @@ launched per step, and a loop driven from here, step by step with the host's sol
 step's parts.  The radius of a whole-scene 4 degree error (0.35 here) is out of the grid's reach at this density, so
 the loop from the identity is not what is timed.
 
-Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]] [--register R]"""
+With --render the tool measures the depth-map evaluation instead (dpe_cloud_render_stage once, then
+dpe_cloud_render_view and dpe_depth_score per view in a warm context, against dpe_host_cloud_render on at most 16
+host threads and the serial dpe_host_depth_score): the 800 x 600 scene's cloud, 1.92 million points, into 10 views
+at 1600 x 1200 on an arc around the scene, with splat half-widths 0 and 2, the estimate being the rendered map with
+1 % noise, and writes profiles/depth_render.json: the staging's wall time and upload part, and per half-width the
+device parts of a view (render, score with its upload, download: dpe_cloud_last_timings) and the wall time of a view
+on either path, each as median, min and max over views and --reps runs after a warm-up.  Both paths must give the same
+bits, which is checked on every view.  The contention case is 10^6 points on ONE pixel of a 1600 x 1200 view (their
+depths a permutation, so the minimum keeps falling) against 10^6 points of the scene's cloud in the same view.
+
+Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]] [--register R] [--render]"""
 import argparse
 import json
 import os
@@ -54,8 +64,9 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--voxel", type=float, default=None, help="measure the voxel down-sampling at this edge instead")
 ap.add_argument("--ab", nargs="+", default=None, help="with --voxel: builds of libdpe_mvs.so to compare, interleaved")
 ap.add_argument("--register", type=float, default=None, help="measure the ICP step at this match radius instead")
+ap.add_argument("--render", action="store_true", help="measure the depth-map evaluation (render and score) instead")
 a = ap.parse_args()
-a.out = a.out or os.path.join(ROOT, "profiles", "cloud_register.json" if a.register is not None else
+a.out = a.out or os.path.join(ROOT, "profiles", "depth_render.json" if a.render else "cloud_register.json" if a.register is not None else
                               "cloud_eval.json" if a.voxel is None else "cloud_voxel.json")
 
 
@@ -256,6 +267,115 @@ def register_profile():
     ctx.close()
     return out
 
+
+def spread(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))}
+
+
+def arc_cameras(n, W, H):
+    """n cameras at W x H on the synthetic scene's arc (synthetic.make_scene), -15 to 15 degrees"""
+    import math
+    fx = 1.2 * W
+    K = np.array([[fx, 0, W / 2.0], [0, fx, H / 2.0], [0, 0, 1.0]])
+    O = np.array([0.0, 0.0, 5.0])
+    cams = []
+    for i in range(n):
+        th = math.radians(-15.0 + 30.0 * i / max(1, n - 1))
+        Cc = O + 5.0 * np.array([math.sin(th), 0.25 * math.sin(1.7 * i) / 5.0, -math.cos(th)])
+        R = synthetic._look_at(Cc, O)
+        cams.append(synthetic.make_camera(K, R, -R @ Cc, W, H, 1.0, 20.0))
+    return cams
+
+
+def render_profile():
+    W, H, V, TAUS = 1600, 1200, 10, [1e-3, 1e-2]
+    sc = synthetic.make_scene(800, 600, 4)
+    P = synthetic.gt_point_cloud(sc)
+    del sc
+    cams = arc_cameras(V, W, H)
+    out = {"points": int(len(P)), "views": V, "size": [W, H], "reps": a.reps,
+           "host_threads": min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 16)), "splats": []}
+    ctx = native.PatchMatchContext(0)
+    ctx.set_timing(True)
+    ctx.cloud_render_stage(P)                                              # warm-up: the allocation
+    stage_wall, stage_ms = [], []
+    for _ in range(a.reps):
+        t = time.perf_counter()
+        ctx.cloud_render_stage(P)
+        stage_wall.append(time.perf_counter() - t)
+        stage_ms.append(ctx.cloud_timings()["stage"])
+    out["stage_seconds"], out["stage_upload_ms"] = spread(stage_wall), spread(stage_ms)
+    rng = np.random.default_rng(4)
+    for s in (0, 2):
+        row = {"splat": s, "identical": True}
+        host_maps, ests, host_render, host_score, host_scores = [], [], [], [], []
+        for cam in cams:
+            t = time.perf_counter()
+            g = pipeline.render_cloud(P, cam, s)
+            host_render.append(time.perf_counter() - t)
+            e = (g * (1 + 0.01 * rng.standard_normal(g.shape))).astype(np.float32)
+            t = time.perf_counter()
+            host_scores.append(pipeline.score_depth(e, g, TAUS, relative=True))
+            host_score.append(time.perf_counter() - t)
+            host_maps.append(g)
+            ests.append(e)
+        row["coverage"] = float(np.mean([(g > 0).mean() for g in host_maps]))
+        render_ms, score_ms, upload_ms, download_ms, view_wall = [], [], [], [], []
+        for r in range(a.reps + 1):                                        # the first round is the warm-up
+            for cam, g, e, hs in zip(cams, host_maps, ests, host_scores):
+                t = time.perf_counter()
+                ctx.cloud_render_view(cam, s, download=False)
+                tr = ctx.cloud_timings()
+                d = ctx.depth_score(e, None, TAUS, relative=True)
+                wall = time.perf_counter() - t
+                ts = ctx.cloud_timings()
+                if r == 0:
+                    got = ctx.cloud_render_view(cam, s)
+                    d.update(pipeline.depth_stats(d))
+                    row["identical"] = bool(row["identical"] and got.tobytes() == g.tobytes() and d == hs)
+                    continue
+                render_ms.append(tr["build"])
+                upload_ms.append(ts["stage"])
+                score_ms.append(ts["query"])
+                download_ms.append(ts["download"])
+                view_wall.append(wall)
+        row["device_parts_ms"] = {"render": spread(render_ms), "score_upload": spread(upload_ms), "score": spread(score_ms),
+                                  "score_download": spread(download_ms)}
+        row["device_view_seconds"] = spread(view_wall)
+        row["host_render_seconds"], row["host_score_seconds"] = spread(host_render), spread(host_score)
+        out["splats"].append(row)
+        print(json.dumps(row), flush=True)
+    # contention: every point on one pixel against as many points of the scene
+    n = 1_000_000
+    d = np.random.default_rng(2).permutation(n).astype(np.float32) * np.float32(2 ** -16) + np.float32(1)
+    pixel = synthetic.make_camera(np.eye(3), np.eye(3), np.zeros(3), W, H, 0.1, 100.0)
+    crowd = np.stack([np.float32(800) * d, np.float32(600) * d, d], -1).astype(np.float32)
+    out["contention"] = []
+    for name, pts, cam in (("one_pixel", crowd, pixel), ("scene", P[:n], cams[V // 2])):
+        ctx.cloud_render_stage(pts)
+        for s in (0, 2):
+            ms = []
+            for r in range(a.reps + 1):
+                got = ctx.cloud_render_view(cam, s, download=(r == 0))
+                if r:
+                    ms.append(ctx.cloud_timings()["build"])
+                else:
+                    same = bool(got.tobytes() == pipeline.render_cloud(pts, cam, s).tobytes())
+            row = {"cloud": name, "points": int(len(pts)), "splat": s, "render_ms": spread(ms), "identical": same}
+            out["contention"].append(row)
+            print(json.dumps(row), flush=True)
+    ctx.close()
+    return out
+
+
+if a.render:
+    result = render_profile()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("written", a.out)
+    sys.exit(0)
 
 if a.register is not None:
     result = register_profile()
