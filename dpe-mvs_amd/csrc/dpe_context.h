@@ -219,55 +219,79 @@ struct PointsScratch {
   DevArr<uint8_t> weak;
 };
 
-// cloud evaluation (dpe_cloud.hip: dpe_cloud_nn / dpe_cloud_nn_pair): scratch, allocated on first use and
-// grown on demand.  `ev` is declared first and so outlives the buffers.
-struct CloudScratch {
-  std::vector<Event> ev;             // timing (dpe_set_timing): start, staged, then (build, query, download) per direction
-  float ms[4] = {0, 0, 0, 0};        // dpe_cloud_last_timings: stage, build, query, download of the last call
+// The cloud section (dpe_cloud.hip): scratch, allocated on first use and grown on demand.
+//
+// its timer (dpe_set_timing): ev[0] is the start of the call, ev[k] its k-th mark, and slot[k - 1] the entry of ms[]
+// that the time from ev[k - 1] to ev[k] is added to
+struct CloudTimer {
+  std::vector<Event> ev;             // the pool, grown on demand
+  std::vector<int> slot;
+  bool on = false;                   // the call in flight is timed
+  float ms[4] = {0, 0, 0, 0};        // dpe_cloud_last_timings: the parts of the last call (include/dpe_mvs.h names them)
   bool timed = false;
-  DevArr<float> pts[2];              // the two clouds as the caller packs them, f32 [k][3]
-  DevArr<uint32_t> bounds;           // per cloud 8 words: k_cloud_bounds' keys and the finite count
-  DevArr<float4> st, sq;             // target / query points in bucket order: (x, y, z, original index)
-  DevArr<int> tcnt, qcnt;            // per bucket: counts -> starts -> ends
-  DevArr<float> out;                 // the distances, by original index
-  // dpe_cloud_voxel (pass_voxel.h); the cloud is staged in pts[0], its bounds in bounds[0..7]
-  DevArr<uint8_t> vrgb;              // the colours as the caller packs them, u8 [n][3]
-  DevArr<int4> vcell;                // per point: cell and valid flag
-  DevArr<uint32_t> vfrac;            // per point: the three lattice fractions
-  DevArr<int> vowner, vcount;        // the table, per slot
-  DevArr<uint32_t> vfirst;
-  DevArr<unsigned long long> vsum, vcsum;   // per slot and axis / channel
-  DevArr<int> vslot_at, vbcnt;       // per point: the slot it is the first point of, or -1; per block: marked -> offsets
-  DevArr<uint32_t> verr;             // the insert kernel's error word
-  DevArr<float> vout_xyz;            // the records
-  DevArr<uint8_t> vout_rgb;
-  DevArr<int> vout_first, vout_count;
-  // dpe_cloud_nn_index and the ICP step (pass_register.h).  A staged pair is the source in pts[0], the target in
-  // pts[1] and the target's grid in st / tcnt; every other cloud call of the context overwrites them and ends it
-  DevArr<int> idx;                   // the matches, by original index (the distances are `out`)
+};
+// dpe_cloud_voxel (pass_voxel.h); the cloud is staged in pts[0], its bounds in bounds[0..7]
+struct VoxelScratch {
+  DevArr<uint8_t> rgb;               // the colours as the caller packs them, u8 [n][3]
+  DevArr<int4> cell;                 // per point: cell and valid flag
+  DevArr<uint32_t> frac;             // per point: the three lattice fractions
+  DevArr<int> owner, count;          // the table, per slot
+  DevArr<uint32_t> first;
+  DevArr<unsigned long long> sum, csum;   // per slot and axis / channel
+  DevArr<int> slot_at, bcnt;         // per point: the slot it is the first point of, or -1; per block: marked -> offsets
+  DevArr<uint32_t> err;              // the insert kernel's error word
+  DevArr<float> out_xyz;             // the records
+  DevArr<uint8_t> out_rgb;
+  DevArr<int> out_first, out_count;
+};
+// the ICP step (pass_register.h) over a staged pair: the source in pts[0], the target in pts[1], the target's grid
+// in st / tcnt
+struct IcpStage {
   DevArr<float> moved;               // the source under the step's transform, f32 [n][3]
   DevArr<double> part[2];            // the sums' partials, 16 per block, level by level
   DevArr<unsigned long long> matched;
-  bool icp_staged = false;
-  size_t icp_n = 0, icp_m = 0, icp_tfinite = 0;
-  CloudGrid icp_grid;
-  double icp_os[3] = {0, 0, 0}, icp_ot[3] = {0, 0, 0};   // per-axis minima of the finite source / target points
-  // the depth-map evaluation (pass_render.h).  A staged scan is pts[0]; every other cloud call of the context
-  // overwrites it and ends the staging.  The rendered map and the score's buffers are its own.
-  bool render_staged = false;
-  size_t render_n = 0;
-  DevArr<uint32_t> rmap;             // the z-buffer of the last view, after k_render_finish the map f32 [h][w]
-  int rmap_w = 0, rmap_h = 0;        // 0: no map rendered yet
-  DevArr<float> s_est, s_gt, s_err;  // dpe_depth_score: the caller's maps and the error map
-  DevArr<double> s_part[2];          // the three sums' partials, level by level
-  DevArr<unsigned long long> s_cnt;  // n_gt, n_est, n_both, within[16]
+  size_t n = 0, m = 0, tfinite = 0;
+  CloudGrid grid;
+  double os[3] = {0, 0, 0}, ot[3] = {0, 0, 0};   // per-axis minima of the finite source / target points
+};
+// the depth-map evaluation (pass_render.h): a staged scan is pts[0]; the rendered map is its own
+struct RenderStage {
+  size_t n = 0;
+  DevArr<uint32_t> map;              // the z-buffer of the last view, after k_render_finish the map f32 [h][w]
+  int map_w = 0, map_h = 0;          // 0: no map rendered yet
+};
+struct ScoreScratch {
+  DevArr<float> est, gt, err;        // dpe_depth_score: the caller's maps and the error map
+  DevArr<double> part[2];            // the three sums' partials, level by level
+  DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16]
+};
+// what stays in pts[] for later calls.  The calls that restage pts[] (nn, pair, index, voxel, icp_stage, render_stage)
+// end it; icp_step, render_view and depth_score leave it alone
+enum class CloudResident { None, IcpPair, RenderScan };
+
+// `timer` (its events) is declared first and so outlives the buffers.
+struct CloudScratch {
+  CloudTimer timer;
+  // what is staged
+  DevArr<float> pts[2];              // the two clouds as the caller packs them, f32 [k][3]
+  DevArr<uint32_t> bounds;           // per cloud 8 words: k_cloud_bounds' keys and the finite count
+  CloudResident resident = CloudResident::None;
+  // the grid and the query (pass_cloud.h)
+  DevArr<float4> st, sq;             // target / query points in bucket order: (x, y, z, original index)
+  DevArr<int> tcnt, qcnt;            // per bucket: counts -> starts -> ends
+  DevArr<float> out;                 // the distances, by original index
+  DevArr<int> idx;                   // the matches, by original index (dpe_cloud_nn_index, the ICP step)
+  VoxelScratch voxel;
+  IcpStage icp;
+  RenderStage render;
+  ScoreScratch score;
 };
 
 }  // namespace dpe
 
 // Every member owns what it holds, so `delete ctx` frees the context.  Members are destroyed in
 // reverse order: the streams and events are declared first and so outlive every buffer (the events of
-// one group alone, tat.ev, viz.ev, points.ev and cloud.ev, are the first members of their group).
+// one group alone, tat.ev, viz.ev, points.ev and cloud.timer.ev, are the first members of their group).
 struct DpeContext {
   int device = 0;
   dpe::Stream stream;

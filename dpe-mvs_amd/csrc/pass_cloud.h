@@ -13,6 +13,7 @@
 //   k_cloud_query   one thread per query in BUCKET order, so the lanes of a wave mostly share their 27
 //                   neighbour cells and read the same target points: the running minimum over the buckets
 //                   of those cells, written back by original index
+//   k_cloud_match   the same walk with the running pair (best, best_j), for the registration (pass_register.h)
 //
 // The target and the query go through the same three build steps over the same grid.  The slots within a
 // bucket depend on the schedule; the result is a minimum over a set and does not.  No LDS and no scratch.
@@ -21,10 +22,12 @@
 #include <hip/hip_runtime.h>
 
 #include "cloud_dist.h"
+#include "cloud_reg.h"     // icp_take
+#include "tree_sum.h"      // kTreeBlock
 
 namespace dpe {
 
-constexpr int kCloudBlock = 256;
+constexpr int kCloudBlock = kTreeBlock;
 constexpr int kCloudScanPer = 8;   // counts per thread and round of k_cloud_scan
 
 // keys whose unsigned order is the floats' order (finite values)
@@ -121,7 +124,41 @@ __global__ void __launch_bounds__(kCloudBlock) k_cloud_fill(const float* __restr
   sorted[slot] = make_float4(x, y, z, __int_as_float((int)i));
 }
 
-// sq: the n queries in bucket order; st / tend: the target's points in bucket order and the buckets' ends
+// The walk of one query over the 27 cells around its own (cloud_dist.h says why they are enough), as the host
+// writes it (cloud_query_range, host/cloud_eval.cpp).  The caller starts best at R2 and best_j at -1; best ends as
+// min(R2, min_j d2), and with kIndex the running pair (best, best_j) as the lexicographic minimum of (d2, j), a
+// set's minimum whatever the slots' order.
+// st / tend: the target's points in bucket order and the buckets' ends
+template <bool kIndex>
+__device__ inline void cloud_walk(const float4 q, const float4* __restrict__ st, const int* __restrict__ tend,
+                                  const CloudGrid& g, float& best, int& best_j) {
+  if (!cloud_finite3(q.x, q.y, q.z)) return;
+  const int32_t c[3] = {cloud_cell(q.x, g.o[0], g.h, g.hi[0]), cloud_cell(q.y, g.o[1], g.h, g.hi[1]),
+                        cloud_cell(q.z, g.o[2], g.h, g.hi[2])};
+  const int32_t top[3] = {(int32_t)g.hi[0], (int32_t)g.hi[1], (int32_t)g.hi[2]};
+  for (int dz = -1; dz <= 1; ++dz) {
+    const int32_t iz = c[2] + dz;
+    if (iz < 0 || iz > top[2]) continue;
+    for (int dy = -1; dy <= 1; ++dy) {
+      const int32_t iy = c[1] + dy;
+      if (iy < 0 || iy > top[1]) continue;
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int32_t ix = c[0] + dx;
+        if (ix < 0 || ix > top[0]) continue;
+        const uint32_t b = cloud_bucket(ix, iy, iz, g.mask);
+        const int j1 = tend[b];
+        for (int j = b ? tend[b - 1] : 0; j < j1; ++j) {
+          const float4 t = st[j];
+          const float s = cloud_d2(q.x, q.y, q.z, t.x, t.y, t.z);
+          if constexpr (kIndex) icp_take(s, __float_as_int(t.w), best, best_j);
+          else best = s < best ? s : best;
+        }
+      }
+    }
+  }
+}
+
+// sq: the n queries in bucket order; the distances are written back by original index
 __global__ void __launch_bounds__(kCloudBlock) k_cloud_query(const float4* __restrict__ sq, int n, const float4* __restrict__ st,
                                                              const int* __restrict__ tend, CloudGrid g,
                                                              float* __restrict__ out) {
@@ -129,31 +166,24 @@ __global__ void __launch_bounds__(kCloudBlock) k_cloud_query(const float4* __res
   if (i >= (size_t)n) return;
   const float4 q = sq[i];
   float best = g.r2;
-  if (cloud_finite3(q.x, q.y, q.z)) {
-    const int32_t c[3] = {cloud_cell(q.x, g.o[0], g.h, g.hi[0]), cloud_cell(q.y, g.o[1], g.h, g.hi[1]),
-                          cloud_cell(q.z, g.o[2], g.h, g.hi[2])};
-    const int32_t top[3] = {(int32_t)g.hi[0], (int32_t)g.hi[1], (int32_t)g.hi[2]};
-    for (int dz = -1; dz <= 1; ++dz) {
-      const int32_t iz = c[2] + dz;
-      if (iz < 0 || iz > top[2]) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int32_t iy = c[1] + dy;
-        if (iy < 0 || iy > top[1]) continue;
-        for (int dx = -1; dx <= 1; ++dx) {
-          const int32_t ix = c[0] + dx;
-          if (ix < 0 || ix > top[0]) continue;
-          const uint32_t b = cloud_bucket(ix, iy, iz, g.mask);
-          const int j1 = tend[b];
-          for (int j = b ? tend[b - 1] : 0; j < j1; ++j) {
-            const float4 t = st[j];
-            const float s = cloud_d2(q.x, q.y, q.z, t.x, t.y, t.z);
-            best = s < best ? s : best;
-          }
-        }
-      }
-    }
-  }
+  int best_j = -1;
+  cloud_walk<false>(q, st, tend, g, best, best_j);
   out[(size_t)__float_as_int(q.w)] = best;
+}
+
+// k_cloud_query with the nearest point's index (dpe_cloud_nn_index, the ICP step's match)
+__global__ void __launch_bounds__(kCloudBlock) k_cloud_match(const float4* __restrict__ sq, int n, const float4* __restrict__ st,
+                                                             const int* __restrict__ tend, CloudGrid g,
+                                                             float* __restrict__ out, int* __restrict__ idx) {
+  const size_t i = (size_t)blockIdx.x * kCloudBlock + threadIdx.x;
+  if (i >= (size_t)n) return;
+  const float4 q = sq[i];
+  float best = g.r2;
+  int best_j = -1;
+  cloud_walk<true>(q, st, tend, g, best, best_j);
+  const size_t at = (size_t)__float_as_int(q.w);
+  out[at] = best;
+  idx[at] = best_j;
 }
 
 }  // namespace dpe

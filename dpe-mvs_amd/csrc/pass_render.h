@@ -10,21 +10,20 @@
 //                    stale value can make a thread try an atomic it did not need, never skip one it did
 //   k_render_finish  one thread per pixel: +inf's bits become 0.0f; the buffer is then the map, f32 [h][w]
 //   k_depth_score    block = 256 consecutive pixels: every thread forms its pixel's three terms (+0.0 unless both
-//                    depths are usable), the block sums them by the xor butterfly of pass_register.h (the same
-//                    tree: six levels in a wave, (w0 + w1) + (w2 + w3) through LDS); the counters go by ballot and
+//                    depths are usable), the block sums them by the butterfly of tree_sum.h, and k_tree_reduce<3>
+//                    takes the block results from there; the counters go by ballot and
 //                    popcount into one LDS slot per wave and counter, then one integer atomic per block and counter
-//   k_depth_reduce   the same butterfly over 256 consecutive partials, launched until one block's result is left
 //
 // No float atomics, no scratch.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "depth_eval.h"
-#include "pass_register.h"   // icp_shfl_xor
+#include "tree_sum.h"
 
 namespace dpe {
 
-constexpr int kRenderBlock = 256;
+constexpr int kRenderBlock = kTreeBlock;
 constexpr int kDepthCounters = 3 + DPE_DEPTH_MAX_TAU;   // n_gt, n_est, n_both, within[16]
 
 struct DepthTaus {
@@ -59,28 +58,6 @@ __global__ void __launch_bounds__(kRenderBlock) k_render_finish(uint32_t* __rest
   if (i < npx && zb[i] == kDepthEmpty) zb[i] = 0u;
 }
 
-// t[0..K) of the 256 threads of a block summed by the butterfly; threads 0..K-1 write the K sums to out
-template <int K>
-__device__ inline void depth_block_sum(double* t, double* __restrict__ out) {
-  __shared__ double part[kRenderBlock / 64][K];
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) t[k] = t[k] + icp_shfl_xor(t[k], o);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) part[wave][k] = t[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    const int k = threadIdx.x;
-    const double left = part[0][k] + part[1][k], right = part[2][k] + part[3][k];
-    out[k] = left + right;
-  }
-}
-
 // part: 3 doubles per block; counts: kDepthCounters words; err: the error map or null
 __global__ void __launch_bounds__(kRenderBlock) k_depth_score(const float* __restrict__ est, const float* __restrict__ gt,
                                                               size_t npx, DepthTaus T, double* __restrict__ part,
@@ -101,22 +78,12 @@ __global__ void __launch_bounds__(kRenderBlock) k_depth_score(const float* __res
     const int c = __popcll(__ballot(depth_hit(p, g, T.tau[k], T.mode)));
     if (lane == 0) wc[wave][3 + k] = c;
   }
-  depth_block_sum<kDepthTerms>(t, part + (size_t)blockIdx.x * kDepthTerms);   // its barrier also publishes wc
+  block_tree_sum<kDepthTerms>(t, part + (size_t)blockIdx.x * kDepthTerms);   // its barrier also publishes wc
   if ((int)threadIdx.x < 3 + T.n) {
     const int k = threadIdx.x;
     const int all = wc[0][k] + wc[1][k] + wc[2][k] + wc[3][k];
     if (all > 0) atomicAdd(counts + k, (unsigned long long)all);
   }
-}
-
-// in: cnt partials of 3 doubles; out: one per block of 256 of them
-__global__ void __launch_bounds__(kRenderBlock) k_depth_reduce(const double* __restrict__ in, size_t cnt,
-                                                               double* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * kRenderBlock + threadIdx.x;
-  double t[kDepthTerms];
-#pragma unroll
-  for (int k = 0; k < kDepthTerms; ++k) t[k] = i < cnt ? in[i * kDepthTerms + k] : 0.0;
-  depth_block_sum<kDepthTerms>(t, out + (size_t)blockIdx.x * kDepthTerms);
 }
 
 }  // namespace dpe

@@ -215,14 +215,10 @@ bool cloud_eval_in(DpeContext* ctx, const float* recon, size_t n, const float* g
 
 bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                 int gpu_index, DpeCloudEval* out, std::string& err) {
-  if (gpu_index < 0) return cloud_eval_in(nullptr, recon, n, gt, m, tau, n_tau, radius, out, err);
   float R = 0.0f;
   if (!cloud_eval_args(recon, n, gt, m, tau, n_tau, radius, out, &R, err)) return false;   // before a context is made
-  DpeContext* ctx = dpe_create(gpu_index);
-  if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
-  const bool ok = cloud_eval_in(ctx, recon, n, gt, m, tau, n_tau, radius, out, err);
-  dpe_destroy(ctx);
-  return ok;
+  OwnedContext own(gpu_index, "cloud_eval", err);
+  return own.ok && cloud_eval_in(own.ctx, recon, n, gt, m, tau, n_tau, radius, out, err);
 }
 
 }  // namespace dpe_host
@@ -230,26 +226,17 @@ bool cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const f
 extern "C" {
 
 int dpe_host_cloud_nn(const float* query, size_t n, const float* target, size_t m, float radius, float* d2_out) {
-  std::string err;
-  if (dpe_host::cloud_nn(query, n, target, m, radius, d2_out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return dpe_host::cloud_nn(query, n, target, m, radius, d2_out, err); });
 }
 
 int dpe_host_cloud_nn_index(const float* query, size_t n, const float* target, size_t m, float radius, float* d2_out,
                             int32_t* idx_out) {
-  std::string err;
-  if (dpe_host::cloud_nn_index(query, n, target, m, radius, d2_out, idx_out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return dpe_host::cloud_nn_index(query, n, target, m, radius, d2_out, idx_out, err); });
 }
 
 int dpe_host_cloud_eval(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                         int gpu_index, DpeCloudEval* out) {
-  std::string err;
-  if (dpe_host::cloud_eval(recon, n, gt, m, tau, n_tau, radius, gpu_index, out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return dpe_host::cloud_eval(recon, n, gt, m, tau, n_tau, radius, gpu_index, out, err); });
 }
 
 }  // extern "C"

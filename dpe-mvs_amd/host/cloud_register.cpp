@@ -206,10 +206,7 @@ bool cloud_register_in(DpeContext* ctx, const float* src, size_t n, const float*
     if (!ctx) {
       if (!ix.build(tgt, m, radius, "cloud_register", err)) return false;
     } else if (dpe_cloud_icp_stage(ctx, src, n, tgt, m, radius) != 0) {
-      std::string msg = dpe_last_error();
-      const std::string lead = "dpe_cloud_icp_stage: ";   // the host path's wording: both paths report alike
-      if (msg.compare(0, lead.size(), lead) == 0) msg = msg.substr(lead.size());
-      err = "cloud_register: " + msg;
+      err = device_error("cloud_register", "dpe_cloud_icp_stage");
       return false;
     }
     DpeIcpSums prev{};
@@ -243,14 +240,8 @@ bool cloud_register_in(DpeContext* ctx, const float* src, size_t n, const float*
 static bool cloud_register(const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions* opt, int gpu_index,
                            DpeCloudReg* out, std::string& err) {
   if (!register_args(src, n, tgt, m, opt, out, err)) return false;   // before a context is made
-  DpeContext* ctx = nullptr;
-  if (gpu_index >= 0) {
-    ctx = dpe_create(gpu_index);
-    if (!ctx) { err = std::string("cloud_register: ") + dpe_last_error(); return false; }
-  }
-  const bool ok = cloud_register_in(ctx, src, n, tgt, m, *opt, out, err);
-  if (ctx) dpe_destroy(ctx);
-  return ok;
+  OwnedContext own(gpu_index, "cloud_register", err);
+  return own.ok && cloud_register_in(own.ctx, src, n, tgt, m, *opt, out, err);
 }
 
 static bool cloud_eval_reg(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
@@ -259,11 +250,9 @@ static bool cloud_eval_reg(const float* recon, size_t n, const float* gt, size_t
   if (!register_args(recon, n, gt, m, opt, reg, err)) return false;
   const DpeCloudPrep none{};
   if (!cloud_prep_args(recon, n, gt, m, prep ? *prep : none, err)) return false;
-  DpeContext* ctx = nullptr;
-  if (gpu_index >= 0) {
-    ctx = dpe_create(gpu_index);
-    if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
-  }
+  OwnedContext own(gpu_index, "cloud_eval", err);
+  if (!own.ok) return false;
+  DpeContext* ctx = own.ctx;
   // what is registered: the reconstruction down-sampled but never cropped (the box is in the ground truth's frame),
   // the ground truth as it will be scored
   std::vector<float> a, b, moved(3 * n);
@@ -276,7 +265,6 @@ static bool cloud_eval_reg(const float* recon, size_t n, const float* gt, size_t
     ok = prep ? cloud_eval_prep_in(ctx, moved.data(), n, gt, m, tau, n_tau, radius, prep, out, err)
               : cloud_eval_in(ctx, moved.data(), n, gt, m, tau, n_tau, radius, out, err);
   }
-  if (ctx) dpe_destroy(ctx);
   if (ok) *reg = r;
   return ok;
 }
@@ -287,10 +275,7 @@ extern "C" {
 
 int dpe_host_cloud_icp_step(const float* src, size_t n, const float* tgt, size_t m, float radius, const double* T,
                             DpeIcpSums* out) {
-  std::string err;
-  if (dpe_host::cloud_icp_step(src, n, tgt, m, radius, T, out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return dpe_host::cloud_icp_step(src, n, tgt, m, radius, T, out, err); });
 }
 
 int dpe_host_cloud_transform(const double* T, const float* xyz, size_t n, float* out) {
@@ -303,26 +288,19 @@ int dpe_host_cloud_transform(const double* T, const float* xyz, size_t n, float*
 }
 
 int dpe_host_cloud_solve(const DpeIcpSums* sums, const double* o_s, const double* o_t, double* T) {
-  std::string err = "cloud_solve: bad argument";
-  if (sums && o_s && o_t && T && dpe_host::cloud_solve(*sums, o_s, o_t, T, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return sums && o_s && o_t && T && dpe_host::cloud_solve(*sums, o_s, o_t, T, err); },
+                           "cloud_solve: bad argument");
 }
 
 int dpe_host_cloud_register(const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions* opt, int gpu_index,
                             DpeCloudReg* out) {
-  std::string err;
-  if (dpe_host::cloud_register(src, n, tgt, m, opt, gpu_index, out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return dpe_host::cloud_register(src, n, tgt, m, opt, gpu_index, out, err); });
 }
 
 int dpe_host_cloud_eval_reg(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                             int gpu_index, DpeCloudPrep* prep, const DpeCloudRegOptions* opt, DpeCloudReg* reg, DpeCloudEval* out) {
-  std::string err;
-  if (dpe_host::cloud_eval_reg(recon, n, gt, m, tau, n_tau, radius, gpu_index, prep, opt, reg, out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry(
+      [&](std::string& err) { return dpe_host::cloud_eval_reg(recon, n, gt, m, tau, n_tau, radius, gpu_index, prep, opt, reg, out, err); });
 }
 
 }  // extern "C"

@@ -129,10 +129,7 @@ bool cloud_prepare(DpeContext* ctx, const float* xyz, size_t n, const DpeCloudPr
   if (!ctx) {
     if (!cloud_voxel(pts.data(), m, nullptr, prep.voxel, out.data(), nullptr, first.data(), count.data(), m, &k, err)) return false;
   } else if (dpe_cloud_voxel(ctx, pts.data(), m, nullptr, prep.voxel, out.data(), nullptr, first.data(), count.data(), m, &k) != 0) {
-    std::string msg = dpe_last_error();
-    const std::string lead = "dpe_cloud_voxel: ";      // the host path's wording: both paths report alike
-    if (msg.compare(0, lead.size(), lead) == 0) msg = msg.substr(lead.size());
-    err = "cloud_voxel: " + msg;
+    err = device_error("cloud_voxel", "dpe_cloud_voxel");
     return false;
   }
   out.resize(3 * k);
@@ -166,14 +163,8 @@ bool cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, co
                      int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out, std::string& err) {
   if (!prep) return cloud_eval(recon, n, gt, m, tau, n_tau, radius, gpu_index, out, err);
   if (!cloud_prep_args(recon, n, gt, m, *prep, err)) return false;
-  DpeContext* ctx = nullptr;
-  if (gpu_index >= 0) {
-    ctx = dpe_create(gpu_index);
-    if (!ctx) { err = std::string("cloud_eval: ") + dpe_last_error(); return false; }
-  }
-  const bool ok = cloud_eval_prep_in(ctx, recon, n, gt, m, tau, n_tau, radius, prep, out, err);
-  if (ctx) dpe_destroy(ctx);
-  return ok;
+  OwnedContext own(gpu_index, "cloud_eval", err);
+  return own.ok && cloud_eval_prep_in(own.ctx, recon, n, gt, m, tau, n_tau, radius, prep, out, err);
 }
 
 }  // namespace dpe_host
@@ -182,10 +173,8 @@ extern "C" {
 
 int dpe_host_cloud_voxel(const float* xyz, size_t n, const uint8_t* rgb, float voxel, float* out_xyz, uint8_t* out_rgb,
                          int32_t* out_first, int32_t* out_count, size_t cap, size_t* k) {
-  std::string err;
-  if (dpe_host::cloud_voxel(xyz, n, rgb, voxel, out_xyz, out_rgb, out_first, out_count, cap, k, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry(
+      [&](std::string& err) { return dpe_host::cloud_voxel(xyz, n, rgb, voxel, out_xyz, out_rgb, out_first, out_count, cap, k, err); });
 }
 
 size_t dpe_host_cloud_crop(const float* xyz, size_t n, const uint8_t* rgb, const float* lo, const float* hi, float* out_xyz,
@@ -206,10 +195,8 @@ size_t dpe_host_cloud_crop(const float* xyz, size_t n, const uint8_t* rgb, const
 
 int dpe_host_cloud_eval_prep(const float* recon, size_t n, const float* gt, size_t m, const float* tau, int n_tau, float radius,
                              int gpu_index, DpeCloudPrep* prep, DpeCloudEval* out) {
-  std::string err;
-  if (dpe_host::cloud_eval_prep(recon, n, gt, m, tau, n_tau, radius, gpu_index, prep, out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry(
+      [&](std::string& err) { return dpe_host::cloud_eval_prep(recon, n, gt, m, tau, n_tau, radius, gpu_index, prep, out, err); });
 }
 
 }  // extern "C"

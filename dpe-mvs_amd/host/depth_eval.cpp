@@ -176,68 +176,61 @@ bool depth_eval(const DpeDepthEvalOptions& o, const float* gt_xyz, size_t n_gt, 
   if (!depth_eval_list(dense, map, ids, err)) return false;
   *n_rows = ids.size();
   if (cap < ids.size()) { err = "depth_eval: room for fewer rows than images"; return false; }
-  DpeContext* ctx = nullptr;
-  if (o.gpu_index >= 0) {
-    ctx = dpe_create(o.gpu_index);
-    if (!ctx) { err = std::string("depth_eval: ") + dpe_last_error(); return false; }
-  }
+  OwnedContext own(o.gpu_index, "depth_eval", err);
+  if (!own.ok) return false;
+  DpeContext* ctx = own.ctx;
   auto device_failed = [&]() { err = std::string("depth_eval: ") + dpe_last_error(); return false; };
-  auto run = [&]() {
-    if (ctx && !from_maps && dpe_cloud_render_stage(ctx, gt_xyz, n_gt) != 0) return device_failed();
-    DpeDepthScore sum;
-    std::memset(&sum, 0, sizeof sum);
-    std::vector<float> est, gt, errmap;
-    std::vector<DpeDepthImage> done(ids.size());   // a failure leaves the caller's rows alone
-    for (size_t i = 0; i < ids.size(); ++i) {
-      const fs::path rf = fs::path(dense) / "DPE" / fmt_index(ids[i]);
-      int w = 0, h = 0;
-      if (!read_npy_f32((rf / map).string(), est, w, h, err)) return false;
-      const size_t npx = (size_t)w * (size_t)h;
-      const bool want_gt = !ctx || from_maps || o.write_maps;   // the ground truth on the host
-      if (want_gt) gt.resize(npx);
-      if (o.write_maps) errmap.resize(npx);
-      if (from_maps) {
-        int gw = 0, gh = 0;
-        const std::string path = (fs::path(o.gt_maps_dir) / (fmt_index(ids[i]) + ".npy")).string();
-        if (!read_npy_f32(path, gt, gw, gh, err)) return false;
-        if (gw != w || gh != h) { err = "depth_eval: size mismatch: " + path + " is not of the size of " + (rf / map).string(); return false; }
-      } else {
-        DpeCamera cam;
-        if (!map_camera(dense, ids[i], w, h, cam, err)) return false;
-        if (ctx) {
-          if (dpe_cloud_render_view(ctx, &cam, o.splat, want_gt ? gt.data() : nullptr) != 0) return device_failed();
-        } else if (!cloud_render(gt_xyz, n_gt, cam, o.splat, gt.data(), err)) {
-          return false;
-        }
-      }
-      DpeDepthImage row;
-      std::memset(&row, 0, sizeof row);
-      row.id = ids[i];
-      row.width = w;
-      row.height = h;
-      float* em = o.write_maps ? errmap.data() : nullptr;
+  if (ctx && !from_maps && dpe_cloud_render_stage(ctx, gt_xyz, n_gt) != 0) return device_failed();
+  DpeDepthScore sum;
+  std::memset(&sum, 0, sizeof sum);
+  std::vector<float> est, gt, errmap;
+  std::vector<DpeDepthImage> done(ids.size());   // a failure leaves the caller's rows alone
+  for (size_t i = 0; i < ids.size(); ++i) {
+    const fs::path rf = fs::path(dense) / "DPE" / fmt_index(ids[i]);
+    int w = 0, h = 0;
+    if (!read_npy_f32((rf / map).string(), est, w, h, err)) return false;
+    const size_t npx = (size_t)w * (size_t)h;
+    const bool want_gt = !ctx || from_maps || o.write_maps;   // the ground truth on the host
+    if (want_gt) gt.resize(npx);
+    if (o.write_maps) errmap.resize(npx);
+    if (from_maps) {
+      int gw = 0, gh = 0;
+      const std::string path = (fs::path(o.gt_maps_dir) / (fmt_index(ids[i]) + ".npy")).string();
+      if (!read_npy_f32(path, gt, gw, gh, err)) return false;
+      if (gw != w || gh != h) { err = "depth_eval: size mismatch: " + path + " is not of the size of " + (rf / map).string(); return false; }
+    } else {
+      DpeCamera cam;
+      if (!map_camera(dense, ids[i], w, h, cam, err)) return false;
       if (ctx) {
-        if (dpe_depth_score(ctx, est.data(), from_maps ? gt.data() : nullptr, w, h, o.tau, o.n_tau, o.mode, &row.score, em) != 0)
-          return device_failed();
-      } else if (!depth_score(est.data(), gt.data(), w, h, o.tau, o.n_tau, o.mode, &row.score, em, err)) {
+        if (dpe_cloud_render_view(ctx, &cam, o.splat, want_gt ? gt.data() : nullptr) != 0) return device_failed();
+      } else if (!cloud_render(gt_xyz, n_gt, cam, o.splat, gt.data(), err)) {
         return false;
       }
-      if (o.write_maps) {
-        const std::vector<int64_t> hw = {h, w};
-        if (!write_npy((rf / "depth_gt.npy").string(), gt.data(), hw, "<f4", 4, err) ||
-            !write_npy((rf / "depth_error.npy").string(), errmap.data(), hw, "<f4", 4, err))
-          return false;
-      }
-      done[i] = row;
-      depth_add(&sum, row.score);
     }
-    std::copy(done.begin(), done.end(), rows);
-    *total = sum;
-    return true;
-  };
-  const bool ok = run();
-  if (ctx) dpe_destroy(ctx);
-  return ok;
+    DpeDepthImage row;
+    std::memset(&row, 0, sizeof row);
+    row.id = ids[i];
+    row.width = w;
+    row.height = h;
+    float* em = o.write_maps ? errmap.data() : nullptr;
+    if (ctx) {
+      if (dpe_depth_score(ctx, est.data(), from_maps ? gt.data() : nullptr, w, h, o.tau, o.n_tau, o.mode, &row.score, em) != 0)
+        return device_failed();
+    } else if (!depth_score(est.data(), gt.data(), w, h, o.tau, o.n_tau, o.mode, &row.score, em, err)) {
+      return false;
+    }
+    if (o.write_maps) {
+      const std::vector<int64_t> hw = {h, w};
+      if (!write_npy((rf / "depth_gt.npy").string(), gt.data(), hw, "<f4", 4, err) ||
+          !write_npy((rf / "depth_error.npy").string(), errmap.data(), hw, "<f4", 4, err))
+        return false;
+    }
+    done[i] = row;
+    depth_add(&sum, row.score);
+  }
+  std::copy(done.begin(), done.end(), rows);
+  *total = sum;
+  return true;
 }
 
 }  // namespace
@@ -247,18 +240,14 @@ bool depth_eval(const DpeDepthEvalOptions& o, const float* gt_xyz, size_t n_gt, 
 extern "C" {
 
 int dpe_host_cloud_render(const float* xyz, size_t n, const DpeCamera* cam, int splat, float* depth_out) {
-  std::string err = "cloud_render: bad argument";
-  if (cam && dpe_host::cloud_render(xyz, n, *cam, splat, depth_out, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return cam && dpe_host::cloud_render(xyz, n, *cam, splat, depth_out, err); },
+                           "cloud_render: bad argument");
 }
 
 int dpe_host_depth_score(const float* est, const float* gt, int w, int h, const float* tau, int n_tau, int mode,
                          DpeDepthScore* out, float* err_or_null) {
-  std::string err;
-  if (dpe_host::depth_score(est, gt, w, h, tau, n_tau, mode, out, err_or_null, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry(
+      [&](std::string& err) { return dpe_host::depth_score(est, gt, w, h, tau, n_tau, mode, out, err_or_null, err); });
 }
 
 void dpe_host_depth_stats(const DpeDepthScore* s, int n_tau, DpeDepthStats* out) {
@@ -294,10 +283,8 @@ int dpe_host_depth_eval_list(const char* dense_folder, const char* map_name, int
 
 int dpe_host_depth_eval(const DpeDepthEvalOptions* opt, const float* gt_xyz, size_t n_gt, DpeDepthImage* rows, size_t cap,
                         size_t* n_rows, DpeDepthScore* total) {
-  std::string err = "depth_eval: bad argument";
-  if (opt && dpe_host::depth_eval(*opt, gt_xyz, n_gt, rows, cap, n_rows, total, err)) return 0;
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::c_entry([&](std::string& err) { return opt && dpe_host::depth_eval(*opt, gt_xyz, n_gt, rows, cap, n_rows, total, err); },
+                           "depth_eval: bad argument");
 }
 
 }  // extern "C"

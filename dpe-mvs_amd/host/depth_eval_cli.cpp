@@ -9,13 +9,9 @@
 // depth_error.npy beside each map; --gpu N (the default, N = 0) renders and scores on that device, --cpu on the host:
 // the same numbers.  Prints one table, a row per image and a total; --json also writes the counts and sums.
 // `python -m DPE_MVS.depth_eval` prints the same table.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/dpe_host.h"
+#include "cli_common.h"
 
 static int usage() {
   std::fprintf(stderr, "usage: dpe_depth_eval dense_folder gt.ply tau [tau ...] [--relative] [--splat S] [--map NAME.npy]"
@@ -37,11 +33,11 @@ static void json_score(FILE* f, const DpeDepthScore& s, int n_tau) {
   dpe_host_depth_stats(&s, n_tau, &d);
   std::fprintf(f, "\"n_px\": %lld, \"n_gt\": %lld, \"n_est\": %lld, \"n_both\": %lld, \"within\": [", s.n_px, s.n_gt, s.n_est, s.n_both);
   for (int k = 0; k < n_tau; ++k) std::fprintf(f, "%s%lld", k ? ", " : "", s.within[k]);
-  std::fprintf(f, "], \"sum_abs\": %.17g, \"sum_rel\": %.17g, \"sum_sq\": %.17g, \"accuracy\": [", s.sum_abs, s.sum_rel, s.sum_sq);
-  for (int k = 0; k < n_tau; ++k) std::fprintf(f, "%s%.17g", k ? ", " : "", d.accuracy[k]);
-  std::fprintf(f, "], \"completeness\": [");
-  for (int k = 0; k < n_tau; ++k) std::fprintf(f, "%s%.17g", k ? ", " : "", d.completeness[k]);
-  std::fprintf(f, "], \"mae\": %.17g, \"mre\": %.17g, \"rmse\": %.17g", d.mae, d.mre, d.rmse);
+  std::fprintf(f, "], \"sum_abs\": %.17g, \"sum_rel\": %.17g, \"sum_sq\": %.17g, ", s.sum_abs, s.sum_rel, s.sum_sq);
+  cli_json_array(f, "accuracy", d.accuracy, n_tau);
+  std::fprintf(f, ", ");
+  cli_json_array(f, "completeness", d.completeness, n_tau);
+  std::fprintf(f, ", \"mae\": %.17g, \"mre\": %.17g, \"rmse\": %.17g", d.mae, d.mre, d.rmse);
 }
 
 int main(int argc, char** argv) {
@@ -51,9 +47,8 @@ int main(int argc, char** argv) {
   const char* json = nullptr;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
-    if (a == "--cpu") o.gpu_index = -1;
-    else if (a == "--gpu" && i + 1 < argc) o.gpu_index = std::atoi(argv[++i]);
-    else if (a == "--relative") o.mode = DPE_DEPTH_TAU_REL;
+    if (cli_device_option(argc, argv, i, o.gpu_index)) continue;
+    if (a == "--relative") o.mode = DPE_DEPTH_TAU_REL;
     else if (a == "--maps") o.write_maps = 1;
     else if (a == "--splat" && i + 1 < argc) o.splat = std::atoi(argv[++i]);
     else if (a == "--map" && i + 1 < argc) o.map_name = argv[++i];
@@ -69,17 +64,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "dpe_depth_eval: depth_score: 1 to 16 thresholds expected\n");
     return 1;
   }
-  for (size_t k = first_tau; k < pos.size(); ++k) {
-    char* end = nullptr;
-    o.tau[o.n_tau++] = std::strtof(pos[k], &end);
-    if (end == pos[k] || *end) return usage();
-  }
+  for (size_t k = first_tau; k < pos.size(); ++k)
+    if (!cli_number(pos[k], o.tau[o.n_tau++])) return usage();
   std::vector<float> gt;
   size_t n = 0, n_img = 0;
-  if (!o.gt_maps_dir) {
-    if (dpe_host_read_point_cloud(pos[1], nullptr, 0, &n) != 0) { std::fprintf(stderr, "dpe_depth_eval: %s\n", dpe_pipeline_last_error()); return 1; }
-    gt.resize(3 * n + 3);
-    if (dpe_host_read_point_cloud(pos[1], gt.data(), n, &n) != 0) { std::fprintf(stderr, "dpe_depth_eval: %s\n", dpe_pipeline_last_error()); return 1; }
+  if (!o.gt_maps_dir && !cli_read_cloud(pos[1], gt, n)) {
+    std::fprintf(stderr, "dpe_depth_eval: %s\n", dpe_pipeline_last_error());
+    return 1;
   }
   if (dpe_host_depth_eval_list(o.dense_folder, o.map_name, nullptr, 0, &n_img) != 0) {
     std::fprintf(stderr, "dpe_depth_eval: %s\n", dpe_pipeline_last_error());

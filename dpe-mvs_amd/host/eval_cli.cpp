@@ -9,30 +9,14 @@
 // --register-init: a starting transform, row-major 3 x 4); the table then begins with the radii, the final rms and T.
 // --gpu N (the default, N = 0) runs the distances on that device, --cpu on host threads: the same numbers.
 // Prints one table; --json also writes the struct.  `python -m DPE_MVS.evaluate` prints the same table.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/dpe_host.h"
+#include "cli_common.h"
 
 static int usage() {
   std::fprintf(stderr, "usage: dpe_eval recon.ply gt.ply tau [tau...] [--radius R] [--voxel V] [--crop x0 y0 z0 x1 y1 z1]"
                        " [--gpu N | --cpu] [--json FILE] [--register R [R ...]] [--register-iters N] [--register-init t0 .. t11]\n");
   return 2;
-}
-
-static bool read_cloud(const char* path, std::vector<float>& xyz, size_t& n) {
-  if (dpe_host_read_point_cloud(path, nullptr, 0, &n) != 0) return false;
-  xyz.resize(3 * n + 3);
-  return dpe_host_read_point_cloud(path, xyz.data(), n, &n) == 0;
-}
-
-static void json_array(FILE* f, const char* name, const double* v, int n) {
-  std::fprintf(f, "\"%s\": [", name);
-  for (int k = 0; k < n; ++k) std::fprintf(f, "%s%.17g", k ? ", " : "", v[k]);
-  std::fprintf(f, "]");
 }
 
 int main(int argc, char** argv) {
@@ -47,9 +31,8 @@ int main(int argc, char** argv) {
   ropt.tol = 1e-6;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
-    if (a == "--cpu") gpu = -1;
-    else if (a == "--gpu" && i + 1 < argc) gpu = std::atoi(argv[++i]);
-    else if (a == "--radius" && i + 1 < argc) radius = std::strtof(argv[++i], nullptr);
+    if (cli_device_option(argc, argv, i, gpu)) continue;
+    if (a == "--radius" && i + 1 < argc) radius = std::strtof(argv[++i], nullptr);
     else if (a == "--json" && i + 1 < argc) json = argv[++i];
     else if (a == "--voxel" && i + 1 < argc) { prep.voxel = std::strtof(argv[++i], nullptr); prepared = have_voxel = true; }
     else if (a == "--crop" && i + 6 < argc) {
@@ -61,9 +44,8 @@ int main(int argc, char** argv) {
     else if (a == "--register") {
       registered = true;
       while (i + 1 < argc && ropt.n_radii < DPE_CLOUD_MAX_RADII) {   // the numbers that follow
-        char* end = nullptr;
-        const float r = std::strtof(argv[i + 1], &end);
-        if (end == argv[i + 1] || *end) break;
+        float r = 0.0f;
+        if (!cli_number(argv[i + 1], r)) break;
         ropt.radius[ropt.n_radii++] = r;
         ++i;
       }
@@ -81,17 +63,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "dpe_eval: cloud_eval: the voxel edge is not a finite positive number\n");
     return 1;
   }
-  std::vector<float> tau;
-  for (size_t k = 2; k < pos.size(); ++k) {
-    char* end = nullptr;
-    tau.push_back(std::strtof(pos[k], &end));
-    if (end == pos[k] || *end) return usage();
-  }
+  std::vector<float> tau(pos.size() - 2);
+  for (size_t k = 2; k < pos.size(); ++k)
+    if (!cli_number(pos[k], tau[k - 2])) return usage();
   std::vector<float> recon, gt;
   size_t n = 0, m = 0;
   DpeCloudEval e;
   DpeCloudReg reg{};
-  if (!read_cloud(pos[0], recon, n) || !read_cloud(pos[1], gt, m) ||
+  if (!cli_read_cloud(pos[0], recon, n) || !cli_read_cloud(pos[1], gt, m) ||
       (registered ? dpe_host_cloud_eval_reg(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu,
                                             prepared ? &prep : nullptr, &ropt, &reg, &e)
                   : dpe_host_cloud_eval_prep(recon.data(), n, gt.data(), m, tau.data(), (int)tau.size(), radius, gpu,
@@ -127,10 +106,10 @@ int main(int argc, char** argv) {
     if (!f) { std::fprintf(stderr, "dpe_eval: cannot write %s\n", json); return 1; }
     std::vector<double> t(e.tau, e.tau + e.n_tau);
     std::fprintf(f, "{\"n_tau\": %d, \"radius\": %.17g, ", e.n_tau, (double)e.radius);
-    json_array(f, "tau", t.data(), e.n_tau); std::fprintf(f, ", ");
-    json_array(f, "precision", e.precision, e.n_tau); std::fprintf(f, ", ");
-    json_array(f, "recall", e.recall, e.n_tau); std::fprintf(f, ", ");
-    json_array(f, "fscore", e.fscore, e.n_tau);
+    cli_json_array(f, "tau", t.data(), e.n_tau); std::fprintf(f, ", ");
+    cli_json_array(f, "precision", e.precision, e.n_tau); std::fprintf(f, ", ");
+    cli_json_array(f, "recall", e.recall, e.n_tau); std::fprintf(f, ", ");
+    cli_json_array(f, "fscore", e.fscore, e.n_tau);
     std::fprintf(f, ", \"mean_accuracy_truncated\": %.17g, \"mean_completeness_truncated\": %.17g, ", e.mean_accuracy_truncated,
                  e.mean_completeness_truncated);
     std::fprintf(f, "\"n_recon\": %llu, \"n_gt\": %llu, \"dropped_recon\": %llu, \"dropped_gt\": %llu", e.n_recon, e.n_gt,

@@ -141,6 +141,38 @@ bool consistency_args_ok(int n_views, int ref, const int* src, int ns, int min_v
 // pipeline.cpp: the message dpe_pipeline_last_error returns on this thread (the helpers of cloud_eval.cpp and
 // ply_read.cpp report through it)
 void set_last_error(const std::string& msg);
+// the extern "C" form of a host function: 0, or 1 with its message (`otherwise` when it left none) for
+// dpe_pipeline_last_error
+template <class F>
+int c_entry(F&& run, const char* otherwise = "") {
+  std::string err = otherwise;
+  if (run(err)) return 0;
+  set_last_error(err);
+  return 1;
+}
+// The context of a tool that runs on either path: none for gpu_index < 0 (the host path), else one of its own on that
+// device, destroyed with the owner.  A failed dpe_create leaves ok false and err = who + ": " + dpe_last_error()
+struct OwnedContext {
+  DpeContext* ctx = nullptr;
+  bool ok = true;
+  OwnedContext(int gpu_index, const char* who, std::string& err) {
+    if (gpu_index < 0) return;
+    ctx = dpe_create(gpu_index);
+    ok = ctx != nullptr;
+    if (!ok) err = std::string(who) + ": " + dpe_last_error();
+  }
+  ~OwnedContext() { if (ctx) dpe_destroy(ctx); }
+  OwnedContext(const OwnedContext&) = delete;
+  OwnedContext& operator=(const OwnedContext&) = delete;
+};
+// dpe_last_error() in the host path's wording, so both paths report alike: the device entry's name in front gives
+// way to the host function's
+inline std::string device_error(const char* who, const char* entry) {
+  std::string msg = dpe_last_error();
+  const std::string lead = std::string(entry) + ": ";
+  if (msg.compare(0, lead.size(), lead) == 0) msg = msg.substr(lead.size());
+  return std::string(who) + ": " + msg;
+}
 // cloud_eval.cpp: the truncated nearest-neighbour distance of dpe_cloud_nn (dpe_mvs.h) over the same grid
 // (csrc/cloud_dist.h) on host threads, and the evaluation built on it (gpu_index < 0: that path, else
 // dpe_cloud_nn_pair in a context of its own; the counts and means on the host either way)

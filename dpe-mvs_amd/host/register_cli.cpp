@@ -5,13 +5,9 @@
 // (default: the identity).  --gpu N (the default, N = 0) runs the steps on that device, --cpu on host threads: the
 // same bytes.  Prints T (%.17g) and one line per stage; the reader and the writer are bin/dpe_voxel's.
 // `python -m DPE_MVS.register` does the same.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/dpe_host.h"
+#include "cli_common.h"
 
 static int usage() {
   std::fprintf(stderr, "usage: dpe_register src.ply tgt.ply out.ply R [R ...] [--iters N] [--init t0 .. t11] [--gpu N | --cpu]\n");
@@ -26,9 +22,8 @@ int main(int argc, char** argv) {
   opt.tol = 1e-6;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
-    if (a == "--cpu") gpu = -1;
-    else if (a == "--gpu" && i + 1 < argc) gpu = std::atoi(argv[++i]);
-    else if (a == "--iters" && i + 1 < argc) opt.max_iters = std::atoi(argv[++i]);
+    if (cli_device_option(argc, argv, i, gpu)) continue;
+    if (a == "--iters" && i + 1 < argc) opt.max_iters = std::atoi(argv[++i]);
     else if (a == "--init" && i + 12 < argc) {
       for (int k = 0; k < 12; ++k) opt.init[k] = std::strtod(argv[++i], nullptr);
       opt.use_init = 1;
@@ -37,23 +32,14 @@ int main(int argc, char** argv) {
     else pos.push_back(argv[i]);
   }
   if (pos.size() < 4 || pos.size() > 3 + DPE_CLOUD_MAX_RADII) return usage();
-  for (size_t k = 3; k < pos.size(); ++k) {
-    char* end = nullptr;
-    opt.radius[opt.n_radii++] = std::strtof(pos[k], &end);
-    if (end == pos[k] || *end) return usage();
-  }
+  for (size_t k = 3; k < pos.size(); ++k)
+    if (!cli_number(pos[k], opt.radius[opt.n_radii++])) return usage();
   size_t n = 0, m = 0;
   int has_rgb = 0;
-  if (dpe_host_read_point_cloud_rgb(pos[0], nullptr, nullptr, 0, &n, &has_rgb) != 0 ||
-      dpe_host_read_point_cloud(pos[1], nullptr, 0, &m) != 0) {
-    std::fprintf(stderr, "dpe_register: %s\n", dpe_pipeline_last_error());
-    return 1;
-  }
-  std::vector<float> src(3 * n + 3), tgt(3 * m + 3);
-  std::vector<uint8_t> rgb(3 * n + 3);
+  std::vector<float> src, tgt;
+  std::vector<uint8_t> rgb;
   DpeCloudReg reg;
-  if (dpe_host_read_point_cloud_rgb(pos[0], src.data(), rgb.data(), n, &n, &has_rgb) != 0 ||
-      dpe_host_read_point_cloud(pos[1], tgt.data(), m, &m) != 0 ||
+  if (!cli_read_cloud(pos[0], src, n, &rgb, &has_rgb) || !cli_read_cloud(pos[1], tgt, m) ||
       dpe_host_cloud_register(src.data(), n, tgt.data(), m, &opt, gpu, &reg) != 0 ||
       dpe_host_cloud_transform(reg.T, src.data(), n, src.data()) != 0) {
     std::fprintf(stderr, "dpe_register: %s\n", dpe_pipeline_last_error());

@@ -4,13 +4,9 @@
 // --gpu N (the default, N = 0) runs on that device, --cpu the serial host loop: the same bytes.  The output is
 // written by dpe_host_write_point_cloud (a file without colours gets black); the point counts before and after
 // go to stderr.  `python -m DPE_MVS.voxel` does the same.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../include/dpe_host.h"
+#include "cli_common.h"
 
 static int usage() {
   std::fprintf(stderr, "usage: dpe_voxel in.ply out.ply V [--gpu N | --cpu]\n");
@@ -22,28 +18,24 @@ int main(int argc, char** argv) {
   int gpu = 0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
-    if (a == "--cpu") gpu = -1;
-    else if (a == "--gpu" && i + 1 < argc) gpu = std::atoi(argv[++i]);
-    else if (a.rfind("--", 0) == 0) return usage();
+    if (cli_device_option(argc, argv, i, gpu)) continue;
+    if (a.rfind("--", 0) == 0) return usage();
     else pos.push_back(argv[i]);
   }
   if (pos.size() != 3) return usage();
-  char* end = nullptr;
-  const float v = std::strtof(pos[2], &end);
-  if (end == pos[2] || *end) return usage();
+  float v = 0.0f;
+  if (!cli_number(pos[2], v)) return usage();
   size_t n = 0, k = 0;
   int has_rgb = 0;
-  if (dpe_host_read_point_cloud_rgb(pos[0], nullptr, nullptr, 0, &n, &has_rgb) != 0) {
+  std::vector<float> xyz;
+  std::vector<uint8_t> rgb;
+  if (!cli_read_cloud(pos[0], xyz, n, &rgb, &has_rgb)) {
     std::fprintf(stderr, "dpe_voxel: %s\n", dpe_pipeline_last_error());
     return 1;
   }
-  std::vector<float> xyz(3 * n + 3), out(3 * n + 3);
-  std::vector<uint8_t> rgb(3 * n + 3), out_rgb(3 * n + 3);
+  std::vector<float> out(3 * n + 3);
+  std::vector<uint8_t> out_rgb(3 * n + 3);
   std::vector<int32_t> first(n + 1), count(n + 1);
-  if (dpe_host_read_point_cloud_rgb(pos[0], xyz.data(), rgb.data(), n, &n, &has_rgb) != 0) {
-    std::fprintf(stderr, "dpe_voxel: %s\n", dpe_pipeline_last_error());
-    return 1;
-  }
   const uint8_t* colours = has_rgb ? rgb.data() : nullptr;
   if (gpu < 0) {
     if (dpe_host_cloud_voxel(xyz.data(), n, colours, v, out.data(), out_rgb.data(), first.data(), count.data(), n, &k) != 0) {

@@ -14,15 +14,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dpe_host.h"
+#include "no_device.h"
 
-// ---- what host/pipeline.cpp and libdpe_mvs.so provide in the library
-static std::string g_msg;
-namespace dpe_host { void set_last_error(const std::string& m) { g_msg = m; } }
-extern "C" const char* dpe_pipeline_last_error(void) { return g_msg.c_str(); }
-extern "C" DpeContext* dpe_create(int) { return nullptr; }
-extern "C" void dpe_destroy(DpeContext*) {}
-extern "C" const char* dpe_last_error(void) { return "no device in this program"; }
+// ---- the device entry of these sources (no_device.h: the rest of what the library provides)
 extern "C" int dpe_cloud_nn_pair(DpeContext*, const float*, size_t, const float*, size_t, float, float*, float*) { return DPE_ERR_ARG; }
 
 static int fail(const std::string& what) {

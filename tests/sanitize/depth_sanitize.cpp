@@ -16,20 +16,14 @@
 
 #include <unistd.h>
 
-#include "../../include/dpe_host.h"
+#include "no_device.h"
 
 namespace fs = std::filesystem;
 
-// ---- what host/pipeline.cpp, host/points.cpp and libdpe_mvs.so provide in the library
-static std::string g_msg;
+// ---- what host/points.cpp provides in the library, and the device entries of these sources (no_device.h: the rest)
 namespace dpe_host {
-void set_last_error(const std::string& m) { g_msg = m; }
 void scale_intrinsics(DpeCamera& cam, float sx, float sy) { cam.K[0] *= sx; cam.K[2] *= sx; cam.K[4] *= sy; cam.K[5] *= sy; }
 }  // namespace dpe_host
-extern "C" const char* dpe_pipeline_last_error(void) { return g_msg.c_str(); }
-extern "C" DpeContext* dpe_create(int) { return nullptr; }
-extern "C" void dpe_destroy(DpeContext*) {}
-extern "C" const char* dpe_last_error(void) { return "no device in this program"; }
 extern "C" int dpe_cloud_render_stage(DpeContext*, const float*, size_t) { return DPE_ERR_ARG; }
 extern "C" int dpe_cloud_render_view(DpeContext*, const DpeCamera*, int, float*) { return DPE_ERR_ARG; }
 extern "C" int dpe_depth_score(DpeContext*, const float*, const float*, int, int, const float*, int, int, DpeDepthScore*, float*) {

@@ -11,12 +11,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dpe_host.h"
+#include "no_device.h"
 
-// ---- what host/pipeline.cpp, host/cloud_voxel.cpp and libdpe_mvs.so provide in the library
-static std::string g_msg;
+// ---- what host/cloud_voxel.cpp provides in the library, and the device entries of these sources (no_device.h: the rest)
 namespace dpe_host {
-void set_last_error(const std::string& m) { g_msg = m; }
 bool cloud_prep_args(const float*, size_t, const float*, size_t, const DpeCloudPrep&, std::string&) { return true; }
 bool cloud_prepare(DpeContext*, const float* xyz, size_t n, const DpeCloudPrep&, bool, std::vector<float>& pts, std::string&) {
   pts.assign(xyz, xyz + 3 * n);   // no voxels and no crop in this program
@@ -28,10 +26,6 @@ bool cloud_eval_prep_in(DpeContext*, const float*, size_t, const float*, size_t,
   return false;
 }
 }  // namespace dpe_host
-extern "C" const char* dpe_pipeline_last_error(void) { return g_msg.c_str(); }
-extern "C" DpeContext* dpe_create(int) { return nullptr; }
-extern "C" void dpe_destroy(DpeContext*) {}
-extern "C" const char* dpe_last_error(void) { return "no device in this program"; }
 extern "C" int dpe_cloud_nn_pair(DpeContext*, const float*, size_t, const float*, size_t, float, float*, float*) { return DPE_ERR_ARG; }
 extern "C" int dpe_cloud_icp_stage(DpeContext*, const float*, size_t, const float*, size_t, float) { return DPE_ERR_ARG; }
 extern "C" int dpe_cloud_icp_step(DpeContext*, const double*, DpeIcpSums*) { return DPE_ERR_ARG; }

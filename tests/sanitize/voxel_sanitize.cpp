@@ -17,12 +17,10 @@
 #include <tuple>
 #include <vector>
 
-#include "../../include/dpe_host.h"
+#include "no_device.h"
 
-// ---- what host/pipeline.cpp, host/cloud_eval.cpp and libdpe_mvs.so provide in the library
-static std::string g_msg;
+// ---- what host/cloud_eval.cpp provides in the library, and the device entry of these sources (no_device.h: the rest)
 namespace dpe_host {
-void set_last_error(const std::string& m) { g_msg = m; }
 bool cloud_eval_in(DpeContext*, const float*, size_t, const float*, size_t, const float*, int, float, DpeCloudEval*, std::string& err) {
   err = "no distances in this program";
   return false;
@@ -32,10 +30,6 @@ bool cloud_eval(const float*, size_t, const float*, size_t, const float*, int, f
   return false;
 }
 }  // namespace dpe_host
-extern "C" const char* dpe_pipeline_last_error(void) { return g_msg.c_str(); }
-extern "C" DpeContext* dpe_create(int) { return nullptr; }
-extern "C" void dpe_destroy(DpeContext*) {}
-extern "C" const char* dpe_last_error(void) { return "no device in this program"; }
 extern "C" int dpe_cloud_voxel(DpeContext*, const float*, size_t, const uint8_t*, float, float*, uint8_t*, int32_t*, int32_t*, size_t,
                                size_t*) { return DPE_ERR_ARG; }
 
