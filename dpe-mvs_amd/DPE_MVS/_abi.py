@@ -57,6 +57,23 @@ def depth_score_dict(s: DpeDepthScore, n_tau: int) -> dict:
                 within=[int(v) for v in s.within[:n_tau]], sum_abs=s.sum_abs, sum_rel=s.sum_rel, sum_sq=s.sum_sq)
 
 
+NORMAL_MAX_TAU = 16
+NORMAL_BINS = 180
+NORMAL_SUMS = 10
+
+
+class DpeNormalScore(C.Structure):   # include/dpe_mvs.h (one normal map against its ground truth: counts, histogram and pairwise sums)
+    _fields_ = [("n_px", C.c_longlong), ("n_gt", C.c_longlong), ("n_est", C.c_longlong), ("n_both", C.c_longlong),
+                ("within", C.c_longlong * NORMAL_MAX_TAU), ("hist", C.c_longlong * NORMAL_BINS), ("sum_dist", C.c_double),
+                ("sum_dist_sq", C.c_double)]
+
+
+def normal_score_dict(s: DpeNormalScore, n_tau: int) -> dict:
+    return dict(n_px=int(s.n_px), n_gt=int(s.n_gt), n_est=int(s.n_est), n_both=int(s.n_both),
+                within=[int(v) for v in s.within[:n_tau]], hist=[int(v) for v in s.hist], sum_dist=s.sum_dist,
+                sum_dist_sq=s.sum_dist_sq)
+
+
 class DpePatchMatchParams(C.Structure):
     _fields_ = [
         ("max_iterations", C.c_int),

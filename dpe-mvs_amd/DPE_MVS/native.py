@@ -31,6 +31,7 @@ EXPORTED = [
     "dpe_cloud_nn", "dpe_cloud_nn_pair", "dpe_cloud_launches", "dpe_cloud_last_timings", "dpe_cloud_voxel",
     "dpe_cloud_nn_index", "dpe_cloud_icp_stage", "dpe_cloud_icp_step",
     "dpe_cloud_render_stage", "dpe_cloud_render_view", "dpe_depth_score",
+    "dpe_cloud_normals", "dpe_cloud_render_stage_normals", "dpe_cloud_render_view_normals", "dpe_normal_score",
 ]
 
 VIZ_DEPTH, VIZ_NORMAL, VIZ_WEAK = 0, 1, 2
@@ -159,6 +160,15 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dpe_depth_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                     C.POINTER(_abi.DpeDepthScore), C.c_void_p]
     lib.dpe_depth_score.restype = C.c_int
+    lib.dpe_cloud_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.dpe_cloud_normals.restype = C.c_int
+    lib.dpe_cloud_render_stage_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.dpe_cloud_render_stage_normals.restype = C.c_int
+    lib.dpe_cloud_render_view_normals.argtypes = [C.c_void_p, C.POINTER(_abi.DpeCamera), C.c_int, C.c_void_p, C.c_void_p]
+    lib.dpe_cloud_render_view_normals.restype = C.c_int
+    lib.dpe_normal_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                     C.POINTER(_abi.DpeNormalScore), C.c_void_p]
+    lib.dpe_normal_score.restype = C.c_int
     for fn in ("dpe_state_clear", "dpe_image_cache_clear"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = None
@@ -509,10 +519,17 @@ class PatchMatchContext:
         return dict(matched=int(s.matched), d2=s.d2, a=list(s.a), b=list(s.b), ab=list(s.ab))
 
     # depth-map evaluation (include/dpe_mvs.h: dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score)
-    def cloud_render_stage(self, points) -> None:
-        """Uploads a scan f32 [n, 3]; it stays resident for cloud_render_view until the next cloud call of the context."""
+    def cloud_render_stage(self, points, normals=None) -> None:
+        """Uploads a scan f32 [n, 3]; it stays resident for cloud_render_view until the next cloud call of the context.
+        With `normals` f32 [n, 3] (cloud_normals', or any other) the staging also serves cloud_render_view_normals."""
         p = as_cloud(points)
-        _check(_LIB.dpe_cloud_render_stage(self._ctx, p.ctypes.data, len(p)), "dpe_cloud_render_stage")
+        if normals is None:
+            _check(_LIB.dpe_cloud_render_stage(self._ctx, p.ctypes.data, len(p)), "dpe_cloud_render_stage")
+            return
+        nm = as_cloud(normals)
+        if len(nm) != len(p):
+            raise ValueError("expected one normal per point")
+        _check(_LIB.dpe_cloud_render_stage_normals(self._ctx, p.ctypes.data, nm.ctypes.data, len(p)), "dpe_cloud_render_stage_normals")
 
     def cloud_render_view(self, cam: _abi.DpeCamera, splat: int = 0, download: bool = True):
         """The staged scan rendered into `cam` (at the map's size) with a z-buffer and a splat half-width of 0 to 8:
@@ -541,6 +558,50 @@ class PatchMatchContext:
                                     t.ctypes.data, len(t), _abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS, C.byref(s),
                                     None if err is None else err.ctypes.data), "dpe_depth_score")
         d = _abi.depth_score_dict(s, len(t))
+        return (d, err) if want_error else d
+
+    # normal-map evaluation (include/dpe_mvs.h: dpe_cloud_normals, dpe_cloud_render_view_normals, dpe_normal_score)
+    def cloud_normals(self, points, radius: float, min_neighbours: int = 3, want_sums: bool = False) -> tuple:
+        """A normal per point of the cloud f32 [n, 3] by PCA over the points within `radius` of it: (normals f32 [n, 3],
+        counts i32 [n]) and with want_sums the ten integer sums i64 [n, 10] as well.  (0, 0, 0) where a point has fewer
+        than min_neighbours neighbours (itself included), collinear ones, or a non-finite coordinate.  The bits of the
+        host loop (pipeline.estimate_normals)."""
+        p = as_cloud(points)
+        n = len(p)
+        normals, counts = np.empty((n, 3), np.float32), np.empty(n, np.int32)
+        sums = np.empty((n, _abi.NORMAL_SUMS), np.int64) if want_sums else None
+        _check(_LIB.dpe_cloud_normals(self._ctx, p.ctypes.data, n, float(radius), int(min_neighbours), normals.ctypes.data,
+                                      counts.ctypes.data, None if sums is None else sums.ctypes.data), "dpe_cloud_normals")
+        return (normals, counts, sums) if want_sums else (normals, counts)
+
+    def cloud_render_view_normals(self, cam: _abi.DpeCamera, splat: int = 0, download: bool = True):
+        """The staged scan and its normals rendered into `cam`: (depth f32 [height, width] with cloud_render_view's bits,
+        normals f32 [height, width, 3] in the world frame, the normal of the point that wins the pixel turned towards
+        the camera, zeros where there is none).  Both maps stay resident for depth_score and normal_score;
+        download=False returns (None, None)."""
+        w, h = int(cam.width), int(cam.height)
+        depth = np.empty((max(h, 0), max(w, 0)), np.float32) if download else None
+        normal = np.empty((max(h, 0), max(w, 0), 3), np.float32) if download else None
+        _check(_LIB.dpe_cloud_render_view_normals(self._ctx, C.byref(cam), int(splat), None if depth is None else depth.ctypes.data,
+                                                  None if normal is None else normal.ctypes.data), "dpe_cloud_render_view_normals")
+        return depth, normal
+
+    def normal_score(self, est, gt, cos_taus, want_error: bool = False):
+        """The normal map `est` f32 [h, w, 3] against `gt` (None: the last rendered normal map) at the thresholds
+        `cos_taus`, COSINES of the angles: the counts, the 180-bin histogram and the two pairwise sums as a dict
+        (pipeline.score_normals gives the same bits on the host); with want_error (dict, error map f32 [h, w])."""
+        e = np.ascontiguousarray(est, np.float32)
+        if e.ndim != 3 or e.shape[2] != 3:
+            raise ValueError("expected a map of shape [h, w, 3]")
+        g = None if gt is None else np.ascontiguousarray(gt, np.float32)
+        if g is not None and g.shape != e.shape:
+            raise ValueError("the maps differ in shape")
+        t = np.ascontiguousarray(np.atleast_1d(cos_taus), np.float32)
+        s = _abi.DpeNormalScore()
+        err = np.empty(e.shape[:2], np.float32) if want_error else None
+        _check(_LIB.dpe_normal_score(self._ctx, e.ctypes.data, None if g is None else g.ctypes.data, e.shape[1], e.shape[0],
+                                     t.ctypes.data, len(t), C.byref(s), None if err is None else err.ctypes.data), "dpe_normal_score")
+        d = _abi.normal_score_dict(s, len(t))
         return (d, err) if want_error else d
 
     def cloud_timings(self) -> dict:

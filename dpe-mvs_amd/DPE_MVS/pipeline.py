@@ -120,6 +120,25 @@ class DpeDepthImage(C.Structure):   # include/dpe_host.h
     _fields_ = [("id", C.c_int), ("width", C.c_int), ("height", C.c_int), ("score", DpeDepthScore)]
 
 
+DpeNormalScore = _abi.DpeNormalScore   # include/dpe_mvs.h
+NORMAL_MAX_TAU = _abi.NORMAL_MAX_TAU
+
+
+class DpeNormalStats(C.Structure):   # include/dpe_host.h
+    _fields_ = [("share", C.c_double * NORMAL_MAX_TAU), ("completeness", C.c_double * NORMAL_MAX_TAU),
+                ("mean_cos_dist", C.c_double), ("median_deg", C.c_double), ("mean_deg", C.c_double)]
+
+
+class DpeNormalEvalOptions(C.Structure):   # include/dpe_host.h
+    _fields_ = [("dense_folder", C.c_char_p), ("map_name", C.c_char_p), ("gt_maps_dir", C.c_char_p), ("radius", C.c_float),
+                ("min_nb", C.c_int), ("splat", C.c_int), ("n_tau", C.c_int), ("cos_tau", C.c_float * NORMAL_MAX_TAU),
+                ("write_maps", C.c_int), ("gpu_index", C.c_int)]
+
+
+class DpeNormalImage(C.Structure):   # include/dpe_host.h
+    _fields_ = [("id", C.c_int), ("width", C.c_int), ("height", C.c_int), ("score", DpeNormalScore)]
+
+
 class PipelineError(RuntimeError):
     pass
 
@@ -202,6 +221,20 @@ def lib() -> C.CDLL:
         L.dpe_host_depth_eval_list.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.dpe_host_depth_eval.argtypes = [C.POINTER(DpeDepthEvalOptions), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.POINTER(C.c_size_t), C.POINTER(DpeDepthScore)]
+        L.dpe_host_cloud_normals.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dpe_host_cloud_render_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_abi.DpeCamera), C.c_int,
+                                                    C.c_void_p, C.c_void_p]
+        L.dpe_host_normal_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.POINTER(DpeNormalScore), C.c_void_p]
+        L.dpe_host_normal_edges.argtypes = [C.c_void_p]
+        L.dpe_host_normal_edges.restype = None
+        L.dpe_host_normal_cos.argtypes = [C.c_double]
+        L.dpe_host_normal_cos.restype = C.c_float
+        L.dpe_host_normal_stats.argtypes = [C.POINTER(DpeNormalScore), C.c_int, C.POINTER(DpeNormalStats)]
+        L.dpe_host_normal_stats.restype = None
+        L.dpe_host_read_npy_f32x3.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.dpe_host_normal_eval.argtypes = [C.POINTER(DpeNormalEvalOptions), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(DpeNormalScore)]
         _lib = L
     return _lib
 
@@ -846,6 +879,197 @@ def format_depth_eval(e: dict) -> str:
         return ("%8s %11s %10d %10d %10d %12.6g %12.6g %12.6g" % (name, size, s["n_gt"], s["n_est"], s["n_both"], s["mae"], s["mre"],
                                                                    s["rmse"])
                 + "".join(" %10.6f %10.6f" % v for v in zip(s["accuracy"], s["completeness"])))
+
+    rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
+    rows.append(row("total", "-", e["total"]))
+    return "\n".join(rows) + "\n"
+
+
+# ------------------------------------------------------------------------------ normal-map evaluation (C++, normal_eval.cpp)
+def read_npy_f32x3(path: str) -> np.ndarray:
+    """A 3-D '<f4' .npy v1.0 in C order of shape [h, w, 3] through the host library's reader
+    (dpe_host_read_npy_f32x3): f32 [h, w, 3].  PipelineError with the reader's message for what it refuses."""
+    w, h = C.c_int(), C.c_int()
+    if lib().dpe_host_read_npy_f32x3(os.fsencode(path), None, 0, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    out = np.empty((h.value, w.value, 3), np.float32)
+    if lib().dpe_host_read_npy_f32x3(os.fsencode(path), out.ctypes.data, out.size, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def normal_edges() -> np.ndarray:
+    """The 180 bin edges of the score's histogram, E[b] = (float)cos(b degrees): the table both paths use."""
+    e = np.empty(_abi.NORMAL_BINS, np.float32)
+    lib().dpe_host_normal_edges(e.ctypes.data)
+    return e
+
+
+def normal_cos(deg: float) -> float:
+    """A threshold in degrees as the cosine the score takes (dpe_host_normal_cos, the one place where this happens)."""
+    return float(lib().dpe_host_normal_cos(float(deg)))
+
+
+def estimate_normals(points, radius: float, min_neighbours: int = 3, gpu_index: int = -1, want_sums: bool = False) -> tuple:
+    """A normal per point of the cloud f32 [n, 3] by PCA over the points within `radius` of it (include/dpe_mvs.h,
+    dpe_cloud_normals, states the contract): (normals f32 [n, 3], counts i32 [n]), with want_sums also the ten integer
+    sums i64 [n, 10].  (0, 0, 0) = no normal: fewer than min_neighbours neighbours (the point itself counts),
+    collinear neighbours, or a non-finite point.  The sign makes the component of largest magnitude positive; a view
+    turns it towards its camera (render_cloud_normals).  gpu_index < 0: on host threads (dpe_host_cloud_normals), else
+    on that device: the same bits."""
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            return ctx.cloud_normals(points, radius, min_neighbours, want_sums)
+        except native.DpeError as e:
+            raise PipelineError(str(e)) from None
+        finally:
+            ctx.close()
+    p = _as_cloud(points)
+    n = len(p)
+    normals, counts = np.empty((n, 3), np.float32), np.empty(n, np.int32)
+    sums = np.empty((n, _abi.NORMAL_SUMS), np.int64) if want_sums else None
+    if lib().dpe_host_cloud_normals(p.ctypes.data, n, float(radius), int(min_neighbours), normals.ctypes.data, counts.ctypes.data,
+                                    None if sums is None else sums.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return (normals, counts, sums) if want_sums else (normals, counts)
+
+
+def render_cloud_normals(points, normals, cam: _abi.DpeCamera, splat: int = 0, gpu_index: int = -1) -> tuple:
+    """The scan `points` and its per-point `normals` (both f32 [n, 3]) rendered into `cam`: (depth f32 [height, width],
+    render_cloud's bits, normal map f32 [height, width, 3] in the world frame).  A pixel takes the normal of the point
+    that wins its z-buffer (the lexicographic minimum of depth bits and index), turned towards the camera; zeros where
+    no point falls or the winner has no normal.  gpu_index < 0: the host loop, else on that device: the same bits."""
+    p, nm = _as_cloud(points), _as_cloud(normals)
+    if len(p) != len(nm):
+        raise PipelineError("cloud_render_normals: one normal per point expected")
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            ctx.cloud_render_stage(p, nm)
+            return ctx.cloud_render_view_normals(cam, splat)
+        except native.DpeError as e:
+            raise PipelineError(str(e)) from None
+        finally:
+            ctx.close()
+    h, w = max(int(cam.height), 0), max(int(cam.width), 0)
+    depth, normal = np.empty((h, w), np.float32), np.empty((h, w, 3), np.float32)
+    if lib().dpe_host_cloud_render_normals(p.ctypes.data, nm.ctypes.data, len(p), C.byref(cam), int(splat), depth.ctypes.data,
+                                           normal.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    return depth, normal
+
+
+def normal_stats(score: dict) -> dict:
+    """What is derived from a score's counts, histogram and sums, in double (dpe_host_normal_stats, the one function
+    both paths and both programs go through): share and completeness per threshold, mean_cos_dist, and median_deg
+    and mean_deg from the histogram to its 1 degree resolution; 0 for an empty denominator."""
+    s, d = DpeNormalScore(), DpeNormalStats()
+    k = len(score["within"])
+    for name in ("n_px", "n_gt", "n_est", "n_both", "sum_dist", "sum_dist_sq"):
+        setattr(s, name, score[name])
+    for i, v in enumerate(score["within"]):
+        s.within[i] = v
+    for i, v in enumerate(score["hist"]):
+        s.hist[i] = v
+    lib().dpe_host_normal_stats(C.byref(s), k, C.byref(d))
+    return dict(share=list(d.share[:k]), completeness=list(d.completeness[:k]), mean_cos_dist=d.mean_cos_dist,
+                median_deg=d.median_deg, mean_deg=d.mean_deg)
+
+
+def _normal_dict(s: DpeNormalScore, k: int) -> dict:
+    d = _abi.normal_score_dict(s, k)
+    d.update(normal_stats(d))
+    return d
+
+
+def score_normals(est, gt, taus_deg=None, cos_taus=None, gpu_index: int = -1, want_error: bool = False):
+    """The normal map `est` against the ground-truth map `gt` (f32 [h, w, 3]) at 1 to 16 thresholds, angles in degrees
+    (taus_deg, turned into cosines by normal_cos) or their cosines directly (cos_taus).  A dict of the counts n_px,
+    n_gt, n_est, n_both, within[k], the histogram hist[180] of the angle in degrees, the pairwise sums sum_dist and
+    sum_dist_sq of 1 - cos (include/dpe_mvs.h, dpe_normal_score) and normal_stats of them.  A pixel counts where both
+    maps hold a finite non-zero vector; the vectors need not be unit.  gpu_index < 0: the host loop, else on that
+    device: equal dicts.  want_error: (dict, error map f32 [h, w]: the cosine where both have a normal, -2 where only
+    gt has, else -3)."""
+    if (taus_deg is None) == (cos_taus is None):
+        raise PipelineError("normal_score: thresholds in degrees or as cosines expected, not both")
+    t = (np.ascontiguousarray(np.atleast_1d(cos_taus), np.float32) if cos_taus is not None
+         else np.array([normal_cos(v) for v in np.atleast_1d(taus_deg)], np.float32))
+    e, g = np.ascontiguousarray(est, np.float32), np.ascontiguousarray(gt, np.float32)
+    if e.ndim != 3 or e.shape[2] != 3 or g.shape != e.shape:
+        raise PipelineError("normal_score: size mismatch: two maps of one shape [h, w, 3] expected")
+    if gpu_index >= 0:
+        from . import native
+        ctx = native.PatchMatchContext(int(gpu_index))
+        try:
+            r = ctx.normal_score(e, g, t, want_error)
+        except native.DpeError as x:
+            raise PipelineError(str(x)) from None
+        finally:
+            ctx.close()
+        d, err = r if want_error else (r, None)
+        d.update(normal_stats(d))
+        return (d, err) if want_error else d
+    s = DpeNormalScore()
+    err = np.empty(e.shape[:2], np.float32) if want_error else None
+    if lib().dpe_host_normal_score(e.ctypes.data, g.ctypes.data, e.shape[1], e.shape[0], t.ctypes.data, len(t), C.byref(s),
+                                   None if err is None else err.ctypes.data) != 0:
+        raise PipelineError(_last_error())
+    d = _normal_dict(s, len(t))
+    return (d, err) if want_error else d
+
+
+def evaluate_normal_maps(dense_folder: str, gt, radius, taus_deg, min_neighbours: int = 3, splat: int = 0,
+                         gt_normals: str | None = None, write_maps: bool = False, gpu_index: int = -1) -> dict:
+    """The normal maps DPE/%08d/normal.npy of a dense folder, in ascending image id, against the scan `gt` (f32
+    [n, 3]): its normals are estimated once (estimate_normals: radius, min_neighbours) and rendered into each
+    cams/%08d_cam.txt at the map's size (render_cloud_normals, half-width `splat`); or, with gt_normals = a folder,
+    against its %08d.npy [h, w, 3] (dpe_host_normal_eval).  write_maps also writes normal_gt.npy and normal_error.npy
+    beside each map.  gpu_index < 0: on the host, else everything in one context of that device: equal dicts.
+    Keys: map, radius, min_neighbours, splat, tau_deg, n_gt_points, images (a list of score_normals' dicts with id,
+    width, height) and total (the counts added, the sums added in ascending id, and normal_stats of them)."""
+    deg = [float(v) for v in np.atleast_1d(taus_deg)]
+    if len(deg) < 1 or len(deg) > NORMAL_MAX_TAU:
+        raise PipelineError("normal_score: 1 to 16 thresholds expected")
+    if gt is None and gt_normals is None:
+        raise PipelineError("normal_eval: a scan or a folder of ground-truth normal maps expected")
+    p = _as_cloud(np.empty((0, 3), np.float32) if gt is None else gt)
+    o = DpeNormalEvalOptions()
+    o.dense_folder, o.map_name = os.fsencode(dense_folder), None
+    o.gt_maps_dir = None if gt_normals is None else os.fsencode(gt_normals)
+    o.radius = 0.0 if radius is None else float(radius)
+    o.min_nb, o.splat, o.n_tau = int(min_neighbours), int(splat), len(deg)
+    for k, v in enumerate(deg):
+        o.cos_tau[k] = normal_cos(v)
+    o.write_maps, o.gpu_index = int(bool(write_maps)), int(gpu_index)
+    n = C.c_size_t()
+    if lib().dpe_host_depth_eval_list(o.dense_folder, b"normal.npy", None, 0, C.byref(n)) != 0:
+        n = C.c_size_t(0)   # dpe_host_normal_eval lists again and reports what it refuses in its own words
+    rows, total = (DpeNormalImage * max(n.value, 1))(), DpeNormalScore()
+    if lib().dpe_host_normal_eval(C.byref(o), p.ctypes.data, len(p), rows, n.value, C.byref(n), C.byref(total)) != 0:
+        raise PipelineError(_last_error())
+    k = len(deg)
+    images = [dict(_normal_dict(r.score, k), id=int(r.id), width=int(r.width), height=int(r.height)) for r in rows[:n.value]]
+    return dict(map="normal.npy", radius=(None if gt_normals is not None else float(np.float32(o.radius))),
+                min_neighbours=int(min_neighbours), splat=int(splat), tau_deg=[float(np.float32(v)) for v in deg],
+                n_gt_points=(None if gt_normals is not None else len(p)), images=images, total=_normal_dict(total, k))
+
+
+def format_normal_eval(e: dict) -> str:
+    """The table bin/dpe_normal_eval prints, from evaluate_normal_maps' dict."""
+    gt = "maps" if e["n_gt_points"] is None else "cloud of %d points, radius %.9g, min neighbours %d, splat %d" % (
+        e["n_gt_points"], e["radius"], e["min_neighbours"], e["splat"])
+    k = len(e["tau_deg"])
+    rows = ["map %s, ground truth %s, thresholds in degrees %s" % (e["map"], gt, " ".join("%.9g" % v for v in e["tau_deg"])),
+            "%8s %11s %10s %10s %10s %12s %10s %10s" % ("image", "size", "n_gt", "n_est", "n_both", "cos_dist", "median", "mean")
+            + "".join(" %10s %10s" % ("within[%d]" % i, "comp[%d]" % i) for i in range(k))]
+
+    def row(name, size, s):
+        return ("%8s %11s %10d %10d %10d %12.6g %10.1f %10.4f" % (name, size, s["n_gt"], s["n_est"], s["n_both"], s["mean_cos_dist"],
+                                                                  s["median_deg"], s["mean_deg"])
+                + "".join(" %10.6f %10.6f" % v for v in zip(s["share"], s["completeness"])))
 
     rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
     rows.append(row("total", "-", e["total"]))

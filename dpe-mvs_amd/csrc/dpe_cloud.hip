@@ -1,8 +1,9 @@
 // dpe_cloud.hip -- the cloud evaluation's distances (dpe_cloud_nn, dpe_cloud_nn_pair), the voxel
 // down-sampling (dpe_cloud_voxel) and the registration's device half (dpe_cloud_nn_index, dpe_cloud_icp_stage,
-// dpe_cloud_icp_step) and the depth-map evaluation (dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score)
-// of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h, pass_register.h, pass_render.h and tree_sum.h
-// over the context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
+// dpe_cloud_icp_step), the depth-map evaluation (dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score) and
+// the normal-map evaluation (dpe_cloud_normals, dpe_cloud_render_stage_normals, dpe_cloud_render_view_normals,
+// dpe_normal_score) of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h, pass_register.h, pass_render.h,
+// pass_normals.h and tree_sum.h over the context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
 // contract is dpe_mvs.hip's (dpe_entry.h): these calls wait until the context is quiet, use its stream and
 // return with it synchronised.
 //
@@ -19,12 +20,13 @@
 #include "pass_voxel.h"
 #include "pass_register.h"
 #include "pass_render.h"
+#include "pass_normals.h"
 #include "dpe_entry.h"
 #include "dpe_context.h"
 
 using namespace dpe;
 
-static_assert(kCloudBlock == kTreeBlock && kRenderBlock == kTreeBlock && kVoxelBlock == kTreeBlock,
+static_assert(kCloudBlock == kTreeBlock && kRenderBlock == kTreeBlock && kVoxelBlock == kTreeBlock && kNormalBlock == kTreeBlock,
               "every kernel of the section runs in blocks of the tree's 256 leaves");
 
 static std::atomic<long long> g_cloud_launches{0};
@@ -370,17 +372,22 @@ int icp_step(DpeContext* c, const double* T, DpeIcpSums* out) {
   return timer_finish(c);
 }
 
-// dpe_cloud_render_stage: the scan resident in pts[0].  Timings: [0] stage
-int render_stage(DpeContext* c, const float* xyz, size_t n) {
+// dpe_cloud_render_stage: the scan resident in pts[0], with its normals when they are given.  Timings: [0] stage
+int render_stage(DpeContext* c, const float* xyz, const float* normals, size_t n) {
   CloudScratch& v = c->cloud;
   TRY(cloud_begin(c, false));
   if (n > 0) {
     HIPC(v.pts[0].ensure(3 * n));
     HIPC(hipMemcpyAsync(v.pts[0].p, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (normals) {
+      HIPC(v.normals.staged.ensure(3 * n));
+      HIPC(hipMemcpyAsync(v.normals.staged.p, normals, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    }
   }
   TRY(timer_mark(c, 0));
   HIPC(hipStreamSynchronize(c->stream));
   v.render.n = n;
+  v.normals.has_staged = normals != nullptr;
   v.resident = CloudResident::RenderScan;
   return timer_finish(c);
 }
@@ -391,6 +398,7 @@ int render_view(DpeContext* c, const DpeCamera& cam, int splat, float* depth_out
   TRY(cloud_begin(c, true));
   const size_t npx = (size_t)cam.width * (size_t)cam.height, n = r.n;
   r.map_w = r.map_h = 0;   // the old map goes with the first launch
+  c->cloud.normals.map_w = c->cloud.normals.map_h = 0;   // and a normal map would belong to another depth map
   HIPC(r.map.ensure(npx));
   LAUNCH(k_render_clear, cloud_blocks(npx), c, r.map.p, npx);
   if (n > 0) LAUNCH(k_render_splat, cloud_blocks(n), c, c->cloud.pts[0].p, (int)n, cam, splat, r.map.p);
@@ -446,11 +454,185 @@ int depth_score(DpeContext* c, const float* est, const float* gt, int w, int h, 
   return timer_finish(c);
 }
 
+// dpe_cloud_normals.  Timings: [0] stage, [1] build, [2] normals, [3] download
+int normals_run(DpeContext* c, const float* xyz, size_t n, float radius, int min_nb, float* normal_out, int32_t* count_out,
+                long long* sums_out) {
+  CloudScratch& v = c->cloud;
+  NormalScratch& s = v.normals;
+  TRY(cloud_begin(c, false));
+  TRY(cloud_stage(c, 0, xyz, n));
+  if (n == 0) { HIPC(hipStreamSynchronize(c->stream)); return DPE_OK; }
+  TRY(timer_mark(c, 0));
+  CloudBounds bd[2];
+  TRY(cloud_bounds_fetch(c, bd));
+  const size_t finite = bd[0].finite;
+  if (finite == 0) {   // no neighbour anywhere: no launch
+    memset(normal_out, 0, 3 * n * sizeof(float));
+    memset(count_out, 0, n * sizeof(int32_t));
+    if (sums_out) memset(sums_out, 0, (size_t)kNormalSums * n * sizeof(long long));
+    return DPE_OK;
+  }
+  CloudGrid g;
+  if (!cloud_grid_make(bd[0].lo, bd[0].hi, finite, radius, &g)) {
+    g_err = "dpe_cloud_normals: radius too small for the cloud's extent";
+    return DPE_ERR_ARG;
+  }
+  HIPC(v.st.ensure(finite));
+  HIPC(s.normal.ensure(3 * n));
+  HIPC(s.count.ensure(n));
+  if (sums_out) HIPC(s.sums.ensure((size_t)kNormalSums * n));
+  // a non-finite point has no thread: its outputs are the zeros written here
+  HIPC(hipMemsetAsync(s.normal.p, 0, 3 * n * sizeof(float), c->stream));
+  HIPC(hipMemsetAsync(s.count.p, 0, n * sizeof(int), c->stream));
+  if (sums_out) HIPC(hipMemsetAsync(s.sums.p, 0, (size_t)kNormalSums * n * sizeof(long long), c->stream));
+  TRY(cloud_build(c, v.pts[0].p, n, g, 0, v.tcnt, v.st.p));
+  TRY(timer_mark(c, 1));
+  LAUNCH(k_cloud_normal, cloud_blocks(finite), c, v.st.p, (int)finite, v.tcnt.p, g, normal_scale(radius), min_nb, s.normal.p,
+         s.count.p, sums_out ? s.sums.p : nullptr);
+  TRY(timer_mark(c, 2));
+  HIPC(hipMemcpyAsync(normal_out, s.normal.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(count_out, s.count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (sums_out)
+    HIPC(hipMemcpyAsync(sums_out, s.sums.p, (size_t)kNormalSums * n * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  TRY(timer_mark(c, 3));
+  HIPC(hipStreamSynchronize(c->stream));
+  return timer_finish(c);
+}
+
+// dpe_cloud_render_view_normals of the staged scan and its normals.  Timings: [1] render, [3] download
+int render_view_normals(DpeContext* c, const DpeCamera& cam, int splat, float* depth_out, float* normal_out) {
+  RenderStage& r = c->cloud.render;
+  NormalScratch& s = c->cloud.normals;
+  TRY(cloud_begin(c, true));
+  const size_t npx = (size_t)cam.width * (size_t)cam.height, n = r.n;
+  r.map_w = r.map_h = 0;   // the old maps go with the first launch
+  s.map_w = s.map_h = 0;
+  HIPC(r.map.ensure(npx));
+  HIPC(s.zb.ensure(npx));
+  HIPC(s.winner.ensure(npx));
+  HIPC(s.map.ensure(3 * npx));
+  LAUNCH(k_render_clear64, cloud_blocks(npx), c, s.zb.p, npx);
+  if (n > 0) LAUNCH(k_render_splat_idx, cloud_blocks(n), c, c->cloud.pts[0].p, (int)n, cam, splat, s.zb.p);
+  LAUNCH(k_render_finish_idx, cloud_blocks(npx), c, s.zb.p, npx, r.map.p, s.winner.p);
+  LAUNCH(k_render_normals, cloud_blocks(npx), c, c->cloud.pts[0].p, s.staged.p, s.winner.p, npx, cam, s.map.p);
+  TRY(timer_mark(c, 1));
+  if (depth_out) HIPC(hipMemcpyAsync(depth_out, r.map.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (normal_out) HIPC(hipMemcpyAsync(normal_out, s.map.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  TRY(timer_mark(c, 3));
+  HIPC(hipStreamSynchronize(c->stream));
+  r.map_w = s.map_w = cam.width;
+  r.map_h = s.map_h = cam.height;
+  return timer_finish(c);
+}
+
+// dpe_normal_score; gt == nullptr: against the resident normal map.  Timings: [0] upload, [2] score, [3] download
+int normal_score(DpeContext* c, const float* est, const float* gt, int w, int h, const NormalTaus& T, DpeNormalScore* out,
+                 float* err) {
+  NormalScratch& v = c->cloud.normals;
+  TRY(cloud_begin(c, true));
+  const size_t npx = (size_t)w * (size_t)h, blocks = cloud_blocks(npx);
+  HIPC(v.est.ensure(3 * npx));
+  if (gt) HIPC(v.gt.ensure(3 * npx));
+  if (err) HIPC(v.err.ensure(npx));
+  HIPC(v.part[0].ensure(blocks * kNormalTerms));
+  HIPC(v.part[1].ensure((size_t)cloud_blocks(blocks) * kNormalTerms));
+  HIPC(v.cnt.ensure(kNormalCounters));
+  if (v.edges.n == 0) {   // the table of the one host function, uploaded once per context
+    float E[kNormalBins];
+    normal_edges(E);
+    HIPC(v.edges.ensure(kNormalBins));
+    HIPC(hipMemcpyAsync(v.edges.p, E, sizeof E, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));   // E leaves the stack
+  }
+  HIPC(hipMemcpyAsync(v.est.p, est, 3 * npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (gt) HIPC(hipMemcpyAsync(v.gt.p, gt, 3 * npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemsetAsync(v.cnt.p, 0, kNormalCounters * sizeof(unsigned long long), c->stream));
+  TRY(timer_mark(c, 0));
+  LAUNCH(k_normal_score, blocks, c, v.est.p, gt ? v.gt.p : v.map.p, npx, T, v.edges.p, v.part[0].p, v.cnt.p,
+         err ? v.err.p : nullptr);
+  int at;
+  TRY(tree_reduce<kNormalTerms>(c, v.part, blocks, &at));
+  TRY(timer_mark(c, 2));
+  double sums[kNormalTerms];
+  unsigned long long counts[kNormalCounters];
+  HIPC(hipMemcpyAsync(sums, v.part[at].p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(counts, v.cnt.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+  if (err) HIPC(hipMemcpyAsync(err, v.err.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  TRY(timer_mark(c, 3));
+  HIPC(hipStreamSynchronize(c->stream));
+  DpeNormalScore s;
+  memset(&s, 0, sizeof s);
+  s.n_px = (long long)npx;
+  s.n_gt = (long long)counts[0];
+  s.n_est = (long long)counts[1];
+  s.n_both = (long long)counts[2];
+  for (int k = 0; k < T.n; ++k) s.within[k] = (long long)counts[3 + k];
+  for (int b = 0; b < kNormalBins; ++b) s.hist[b] = (long long)counts[3 + DPE_NORMAL_MAX_TAU + b];
+  s.sum_dist = sums[0];
+  s.sum_dist_sq = sums[1];
+  *out = s;
+  return timer_finish(c);
+}
+
 }  // namespace
+
+extern "C" int dpe_cloud_normals(DpeContext* c, const float* xyz, size_t n, float radius, int min_nb, float* normal_out,
+                                 int32_t* count_out, long long* sums_out) {
+  const bool ok = cloud_args_ok(xyz, n, nullptr, 0, radius, normal_out, nullptr, false) && (count_out || n == 0) &&
+                  min_nb >= kNormalMinNb;
+  TRY(enter(c, ok, "dpe_cloud_normals: bad argument"));
+  return normals_run(c, xyz, n, radius, min_nb, normal_out, count_out, sums_out);
+}
+
+extern "C" int dpe_cloud_render_stage_normals(DpeContext* c, const float* xyz, const float* normals, size_t n) {
+  float none = 0.f;   // n == 0: no entry, and the staging still counts as one with normals
+  TRY(enter(c, n <= (size_t)INT_MAX && ((xyz && normals) || n == 0), "dpe_cloud_render_stage_normals: bad argument"));
+  return render_stage(c, xyz, normals ? normals : &none, n);
+}
+
+extern "C" int dpe_cloud_render_view_normals(DpeContext* c, const DpeCamera* cam, int splat, float* depth_out,
+                                             float* normal_out) {
+  const bool ok = cam && cam->width >= 1 && cam->height >= 1 && splat >= 0 && splat <= DPE_DEPTH_MAX_SPLAT;
+  TRY(enter(c, ok, "dpe_cloud_render_view_normals: bad argument"));
+  if (c->cloud.resident != CloudResident::RenderScan) {
+    g_err = "dpe_cloud_render_view_normals: no staged cloud (dpe_cloud_render_stage_normals comes first)";
+    return DPE_ERR_STATE;
+  }
+  if (!c->cloud.normals.has_staged) {
+    g_err = "dpe_cloud_render_view_normals: no staged normals (dpe_cloud_render_stage_normals comes first)";
+    return DPE_ERR_STATE;
+  }
+  return render_view_normals(c, *cam, splat, depth_out, normal_out);
+}
+
+extern "C" int dpe_normal_score(DpeContext* c, const float* est, const float* gt, int w, int h, const float* cos_tau, int n_tau,
+                                DpeNormalScore* out, float* err) {
+  bool ok = est && w >= 1 && h >= 1 && cos_tau && n_tau >= 1 && n_tau <= DPE_NORMAL_MAX_TAU && out;
+  NormalTaus T;
+  memset(&T, 0, sizeof T);
+  for (int k = 0; ok && k < n_tau; ++k) {
+    ok = std::isfinite(cos_tau[k]) && cos_tau[k] >= -1.0f && cos_tau[k] <= 1.0f;
+    T.c[k] = cos_tau[k];
+  }
+  T.n = n_tau;
+  TRY(enter(c, ok, "dpe_normal_score: bad argument"));
+  if (!gt) {
+    const NormalScratch& s = c->cloud.normals;
+    if (s.map_w == 0) {
+      g_err = "dpe_normal_score: no rendered map (dpe_cloud_render_view_normals comes first, or pass gt)";
+      return DPE_ERR_STATE;
+    }
+    if (s.map_w != w || s.map_h != h) {
+      g_err = "dpe_normal_score: the size differs from the rendered map's";
+      return DPE_ERR_ARG;
+    }
+  }
+  return normal_score(c, est, gt, w, h, T, out, err);
+}
 
 extern "C" int dpe_cloud_render_stage(DpeContext* c, const float* xyz, size_t n) {
   TRY(enter(c, n <= (size_t)INT_MAX && (xyz || n == 0), "dpe_cloud_render_stage: bad argument"));
-  return render_stage(c, xyz, n);
+  return render_stage(c, xyz, nullptr, n);
 }
 
 extern "C" int dpe_cloud_render_view(DpeContext* c, const DpeCamera* cam, int splat, float* depth_out) {

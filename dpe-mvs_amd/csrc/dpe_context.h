@@ -265,8 +265,26 @@ struct ScoreScratch {
   DevArr<double> part[2];            // the three sums' partials, level by level
   DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16]
 };
-// what stays in pts[] for later calls.  The calls that restage pts[] (nn, pair, index, voxel, icp_stage, render_stage)
-// end it; icp_step, render_view and depth_score leave it alone
+// the normal-map evaluation (pass_normals.h): the cloud of dpe_cloud_normals is pts[0] and its grid st / tcnt; a staged
+// scan's normals sit beside pts[0]; a view with normals renders into `zb` first and leaves the depth map in render.map
+struct NormalScratch {
+  DevArr<float> normal;              // dpe_cloud_normals: the normals, f32 [n][3], by original index
+  DevArr<int> count;                 //   the neighbour counts
+  DevArr<long long> sums;            //   the ten sums per point, when asked for
+  DevArr<float> staged;              // the staged scan's normals, f32 [n][3]
+  bool has_staged = false;           // the staging in pts[0] came with normals
+  DevArr<unsigned long long> zb;     // the z-buffer with winners: bits(z) << 32 | index
+  DevArr<int> winner;                // per pixel the winning point, -1 where empty
+  DevArr<float> map;                 // the rendered normal map, f32 [h][w][3]
+  int map_w = 0, map_h = 0;          // 0: no normal map rendered yet
+  DevArr<float> est, gt, err;        // dpe_normal_score: the caller's maps and the error map
+  DevArr<float> edges;               // the 180 bin edges, uploaded once
+  DevArr<double> part[2];            // the two sums' partials, level by level
+  DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16], hist[180]
+};
+// what stays in pts[] for later calls.  The calls that restage pts[] (nn, pair, index, voxel, normals, icp_stage,
+// render_stage, render_stage_normals) end it; icp_step, render_view, render_view_normals, depth_score and normal_score
+// leave it alone
 enum class CloudResident { None, IcpPair, RenderScan };
 
 // `timer` (its events) is declared first and so outlives the buffers.
@@ -285,6 +303,7 @@ struct CloudScratch {
   IcpStage icp;
   RenderStage render;
   ScoreScratch score;
+  NormalScratch normals;
 };
 
 }  // namespace dpe

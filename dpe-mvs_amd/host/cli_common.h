@@ -1,4 +1,4 @@
-// cli_common.h — what the command lines bin/dpe_eval, bin/dpe_voxel, bin/dpe_register and bin/dpe_depth_eval share:
+// cli_common.h — what the command lines bin/dpe_eval, bin/dpe_voxel, bin/dpe_register, bin/dpe_depth_eval and bin/dpe_normal_eval share:
 // the device option, a PLY into vectors, a number that must be the whole argument, and the JSON array writer.
 #pragma once
 #include <cstdint>

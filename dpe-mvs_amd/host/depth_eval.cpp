@@ -135,11 +135,13 @@ namespace {
 
 const char* map_name_of(const char* name) { return name && *name ? name : "depth.npy"; }
 
+}  // namespace
+
 // the image ids of the folder: DPE/<8 digits> that hold the map, ascending
-bool depth_eval_list(const std::string& dense, const std::string& map, std::vector<int>& ids, std::string& err) {
+bool eval_list(const char* who, const std::string& dense, const std::string& map, std::vector<int>& ids, std::string& err) {
   const fs::path root = fs::path(dense) / "DPE";
   std::error_code ec;
-  if (!fs::is_directory(root, ec)) { err = "depth_eval: no DPE folder in " + dense; return false; }
+  if (!fs::is_directory(root, ec)) { err = std::string(who) + ": no DPE folder in " + dense; return false; }
   for (fs::directory_iterator it(root, ec), end; !ec && it != end; it.increment(ec)) {
     const std::string name = it->path().filename().string();
     if (name.size() != 8 || !std::all_of(name.begin(), name.end(), [](char c) { return c >= '0' && c <= '9'; })) continue;
@@ -147,7 +149,7 @@ bool depth_eval_list(const std::string& dense, const std::string& map, std::vect
     ids.push_back(std::atoi(name.c_str()));
   }
   std::sort(ids.begin(), ids.end());
-  if (ids.empty()) { err = "depth_eval: no such map: no DPE/<id>/" + map + " in " + dense; return false; }
+  if (ids.empty()) { err = std::string(who) + ": no such map: no DPE/<id>/" + map + " in " + dense; return false; }
   return true;
 }
 
@@ -163,6 +165,8 @@ bool map_camera(const std::string& dense, int id, int w, int h, DpeCamera& cam, 
   return true;
 }
 
+namespace {
+
 bool depth_eval(const DpeDepthEvalOptions& o, const float* gt_xyz, size_t n_gt, DpeDepthImage* rows, size_t cap, size_t* n_rows,
                 DpeDepthScore* total, std::string& err) {
   if (!o.dense_folder || !n_rows || !total || (!rows && cap)) { err = "depth_eval: bad argument"; return false; }
@@ -173,7 +177,7 @@ bool depth_eval(const DpeDepthEvalOptions& o, const float* gt_xyz, size_t n_gt, 
   if (!from_maps && !render_args_ok(gt_xyz, n_gt, &none, o.splat, err)) return false;
   const std::string dense = o.dense_folder, map = map_name_of(o.map_name);
   std::vector<int> ids;
-  if (!depth_eval_list(dense, map, ids, err)) return false;
+  if (!eval_list("depth_eval", dense, map, ids, err)) return false;
   *n_rows = ids.size();
   if (cap < ids.size()) { err = "depth_eval: room for fewer rows than images"; return false; }
   OwnedContext own(o.gpu_index, "depth_eval", err);
@@ -272,7 +276,7 @@ int dpe_host_read_npy_f32(const char* path, float* data, size_t cap, int* w, int
 int dpe_host_depth_eval_list(const char* dense_folder, const char* map_name, int* ids, size_t cap, size_t* n) {
   std::string err = "depth_eval: bad argument";
   std::vector<int> v;
-  if (dense_folder && n && dpe_host::depth_eval_list(dense_folder, dpe_host::map_name_of(map_name), v, err)) {
+  if (dense_folder && n && dpe_host::eval_list("depth_eval", dense_folder, dpe_host::map_name_of(map_name), v, err)) {
     *n = v.size();
     if (ids && cap >= v.size()) std::copy(v.begin(), v.end(), ids);
     return 0;

@@ -226,5 +226,21 @@ bool depth_score(const float* est, const float* gt, int w, int h, const float* t
                  float* errmap, std::string& err);
 void depth_stats(const DpeDepthScore& s, int n_tau, DpeDepthStats* out);
 void depth_add(DpeDepthScore* total, const DpeDepthScore& s);
+// what the folder tools share: the image ids DPE/<8 digits> of `dense` that hold `map`, ascending (`who` leads the
+// message), and the camera of image `id` at the size w x h of its map (map_view's arithmetic)
+bool eval_list(const char* who, const std::string& dense, const std::string& map, std::vector<int>& ids, std::string& err);
+bool map_camera(const std::string& dense, int id, int w, int h, DpeCamera& cam, std::string& err);
+// a 3-D '<f4' .npy v1.0 in C order, [h][w][3]; refusals as read_npy_f32's
+bool read_npy_f32x3(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err);
+// normal_eval.cpp: the normal-map evaluation (dpe_cloud_normals, dpe_cloud_render_view_normals and dpe_normal_score of
+// dpe_mvs.h) as loops over the same arithmetic (csrc/normal_eval.h), what is derived from a score, and total += s
+bool cloud_normals(const float* xyz, size_t n, float radius, int min_nb, float* normal, int32_t* count, long long* sums,
+                   std::string& err);
+bool cloud_render_normals(const float* xyz, const float* normals, size_t n, const DpeCamera& cam, int splat, float* depth,
+                          float* normal, std::string& err);
+bool normal_score(const float* est, const float* gt, int w, int h, const float* cos_tau, int n_tau, DpeNormalScore* out,
+                  float* errmap, std::string& err);
+void normal_stats(const DpeNormalScore& s, int n_tau, DpeNormalStats* out);
+void normal_add(DpeNormalScore* total, const DpeNormalScore& s);
 
 }  // namespace dpe_host

@@ -104,7 +104,8 @@ static bool npy_value(const std::string& dict, const char* key, std::string& val
   return true;
 }
 
-bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err) {
+// a '<f4' .npy v1.0 in C order of exactly `rank` dimensions (2 or 3), each 1 .. 2^31 - 1, into data and dim[]
+static bool read_npy_f32_rank(const std::string& path, int rank, std::vector<float>& data, long long* dim, std::string& err) {
   std::ifstream in(path, std::ios::binary);
   if (!in) { err = "cannot read npy: " + path; return false; }
   unsigned char pre[10];
@@ -121,13 +122,13 @@ bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int
   }
   if (descr != "'<f4'") { err = "unsupported .npy dtype " + descr + " ('<f4' expected): " + path; return false; }
   if (order != "False") { err = "Fortran-ordered .npy is not supported: " + path; return false; }
-  // "(h, w)": exactly two decimal numbers, each 1 .. 2^31 - 1
-  long long dim[2] = {0, 0};
+  // "(h, w)" or "(h, w, c)": exactly `rank` decimal numbers, each 1 .. 2^31 - 1
   int nd = 0;
+  for (int k = 0; k < rank; ++k) dim[k] = 0;
   bool ok = shape.size() >= 2 && shape.front() == '(' && shape.back() == ')';
   for (size_t i = 1; ok && i + 1 < shape.size();) {
     if (shape[i] == ' ' || shape[i] == ',') { ++i; continue; }
-    if (shape[i] < '0' || shape[i] > '9' || nd == 2) { ok = false; break; }
+    if (shape[i] < '0' || shape[i] > '9' || nd == rank) { ok = false; break; }
     long long v = 0;
     for (; i + 1 < shape.size() && shape[i] >= '0' && shape[i] <= '9'; ++i) {
       v = v * 10 + (shape[i] - '0');
@@ -135,8 +136,16 @@ bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int
     }
     dim[nd++] = v;
   }
-  if (!ok || nd != 2 || dim[0] < 1 || dim[1] < 1) { err = "a 2-D .npy of at least 1 x 1 expected, shape " + shape + ": " + path; return false; }
-  const unsigned long long want = (unsigned long long)dim[0] * (unsigned long long)dim[1] * 4ull;
+  for (int k = 0; k < rank; ++k) ok = ok && nd == rank && dim[k] >= 1;
+  if (ok && rank == 3) ok = dim[2] == 3;
+  if (!ok) {
+    err = (rank == 2 ? "a 2-D .npy of at least 1 x 1 expected, shape " : "a 3-D .npy [h][w][3] of at least 1 x 1 x 3 expected, shape ") +
+          shape + ": " + path;
+    return false;
+  }
+  const unsigned long long cells = (unsigned long long)dim[0] * (unsigned long long)dim[1];   // below 2^62
+  if (rank == 3 && cells > (1ull << 60)) { err = "truncated .npy data: " + path; return false; }   // 12 bytes each: no file is that long
+  const unsigned long long want = cells * (rank == 3 ? 3ull : 1ull) * 4ull;
   const std::streampos body = in.tellg();
   in.seekg(0, std::ios::end);
   const unsigned long long have = (unsigned long long)(in.tellg() - body);
@@ -146,6 +155,20 @@ bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int
   in.seekg(body);
   data.resize((size_t)(want / 4));
   if (!in.read(reinterpret_cast<char*>(data.data()), (std::streamsize)want)) { err = "truncated .npy data: " + path; return false; }
+  return true;
+}
+
+bool read_npy_f32(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err) {
+  long long dim[3];
+  if (!read_npy_f32_rank(path, 2, data, dim, err)) return false;
+  h = (int)dim[0];
+  w = (int)dim[1];
+  return true;
+}
+
+bool read_npy_f32x3(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err) {
+  long long dim[3];
+  if (!read_npy_f32_rank(path, 3, data, dim, err)) return false;
   h = (int)dim[0];
   w = (int)dim[1];
   return true;

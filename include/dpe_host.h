@@ -456,6 +456,67 @@ int dpe_host_depth_eval_list(const char* dense_folder, const char* map_name, int
 int dpe_host_depth_eval(const DpeDepthEvalOptions* opt, const float* gt_xyz, size_t n_gt, DpeDepthImage* rows, size_t cap,
                         size_t* n_rows, DpeDepthScore* total);
 
+/*
+ * Normal-map evaluation: the estimated maps DPE/%08d/normal.npy of a dense folder against the normals of a
+ * ground-truth scan (estimated by PCA over each point's radius neighbourhood) rendered into each view, or against
+ * ground-truth normal maps.  No counterpart in the reference.  dpe_mvs.h states the contract of the three parts
+ * (dpe_cloud_normals, dpe_cloud_render_view_normals, dpe_normal_score); csrc/normal_eval.h holds their arithmetic.
+ *   dpe_host_cloud_normals         the point normals over dpe_host_cloud_nn's grid on host threads (at most 16), a cell
+ *                                  of the 27 skipped when an earlier one gave its bucket: the device path's bits,
+ *                                  counts and sums.
+ *   dpe_host_cloud_render_normals  the render with winners as a loop over the points (64-bit words bits(z) << 32 |
+ *                                  index, their minimum per pixel): depth map and world-frame normal map, either may
+ *                                  be NULL.
+ *   dpe_host_normal_score          the score as a serial loop over the pixels with the pairwise tree taken literally.
+ *   dpe_host_normal_edges          E[0..180): the bin edges (float)cos(b degrees), THE function both paths use.
+ *   dpe_host_normal_cos            a threshold in degrees as the cosine the score takes: (float)cos((double)deg * pi /
+ *                                  180), the one place where degrees become cosines.
+ *   dpe_host_normal_stats          everything derived, in double, for both paths and both programs: share[k] =
+ *                                  within[k] / n_both, completeness[k] = within[k] / n_gt, mean_cos_dist = sum_dist /
+ *                                  n_both, and from the histogram to its 1 degree resolution, a pixel of bin b counted
+ *                                  at b + 0.5 degrees: mean_deg, and median_deg of the first bin at which the
+ *                                  cumulative count reaches half of n_both; 0 where the denominator is 0.
+ *   dpe_host_read_npy_f32x3        dpe_host_read_npy_f32 for a 3-D '<f4' [h][w][3]; the same refusals.
+ *   dpe_host_normal_eval           dpe_host_depth_eval's folder walk over normal.npy (map_name NULL): rows in ascending
+ *                                  id and their total (the integers add, the two doubles are added sequentially in
+ *                                  that order).  gt_maps_dir == NULL: the normals of the scan gt_xyz are estimated once
+ *                                  (radius, min_nb), staged with it and rendered into every view at the map's size
+ *                                  (the depth tool's camera rule); else gt_maps_dir/%08d.npy [h][w][3] is the ground
+ *                                  truth.  write_maps: normal_gt.npy and normal_error.npy beside each map.  gpu_index <
+ *                                  0: the host functions above; else everything in one context of that device: equal
+ *                                  rows.
+ * All return 0, or nonzero with the message in dpe_pipeline_last_error().
+ * Left out: a DpePipelineOptions field, reading or writing a PLY with normals, curvature or planarity output.
+ */
+typedef struct DpeNormalStats {
+  double share[DPE_NORMAL_MAX_TAU], completeness[DPE_NORMAL_MAX_TAU], mean_cos_dist, median_deg, mean_deg;
+} DpeNormalStats;
+typedef struct DpeNormalEvalOptions {
+  const char* dense_folder;
+  const char* map_name;       /* NULL: "normal.npy" */
+  const char* gt_maps_dir;    /* NULL: estimate and render the scan's normals */
+  float radius;               /* of the PCA neighbourhood */
+  int min_nb, splat, n_tau;
+  float cos_tau[DPE_NORMAL_MAX_TAU];
+  int write_maps, gpu_index;
+} DpeNormalEvalOptions;
+typedef struct DpeNormalImage {
+  int id, width, height;
+  DpeNormalScore score;
+} DpeNormalImage;
+int dpe_host_cloud_normals(const float* xyz, size_t n, float radius, int min_nb, float* normal_out, int32_t* count_out,
+                           long long* sums_out_or_null);
+int dpe_host_cloud_render_normals(const float* xyz, const float* normals, size_t n, const DpeCamera* cam, int splat,
+                                  float* depth_out_or_null, float* normal_out_or_null);
+int dpe_host_normal_score(const float* est, const float* gt, int w, int h, const float* cos_tau, int n_tau,
+                          DpeNormalScore* out, float* err_or_null);
+void dpe_host_normal_edges(float* edges);
+float dpe_host_normal_cos(double deg);
+void dpe_host_normal_stats(const DpeNormalScore* s, int n_tau, DpeNormalStats* out);
+int dpe_host_read_npy_f32x3(const char* path, float* data, size_t cap, int* w, int* h);
+int dpe_host_normal_eval(const DpeNormalEvalOptions* opt, const float* gt_xyz, size_t n_gt, DpeNormalImage* rows, size_t cap,
+                         size_t* n_rows, DpeNormalScore* total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -615,6 +615,86 @@ int dpe_cloud_render_view(DpeContext* ctx, const DpeCamera* cam, int splat, floa
 int dpe_depth_score(DpeContext* ctx, const float* est, const float* gt_or_null, int w, int h, const float* tau, int n_tau,
                     int mode, DpeDepthScore* out, float* err_or_null);
 
+/*
+ * Normal-map evaluation: a normal for every point of a scan by PCA over its radius neighbourhood, the winning
+ * point's normal rendered into a view beside the z-buffer depth, and an estimated normal map scored against such a
+ * map pixel by pixel.  No counterpart in the reference.  csrc/normal_eval.h holds the arithmetic once, for the
+ * kernels (csrc/pass_normals.h) and the host loops (host/normal_eval.cpp, dpe_host.h); every reduction is an integer
+ * sum, a lexicographic minimum or the pairwise tree above, so the device gives the host loop's bits whatever the
+ * schedule.  IEEE division and square root, no contraction.
+ *
+ * Point normals.  The cloud, R and the refusals are dpe_cloud_nn's; min_nb must be in 3..2^31-1 (DPE_ERR_ARG).
+ *   N(i) = { j : P[j] finite, d2(P[i], P[j]) < R2 }   dpe_cloud_nn's d2, R2 = R*R and strict <; a finite point is
+ *                                                    its own neighbour
+ *   per neighbour and axis: dx = P[i].x - P[j].x in float (the term d2 forms), k = (int64)((double)dx * S) truncated
+ *   toward zero, S = 32768.0 / (double)R, one rounded division.  |k| <= 2^15 + 1, so the largest sum of products
+ *   stays below 2^62 for any n: that is why the lattice is 2^15 steps per radius and not finer.
+ *   sums[10] (int64): the count; sum k_x, k_y, k_z; sum k_x k_x, k_x k_y, k_x k_z, k_y k_y, k_y k_z, k_z k_z.
+ *   Integers: the serial loop's to the bit under any order (the voxel lattice's argument; a float covariance would
+ *   depend on the slot order inside a bucket).
+ *   C_ab = (double)m_ab - ((double)s_a * (double)s_b) / (double)cnt, rounded double operations in this order.
+ *   The eigenvector of the smallest eigenvalue by cyclic Jacobi in double: pairs (0,1), (0,2), (1,2), always 8
+ *   sweeps, a rotation skipped when its off-diagonal entry is 0; per rotation theta = (a_qq - a_pp) / (2 a_pq),
+ *   t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c, a_pp -= t a_pq,
+ *   a_qq += t a_pq, a_pq = 0, (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq) and V's columns p, q likewise
+ *   (csrc/normal_eval.h, normal_rotate, is the text).  Ties between eigenvalues go to the lowest index.  The vector
+ *   is divided by its length in double, its sign chosen so that the component of largest magnitude is positive (a
+ *   tie to the lowest axis), and rounded to float once.
+ *   Valid iff cnt >= min_nb and the middle eigenvalue > 0 (not collinear, not one repeated point); otherwise the
+ *   normal is (0, 0, 0), "no normal" everywhere below.  A non-finite point gets count 0, sums 0 and no normal.
+ *
+ * Render with normals.  Point, pixel and splat rules are dpe_cloud_render_view's.  The winner of a pixel is the
+ * lexicographic minimum of (bits(z), point index) over the points that cover it; the depth map has
+ * dpe_cloud_render_view's bits.  The normal map is f32 [h][w][3] in the WORLD frame (the frame of normal.npy).  A
+ * pixel takes its winner's normal; if that is "no normal" (three zeros) or no point covers it, the pixel has none:
+ * the winner decides, a farther point is never consulted.  Orientation towards the camera: p_cam = ProjectCamera's
+ * (tx, ty, tz) of the winner, n_cam = R n row by row (TransformNormal2RefCam's order), s = (n_cam.x * p_cam.x +
+ * n_cam.y * p_cam.y) + n_cam.z * p_cam.z in float; the world normal is negated iff s > 0.
+ *
+ * Score.  est and gt f32 [h][w][3]; 1 to 16 thresholds given as COSINES, each finite and in [-1, 1]; anything else
+ * is DPE_ERR_ARG.  Per pixel in index order, in float:
+ *   ee = (ex*ex + ey*ey) + ez*ez, gg likewise; est_ok = three finite components (by their bits) and 0 < bits(ee) <
+ *   0x7F800000; gt_ok likewise; both = est_ok && gt_ok && the same test of ee * gg
+ *   c = ((ex*gx + ey*gy) + ez*gz) / sqrtf(ee * gg), clamped to [-1, 1];  hit[k] = both && c > cos_tau[k]  (strict)
+ *   bin = #{ b in 1..179 : c < E[b] },  E[b] = (float)cos((double)b * pi / 180): one host function fills E, for both
+ *   paths; the device is handed the table and computes no cosine
+ * n_px, n_gt, n_est, n_both, within[k], hist[bin] count the pixels (hist over the `both` pixels: its sum is n_both);
+ * sum_dist = sum of 1.0 - (double)c and sum_dist_sq = sum of its square, each by PAIRWISE SUMMATION IN PIXEL-INDEX
+ * ORDER (the tree of dpe_cloud_icp_step), a pixel that is not `both` adding +0.0.  The error map, when asked for: c
+ * where both, -2.0f where only the ground truth has a normal, -3.0f otherwise.  Everything derived is the host's:
+ * dpe_host_normal_stats (dpe_host.h).
+ *
+ *   dpe_cloud_normals              one grid of edge R over the cloud (target and query at once), one thread per
+ *                                  point walking its 27 cells, a cell skipped when an earlier cell of the 27 gave
+ *                                  its bucket already (so no point is counted twice), the solve in the same
+ *                                  thread.  normal_out f32 [n][3], count_out i32 [n] (the count, at most n),
+ *                                  sums_out i64 [n][10] or NULL.  Synchronous; ends any staging.
+ *                                  dpe_cloud_last_timings: [0] stage, [1] build, [2] normals, [3] download.
+ *   dpe_cloud_render_stage_normals dpe_cloud_render_stage plus the per-point normals f32 [n][3] (from
+ *                                  dpe_cloud_normals or anywhere else); starts and ends as that staging does.
+ *   dpe_cloud_render_view_normals  one view of a staging WITH normals (otherwise DPE_ERR_STATE, "no staged
+ *                                  normals"); both outputs may be NULL.  The depth map becomes the resident map of
+ *                                  dpe_depth_score, the normal map the resident map of dpe_normal_score.
+ *                                  dpe_cloud_render_view on a staging with normals works as before.
+ *   dpe_normal_score               gt == NULL: against the last rendered normal map (dpe_depth_score's rules).
+ * Concurrency, error strings, buffers, dpe_cloud_launches and the timings' slots are dpe_cloud_render_view's.
+ * Left out: point-to-plane ICP and normals in voxel records (which this unblocks), reading or writing a PLY with
+ * normals, curvature or planarity output.
+ */
+#define DPE_NORMAL_MAX_TAU 16
+#define DPE_NORMAL_BINS 180
+typedef struct DpeNormalScore {
+  long long n_px, n_gt, n_est, n_both, within[DPE_NORMAL_MAX_TAU], hist[DPE_NORMAL_BINS];
+  double sum_dist, sum_dist_sq;
+} DpeNormalScore;
+int dpe_cloud_normals(DpeContext* ctx, const float* xyz, size_t n, float radius, int min_nb, float* normal_out,
+                      int32_t* count_out, long long* sums_out_or_null);
+int dpe_cloud_render_stage_normals(DpeContext* ctx, const float* xyz, const float* normals, size_t n);
+int dpe_cloud_render_view_normals(DpeContext* ctx, const DpeCamera* cam, int splat, float* depth_out_or_null,
+                                  float* normal_out_or_null);
+int dpe_normal_score(DpeContext* ctx, const float* est, const float* gt_or_null, int w, int h, const float* cos_tau,
+                     int n_tau, DpeNormalScore* out, float* err_or_null);
+
 /* Device bytes held at the moment by every context of the process (their buffers, resident states and
  * cached images; tests: a destroyed context gives back all it allocated). */
 long long dpe_live_device_bytes(void);

@@ -44,7 +44,19 @@ on either path, each as median, min and max over views and --reps runs after a w
 bits, which is checked on every view.  The contention case is 10^6 points on ONE pixel of a 1600 x 1200 view (their
 depths a permutation, so the minimum keeps falling) against 10^6 points of the scene's cloud in the same view.
 
-Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]] [--register R] [--render]"""
+With --normals R the tool measures the normal-map evaluation instead and writes profiles/cloud_normals.json.  Point
+normals: dpe_cloud_normals in a warm context against dpe_host_cloud_normals (at most 16 host threads) on the two cloud
+sizes above, at radius R (R = 0: the radius of the distances above, 2 tau = 4 pixel footprints), with the device parts
+(stage, build, normals, download: dpe_cloud_last_timings), and beside the normals part the match part of
+dpe_cloud_nn_index of the cloud against itself at the same radius: k_cloud_match makes the same walk, so the ratio
+prices the ten sums and the solve.  Render: the 800 x 600 cloud staged with its normals, then dpe_cloud_render_view_normals
+and dpe_cloud_render_view into the --render views' middle camera at 1600 x 1200 with half-widths 0 and 2 (the render part
+of each), and the host render with normals.  Score: dpe_normal_score of a 1600 x 1200 map against the rendered one with
+noise, and of a map of ONE plane (every pixel of a wave in one bin of the block's LDS histogram), against the serial host
+score.  Both paths must give the same bits, which is checked on every case.
+
+Usage: python tools/cloud_eval_prof.py [--out profiles/cloud_eval.json] [--reps 5] [--voxel V [--ab LIB LIB...]] [--register R] [--render]
+       [--normals R]"""
 import argparse
 import json
 import os
@@ -65,8 +77,9 @@ ap.add_argument("--voxel", type=float, default=None, help="measure the voxel dow
 ap.add_argument("--ab", nargs="+", default=None, help="with --voxel: builds of libdpe_mvs.so to compare, interleaved")
 ap.add_argument("--register", type=float, default=None, help="measure the ICP step at this match radius instead")
 ap.add_argument("--render", action="store_true", help="measure the depth-map evaluation (render and score) instead")
+ap.add_argument("--normals", type=float, default=None, help="measure the normal-map evaluation at this PCA radius instead (0: 2 tau)")
 a = ap.parse_args()
-a.out = a.out or os.path.join(ROOT, "profiles", "depth_render.json" if a.render else "cloud_register.json" if a.register is not None else
+a.out = a.out or os.path.join(ROOT, "profiles", "cloud_normals.json" if a.normals is not None else "depth_render.json" if a.render else "cloud_register.json" if a.register is not None else
                               "cloud_eval.json" if a.voxel is None else "cloud_voxel.json")
 
 
@@ -367,6 +380,103 @@ def render_profile():
     ctx.close()
     return out
 
+
+def normals_profile():
+    out = {"reps": a.reps, "host_threads": min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or 16)), "sizes": []}
+    ctx = native.PatchMatchContext(0)
+    ctx.set_timing(True)
+    A = nrm = None
+    for W, H in ((256, 192), (800, 600)):
+        sc = synthetic.make_scene(W, H, 4)
+        A = synthetic.gt_point_cloud(sc)
+        del sc
+        R = a.normals if a.normals > 0 else 4 * 5.0 / (1.2 * W)
+        t = time.perf_counter()
+        h_nrm, h_cnt = pipeline.estimate_normals(A, R)
+        host_s = time.perf_counter() - t
+
+        def device():
+            r = ctx.cloud_normals(A, R)
+            return r, ctx.cloud_timings()
+        dev_s, ((nrm, cnt), parts) = best_of(device, a.reps)
+        parts = dict(zip(("stage", "build", "normals", "download"), parts.values()))
+
+        def match():
+            ctx.cloud_nn_index(A, A, R)
+            return ctx.cloud_timings()["query"]
+        match_ms = best_of(match, a.reps)[1]
+        row = {"points": int(len(A)), "radius": R, "mean_neighbours": float(cnt.mean()), "max_neighbours": int(cnt.max()),
+               "with_normal": float(nrm.any(axis=1).mean()), "host_seconds": host_s, "device_seconds": dev_s, "device_parts_ms": parts,
+               "match_ms_same_cloud_and_radius": match_ms, "normals_over_match": parts["normals"] / match_ms,
+               "identical": bool(nrm.tobytes() == h_nrm.tobytes() and np.array_equal(cnt, h_cnt))}
+        out["sizes"].append(row)
+        print(json.dumps(row), flush=True)
+    # the render: the 800 x 600 cloud and its normals into one 1600 x 1200 view
+    Wv, Hv = 1600, 1200
+    cam = arc_cameras(10, Wv, Hv)[5]
+    ctx.cloud_render_stage(A, nrm)
+    out["render"] = []
+    gt = None
+    for s in (0, 2):
+        t = time.perf_counter()
+        h_depth, h_normal = pipeline.render_cloud_normals(A, nrm, cam, s)
+        host_s = time.perf_counter() - t
+        with_ms, plain_ms = [], []
+        for r in range(a.reps + 1):                                        # the first round is the warm-up
+            depth, normal = ctx.cloud_render_view_normals(cam, s, download=(r == 0))
+            if r == 0:
+                same = bool(depth.tobytes() == h_depth.tobytes() and normal.tobytes() == h_normal.tobytes())
+            else:
+                with_ms.append(ctx.cloud_timings()["build"])
+            ctx.cloud_render_view(cam, s, download=False)
+            if r:
+                plain_ms.append(ctx.cloud_timings()["build"])
+        row = {"splat": s, "size": [Wv, Hv], "points": int(len(A)), "coverage": float((h_depth > 0).mean()),
+               "with_normal": float(h_normal.any(axis=2).mean()), "render_with_normals_ms": spread(with_ms), "render_plain_ms": spread(plain_ms),
+               "host_render_with_normals_seconds": host_s, "identical": same}
+        out["render"].append(row)
+        print(json.dumps(row), flush=True)
+        gt = h_normal
+    # the score: a noisy copy of the rendered map, and one plane
+    rng = np.random.default_rng(4)
+    cos_taus = [pipeline.normal_cos(v) for v in (11.25, 22.5, 30.0)]
+    noisy = (gt + 0.1 * rng.standard_normal(gt.shape)).astype(np.float32)
+    plane_gt = np.tile(np.array([(0, 0, -1)], np.float32), (Hv, Wv, 1))
+    plane_est = np.tile(np.array([(0.6, 0, -0.8)], np.float32), (Hv, Wv, 1))
+    out["score"] = []
+    for name, e, g in (("rendered map with noise", noisy, gt), ("one plane: every pixel in one bin", plane_est, plane_gt)):
+        t = time.perf_counter()
+        hs = pipeline.score_normals(e, g, cos_taus=cos_taus)
+        host_s = time.perf_counter() - t
+        score_ms, upload_ms, wall = [], [], []
+        for r in range(a.reps + 1):
+            t = time.perf_counter()
+            d = ctx.normal_score(e, g, cos_taus)
+            dt = time.perf_counter() - t
+            if r == 0:
+                d.update(pipeline.normal_stats(d))
+                same = bool(d == hs)
+                continue
+            ts = ctx.cloud_timings()
+            score_ms.append(ts["query"])
+            upload_ms.append(ts["stage"])
+            wall.append(dt)
+        row = {"case": name, "pixels": Wv * Hv, "n_both": hs["n_both"], "largest_bin": max(hs["hist"]), "score_ms": spread(score_ms),
+               "upload_ms": spread(upload_ms), "device_seconds": spread(wall), "host_seconds": host_s, "identical": same}
+        out["score"].append(row)
+        print(json.dumps(row), flush=True)
+    ctx.close()
+    return out
+
+
+if a.normals is not None:
+    result = normals_profile()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("written", a.out)
+    sys.exit(0)
 
 if a.render:
     result = render_profile()
