@@ -545,19 +545,23 @@ class PatchMatchContext:
         """The map `est` f32 [h, w] against `gt` (None: the last rendered map) at the thresholds `taus`: the counts and
         the three pairwise sums as a dict (pipeline.score_depth gives the same bits on the host); with want_error
         (dict, error map f32 [h, w])."""
+        mode = (_abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS,)
+        return self._map_score("dpe_depth_score", (), _abi.DpeDepthScore(), _abi.depth_score_dict, est, gt, taus, mode, want_error)
+
+    def _map_score(self, entry: str, channels: tuple, s, to_dict, est, gt, taus, extra: tuple, want_error: bool):
+        """depth_score and normal_score: maps of shape [h, w] + channels through the library's `entry`, whose
+        arguments between the thresholds and the score struct `s` are `extra`."""
         e = np.ascontiguousarray(est, np.float32)
-        if e.ndim != 2:
-            raise ValueError("expected a map of shape [h, w]")
+        if e.ndim != 2 + len(channels) or e.shape[2:] != channels:
+            raise ValueError("expected a map of shape [h, w%s]" % "".join(", %d" % c for c in channels))
         g = None if gt is None else np.ascontiguousarray(gt, np.float32)
         if g is not None and g.shape != e.shape:
             raise ValueError("the maps differ in shape")
         t = np.ascontiguousarray(np.atleast_1d(taus), np.float32)
-        s = _abi.DpeDepthScore()
-        err = np.empty(e.shape, np.float32) if want_error else None
-        _check(_LIB.dpe_depth_score(self._ctx, e.ctypes.data, None if g is None else g.ctypes.data, e.shape[1], e.shape[0],
-                                    t.ctypes.data, len(t), _abi.DEPTH_TAU_REL if relative else _abi.DEPTH_TAU_ABS, C.byref(s),
-                                    None if err is None else err.ctypes.data), "dpe_depth_score")
-        d = _abi.depth_score_dict(s, len(t))
+        err = np.empty(e.shape[:2], np.float32) if want_error else None
+        _check(getattr(_LIB, entry)(self._ctx, e.ctypes.data, None if g is None else g.ctypes.data, e.shape[1], e.shape[0],
+                                    t.ctypes.data, len(t), *extra, C.byref(s), None if err is None else err.ctypes.data), entry)
+        d = to_dict(s, len(t))
         return (d, err) if want_error else d
 
     # normal-map evaluation (include/dpe_mvs.h: dpe_cloud_normals, dpe_cloud_render_view_normals, dpe_normal_score)
@@ -590,24 +594,13 @@ class PatchMatchContext:
         """The normal map `est` f32 [h, w, 3] against `gt` (None: the last rendered normal map) at the thresholds
         `cos_taus`, COSINES of the angles: the counts, the 180-bin histogram and the two pairwise sums as a dict
         (pipeline.score_normals gives the same bits on the host); with want_error (dict, error map f32 [h, w])."""
-        e = np.ascontiguousarray(est, np.float32)
-        if e.ndim != 3 or e.shape[2] != 3:
-            raise ValueError("expected a map of shape [h, w, 3]")
-        g = None if gt is None else np.ascontiguousarray(gt, np.float32)
-        if g is not None and g.shape != e.shape:
-            raise ValueError("the maps differ in shape")
-        t = np.ascontiguousarray(np.atleast_1d(cos_taus), np.float32)
-        s = _abi.DpeNormalScore()
-        err = np.empty(e.shape[:2], np.float32) if want_error else None
-        _check(_LIB.dpe_normal_score(self._ctx, e.ctypes.data, None if g is None else g.ctypes.data, e.shape[1], e.shape[0],
-                                     t.ctypes.data, len(t), C.byref(s), None if err is None else err.ctypes.data), "dpe_normal_score")
-        d = _abi.normal_score_dict(s, len(t))
-        return (d, err) if want_error else d
+        return self._map_score("dpe_normal_score", (3,), _abi.DpeNormalScore(), _abi.normal_score_dict, est, gt, cos_taus, (), want_error)
 
     def cloud_timings(self) -> dict:
         """Device milliseconds of the last cloud_nn / cloud_nn_pair's parts (timing enabled), else {}.  After
         cloud_voxel the four slots are, in this order, stage, cells + insert, emit and download; after
-        cloud_render_stage, cloud_render_view and depth_score stage, render, score and download."""
+        cloud_render_stage, cloud_render_view, cloud_render_view_normals, depth_score and normal_score stage, render,
+        score and download; after cloud_normals stage, grid build, normals and download."""
         buf = (C.c_float * 4)()
         n = _LIB.dpe_cloud_last_timings(self._ctx, buf, 4)
         return {k: float(buf[i]) for i, k in enumerate(("stage", "build", "query", "download")) if i < n}

@@ -488,6 +488,20 @@ def _last_error() -> str:
     return lib().dpe_pipeline_last_error().decode(errors="replace")
 
 
+def _on_device(gpu_index: int, run, wrap_errors: bool = True):
+    """run(ctx) on a context of its own on that device, closed afterwards; native.DpeError becomes PipelineError."""
+    from . import native
+    ctx = native.PatchMatchContext(int(gpu_index))
+    try:
+        return run(ctx)
+    except native.DpeError as e:
+        if not wrap_errors:
+            raise
+        raise PipelineError(str(e)) from None
+    finally:
+        ctx.close()
+
+
 def _as_cloud(points) -> np.ndarray:
     a = np.ascontiguousarray(points, np.float32)
     if a.ndim != 2 or a.shape[1] != 3:
@@ -558,13 +572,8 @@ def voxel_down_sample(points, voxel: float, colors=None, gpu_index: int = -1):
     (xyz f32 [k, 3] lattice centroids, colours u8 [k, 3] means rounded half up or None, first i32 [k] lowest
     original index, count i32 [k]), in ascending `first`.  gpu_index < 0: the serial host loop
     (dpe_host_cloud_voxel), else native.PatchMatchContext.cloud_voxel on that device: the same bits."""
-    if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            return ctx.cloud_voxel(points, voxel, colors)
-        finally:
-            ctx.close()
+    if gpu_index >= 0:   # the device's own error, as before there was a shared helper
+        return _on_device(gpu_index, lambda ctx: ctx.cloud_voxel(points, voxel, colors), wrap_errors=False)
     p = _as_cloud(points)
     c = _as_colors(colors, len(p))
     n = len(p)
@@ -745,18 +754,50 @@ def format_cloud_eval(e: dict) -> str:
     return "\n".join(rows) + "\n"
 
 
+# ------------------------------------------------------------------------------ what the two map evaluations share
+def _read_npy(entry, path: str, channels: tuple) -> np.ndarray:
+    """A dpe_host_read_npy_* entry in its two calls: the size, then the values into f32 [h, w] + channels."""
+    w, h = C.c_int(), C.c_int()
+    if entry(os.fsencode(path), None, 0, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    out = np.empty((h.value, w.value) + channels, np.float32)
+    if entry(os.fsencode(path), out.ctypes.data, out.size, C.byref(w), C.byref(h)) != 0:
+        raise PipelineError(_last_error())
+    return out
+
+
+def _score_struct(s, score: dict, sums: tuple):
+    """The score struct `s` filled from a score's dict: the counts, the named sums, within[] and, where it has one, hist[]."""
+    for name in ("n_px", "n_gt", "n_est", "n_both") + sums:
+        setattr(s, name, score[name])
+    for name in ("within", "hist"):
+        for i, v in enumerate(score.get(name, ())):
+            getattr(s, name)[i] = v
+    return s
+
+
+def _format_map_eval(e: dict, first: str, col_fmt: str, cols: tuple, row_fmt: str, keys: tuple, share: str, share_key: str) -> str:
+    """The table of a folder evaluation: the line `first`, the header (the metric's three columns `cols`, then
+    `share`[k] and comp[k] per threshold), a row per image and the total."""
+    k = len(e["total"]["within"])
+    rows = [first, ("%8s %11s %10s %10s %10s" + col_fmt) % (("image", "size", "n_gt", "n_est", "n_both") + cols)
+            + "".join(" %10s %10s" % ("%s[%d]" % (share, i), "comp[%d]" % i) for i in range(k))]
+
+    def row(name, size, s):
+        return (("%8s %11s %10d %10d %10d" + row_fmt) % ((name, size, s["n_gt"], s["n_est"], s["n_both"]) + tuple(s[n] for n in keys))
+                + "".join(" %10.6f %10.6f" % v for v in zip(s[share_key], s["completeness"])))
+
+    rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
+    rows.append(row("total", "-", e["total"]))
+    return "\n".join(rows) + "\n"
+
+
 # ------------------------------------------------------------------------------ depth-map evaluation (C++, depth_eval.cpp)
 def read_npy_f32(path: str) -> np.ndarray:
     """A 2-D '<f4' .npy v1.0 in C order through the host library's reader (dpe_host_read_npy_f32): f32 [h, w].
     PipelineError with the reader's message for what it refuses (another dtype, rank or order, a body that is
     shorter or longer than the header says)."""
-    w, h = C.c_int(), C.c_int()
-    if lib().dpe_host_read_npy_f32(os.fsencode(path), None, 0, C.byref(w), C.byref(h)) != 0:
-        raise PipelineError(_last_error())
-    out = np.empty((h.value, w.value), np.float32)
-    if lib().dpe_host_read_npy_f32(os.fsencode(path), out.ctypes.data, out.size, C.byref(w), C.byref(h)) != 0:
-        raise PipelineError(_last_error())
-    return out
+    return _read_npy(lib().dpe_host_read_npy_f32, path, ())
 
 
 def render_cloud(points, cam: _abi.DpeCamera, splat: int = 0, gpu_index: int = -1) -> np.ndarray:
@@ -765,15 +806,7 @@ def render_cloud(points, cam: _abi.DpeCamera, splat: int = 0, gpu_index: int = -
     does (include/dpe_mvs.h, dpe_cloud_render_view, states the contract; no occlusion test beyond the z-buffer).
     gpu_index < 0: the host loop (dpe_host_cloud_render), else on that device: the same bits."""
     if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            ctx.cloud_render_stage(points)
-            return ctx.cloud_render_view(cam, splat)
-        except native.DpeError as e:
-            raise PipelineError(str(e)) from None
-        finally:
-            ctx.close()
+        return _on_device(gpu_index, lambda ctx: (ctx.cloud_render_stage(points), ctx.cloud_render_view(cam, splat))[1])
     p = _as_cloud(points)
     out = np.empty((max(int(cam.height), 0), max(int(cam.width), 0)), np.float32)
     if lib().dpe_host_cloud_render(p.ctypes.data, len(p), C.byref(cam), int(splat), out.ctypes.data) != 0:
@@ -785,12 +818,8 @@ def depth_stats(score: dict) -> dict:
     """What is derived from a score's counts and sums, in double (dpe_host_depth_stats, the one function both paths
     and both programs go through): accuracy and completeness per threshold, mae, mre, rmse; 0 for an empty
     denominator."""
-    s, d = DpeDepthScore(), DpeDepthStats()
+    s, d = _score_struct(DpeDepthScore(), score, ("sum_abs", "sum_rel", "sum_sq")), DpeDepthStats()
     k = len(score["within"])
-    for name in ("n_px", "n_gt", "n_est", "n_both", "sum_abs", "sum_rel", "sum_sq"):
-        setattr(s, name, score[name])
-    for i, v in enumerate(score["within"]):
-        s.within[i] = v
     lib().dpe_host_depth_stats(C.byref(s), k, C.byref(d))
     return dict(accuracy=list(d.accuracy[:k]), completeness=list(d.completeness[:k]), mae=d.mae, mre=d.mre, rmse=d.rmse)
 
@@ -812,14 +841,7 @@ def score_depth(est, gt, taus, relative: bool = False, gpu_index: int = -1, want
     if e.ndim != 2 or g.shape != e.shape:
         raise PipelineError("depth_score: size mismatch: two maps of one shape [h, w] expected")
     if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            r = ctx.depth_score(e, g, t, relative, want_error)
-        except native.DpeError as x:
-            raise PipelineError(str(x)) from None
-        finally:
-            ctx.close()
+        r = _on_device(gpu_index, lambda ctx: ctx.depth_score(e, g, t, relative, want_error))
         d, err = r if want_error else (r, None)
         d.update(depth_stats(d))
         return (d, err) if want_error else d
@@ -869,33 +891,17 @@ def evaluate_depth_maps(dense_folder: str, gt, taus, relative: bool = False, spl
 def format_depth_eval(e: dict) -> str:
     """The table bin/dpe_depth_eval prints, from evaluate_depth_maps' dict."""
     gt = "maps" if e["n_gt_points"] is None else "cloud of %d points, splat %d" % (e["n_gt_points"], e["splat"])
-    k = len(e["tau"])
-    rows = ["map %s, ground truth %s, %s thresholds %s" % (e["map"], gt, "relative" if e["relative"] else "absolute",
-                                                           " ".join("%.9g" % v for v in e["tau"])),
-            "%8s %11s %10s %10s %10s %12s %12s %12s" % ("image", "size", "n_gt", "n_est", "n_both", "mae", "mre", "rmse")
-            + "".join(" %10s %10s" % ("acc[%d]" % i, "comp[%d]" % i) for i in range(k))]
-
-    def row(name, size, s):
-        return ("%8s %11s %10d %10d %10d %12.6g %12.6g %12.6g" % (name, size, s["n_gt"], s["n_est"], s["n_both"], s["mae"], s["mre"],
-                                                                   s["rmse"])
-                + "".join(" %10.6f %10.6f" % v for v in zip(s["accuracy"], s["completeness"])))
-
-    rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
-    rows.append(row("total", "-", e["total"]))
-    return "\n".join(rows) + "\n"
+    first = "map %s, ground truth %s, %s thresholds %s" % (e["map"], gt, "relative" if e["relative"] else "absolute",
+                                                          " ".join("%.9g" % v for v in e["tau"]))
+    return _format_map_eval(e, first, " %12s %12s %12s", ("mae", "mre", "rmse"), " %12.6g %12.6g %12.6g", ("mae", "mre", "rmse"),
+                            "acc", "accuracy")
 
 
 # ------------------------------------------------------------------------------ normal-map evaluation (C++, normal_eval.cpp)
 def read_npy_f32x3(path: str) -> np.ndarray:
     """A 3-D '<f4' .npy v1.0 in C order of shape [h, w, 3] through the host library's reader
     (dpe_host_read_npy_f32x3): f32 [h, w, 3].  PipelineError with the reader's message for what it refuses."""
-    w, h = C.c_int(), C.c_int()
-    if lib().dpe_host_read_npy_f32x3(os.fsencode(path), None, 0, C.byref(w), C.byref(h)) != 0:
-        raise PipelineError(_last_error())
-    out = np.empty((h.value, w.value, 3), np.float32)
-    if lib().dpe_host_read_npy_f32x3(os.fsencode(path), out.ctypes.data, out.size, C.byref(w), C.byref(h)) != 0:
-        raise PipelineError(_last_error())
-    return out
+    return _read_npy(lib().dpe_host_read_npy_f32x3, path, (3,))
 
 
 def normal_edges() -> np.ndarray:
@@ -918,14 +924,7 @@ def estimate_normals(points, radius: float, min_neighbours: int = 3, gpu_index: 
     turns it towards its camera (render_cloud_normals).  gpu_index < 0: on host threads (dpe_host_cloud_normals), else
     on that device: the same bits."""
     if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            return ctx.cloud_normals(points, radius, min_neighbours, want_sums)
-        except native.DpeError as e:
-            raise PipelineError(str(e)) from None
-        finally:
-            ctx.close()
+        return _on_device(gpu_index, lambda ctx: ctx.cloud_normals(points, radius, min_neighbours, want_sums))
     p = _as_cloud(points)
     n = len(p)
     normals, counts = np.empty((n, 3), np.float32), np.empty(n, np.int32)
@@ -945,15 +944,7 @@ def render_cloud_normals(points, normals, cam: _abi.DpeCamera, splat: int = 0, g
     if len(p) != len(nm):
         raise PipelineError("cloud_render_normals: one normal per point expected")
     if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            ctx.cloud_render_stage(p, nm)
-            return ctx.cloud_render_view_normals(cam, splat)
-        except native.DpeError as e:
-            raise PipelineError(str(e)) from None
-        finally:
-            ctx.close()
+        return _on_device(gpu_index, lambda ctx: (ctx.cloud_render_stage(p, nm), ctx.cloud_render_view_normals(cam, splat))[1])
     h, w = max(int(cam.height), 0), max(int(cam.width), 0)
     depth, normal = np.empty((h, w), np.float32), np.empty((h, w, 3), np.float32)
     if lib().dpe_host_cloud_render_normals(p.ctypes.data, nm.ctypes.data, len(p), C.byref(cam), int(splat), depth.ctypes.data,
@@ -966,14 +957,8 @@ def normal_stats(score: dict) -> dict:
     """What is derived from a score's counts, histogram and sums, in double (dpe_host_normal_stats, the one function
     both paths and both programs go through): share and completeness per threshold, mean_cos_dist, and median_deg
     and mean_deg from the histogram to its 1 degree resolution; 0 for an empty denominator."""
-    s, d = DpeNormalScore(), DpeNormalStats()
+    s, d = _score_struct(DpeNormalScore(), score, ("sum_dist", "sum_dist_sq")), DpeNormalStats()
     k = len(score["within"])
-    for name in ("n_px", "n_gt", "n_est", "n_both", "sum_dist", "sum_dist_sq"):
-        setattr(s, name, score[name])
-    for i, v in enumerate(score["within"]):
-        s.within[i] = v
-    for i, v in enumerate(score["hist"]):
-        s.hist[i] = v
     lib().dpe_host_normal_stats(C.byref(s), k, C.byref(d))
     return dict(share=list(d.share[:k]), completeness=list(d.completeness[:k]), mean_cos_dist=d.mean_cos_dist,
                 median_deg=d.median_deg, mean_deg=d.mean_deg)
@@ -1001,14 +986,7 @@ def score_normals(est, gt, taus_deg=None, cos_taus=None, gpu_index: int = -1, wa
     if e.ndim != 3 or e.shape[2] != 3 or g.shape != e.shape:
         raise PipelineError("normal_score: size mismatch: two maps of one shape [h, w, 3] expected")
     if gpu_index >= 0:
-        from . import native
-        ctx = native.PatchMatchContext(int(gpu_index))
-        try:
-            r = ctx.normal_score(e, g, t, want_error)
-        except native.DpeError as x:
-            raise PipelineError(str(x)) from None
-        finally:
-            ctx.close()
+        r = _on_device(gpu_index, lambda ctx: ctx.normal_score(e, g, t, want_error))
         d, err = r if want_error else (r, None)
         d.update(normal_stats(d))
         return (d, err) if want_error else d
@@ -1061,19 +1039,9 @@ def format_normal_eval(e: dict) -> str:
     """The table bin/dpe_normal_eval prints, from evaluate_normal_maps' dict."""
     gt = "maps" if e["n_gt_points"] is None else "cloud of %d points, radius %.9g, min neighbours %d, splat %d" % (
         e["n_gt_points"], e["radius"], e["min_neighbours"], e["splat"])
-    k = len(e["tau_deg"])
-    rows = ["map %s, ground truth %s, thresholds in degrees %s" % (e["map"], gt, " ".join("%.9g" % v for v in e["tau_deg"])),
-            "%8s %11s %10s %10s %10s %12s %10s %10s" % ("image", "size", "n_gt", "n_est", "n_both", "cos_dist", "median", "mean")
-            + "".join(" %10s %10s" % ("within[%d]" % i, "comp[%d]" % i) for i in range(k))]
-
-    def row(name, size, s):
-        return ("%8s %11s %10d %10d %10d %12.6g %10.1f %10.4f" % (name, size, s["n_gt"], s["n_est"], s["n_both"], s["mean_cos_dist"],
-                                                                  s["median_deg"], s["mean_deg"])
-                + "".join(" %10.6f %10.6f" % v for v in zip(s["share"], s["completeness"])))
-
-    rows += [row("%08d" % s["id"], "%dx%d" % (s["width"], s["height"]), s) for s in e["images"]]
-    rows.append(row("total", "-", e["total"]))
-    return "\n".join(rows) + "\n"
+    first = "map %s, ground truth %s, thresholds in degrees %s" % (e["map"], gt, " ".join("%.9g" % v for v in e["tau_deg"]))
+    return _format_map_eval(e, first, " %12s %10s %10s", ("cos_dist", "median", "mean"), " %12.6g %10.1f %10.4f",
+                            ("mean_cos_dist", "median_deg", "mean_deg"), "within", "share")
 
 
 # ------------------------------------------------------------------------------ EdgeSegment (C++, edges.cpp)

@@ -2,10 +2,10 @@
 // down-sampling (dpe_cloud_voxel) and the registration's device half (dpe_cloud_nn_index, dpe_cloud_icp_stage,
 // dpe_cloud_icp_step), the depth-map evaluation (dpe_cloud_render_stage, dpe_cloud_render_view, dpe_depth_score) and
 // the normal-map evaluation (dpe_cloud_normals, dpe_cloud_render_stage_normals, dpe_cloud_render_view_normals,
-// dpe_normal_score) of include/dpe_mvs.h: the kernels of pass_cloud.h, pass_voxel.h, pass_register.h, pass_render.h,
-// pass_normals.h and tree_sum.h over the context's cloud scratch.  A unit of libdpe_mvs.so; the concurrency
-// contract is dpe_mvs.hip's (dpe_entry.h): these calls wait until the context is quiet, use its stream and
-// return with it synchronised.
+// dpe_normal_score; one render_view and one score_run<Metric> serve both) of include/dpe_mvs.h: the kernels of
+// pass_cloud.h, pass_voxel.h, pass_register.h, pass_render.h, pass_normals.h and tree_sum.h over the context's cloud
+// scratch.  A unit of libdpe_mvs.so; the concurrency contract is dpe_mvs.hip's (dpe_entry.h): these calls wait until
+// the context is quiet, use its stream and return with it synchronised.
 //
 // Every call opens with cloud_begin, launches through LAUNCH and, when it ran to its end, closes with timer_finish:
 // a call that returns early (an empty cloud, nothing to match, an error) leaves no timings.
@@ -392,66 +392,111 @@ int render_stage(DpeContext* c, const float* xyz, const float* normals, size_t n
   return timer_finish(c);
 }
 
-// dpe_cloud_render_view of the staged scan.  Timings: [1] render, [3] download
-int render_view(DpeContext* c, const DpeCamera& cam, int splat, float* depth_out) {
+// dpe_cloud_render_view and dpe_cloud_render_view_normals of the staged scan.  A plain view invalidates the resident
+// normal map, which would belong to another depth map; a view with normals leaves both.  Timings: [1] render,
+// [3] download
+int render_view(DpeContext* c, const DpeCamera& cam, int splat, bool with_normals, float* depth_out, float* normal_out) {
   RenderStage& r = c->cloud.render;
+  NormalScratch& s = c->cloud.normals;
   TRY(cloud_begin(c, true));
   const size_t npx = (size_t)cam.width * (size_t)cam.height, n = r.n;
-  r.map_w = r.map_h = 0;   // the old map goes with the first launch
-  c->cloud.normals.map_w = c->cloud.normals.map_h = 0;   // and a normal map would belong to another depth map
+  const float* pts = c->cloud.pts[0].p;
+  r.map_w = r.map_h = 0;   // the old maps go with the first launch
+  s.map_w = s.map_h = 0;
   HIPC(r.map.ensure(npx));
-  LAUNCH(k_render_clear, cloud_blocks(npx), c, r.map.p, npx);
-  if (n > 0) LAUNCH(k_render_splat, cloud_blocks(n), c, c->cloud.pts[0].p, (int)n, cam, splat, r.map.p);
-  LAUNCH(k_render_finish, cloud_blocks(npx), c, r.map.p, npx);
+  if (with_normals) {
+    HIPC(s.zb.ensure(npx));
+    HIPC(s.winner.ensure(npx));
+    HIPC(s.map.ensure(3 * npx));
+    LAUNCH(k_render_clear<unsigned long long>, cloud_blocks(npx), c, s.zb.p, npx);
+    if (n > 0) LAUNCH(k_render_splat<unsigned long long>, cloud_blocks(n), c, pts, (int)n, cam, splat, s.zb.p);
+    LAUNCH(k_render_finish_idx, cloud_blocks(npx), c, s.zb.p, npx, r.map.p, s.winner.p);
+    LAUNCH(k_render_normals, cloud_blocks(npx), c, pts, s.staged.p, s.winner.p, npx, cam, s.map.p);
+  } else {
+    LAUNCH(k_render_clear<uint32_t>, cloud_blocks(npx), c, r.map.p, npx);
+    if (n > 0) LAUNCH(k_render_splat<uint32_t>, cloud_blocks(n), c, pts, (int)n, cam, splat, r.map.p);
+    LAUNCH(k_render_finish, cloud_blocks(npx), c, r.map.p, npx);
+  }
   TRY(timer_mark(c, 1));
   if (depth_out) HIPC(hipMemcpyAsync(depth_out, r.map.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (normal_out) HIPC(hipMemcpyAsync(normal_out, s.map.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   TRY(timer_mark(c, 3));
   HIPC(hipStreamSynchronize(c->stream));
   r.map_w = cam.width;
   r.map_h = cam.height;
+  if (with_normals) { s.map_w = cam.width; s.map_h = cam.height; }
   return timer_finish(c);
 }
 
-// dpe_depth_score; gt == nullptr: against the resident map.  Timings: [0] upload, [2] score, [3] download
-int depth_score(DpeContext* c, const float* est, const float* gt, int w, int h, const DepthTaus& T, DpeDepthScore* out,
-                float* err) {
+// dpe_depth_score and dpe_normal_score; gt == nullptr: against the resident map `resident`.  Timings: [0] upload,
+// [2] score, [3] download
+template <typename M>
+int score_run(DpeContext* c, const float* est, const float* gt, const float* resident, int w, int h, const typename M::Taus& T,
+              typename M::Score* out, float* err) {
   ScoreScratch& v = c->cloud.score;
   TRY(cloud_begin(c, true));
-  const size_t npx = (size_t)w * (size_t)h, blocks = cloud_blocks(npx);
-  HIPC(v.est.ensure(npx));
-  if (gt) HIPC(v.gt.ensure(npx));
+  const size_t npx = (size_t)w * (size_t)h, blocks = cloud_blocks(npx), nval = M::kChannels * npx;
+  HIPC(v.est.ensure(nval));
+  if (gt) HIPC(v.gt.ensure(nval));
   if (err) HIPC(v.err.ensure(npx));
-  HIPC(v.part[0].ensure(blocks * kDepthTerms));
-  HIPC(v.part[1].ensure((size_t)cloud_blocks(blocks) * kDepthTerms));
-  HIPC(v.cnt.ensure(kDepthCounters));
-  HIPC(hipMemcpyAsync(v.est.p, est, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (gt) HIPC(hipMemcpyAsync(v.gt.p, gt, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemsetAsync(v.cnt.p, 0, kDepthCounters * sizeof(unsigned long long), c->stream));
+  HIPC(v.part[0].ensure(blocks * M::kTerms));
+  HIPC(v.part[1].ensure((size_t)cloud_blocks(blocks) * M::kTerms));
+  HIPC(v.cnt.ensure(M::kCounters));
+  const float* edges = nullptr;
+  if constexpr (M::kBins > 0) {
+    DevArr<float>& e = c->cloud.normals.edges;
+    if (e.n == 0) {   // the table of the one host function, uploaded once per context
+      float E[M::kBins];
+      M::edges(E);
+      HIPC(e.ensure(M::kBins));
+      HIPC(hipMemcpyAsync(e.p, E, sizeof E, hipMemcpyHostToDevice, c->stream));
+      HIPC(hipStreamSynchronize(c->stream));   // E leaves the stack
+    }
+    edges = e.p;
+  }
+  HIPC(hipMemcpyAsync(v.est.p, est, nval * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (gt) HIPC(hipMemcpyAsync(v.gt.p, gt, nval * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemsetAsync(v.cnt.p, 0, M::kCounters * sizeof(unsigned long long), c->stream));
   TRY(timer_mark(c, 0));
-  const float* g = gt ? v.gt.p : reinterpret_cast<const float*>(c->cloud.render.map.p);
-  LAUNCH(k_depth_score, blocks, c, v.est.p, g, npx, T, v.part[0].p, v.cnt.p, err ? v.err.p : nullptr);
+  LAUNCH(k_map_score<M>, blocks, c, v.est.p, gt ? v.gt.p : resident, npx, T, v.part[0].p, v.cnt.p,
+         err ? v.err.p : nullptr, edges);
   int at;
-  TRY(tree_reduce<kDepthTerms>(c, v.part, blocks, &at));
+  TRY(tree_reduce<M::kTerms>(c, v.part, blocks, &at));
   TRY(timer_mark(c, 2));
-  double sums[kDepthTerms];
-  unsigned long long counts[kDepthCounters];
+  double sums[M::kTerms];
+  unsigned long long counts[M::kCounters];
   HIPC(hipMemcpyAsync(sums, v.part[at].p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipMemcpyAsync(counts, v.cnt.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
   if (err) HIPC(hipMemcpyAsync(err, v.err.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   TRY(timer_mark(c, 3));
   HIPC(hipStreamSynchronize(c->stream));
-  DpeDepthScore s;
-  memset(&s, 0, sizeof s);
-  s.n_px = (long long)npx;
-  s.n_gt = (long long)counts[0];
-  s.n_est = (long long)counts[1];
-  s.n_both = (long long)counts[2];
-  for (int k = 0; k < T.n; ++k) s.within[k] = (long long)counts[3 + k];
-  s.sum_abs = sums[0];
-  s.sum_rel = sums[1];
-  s.sum_sq = sums[2];
-  *out = s;
+  *out = score_of<M>(npx, T.n, counts, sums);
   return timer_finish(c);
+}
+
+// the camera and the splat of a render, and the scan staged before it (`stage`: the call that stages)
+int render_enter(DpeContext* c, const DpeCamera* cam, int splat, const char* who, const char* stage) {
+  const bool ok = cam && cam->width >= 1 && cam->height >= 1 && splat >= 0 && splat <= DPE_DEPTH_MAX_SPLAT;
+  TRY(enter(c, ok, (std::string(who) + ": bad argument").c_str()));
+  if (c->cloud.resident != CloudResident::RenderScan) {
+    g_err = std::string(who) + ": no staged cloud (" + stage + " comes first)";
+    return DPE_ERR_STATE;
+  }
+  return DPE_OK;
+}
+
+// a score without gt: the resident map (map_w x map_h, 0: none, rendered by `view`) must be there and of the size
+int score_resident_ok(const float* gt, int map_w, int map_h, int w, int h, const char* who, const char* view) {
+  if (gt) return DPE_OK;
+  if (map_w == 0) {
+    g_err = std::string(who) + ": no rendered map (" + view + " comes first, or pass gt)";
+    return DPE_ERR_STATE;
+  }
+  if (map_w != w || map_h != h) {
+    g_err = std::string(who) + ": the size differs from the rendered map's";
+    return DPE_ERR_ARG;
+  }
+  return DPE_OK;
 }
 
 // dpe_cloud_normals.  Timings: [0] stage, [1] build, [2] normals, [3] download
@@ -499,81 +544,6 @@ int normals_run(DpeContext* c, const float* xyz, size_t n, float radius, int min
   return timer_finish(c);
 }
 
-// dpe_cloud_render_view_normals of the staged scan and its normals.  Timings: [1] render, [3] download
-int render_view_normals(DpeContext* c, const DpeCamera& cam, int splat, float* depth_out, float* normal_out) {
-  RenderStage& r = c->cloud.render;
-  NormalScratch& s = c->cloud.normals;
-  TRY(cloud_begin(c, true));
-  const size_t npx = (size_t)cam.width * (size_t)cam.height, n = r.n;
-  r.map_w = r.map_h = 0;   // the old maps go with the first launch
-  s.map_w = s.map_h = 0;
-  HIPC(r.map.ensure(npx));
-  HIPC(s.zb.ensure(npx));
-  HIPC(s.winner.ensure(npx));
-  HIPC(s.map.ensure(3 * npx));
-  LAUNCH(k_render_clear64, cloud_blocks(npx), c, s.zb.p, npx);
-  if (n > 0) LAUNCH(k_render_splat_idx, cloud_blocks(n), c, c->cloud.pts[0].p, (int)n, cam, splat, s.zb.p);
-  LAUNCH(k_render_finish_idx, cloud_blocks(npx), c, s.zb.p, npx, r.map.p, s.winner.p);
-  LAUNCH(k_render_normals, cloud_blocks(npx), c, c->cloud.pts[0].p, s.staged.p, s.winner.p, npx, cam, s.map.p);
-  TRY(timer_mark(c, 1));
-  if (depth_out) HIPC(hipMemcpyAsync(depth_out, r.map.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (normal_out) HIPC(hipMemcpyAsync(normal_out, s.map.p, 3 * npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  TRY(timer_mark(c, 3));
-  HIPC(hipStreamSynchronize(c->stream));
-  r.map_w = s.map_w = cam.width;
-  r.map_h = s.map_h = cam.height;
-  return timer_finish(c);
-}
-
-// dpe_normal_score; gt == nullptr: against the resident normal map.  Timings: [0] upload, [2] score, [3] download
-int normal_score(DpeContext* c, const float* est, const float* gt, int w, int h, const NormalTaus& T, DpeNormalScore* out,
-                 float* err) {
-  NormalScratch& v = c->cloud.normals;
-  TRY(cloud_begin(c, true));
-  const size_t npx = (size_t)w * (size_t)h, blocks = cloud_blocks(npx);
-  HIPC(v.est.ensure(3 * npx));
-  if (gt) HIPC(v.gt.ensure(3 * npx));
-  if (err) HIPC(v.err.ensure(npx));
-  HIPC(v.part[0].ensure(blocks * kNormalTerms));
-  HIPC(v.part[1].ensure((size_t)cloud_blocks(blocks) * kNormalTerms));
-  HIPC(v.cnt.ensure(kNormalCounters));
-  if (v.edges.n == 0) {   // the table of the one host function, uploaded once per context
-    float E[kNormalBins];
-    normal_edges(E);
-    HIPC(v.edges.ensure(kNormalBins));
-    HIPC(hipMemcpyAsync(v.edges.p, E, sizeof E, hipMemcpyHostToDevice, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));   // E leaves the stack
-  }
-  HIPC(hipMemcpyAsync(v.est.p, est, 3 * npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (gt) HIPC(hipMemcpyAsync(v.gt.p, gt, 3 * npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPC(hipMemsetAsync(v.cnt.p, 0, kNormalCounters * sizeof(unsigned long long), c->stream));
-  TRY(timer_mark(c, 0));
-  LAUNCH(k_normal_score, blocks, c, v.est.p, gt ? v.gt.p : v.map.p, npx, T, v.edges.p, v.part[0].p, v.cnt.p,
-         err ? v.err.p : nullptr);
-  int at;
-  TRY(tree_reduce<kNormalTerms>(c, v.part, blocks, &at));
-  TRY(timer_mark(c, 2));
-  double sums[kNormalTerms];
-  unsigned long long counts[kNormalCounters];
-  HIPC(hipMemcpyAsync(sums, v.part[at].p, sizeof sums, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(counts, v.cnt.p, sizeof counts, hipMemcpyDeviceToHost, c->stream));
-  if (err) HIPC(hipMemcpyAsync(err, v.err.p, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  TRY(timer_mark(c, 3));
-  HIPC(hipStreamSynchronize(c->stream));
-  DpeNormalScore s;
-  memset(&s, 0, sizeof s);
-  s.n_px = (long long)npx;
-  s.n_gt = (long long)counts[0];
-  s.n_est = (long long)counts[1];
-  s.n_both = (long long)counts[2];
-  for (int k = 0; k < T.n; ++k) s.within[k] = (long long)counts[3 + k];
-  for (int b = 0; b < kNormalBins; ++b) s.hist[b] = (long long)counts[3 + DPE_NORMAL_MAX_TAU + b];
-  s.sum_dist = sums[0];
-  s.sum_dist_sq = sums[1];
-  *out = s;
-  return timer_finish(c);
-}
-
 }  // namespace
 
 extern "C" int dpe_cloud_normals(DpeContext* c, const float* xyz, size_t n, float radius, int min_nb, float* normal_out,
@@ -592,17 +562,12 @@ extern "C" int dpe_cloud_render_stage_normals(DpeContext* c, const float* xyz, c
 
 extern "C" int dpe_cloud_render_view_normals(DpeContext* c, const DpeCamera* cam, int splat, float* depth_out,
                                              float* normal_out) {
-  const bool ok = cam && cam->width >= 1 && cam->height >= 1 && splat >= 0 && splat <= DPE_DEPTH_MAX_SPLAT;
-  TRY(enter(c, ok, "dpe_cloud_render_view_normals: bad argument"));
-  if (c->cloud.resident != CloudResident::RenderScan) {
-    g_err = "dpe_cloud_render_view_normals: no staged cloud (dpe_cloud_render_stage_normals comes first)";
-    return DPE_ERR_STATE;
-  }
+  TRY(render_enter(c, cam, splat, "dpe_cloud_render_view_normals", "dpe_cloud_render_stage_normals"));
   if (!c->cloud.normals.has_staged) {
     g_err = "dpe_cloud_render_view_normals: no staged normals (dpe_cloud_render_stage_normals comes first)";
     return DPE_ERR_STATE;
   }
-  return render_view_normals(c, *cam, splat, depth_out, normal_out);
+  return render_view(c, *cam, splat, true, depth_out, normal_out);
 }
 
 extern "C" int dpe_normal_score(DpeContext* c, const float* est, const float* gt, int w, int h, const float* cos_tau, int n_tau,
@@ -616,18 +581,9 @@ extern "C" int dpe_normal_score(DpeContext* c, const float* est, const float* gt
   }
   T.n = n_tau;
   TRY(enter(c, ok, "dpe_normal_score: bad argument"));
-  if (!gt) {
-    const NormalScratch& s = c->cloud.normals;
-    if (s.map_w == 0) {
-      g_err = "dpe_normal_score: no rendered map (dpe_cloud_render_view_normals comes first, or pass gt)";
-      return DPE_ERR_STATE;
-    }
-    if (s.map_w != w || s.map_h != h) {
-      g_err = "dpe_normal_score: the size differs from the rendered map's";
-      return DPE_ERR_ARG;
-    }
-  }
-  return normal_score(c, est, gt, w, h, T, out, err);
+  const NormalScratch& s = c->cloud.normals;
+  TRY(score_resident_ok(gt, s.map_w, s.map_h, w, h, "dpe_normal_score", "dpe_cloud_render_view_normals"));
+  return score_run<NormalMetric>(c, est, gt, s.map.p, w, h, T, out, err);
 }
 
 extern "C" int dpe_cloud_render_stage(DpeContext* c, const float* xyz, size_t n) {
@@ -636,13 +592,8 @@ extern "C" int dpe_cloud_render_stage(DpeContext* c, const float* xyz, size_t n)
 }
 
 extern "C" int dpe_cloud_render_view(DpeContext* c, const DpeCamera* cam, int splat, float* depth_out) {
-  const bool ok = cam && cam->width >= 1 && cam->height >= 1 && splat >= 0 && splat <= DPE_DEPTH_MAX_SPLAT;
-  TRY(enter(c, ok, "dpe_cloud_render_view: bad argument"));
-  if (c->cloud.resident != CloudResident::RenderScan) {
-    g_err = "dpe_cloud_render_view: no staged cloud (dpe_cloud_render_stage comes first)";
-    return DPE_ERR_STATE;
-  }
-  return render_view(c, *cam, splat, depth_out);
+  TRY(render_enter(c, cam, splat, "dpe_cloud_render_view", "dpe_cloud_render_stage"));
+  return render_view(c, *cam, splat, false, depth_out, nullptr);
 }
 
 extern "C" int dpe_depth_score(DpeContext* c, const float* est, const float* gt, int w, int h, const float* tau, int n_tau,
@@ -658,18 +609,9 @@ extern "C" int dpe_depth_score(DpeContext* c, const float* est, const float* gt,
   T.n = n_tau;
   T.mode = mode;
   TRY(enter(c, ok, "dpe_depth_score: bad argument"));
-  if (!gt) {
-    const RenderStage& r = c->cloud.render;
-    if (r.map_w == 0) {
-      g_err = "dpe_depth_score: no rendered map (dpe_cloud_render_view comes first, or pass gt)";
-      return DPE_ERR_STATE;
-    }
-    if (r.map_w != w || r.map_h != h) {
-      g_err = "dpe_depth_score: the size differs from the rendered map's";
-      return DPE_ERR_ARG;
-    }
-  }
-  return depth_score(c, est, gt, w, h, T, out, err);
+  const RenderStage& r = c->cloud.render;
+  TRY(score_resident_ok(gt, r.map_w, r.map_h, w, h, "dpe_depth_score", "dpe_cloud_render_view"));
+  return score_run<DepthMetric>(c, est, gt, reinterpret_cast<const float*>(r.map.p), w, h, T, out, err);
 }
 
 extern "C" int dpe_cloud_nn_index(DpeContext* c, const float* query, size_t n, const float* target, size_t m, float radius,

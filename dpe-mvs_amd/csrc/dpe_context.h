@@ -260,10 +260,13 @@ struct RenderStage {
   DevArr<uint32_t> map;              // the z-buffer of the last view, after k_render_finish the map f32 [h][w]
   int map_w = 0, map_h = 0;          // 0: no map rendered yet
 };
+// dpe_depth_score and dpe_normal_score (score_run): every call uploads or zeroes what it reads here, so nothing in
+// these buffers is resident between calls and the two scores share them.  The resident maps are render.map and
+// normals.map
 struct ScoreScratch {
-  DevArr<float> est, gt, err;        // dpe_depth_score: the caller's maps and the error map
-  DevArr<double> part[2];            // the three sums' partials, level by level
-  DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16]
+  DevArr<float> est, gt, err;        // the caller's maps and the error map
+  DevArr<double> part[2];            // the sums' partials, level by level
+  DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16], then the metric's bins
 };
 // the normal-map evaluation (pass_normals.h): the cloud of dpe_cloud_normals is pts[0] and its grid st / tcnt; a staged
 // scan's normals sit beside pts[0]; a view with normals renders into `zb` first and leaves the depth map in render.map
@@ -277,10 +280,7 @@ struct NormalScratch {
   DevArr<int> winner;                // per pixel the winning point, -1 where empty
   DevArr<float> map;                 // the rendered normal map, f32 [h][w][3]
   int map_w = 0, map_h = 0;          // 0: no normal map rendered yet
-  DevArr<float> est, gt, err;        // dpe_normal_score: the caller's maps and the error map
-  DevArr<float> edges;               // the 180 bin edges, uploaded once
-  DevArr<double> part[2];            // the two sums' partials, level by level
-  DevArr<unsigned long long> cnt;    // n_gt, n_est, n_both, within[16], hist[180]
+  DevArr<float> edges;               // dpe_normal_score: the 180 bin edges, uploaded once
 };
 // what stays in pts[] for later calls.  The calls that restage pts[] (nn, pair, index, voxel, normals, icp_stage,
 // render_stage, render_stage_normals) end it; icp_step, render_view, render_view_normals, depth_score and normal_score

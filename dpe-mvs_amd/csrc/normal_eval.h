@@ -152,11 +152,6 @@ DPE_CHD void normal_orient(const DpeCamera& cam, float x, float y, float z, cons
   out[2] = flip ? -n[2] : n[2];
 }
 
-// the z-buffer word of the render with winners: bits(z) << 32 | point index; its minimum is the lexicographic
-// minimum of (bits(z), index)
-constexpr unsigned long long kNormalEmptyWord = ((unsigned long long)kDepthEmpty << 32) | 0xFFFFFFFFull;
-DPE_CHD unsigned long long normal_word(uint32_t zbits, uint32_t index) { return ((unsigned long long)zbits << 32) | index; }
-
 // THE bin edges: E[b] = (float)cos(b degrees), b = 0..179 (E[0] = 1 is no edge).  Host only; the device gets the table
 inline void normal_edges(float* E) {
   for (int b = 0; b < kNormalBins; ++b) E[b] = (float)std::cos((double)b * 3.14159265358979323846 / 180.0);
@@ -200,5 +195,37 @@ DPE_CHD void normal_terms(const NormalPixel& p, double* t) {
 }
 
 DPE_CHD float normal_error_code(const NormalPixel& p) { return p.both ? p.c : (p.gt_ok ? -2.0f : -3.0f); }
+
+// the thresholds of one score as the kernel takes them: cosines
+struct NormalTaus {
+  float c[DPE_NORMAL_MAX_TAU];
+  int n;
+};
+
+// The normal metric as the generic score sees it (k_map_score, host/map_eval.h): three floats per pixel, two sums and
+// the histogram of kNormalBins bins over the edge table E.  The counters are DepthMetric's, then the bins
+struct NormalMetric {
+  static constexpr int kChannels = 3, kTerms = kNormalTerms, kMaxTau = DPE_NORMAL_MAX_TAU, kBins = kNormalBins;
+  static constexpr int kCounters = 3 + kMaxTau + kBins;
+  using Pixel = NormalPixel;
+  using Taus = NormalTaus;
+  using Score = DpeNormalScore;
+  static DPE_CHD Pixel pixel(const float* est, const float* gt) { return normal_pixel(est[0], est[1], est[2], gt[0], gt[1], gt[2]); }
+  static DPE_CHD bool hit(const Pixel& p, const float*, const Taus& T, int k) { return p.both && p.c > T.c[k]; }
+  static DPE_CHD void terms(const Pixel& p, double* t) { normal_terms(p, t); }
+  static DPE_CHD float error_code(const Pixel& p) { return normal_error_code(p); }
+  static void edges(float* E) { normal_edges(E); }
+  static DPE_CHD int bin(const float* E, const Pixel& p) { return normal_bin(E, p.c); }
+  static void store(Score& s, const unsigned long long* counts, const double* sums) {
+    for (int b = 0; b < kBins; ++b) s.hist[b] = (long long)counts[3 + kMaxTau + b];
+    s.sum_dist = sums[0];
+    s.sum_dist_sq = sums[1];
+  }
+  static void add(Score& total, const Score& s) {
+    for (int b = 0; b < kBins; ++b) total.hist[b] += s.hist[b];
+    total.sum_dist = total.sum_dist + s.sum_dist;
+    total.sum_dist_sq = total.sum_dist_sq + s.sum_dist_sq;
+  }
+};
 
 }  // namespace dpe

@@ -88,37 +88,11 @@ int main(int argc, char** argv) {
   else std::printf("cloud of %llu points, splat %d", (unsigned long long)n, o.splat);
   std::printf(", %s thresholds", o.mode == DPE_DEPTH_TAU_REL ? "relative" : "absolute");
   for (int k = 0; k < o.n_tau; ++k) std::printf(" %.9g", (double)o.tau[k]);
-  std::printf("\n%8s %11s %10s %10s %10s %12s %12s %12s", "image", "size", "n_gt", "n_est", "n_both", "mae", "mre", "rmse");
-  for (int k = 0; k < o.n_tau; ++k) {
-    char acc[32], comp[32];
-    std::snprintf(acc, sizeof acc, "acc[%d]", k);
-    std::snprintf(comp, sizeof comp, "comp[%d]", k);
-    std::printf(" %10s %10s", acc, comp);
-  }
-  std::printf("\n");
-  for (size_t i = 0; i < n_img; ++i) {
-    char name[32], size[32];
-    std::snprintf(name, sizeof name, "%08d", rows[i].id);
-    std::snprintf(size, sizeof size, "%dx%d", rows[i].width, rows[i].height);
-    print_row(name, size, rows[i].score, o.n_tau);
-  }
-  print_row("total", "-", total, o.n_tau);
-  if (json) {
-    FILE* f = std::fopen(json, "w");
-    if (!f) { std::fprintf(stderr, "dpe_depth_eval: cannot write %s\n", json); return 1; }
+  return cli_eval_report("dpe_depth_eval", " %12s %12s %12s", {"mae", "mre", "rmse"}, "acc", rows.data(), n_img, total, o.n_tau, json,
+                         print_row, [&](FILE* f) {
     std::fprintf(f, "{\"map\": \"%s\", \"relative\": %s, \"splat\": %d, \"n_gt_points\": %llu, \"tau\": [", map,
                  o.mode == DPE_DEPTH_TAU_REL ? "true" : "false", o.splat, (unsigned long long)n);
     for (int k = 0; k < o.n_tau; ++k) std::fprintf(f, "%s%.17g", k ? ", " : "", (double)o.tau[k]);
-    std::fprintf(f, "], \"images\": [");
-    for (size_t i = 0; i < n_img; ++i) {
-      std::fprintf(f, "%s{\"id\": %d, \"width\": %d, \"height\": %d, ", i ? ", " : "", rows[i].id, rows[i].width, rows[i].height);
-      json_score(f, rows[i].score, o.n_tau);
-      std::fprintf(f, "}");
-    }
-    std::fprintf(f, "], \"total\": {");
-    json_score(f, total, o.n_tau);
-    std::fprintf(f, "}}\n");
-    std::fclose(f);
-  }
-  return 0;
+    std::fprintf(f, "]");
+  }, json_score);
 }

@@ -219,13 +219,12 @@ bool cloud_solve(const DpeIcpSums& s, const double* o_s, const double* o_t, doub
 bool cloud_register_in(DpeContext* ctx, const float* src, size_t n, const float* tgt, size_t m, const DpeCloudRegOptions& opt,
                        DpeCloudReg* out, std::string& err);
 // depth_eval.cpp: the render of a scan into one view and the score of one map (dpe_cloud_render_view and
-// dpe_depth_score of dpe_mvs.h) as loops over the same arithmetic (csrc/depth_eval.h), what is derived from a score,
-// and total += s
+// dpe_depth_score of dpe_mvs.h) as loops over the same arithmetic (csrc/depth_eval.h; the loops both map evaluations
+// share are map_eval.h's) and what is derived from a score
 bool cloud_render(const float* xyz, size_t n, const DpeCamera& cam, int splat, float* out, std::string& err);
 bool depth_score(const float* est, const float* gt, int w, int h, const float* tau, int n_tau, int mode, DpeDepthScore* out,
                  float* errmap, std::string& err);
 void depth_stats(const DpeDepthScore& s, int n_tau, DpeDepthStats* out);
-void depth_add(DpeDepthScore* total, const DpeDepthScore& s);
 // what the folder tools share: the image ids DPE/<8 digits> of `dense` that hold `map`, ascending (`who` leads the
 // message), and the camera of image `id` at the size w x h of its map (map_view's arithmetic)
 bool eval_list(const char* who, const std::string& dense, const std::string& map, std::vector<int>& ids, std::string& err);
@@ -233,7 +232,7 @@ bool map_camera(const std::string& dense, int id, int w, int h, DpeCamera& cam, 
 // a 3-D '<f4' .npy v1.0 in C order, [h][w][3]; refusals as read_npy_f32's
 bool read_npy_f32x3(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err);
 // normal_eval.cpp: the normal-map evaluation (dpe_cloud_normals, dpe_cloud_render_view_normals and dpe_normal_score of
-// dpe_mvs.h) as loops over the same arithmetic (csrc/normal_eval.h), what is derived from a score, and total += s
+// dpe_mvs.h) as loops over the same arithmetic (csrc/normal_eval.h) and what is derived from a score
 bool cloud_normals(const float* xyz, size_t n, float radius, int min_nb, float* normal, int32_t* count, long long* sums,
                    std::string& err);
 bool cloud_render_normals(const float* xyz, const float* normals, size_t n, const DpeCamera& cam, int splat, float* depth,
@@ -241,6 +240,5 @@ bool cloud_render_normals(const float* xyz, const float* normals, size_t n, cons
 bool normal_score(const float* est, const float* gt, int w, int h, const float* cos_tau, int n_tau, DpeNormalScore* out,
                   float* errmap, std::string& err);
 void normal_stats(const DpeNormalScore& s, int n_tau, DpeNormalStats* out);
-void normal_add(DpeNormalScore* total, const DpeNormalScore& s);
 
 }  // namespace dpe_host

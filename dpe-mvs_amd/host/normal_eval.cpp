@@ -1,25 +1,17 @@
 // normal_eval.cpp — the normal-map evaluation on the host: the normals of a scan's points by PCA over the hashed grid,
 // the render of the winning point's normal into one view and the score of one normal map as include/dpe_mvs.h states
 // them (dpe_cloud_normals, dpe_cloud_render_view_normals, dpe_normal_score), with the pairwise tree taken literally,
-// what is derived from a score, and the evaluation of a dense folder over either path.  The loops are the yardstick of
-// the kernels (csrc/pass_normals.h) and what runs without a GPU; the arithmetic is csrc/normal_eval.h's, which the
+// what is derived from a score, and the evaluation of a dense folder over either path.  The loops, map_eval.h's over
+// NormalMetric beside the point normals' own, are the yardstick of the kernels (csrc/pass_normals.h, csrc/pass_render.h)
+// and what runs without a GPU; the arithmetic is csrc/normal_eval.h's, which the
 // kernels share.  No counterpart in the reference.
-#include "host.h"
+#include "map_eval.h"
 #include "cloud_index.h"
-#include "pairwise_tree.h"
-#include "parallel.h"
 #include "../csrc/normal_eval.h"
 
-#include <algorithm>
 #include <atomic>
 #include <climits>
 #include <cmath>
-#include <cstring>
-#include <filesystem>
-#include <string>
-#include <vector>
-
-namespace fs = std::filesystem;
 
 namespace dpe_host {
 
@@ -27,7 +19,7 @@ namespace {
 
 using dpe::kNormalBins;
 using dpe::kNormalSums;
-using dpe::kNormalTerms;
+using dpe::NormalMetric;
 
 // points [i0, i1) of the cloud the index was built from: k_cloud_normal's walk, the same no-double-count rule
 void normals_range(const CloudIndex& ix, const float* xyz, size_t i0, size_t i1, double S, int min_nb, float* normal,
@@ -56,24 +48,6 @@ void normals_range(const CloudIndex& ix, const float* xyz, size_t i0, size_t i1,
   }
 }
 
-// points [i0, i1) into the z-buffer of words bits(z) << 32 | index
-void render_range(const float* xyz, size_t i0, size_t i1, const DpeCamera& cam, int s, unsigned long long* zb) {
-  const int w = cam.width, h = cam.height;
-  for (size_t i = i0; i < i1; ++i) {
-    int cx, cy;
-    uint32_t z;
-    if (!dpe::depth_point(cam, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cx, cy, z)) continue;
-    const unsigned long long word = dpe::normal_word(z, (uint32_t)i);
-    const int x0 = std::max(0, cx - s), x1 = std::min(w - 1, cx + s);
-    const int y0 = std::max(0, cy - s), y1 = std::min(h - 1, cy + s);
-    for (int y = y0; y <= y1; ++y) {
-      unsigned long long* row = zb + (size_t)y * (size_t)w;
-      for (int x = x0; x <= x1; ++x)
-        if (word < row[x]) row[x] = word;
-    }
-  }
-}
-
 bool score_args_ok(const float* cos_tau, int n_tau, std::string& err) {
   if (!cos_tau || n_tau < 1 || n_tau > DPE_NORMAL_MAX_TAU) { err = "normal_score: 1 to 16 thresholds expected"; return false; }
   for (int k = 0; k < n_tau; ++k)
@@ -97,8 +71,6 @@ bool render_args_ok(const float* xyz, const float* normals, size_t n, const DpeC
   if (splat < 0 || splat > DPE_DEPTH_MAX_SPLAT) { err = "cloud_render_normals: the splat half-width must be 0 to 8"; return false; }
   return true;
 }
-
-constexpr size_t kRenderPerThread = 1u << 16;   // fewer points than this per thread are not worth a z-buffer
 
 }  // namespace
 
@@ -129,14 +101,9 @@ bool cloud_normals(const float* xyz, size_t n, float radius, int min_nb, float* 
 bool cloud_render_normals(const float* xyz, const float* normals, size_t n, const DpeCamera& cam, int splat, float* depth,
                           float* normal, std::string& err) {
   if (!render_args_ok(xyz, normals, n, &cam, splat, err)) return false;
-  const size_t npx = (size_t)cam.width * (size_t)cam.height;
-  const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)host_threads(), n / kRenderPerThread));
-  // one z-buffer of words per thread over its share of the points, merged by minimum below
-  std::vector<unsigned long long> zb((size_t)nt * npx, dpe::kNormalEmptyWord);
-  run_on_threads(nt, [&](int t) { render_range(xyz, n * t / nt, n * (t + 1) / nt, cam, splat, zb.data() + (size_t)t * npx); });
-  for (size_t p = 0; p < npx; ++p) {
-    unsigned long long word = zb[p];
-    for (int t = 1; t < nt; ++t) word = std::min(word, zb[(size_t)t * npx + p]);
+  const std::vector<unsigned long long> zb = render_zbuffer<unsigned long long>(xyz, n, cam, splat);
+  for (size_t p = 0; p < zb.size(); ++p) {
+    const unsigned long long word = zb[p];
     uint32_t z = (uint32_t)(word >> 32);
     const bool empty = z == dpe::kDepthEmpty;
     if (empty) z = 0u;
@@ -157,43 +124,18 @@ bool normal_score(const float* est, const float* gt, int w, int h, const float* 
                   float* errmap, std::string& err) {
   if (!est || !gt || w < 1 || h < 1 || !out) { err = "normal_score: bad argument"; return false; }
   if (!score_args_ok(cos_tau, n_tau, err)) return false;
-  DpeNormalScore s;
-  std::memset(&s, 0, sizeof s);   // the structs are compared as bytes
-  float E[kNormalBins];
-  dpe::normal_edges(E);
-  const size_t npx = (size_t)w * (size_t)h;
-  PairwiseTree<kNormalTerms> tree;
-  for (size_t i = 0; i < npx; ++i) {
-    const float* e = est + 3 * i;
-    const float* g = gt + 3 * i;
-    const dpe::NormalPixel p = dpe::normal_pixel(e[0], e[1], e[2], g[0], g[1], g[2]);
-    s.n_gt += p.gt_ok;
-    s.n_est += p.est_ok;
-    s.n_both += p.both;
-    for (int k = 0; k < n_tau; ++k) s.within[k] += p.both && p.c > cos_tau[k];
-    if (p.both) s.hist[dpe::normal_bin(E, p.c)] += 1;
-    double t[kNormalTerms];
-    dpe::normal_terms(p, t);
-    tree.push(t);
-    if (errmap) errmap[i] = dpe::normal_error_code(p);
-  }
-  double sums[kNormalTerms];
-  tree.finish(sums);
-  s.n_px = (long long)npx;
-  s.sum_dist = sums[0];
-  s.sum_dist_sq = sums[1];
-  *out = s;
+  dpe::NormalTaus T{};
+  std::copy(cos_tau, cos_tau + n_tau, T.c);
+  T.n = n_tau;
+  map_score<NormalMetric>(est, gt, w, h, T, out, errmap);
   return true;
 }
 
 void normal_stats(const DpeNormalScore& s, int n_tau, DpeNormalStats* out) {
   std::memset(out, 0, sizeof *out);
-  const double nb = (double)s.n_both, ng = (double)s.n_gt;
-  for (int k = 0; k < n_tau && k < DPE_NORMAL_MAX_TAU; ++k) {
-    out->share[k] = s.n_both ? (double)s.within[k] / nb : 0.0;
-    out->completeness[k] = s.n_gt ? (double)s.within[k] / ng : 0.0;
-  }
+  stats_shares<NormalMetric>(s, n_tau, out->share, out->completeness);
   if (!s.n_both) return;
+  const double nb = (double)s.n_both;
   out->mean_cos_dist = s.sum_dist / nb;
   // from the histogram: a pixel of bin b stands at b + 0.5 degrees
   double weighted = 0.0;
@@ -207,102 +149,45 @@ void normal_stats(const DpeNormalScore& s, int n_tau, DpeNormalStats* out) {
   out->mean_deg = weighted / nb;
 }
 
-void normal_add(DpeNormalScore* total, const DpeNormalScore& s) {
-  total->n_px += s.n_px;
-  total->n_gt += s.n_gt;
-  total->n_est += s.n_est;
-  total->n_both += s.n_both;
-  for (int k = 0; k < DPE_NORMAL_MAX_TAU; ++k) total->within[k] += s.within[k];
-  for (int b = 0; b < kNormalBins; ++b) total->hist[b] += s.hist[b];
-  total->sum_dist = total->sum_dist + s.sum_dist;
-  total->sum_dist_sq = total->sum_dist_sq + s.sum_dist_sq;
-}
-
 namespace {
 
-const char* map_name_of(const char* name) { return name && *name ? name : "normal.npy"; }
-
-bool normal_eval(const DpeNormalEvalOptions& o, const float* gt_xyz, size_t n_gt, DpeNormalImage* rows, size_t cap, size_t* n_rows,
-                 DpeNormalScore* total, std::string& err) {
-  if (!o.dense_folder || !n_rows || !total || (!rows && cap)) { err = "normal_eval: bad argument"; return false; }
-  if (!score_args_ok(o.cos_tau, o.n_tau, err)) return false;
-  const bool from_maps = o.gt_maps_dir && *o.gt_maps_dir;
-  if (!from_maps) {
-    if (!normals_args_ok(gt_xyz, n_gt, o.radius, o.min_nb, err)) return false;
-    if (o.splat < 0 || o.splat > DPE_DEPTH_MAX_SPLAT) { err = "cloud_render_normals: the splat half-width must be 0 to 8"; return false; }
-  }
-  const std::string dense = o.dense_folder, map = map_name_of(o.map_name);
-  std::vector<int> ids;
-  if (!eval_list("normal_eval", dense, map, ids, err)) return false;
-  *n_rows = ids.size();
-  if (cap < ids.size()) { err = "normal_eval: room for fewer rows than images"; return false; }
-  OwnedContext own(o.gpu_index, "normal_eval", err);
-  if (!own.ok) return false;
-  DpeContext* ctx = own.ctx;
-  auto device_failed = [&]() { err = std::string("normal_eval: ") + dpe_last_error(); return false; };
-  // the scan's normals, once, and the staging of scan and normals
+// map_eval's hooks; the scan's normals are estimated once per folder
+struct NormalEval {
+  using Metric = NormalMetric;
+  using Options = DpeNormalEvalOptions;
+  using Image = DpeNormalImage;
+  static constexpr const char *kWho = "normal_eval", *kMap = "normal.npy", *kGtName = "normal_gt.npy", *kErrName = "normal_error.npy";
   std::vector<float> gt_normals;
-  if (!from_maps) {
-    gt_normals.resize(3 * n_gt);
-    std::vector<int32_t> counts(n_gt);
-    if (ctx) {
-      if (dpe_cloud_normals(ctx, gt_xyz, n_gt, o.radius, o.min_nb, gt_normals.data(), counts.data(), nullptr) != 0) return device_failed();
-      if (dpe_cloud_render_stage_normals(ctx, gt_xyz, gt_normals.data(), n_gt) != 0) return device_failed();
-    } else if (!cloud_normals(gt_xyz, n_gt, o.radius, o.min_nb, gt_normals.data(), counts.data(), nullptr, err)) {
-      return false;
-    }
+  static bool read(const std::string& path, std::vector<float>& data, int& w, int& h, std::string& err) {
+    return read_npy_f32x3(path, data, w, h, err);
   }
-  DpeNormalScore sum;
-  std::memset(&sum, 0, sizeof sum);
-  std::vector<float> est, gt, errmap;
-  std::vector<DpeNormalImage> done(ids.size());   // a failure leaves the caller's rows alone
-  for (size_t i = 0; i < ids.size(); ++i) {
-    const fs::path rf = fs::path(dense) / "DPE" / fmt_index(ids[i]);
-    int w = 0, h = 0;
-    if (!read_npy_f32x3((rf / map).string(), est, w, h, err)) return false;
-    const size_t npx = (size_t)w * (size_t)h;
-    const bool want_gt = !ctx || from_maps || o.write_maps;   // the ground truth on the host
-    if (want_gt) gt.resize(3 * npx);
-    if (o.write_maps) errmap.resize(npx);
-    if (from_maps) {
-      int gw = 0, gh = 0;
-      const std::string path = (fs::path(o.gt_maps_dir) / (fmt_index(ids[i]) + ".npy")).string();
-      if (!read_npy_f32x3(path, gt, gw, gh, err)) return false;
-      if (gw != w || gh != h) { err = "normal_eval: size mismatch: " + path + " is not of the size of " + (rf / map).string(); return false; }
-    } else {
-      DpeCamera cam;
-      if (!map_camera(dense, ids[i], w, h, cam, err)) return false;
-      if (ctx) {
-        if (dpe_cloud_render_view_normals(ctx, &cam, o.splat, nullptr, want_gt ? gt.data() : nullptr) != 0) return device_failed();
-      } else if (!cloud_render_normals(gt_xyz, gt_normals.data(), n_gt, cam, o.splat, nullptr, gt.data(), err)) {
-        return false;
-      }
-    }
-    DpeNormalImage row;
-    std::memset(&row, 0, sizeof row);
-    row.id = ids[i];
-    row.width = w;
-    row.height = h;
-    float* em = o.write_maps ? errmap.data() : nullptr;
-    if (ctx) {
-      if (dpe_normal_score(ctx, est.data(), from_maps ? gt.data() : nullptr, w, h, o.cos_tau, o.n_tau, &row.score, em) != 0)
-        return device_failed();
-    } else if (!normal_score(est.data(), gt.data(), w, h, o.cos_tau, o.n_tau, &row.score, em, err)) {
-      return false;
-    }
-    if (o.write_maps) {
-      const std::vector<int64_t> hw3 = {h, w, 3}, hw = {h, w};
-      if (!write_npy((rf / "normal_gt.npy").string(), gt.data(), hw3, "<f4", 4, err) ||
-          !write_npy((rf / "normal_error.npy").string(), errmap.data(), hw, "<f4", 4, err))
-        return false;
-    }
-    done[i] = row;
-    normal_add(&sum, row.score);
+  bool args_ok(const Options& o, const float* xyz, size_t n, bool from_maps, std::string& err) {
+    if (!score_args_ok(o.cos_tau, o.n_tau, err)) return false;
+    if (from_maps) return true;
+    if (!normals_args_ok(xyz, n, o.radius, o.min_nb, err)) return false;
+    if (o.splat < 0 || o.splat > DPE_DEPTH_MAX_SPLAT) { err = "cloud_render_normals: the splat half-width must be 0 to 8"; return false; }
+    return true;
   }
-  std::copy(done.begin(), done.end(), rows);
-  *total = sum;
-  return true;
-}
+  bool prepare(DpeContext* ctx, const Options& o, const float* xyz, size_t n, std::string& err) {
+    gt_normals.resize(3 * n);
+    std::vector<int32_t> counts(n);
+    if (!ctx) return cloud_normals(xyz, n, o.radius, o.min_nb, gt_normals.data(), counts.data(), nullptr, err);
+    return dpe_cloud_normals(ctx, xyz, n, o.radius, o.min_nb, gt_normals.data(), counts.data(), nullptr) == 0 &&
+           dpe_cloud_render_stage_normals(ctx, xyz, gt_normals.data(), n) == 0;
+  }
+  int render_device(DpeContext* ctx, const DpeCamera& cam, const Options& o, float* gt) {
+    return dpe_cloud_render_view_normals(ctx, &cam, o.splat, nullptr, gt);
+  }
+  bool render_host(const float* xyz, size_t n, const DpeCamera& cam, const Options& o, float* gt, std::string& err) {
+    return cloud_render_normals(xyz, gt_normals.data(), n, cam, o.splat, nullptr, gt, err);
+  }
+  int score_device(DpeContext* ctx, const float* est, const float* gt, int w, int h, const Options& o, DpeNormalScore* out, float* em) {
+    return dpe_normal_score(ctx, est, gt, w, h, o.cos_tau, o.n_tau, out, em);
+  }
+  bool score_host(const float* est, const float* gt, int w, int h, const Options& o, DpeNormalScore* out, float* em, std::string& err) {
+    return normal_score(est, gt, w, h, o.cos_tau, o.n_tau, out, em, err);
+  }
+};
 
 }  // namespace
 
@@ -340,23 +225,13 @@ void dpe_host_normal_stats(const DpeNormalScore* s, int n_tau, DpeNormalStats* o
 }
 
 int dpe_host_read_npy_f32x3(const char* path, float* data, size_t cap, int* w, int* h) {
-  std::string err = "read_npy: bad argument";
-  std::vector<float> v;
-  int mw = 0, mh = 0;
-  if (path && w && h && dpe_host::read_npy_f32x3(path, v, mw, mh, err)) {
-    *w = mw;
-    *h = mh;
-    if (!data) return 0;
-    if (cap >= v.size()) { std::memcpy(data, v.data(), v.size() * sizeof(float)); return 0; }
-    err = "read_npy: room for fewer values than the file holds";
-  }
-  dpe_host::set_last_error(err);
-  return 1;
+  return dpe_host::read_npy_entry(dpe_host::read_npy_f32x3, path, data, cap, w, h);
 }
 
 int dpe_host_normal_eval(const DpeNormalEvalOptions* opt, const float* gt_xyz, size_t n_gt, DpeNormalImage* rows, size_t cap,
                          size_t* n_rows, DpeNormalScore* total) {
-  return dpe_host::c_entry([&](std::string& err) { return opt && dpe_host::normal_eval(*opt, gt_xyz, n_gt, rows, cap, n_rows, total, err); },
+  dpe_host::NormalEval hooks;
+  return dpe_host::c_entry([&](std::string& err) { return opt && dpe_host::map_eval(hooks, *opt, gt_xyz, n_gt, rows, cap, n_rows, total, err); },
                            "normal_eval: bad argument");
 }
 

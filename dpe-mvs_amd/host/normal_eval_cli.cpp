@@ -95,37 +95,11 @@ int main(int argc, char** argv) {
   else std::printf("cloud of %llu points, radius %.9g, min neighbours %d, splat %d", (unsigned long long)n, (double)o.radius, o.min_nb, o.splat);
   std::printf(", thresholds in degrees");
   for (int k = 0; k < o.n_tau; ++k) std::printf(" %.9g", (double)deg[k]);
-  std::printf("\n%8s %11s %10s %10s %10s %12s %10s %10s", "image", "size", "n_gt", "n_est", "n_both", "cos_dist", "median", "mean");
-  for (int k = 0; k < o.n_tau; ++k) {
-    char acc[32], comp[32];
-    std::snprintf(acc, sizeof acc, "within[%d]", k);
-    std::snprintf(comp, sizeof comp, "comp[%d]", k);
-    std::printf(" %10s %10s", acc, comp);
-  }
-  std::printf("\n");
-  for (size_t i = 0; i < n_img; ++i) {
-    char name[32], size[32];
-    std::snprintf(name, sizeof name, "%08d", rows[i].id);
-    std::snprintf(size, sizeof size, "%dx%d", rows[i].width, rows[i].height);
-    print_row(name, size, rows[i].score, o.n_tau);
-  }
-  print_row("total", "-", total, o.n_tau);
-  if (json) {
-    FILE* f = std::fopen(json, "w");
-    if (!f) { std::fprintf(stderr, "dpe_normal_eval: cannot write %s\n", json); return 1; }
+  return cli_eval_report("dpe_normal_eval", " %12s %10s %10s", {"cos_dist", "median", "mean"}, "within", rows.data(), n_img, total,
+                         o.n_tau, json, print_row, [&](FILE* f) {
     std::fprintf(f, "{\"map\": \"normal.npy\", \"splat\": %d, \"radius\": %.9g, \"min_neighbours\": %d, \"n_gt_points\": %llu, \"tau_deg\": [",
                  o.splat, (double)o.radius, o.min_nb, (unsigned long long)n);
     for (int k = 0; k < o.n_tau; ++k) std::fprintf(f, "%s%.9g", k ? ", " : "", (double)deg[k]);
-    std::fprintf(f, "], \"images\": [");
-    for (size_t i = 0; i < n_img; ++i) {
-      std::fprintf(f, "%s{\"id\": %d, \"width\": %d, \"height\": %d, ", i ? ", " : "", rows[i].id, rows[i].width, rows[i].height);
-      json_score(f, rows[i].score, o.n_tau);
-      std::fprintf(f, "}");
-    }
-    std::fprintf(f, "], \"total\": {");
-    json_score(f, total, o.n_tau);
-    std::fprintf(f, "}}\n");
-    std::fclose(f);
-  }
-  return 0;
+    std::fprintf(f, "]");
+  }, json_score);
 }

@@ -1,6 +1,6 @@
 """The bookkeeping of the cloud section (csrc/dpe_cloud.hip): every kernel launch is counted once, whatever call makes
 it, and dpe_cloud_last_timings keeps the slot meanings include/dpe_mvs.h states.  What the calls compute is held to the
-host path by tests/test_cloud_*_gpu.py and tests/test_depth_eval_gpu.py."""
+host path by tests/test_cloud_*_gpu.py, tests/test_depth_eval_gpu.py and tests/test_normal_eval_gpu.py."""
 import math
 
 import numpy as np
@@ -61,6 +61,15 @@ def test_launch_counts_per_call(ctx):
     for (w, h), want in (((16, 16), 1), ((17, 16), 2), ((257, 256), 3)):
         est = np.ones((h, w), F)
         assert launches(lambda: ctx.depth_score(est, est, [0.1])) == want, (w, h)
+        nrm = np.ones((h, w, 3), F)
+        assert launches(lambda: ctx.normal_score(nrm, nrm, [0.5])) == want, (w, h)
+    assert launches(lambda: ctx.cloud_normals(A, R)) == 5                # bounds, 3 build, normal
+    assert launches(lambda: ctx.cloud_normals(nowhere, R)) == 1          # the bounds alone
+    pts = scan(300, 33, 17)
+    assert launches(lambda: ctx.cloud_render_stage(pts, np.ones_like(pts))) == 0
+    assert launches(lambda: ctx.cloud_render_view_normals(cam, 1)) == 4  # clear, splat, finish, normals
+    ctx.cloud_render_stage(np.empty((0, 3), F), np.empty((0, 3), F))
+    assert launches(lambda: ctx.cloud_render_view_normals(cam, 1)) == 3  # an empty scan: no splat
 
 
 def test_timings_contract(ctx):
@@ -89,6 +98,14 @@ def test_timings_contract(ctx):
     timed(lambda: ctx.cloud_render_stage(scan(300, 33, 17)), zero=(1, 2, 3))
     timed(lambda: ctx.cloud_render_view(cam, 1), zero=(0, 2))
     timed(lambda: ctx.depth_score(est, None, [0.1]), zero=(1,))
+    timed(lambda: ctx.cloud_normals(A, R))
+    pts = scan(300, 33, 17)
+    timed(lambda: ctx.cloud_render_stage(pts, np.ones_like(pts)), zero=(1, 2, 3))
+    timed(lambda: ctx.cloud_render_view_normals(cam, 1), zero=(0, 2))
+    timed(lambda: ctx.normal_score(np.ones((17, 33, 3), F), None, [0.5]), zero=(1,))
+    for none in (np.empty((0, 3), F), np.full((5, 3), np.nan, F)):       # no points, or none finite: nothing is timed
+        ctx.cloud_normals(none, R)
+        assert ctx.cloud_timings() == {}
     ctx.cloud_icp_stage(A, np.empty((0, 3), F), R)                       # nothing to match: the step launches and times nothing
     assert ctx.cloud_icp_step(IDENTITY)["matched"] == 0
     assert ctx.cloud_timings() == {}

@@ -114,6 +114,39 @@ def test_device_score_against_the_rendered_map(ctx, name):
     assert same_score(ctx.normal_score(est, None, cos_taus()), host)       # the refusal left the map
 
 
+def test_depth_and_normal_scores_share_their_buffers(ctx):
+    """dpe_depth_score and dpe_normal_score upload into one set of buffers: taken in turn against the resident maps of
+    one view, with a normal score of another size and an explicit gt in between, each gives the host's bits"""
+    pts, nrm, cam, s, want_depth, want_normal, _ = render_normals_case("scatter-65-33-1-4097")
+    rng = np.random.default_rng(8)
+    d_est = (want_depth * (1 + 0.05 * rng.standard_normal(want_depth.shape))).astype(F)
+    d_est[rng.random(want_depth.shape) < 0.1] = np.nan
+    n_est = (want_normal + 0.2 * rng.standard_normal(want_normal.shape)).astype(F)
+    n_est[rng.random(want_normal.shape[:2]) < 0.1] = np.nan
+    host_d, host_d_err = pipeline.score_depth(d_est, want_depth, TAUS, want_error=True)
+    host_n, host_n_err = pipeline.score_normals(n_est, want_normal, cos_taus=cos_taus(), want_error=True)
+    o_est, o_gt, _, _ = score_case("mixed-257-1")
+    host_o, host_o_err = pipeline.score_normals(o_est, o_gt, cos_taus=cos_taus(), want_error=True)
+    assert host_d["n_both"] > 0 and host_n["n_both"] > 0
+    ctx.cloud_render_stage(pts, nrm)
+    ctx.cloud_render_view_normals(cam, s, download=False)
+
+    def depth():
+        got, err = ctx.depth_score(d_est, None, TAUS, want_error=True)
+        assert same_depth_score(got, host_d) and same_bits(err, host_d_err)
+
+    def normal():
+        got, err = ctx.normal_score(n_est, None, cos_taus(), want_error=True)
+        assert same_score(got, host_n) and same_bits(err, host_n_err)
+
+    depth()
+    normal()
+    got, err = ctx.normal_score(o_est, o_gt, cos_taus(), want_error=True)  # 257 x 1: the buffers at another size
+    assert same_score(got, host_o) and same_bits(err, host_o_err)
+    depth()
+    normal()
+
+
 # ------------------------------------------------------------------------------ 4. surfaces on the device
 def test_folder_tool_on_the_device(tmp_path):
     d, ply, maps, sc = normal_folder(tmp_path)
