@@ -23,11 +23,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define DPE_CHD __host__ __device__ __forceinline__
-#else
-#define DPE_CHD inline
-#endif
+#include "chd.h"   // DPE_CHD
 
 namespace dpe {
 

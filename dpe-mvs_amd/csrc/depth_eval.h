@@ -1,12 +1,13 @@
 // depth_eval.h — the arithmetic of the depth-map evaluation (dpe_cloud_render_view and dpe_depth_score of
 // include/dpe_mvs.h, which states the contract) that the host (host/depth_eval.cpp) shares with the kernels
-// (pass_render.h): the projection of a scan point, its centre pixel, the z-buffer's word, the test for a usable depth
+// (pass_render.h): the projection of a scan point and its centre pixel (fusion_world.h's), the z-buffer's word, the test for a usable depth
 // and what one pixel contributes to a score, gathered in DepthMetric for the code that scores any map
 // (k_map_score, host/map_eval.h).  Plain C++, -ffp-contract=off like everything here: every operation below is one
 // rounded single-precision operation with IEEE division, unless a double is written.
 #pragma once
 #include "../../include/dpe_mvs.h"
-#include "cloud_dist.h"   // DPE_CHD, cloud_finite3
+#include "cloud_dist.h"     // cloud_finite3
+#include "fusion_world.h"   // fz_project, fz_pixel
 
 #include <cstring>
 
@@ -29,33 +30,14 @@ DPE_CHD bool depth_ok(float v) {
   return u > 0u && u < kDepthEmpty;
 }
 
-// ProjectCamera in the reference's order: fz_project's expression (fusion_world.h), for host and device
-DPE_CHD void depth_project(const DpeCamera& cam, float x, float y, float z, float& px, float& py, float& depth) {
-  const float tx = cam.R[0] * x + cam.R[1] * y + cam.R[2] * z + cam.t[0];
-  const float ty = cam.R[3] * x + cam.R[4] * y + cam.R[5] * z + cam.t[1];
-  const float tz = cam.R[6] * x + cam.R[7] * y + cam.R[8] * z + cam.t[2];
-  depth = cam.K[6] * tx + cam.K[7] * ty + cam.K[8] * tz;
-  px = (cam.K[0] * tx + cam.K[1] * ty + cam.K[2] * tz) / depth;
-  py = (cam.K[3] * tx + cam.K[4] * ty + cam.K[5] * tz) / depth;
-}
-
-// the centre pixel by fusion's rule (pass_fusion.h): false when the point falls outside a w x h image
-DPE_CHD bool depth_centre(float px, float py, int w, int h, int& cx, int& cy) {
-  const float fx = px + 0.5f, fy = py + 0.5f;
-  if (!(fx > -1.0f && fx < (float)w && fy > -1.0f && fy < (float)h)) return false;
-  cx = (int)fx;
-  cy = (int)fy;
-  return true;
-}
-
 // One scan point in a view: false when it renders nothing, else its centre pixel and the bits of its depth
 DPE_CHD bool depth_point(const DpeCamera& cam, float x, float y, float z, int& cx, int& cy, uint32_t& zbits) {
   if (!cloud_finite3(x, y, z)) return false;
   float px, py, d;
-  depth_project(cam, x, y, z, px, py, d);
+  fz_project(FP3{x, y, z}, cam, px, py, d);
   if (!depth_ok(d)) return false;
   zbits = depth_bits(d);
-  return depth_centre(px, py, cam.width, cam.height, cx, cy);
+  return fz_pixel(px, py, cam.width, cam.height, cx, cy);   // the centre pixel by fusion's rule
 }
 
 // The word of a render's z-buffer and its empty value.  uint32_t: the bits of the depth.  unsigned long long: the

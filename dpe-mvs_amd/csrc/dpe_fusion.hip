@@ -6,6 +6,7 @@
 // is described with the concurrency contract in dpe_mvs.hip.
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <string>
 #include <vector>
 
 #include "pass_fusion.h"
@@ -42,13 +43,23 @@ extern "C" int dpe_fusion_stage(DpeContext* c, const DpeFusionView* views, int n
   return DPE_OK;
 }
 
+// What the entries over the staged views refuse, in this order and with the entry's name in front: nothing staged,
+// a reference view outside them, a source view outside them and (unless self_ok) the reference view among its sources
+static int views_check(DpeContext* c, const char* who, int ref, const int* src, int ns, bool self_ok) {
+  const int n = c->fz.n;
+  if (n < 1) { g_err = std::string(who) + ": nothing staged"; return DPE_ERR_STATE; }
+  if (ref < 0 || ref >= n) { g_err = std::string(who) + ": bad reference view"; return DPE_ERR_ARG; }
+  for (int j = 0; j < ns; ++j) {
+    if (src[j] < 0 || src[j] >= n) { g_err = std::string(who) + ": bad source view"; return DPE_ERR_ARG; }
+    if (!self_ok && src[j] == ref) { g_err = std::string(who) + ": the reference view is among its sources"; return DPE_ERR_ARG; }
+  }
+  return DPE_OK;
+}
+
 extern "C" int dpe_fusion_candidates(DpeContext* c, int ref, const int* src, int ns, int32_t* idx, float* val) {
   TRY(enter(c, src && idx && val && ns >= 0, "dpe_fusion_candidates: bad argument"));
   FusionStage& fz = c->fz;
-  if (fz.n < 1) { g_err = "dpe_fusion_candidates: nothing staged"; return DPE_ERR_STATE; }
-  if (ref < 0 || ref >= fz.n) { g_err = "dpe_fusion_candidates: bad reference view"; return DPE_ERR_ARG; }
-  for (int j = 0; j < ns; ++j)
-    if (src[j] < 0 || src[j] >= fz.n) { g_err = "dpe_fusion_candidates: bad source view"; return DPE_ERR_ARG; }
+  TRY(views_check(c, "dpe_fusion_candidates", ref, src, ns, true));   // a view may be among its own sources here
   if (ns == 0) return DPE_OK;
   const size_t L = (size_t)fz.host[ref].w * fz.host[ref].h;
   HIPC(fz.src.ensure(ns));
@@ -74,12 +85,7 @@ extern "C" int dpe_fusion_consistency(DpeContext* c, int ref, const int* src, in
   if (ns > kConsistencyMaxSrc) { g_err = "dpe_fusion_consistency: more than 255 source views"; return DPE_ERR_ARG; }
   if (min_views < 1 || min_views > 255) { g_err = "dpe_fusion_consistency: min_views outside 1..255"; return DPE_ERR_ARG; }
   FusionStage& fz = c->fz;
-  if (fz.n < 1) { g_err = "dpe_fusion_consistency: nothing staged"; return DPE_ERR_STATE; }
-  if (ref < 0 || ref >= fz.n) { g_err = "dpe_fusion_consistency: bad reference view"; return DPE_ERR_ARG; }
-  for (int j = 0; j < ns; ++j) {
-    if (src[j] < 0 || src[j] >= fz.n) { g_err = "dpe_fusion_consistency: bad source view"; return DPE_ERR_ARG; }
-    if (src[j] == ref) { g_err = "dpe_fusion_consistency: the reference view is among its sources"; return DPE_ERR_ARG; }
-  }
+  TRY(views_check(c, "dpe_fusion_consistency", ref, src, ns, false));
   const size_t L = (size_t)fz.host[ref].w * fz.host[ref].h;
   if (L >= (size_t)1 << 31) { g_err = "dpe_fusion_consistency: view too large"; return DPE_ERR_ARG; }   // the kernel's int pixel index
   HIPC(host_wait(c));   // the buffers below may grow, and the results are read on the host
@@ -144,13 +150,10 @@ extern "C" int dpe_fusion_tat_image(DpeContext* c, int mode, int ref, const int*
   TatFusion& tat = c->tat;
   if (!tat.ready) { g_err = "dpe_fusion_tat_image: dpe_fusion_tat_begin has not run"; return DPE_ERR_STATE; }
   if (mode != DPE_FUSION_TAT_INTERMEDIATE && mode != DPE_FUSION_TAT_ADVANCED) { g_err = "dpe_fusion_tat_image: bad mode"; return DPE_ERR_ARG; }
-  if (ref < 0 || ref >= fz.n) { g_err = "dpe_fusion_tat_image: bad reference view"; return DPE_ERR_ARG; }
+  TRY(views_check(c, "dpe_fusion_tat_image", ref, nullptr, 0, true));   // the reference view before the limit, the sources after
   if (ns > kTatMaxSrc) { g_err = "dpe_fusion_tat_image: more than 31 source views"; return DPE_ERR_TOO_MANY; }
-  for (int j = 0; j < ns; ++j) {
-    if (src[j] < 0 || src[j] >= fz.n) { g_err = "dpe_fusion_tat_image: bad source view"; return DPE_ERR_ARG; }
-    // the kernels read the masks of the source views while they write the reference view's
-    if (src[j] == ref) { g_err = "dpe_fusion_tat_image: the reference view is among its sources"; return DPE_ERR_ARG; }
-  }
+  // the kernels read the masks of the source views while they write the reference view's
+  TRY(views_check(c, "dpe_fusion_tat_image", ref, src, ns, false));
   if (mode == DPE_FUSION_TAT_INTERMEDIATE && ns >= 2 && !dot_thresholds) { g_err = "dpe_fusion_tat_image: no thresholds"; return DPE_ERR_ARG; }
   *n_out = 0;
   if (ns < 2) {   // the k loop starts at 2 (DPE.cpp:1504): no point, no mask
@@ -181,7 +184,7 @@ extern "C" int dpe_fusion_tat_image(DpeContext* c, int mode, int ref, const int*
   k_tat_chunk_carry<<<ns, 256, 0, s>>>(nch, tat.agg.p);
   k_tat_decide<<<nch, kTatChunk, 0, s>>>(fz.cams.p, fz.views.p, tat.views.p, ref, fz.src.p, ns, nch, mode, tat.dthr.p,
                                         tat.last.p, tat.agg.p, tat.rec.p, tat.emit.p, tat.cnt.p);
-  k_tat_offsets<<<1, 256, 0, s>>>(nch, tat.cnt.p, tat.tot.p);
+  k_offsets_scan<256><<<1, 256, 0, s>>>(nch, tat.cnt.p, tat.tot.p);
   k_tat_fill<<<nch, kTatChunk, 0, s>>>((int)L, tat.emit.p, tat.rec.p, tat.cnt.p, dout.p);
   HIPC(hipGetLastError());
   int total = 0;

@@ -37,7 +37,7 @@ static int points_run(DpeContext* c, int mode, const float4* planes, const uint8
   const dim3 grid((unsigned)((w + kPtsCols - 1) / kPtsCols), (unsigned)nseg);
   k_pts_count<<<grid, kPtsCols, 0, s>>>(mode, planes, weak, w, h, nseg, dmin, dmax, v.cnt.p);
   HIPC(hipGetLastError());
-  k_pts_offsets<<<1, 256, 0, s>>>((int)ncell, v.cnt.p, v.tot.p);
+  k_offsets_scan<256><<<1, 256, 0, s>>>((int)ncell, v.cnt.p, v.tot.p);
   HIPC(hipGetLastError());
   k_pts_fill<<<grid, kPtsCols, 0, s>>>(mode, planes, weak, v.bgr.p, cam, w, h, nseg, dmin, dmax, v.cnt.p, v.out.p);
   HIPC(hipGetLastError());

@@ -139,7 +139,7 @@ DPE_CHD bool normal_none(float x, float y, float z) {
 
 // the world normal n of the scan point (x, y, z) as the view `cam` sees it: turned towards the camera
 DPE_CHD void normal_orient(const DpeCamera& cam, float x, float y, float z, const float n[3], float out[3]) {
-  const float tx = cam.R[0] * x + cam.R[1] * y + cam.R[2] * z + cam.t[0];   // depth_project's (tx, ty, tz)
+  const float tx = cam.R[0] * x + cam.R[1] * y + cam.R[2] * z + cam.t[0];   // fz_project's (tx, ty, tz)
   const float ty = cam.R[3] * x + cam.R[4] * y + cam.R[5] * z + cam.t[1];
   const float tz = cam.R[6] * x + cam.R[7] * y + cam.R[8] * z + cam.t[2];
   const float cx = cam.R[0] * n[0] + cam.R[1] * n[1] + cam.R[2] * n[2];     // TransformNormal2RefCam's order

@@ -24,6 +24,7 @@
 #include "cloud_dist.h"
 #include "cloud_reg.h"     // icp_take
 #include "tree_sum.h"      // kTreeBlock
+#include "block_scan.h"
 
 namespace dpe {
 
@@ -82,29 +83,18 @@ __global__ void __launch_bounds__(kCloudBlock) k_cloud_count(const float* __rest
 }
 
 // exclusive scan of cnt[0..nb) in place, one block: a thread sums kCloudScanPer adjacent counts, the
-// block scans the threads' sums (k_pts_offsets' scheme), and a carry runs over the rounds
+// block scans the threads' sums (block_scan.h), and a carry runs over the rounds
 __global__ void __launch_bounds__(kCloudBlock) k_cloud_scan(int nb, int* __restrict__ cnt) {
-  __shared__ int s4[kCloudBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  static_assert(kCloudBlock == kScanBlock, "block_scan scans 256 threads");
+  __shared__ int s4[4];
   int acc = 0;
   for (size_t k0 = 0; k0 < (size_t)nb; k0 += (size_t)kCloudBlock * kCloudScanPer) {
     const size_t k = k0 + (size_t)threadIdx.x * kCloudScanPer;
     int c[kCloudScanPer], sum = 0;
 #pragma unroll
     for (int e = 0; e < kCloudScanPer; ++e) { c[e] = k + e < (size_t)nb ? cnt[k + e] : 0; sum += c[e]; }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s4[wave] = incl;
-    __syncthreads();
-    int before = acc, all = 0;
-#pragma unroll
-    for (int v = 0; v < kCloudBlock / 64; ++v) { if (v < wave) before += s4[v]; all += s4[v]; }
-    __syncthreads();
-    int run = before + incl - sum;
+    int all;
+    int run = acc + block_scan<ScanSum>(sum, s4, &all) - sum;
 #pragma unroll
     for (int e = 0; e < kCloudScanPer; ++e) { if (k + e < (size_t)nb) cnt[k + e] = run; run += c[e]; }
     acc += all;

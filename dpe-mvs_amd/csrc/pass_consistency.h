@@ -9,12 +9,11 @@
 // image runs here and 5 bytes per pixel go back to the host (the candidates of pass_fusion.h carry
 // 16 * ns).  RunFusion's `dynamic_consistency` weight is not computed: it needs glibc's expf.
 //
-// Built from the fusions' device functions: fz_world, fz_pixel (pass_fusion.h) and tat_entry
+// Built from the fusions' functions: fz_world, fz_pixel (fusion_world.h) and tat_entry
 // (pass_fusion_tat.h), so the arithmetic is theirs: the reference's expression order in single
 // precision (-ffp-contract=off), the reprojection error in double rounded once.  The angle test
 // needs no device acosf, as in pass_fusion_tat.h: the host passes D, the smallest float in [-1, 1]
-// whose acosf is below 0.174533 (host/consistency.cpp), and the test is
-// `!(dot >= -1 && dot <= 1) || dot >= D` (GetAngle returns 0 for a NaN acosf).
+// whose acosf is below 0.174533 (host/consistency.cpp), and the test is fz_angle_ok(dot, D).
 #pragma once
 #include "pass_fusion_tat.h"
 
@@ -44,11 +43,11 @@ __global__ void __launch_bounds__(256) k_consistency(const DpeCamera* __restrict
       const FusionViewDev S = views[s];
       const DpeCamera& sc = cams[s];
       int src_c, src_r;
-      if (!fz_pixel(X, S, sc, src_c, src_r)) continue;
+      if (!fz_pixel(X, sc, S.w, S.h, src_c, src_r)) continue;
       const int sp = src_r * S.w + src_c;
       if (!(S.depth[sp] > 0.0f)) continue;
       const TatEntry e = tat_entry(R, rc, p, S, sc, sp);
-      if (e.dist < 2.0f && e.depth < 0.01f && (!(e.dot >= -1.0f && e.dot <= 1.0f) || e.dot >= dot_threshold)) ++n;
+      if (e.dist < 2.0f && e.depth < 0.01f && fz_angle_ok(e.dot, dot_threshold)) ++n;
     }
   }
   count[p] = (uint8_t)n;

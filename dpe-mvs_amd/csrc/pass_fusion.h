@@ -12,23 +12,9 @@
 #pragma once
 #include "../../include/dpe_mvs.h"
 #include "dpe_fusion_types.h"   // FusionViewDev
-#include "fusion_world.h"        // fz_world, fz_project
+#include "fusion_world.h"        // fz_world, fz_pixel, fz_pair, fz_dot
 
 namespace dpe {
-
-// The source pixel (src_c, src_r) = (int(x + 0.5f), int(y + 0.5f)) of the projection of X into view S
-// (DPE.cpp:1318-1321), taken only for x + 0.5, y + 0.5 in (-1, size): the in-range test on the float,
-// so NaN / huge projections are rejected the same way as on the reference's host (where they convert
-// to INT_MIN).  False when the projection lies outside.  The one copy of this test: the candidates
-// below, the Tanks-and-Temples hit (pass_fusion_tat.h) and the consistency count (pass_consistency.h).
-__device__ inline bool fz_pixel(const FP3& X, const FusionViewDev& S, const DpeCamera& sc, int& src_c, int& src_r) {
-  float px, py, pd;
-  fz_project(X, sc, px, py, pd);
-  const float fx = px + 0.5f, fy = py + 0.5f;
-  if (!(fx > -1.0f && fx < (float)S.w && fy > -1.0f && fy < (float)S.h)) return false;
-  src_c = (int)fx; src_r = (int)fy;
-  return true;
-}
 
 // idx[p*ns + j]: source pixel (row-major) when the projection of reference pixel p lands inside
 // source view src[j] on a positive depth with reprojection error < 2 and relative depth difference
@@ -52,7 +38,7 @@ __global__ void __launch_bounds__(256) k_fusion_candidates(const DpeCamera* __re
   }
   const DpeCamera& rc = cams[ref];
   const FP3 X = fz_world(c, r, ref_depth, rc);
-  const float n0 = R.normal[3 * (size_t)p], n1 = R.normal[3 * (size_t)p + 1], n2 = R.normal[3 * (size_t)p + 2];
+  const float rn[3] = {R.normal[3 * (size_t)p], R.normal[3 * (size_t)p + 1], R.normal[3 * (size_t)p + 2]};
   for (int j = 0; j < ns; ++j) {
     int32_t o = -1;
     float e = 0.0f, rel = 0.0f, dot = 0.0f;
@@ -60,22 +46,14 @@ __global__ void __launch_bounds__(256) k_fusion_candidates(const DpeCamera* __re
     const FusionViewDev S = views[s];
     const DpeCamera& sc = cams[s];
     int src_c, src_r;
-    if (fz_pixel(X, S, sc, src_c, src_r)) {
+    if (fz_pixel(X, sc, S.w, S.h, src_c, src_r)) {
       const int sp = src_r * S.w + src_c;
       const float sd = S.depth[sp];
       if (sd > 0.0f) {
-        const FP3 Y = fz_world(src_c, src_r, sd, sc);
-        float tx, ty, pd2;
-        fz_project(Y, rc, tx, ty, pd2);
-        const float dx = (float)c - tx, dy = (float)r - ty;
-        // DPE.cpp:1331 sqrt(pow(c - x, 2) + pow(r - y, 2)): pow(float, int) promotes to double, so the
-        // squares, the sum and the root are double, rounded to float once
-        const float re = (float)__builtin_sqrt((double)dx * dx + (double)dy * dy);
-        const float rl = __builtin_fabsf(pd2 - ref_depth) / ref_depth;
-        if (re < 2.0f && rl < 0.01f) {
-          o = sp; e = re; rel = rl;
-          const float* sn = S.normal + 3 * (size_t)sp;
-          dot = n0 * sn[0] + n1 * sn[1] + n2 * sn[2];
+        const FzPair d = fz_pair(c, r, ref_depth, rc, src_c, src_r, sd, sc);
+        if (d.dist < 2.0f && d.depth < 0.01f) {   // the source normal is read for these only
+          o = sp; e = d.dist; rel = d.depth;
+          dot = fz_dot(rn, S.normal + 3 * (size_t)sp);
         }
       }
     }

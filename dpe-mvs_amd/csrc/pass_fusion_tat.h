@@ -18,15 +18,16 @@
 //                      themselves, and the entry is a pure function of q and j); the k loop, the
 //                      colour, the pixel's own mask, the point into rec[p], emit[p], and the block's
 //                      point count into cnt[chunk]
-//   k_tat_offsets      exclusive sum-scan of cnt over the chunks, the total into *tot
+//   k_offsets_scan     (block_scan.h) exclusive sum-scan of cnt over the chunks, the total into *tot
 //   k_tat_fill         stable compaction of rec into out (image raster order)
 //
 // Arithmetic as in pass_fusion.h: the reference's expression order in single precision
 // (-ffp-contract=off), the reprojection error in double rounded once.  The angle test
 // `GetAngle(n_ref, n_src) < T_k` needs no device acosf: the entry carries the dot product and the host
 // passes D[k], the smallest float in [-1, 1] whose acosf is below T_k (host/fusion_tat.cpp), so the
-// test is `!(dot >= -1 && dot <= 1) || dot >= D[k]` (GetAngle returns 0 for a NaN acosf).
+// test is fz_angle_ok(dot, D[k]) (fusion_world.h).
 #pragma once
+#include "block_scan.h"
 #include "pass_fusion.h"
 
 namespace dpe {
@@ -49,7 +50,7 @@ __device__ inline bool tat_active(const FusionViewDev& R, const uint8_t* block, 
 // has a depth; else -1.  The in-range test on the float (fz_pixel).
 __device__ inline int tat_hit(const FP3& X, const FusionViewDev& S, const DpeCamera& sc, const uint8_t* smask) {
   int src_c, src_r;
-  if (!fz_pixel(X, S, sc, src_c, src_r)) return -1;
+  if (!fz_pixel(X, sc, S.w, S.h, src_c, src_r)) return -1;
   const int sp = src_r * S.w + src_c;
   if (smask[sp] == 1) return -1;
   if (S.depth[sp] <= 0.0f) return -1;
@@ -61,36 +62,13 @@ __device__ inline TatEntry tat_entry(const FusionViewDev& R, const DpeCamera& rc
                                      const DpeCamera& sc, int sp) {
   const int r = q / R.w, c = q - r * R.w;
   const int src_r = sp / S.w, src_c = sp - src_r * S.w;
-  const float ref_depth = R.depth[q];
-  const FP3 Y = fz_world(src_c, src_r, S.depth[sp], sc);
-  float tx, ty, pd2;
-  fz_project(Y, rc, tx, ty, pd2);
-  const float dx = (float)c - tx, dy = (float)r - ty;
+  const FzPair d = fz_pair(c, r, R.depth[q], rc, src_c, src_r, S.depth[sp], sc);
   TatEntry e;
-  e.dist = (float)__builtin_sqrt((double)dx * dx + (double)dy * dy);
-  e.depth = __builtin_fabsf(pd2 - ref_depth) / ref_depth;
-  const float* rn = R.normal + 3 * (size_t)q;
-  const float* sn = S.normal + 3 * (size_t)sp;
-  e.dot = rn[0] * sn[0] + rn[1] * sn[1] + rn[2] * sn[2];
+  e.dist = d.dist;
+  e.depth = d.depth;
+  e.dot = fz_dot(R.normal + 3 * (size_t)q, S.normal + 3 * (size_t)sp);
   e.sp = sp;
   return e;
-}
-
-// inclusive max-scan over a 256-thread block (all threads call it); *all = the block's maximum
-__device__ inline int tat_block_max_scan(int v, int* s4, int* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if (lane >= o) incl = max(incl, t);
-  }
-  if (lane == 63) s4[wave] = incl;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) incl = max(incl, s4[w]);
-  *all = max(max(s4[0], s4[1]), max(s4[2], s4[3]));
-  __syncthreads();
-  return incl;
 }
 
 // last[j*L + p]: the largest pixel q <= p of p's block that is active and hits view src[j], else -1;
@@ -115,7 +93,7 @@ __global__ void __launch_bounds__(kTatChunk) k_tat_hit_scan(const DpeCamera* __r
     const int s = src[j];
     const int v = act && tat_hit(X, views[s], cams[s], tviews[s].mask) >= 0 ? p : -1;
     int all;
-    const int incl = tat_block_max_scan(v, s4, &all);
+    const int incl = block_scan<ScanMax>(v, s4, &all);
     if (p < L) last[(size_t)j * L + p] = incl;
     if (threadIdx.x == 0) agg[j * nch + blockIdx.x] = all;
   }
@@ -130,13 +108,32 @@ __global__ void __launch_bounds__(256) k_tat_chunk_carry(int nch, int* __restric
   for (int k0 = 0; k0 < nch; k0 += 256) {
     const int k = k0 + (int)threadIdx.x;
     int all;
-    sh[threadIdx.x] = tat_block_max_scan(k < nch ? a[k] : -1, s4, &all);
+    sh[threadIdx.x] = block_scan<ScanMax>(k < nch ? a[k] : -1, s4, &all);
     __syncthreads();
     const int before = threadIdx.x > 0 ? sh[threadIdx.x - 1] : -1;
     __syncthreads();
     if (k < nch) a[k] = max(acc, before);
     acc = max(acc, all);
   }
+}
+
+// The entry view src[j] carries at pixel p of chunk blockIdx.x: recomputed at q = max(last, carry), the last pixel
+// up to p that is active and hits the view.  False when there is none so far (the reference's entry is then FLT_MAX
+// in all three tests); else sv = src[j] and the entry.
+__device__ inline bool tat_carried(int j, int p, int L, int nch, const int* __restrict__ last, const int* __restrict__ agg,
+                                   const FusionViewDev& R, const DpeCamera& rc, const DpeCamera* __restrict__ cams,
+                                   const FusionViewDev* __restrict__ views, const TatViewDev* __restrict__ tviews,
+                                   const int* __restrict__ src, int& sv, TatEntry& e) {
+  const int q = max(last[(size_t)j * L + p], agg[j * nch + blockIdx.x]);
+  if (q < 0) return false;
+  sv = src[j];
+  const FusionViewDev S = views[sv];
+  const DpeCamera& sc = cams[sv];
+  const int qr = q / R.w, qc = q - qr * R.w;
+  const int sp = tat_hit(fz_world(qc, qr, R.depth[q], rc), S, sc, tviews[sv].mask);   // the hit k_tat_hit_scan found
+  if (sp < 0) return false;
+  e = tat_entry(R, rc, q, S, sc, sp);
+  return true;
 }
 
 // The k loop of one pixel (DPE.cpp:1504-1534 / :1668-1683).  mode 1 = Intermediate, 2 = Advanced.
@@ -165,19 +162,13 @@ __global__ void __launch_bounds__(kTatChunk) k_tat_decide(const DpeCamera* __res
     // bit k of plane[b] is bit b of count(k).
     uint32_t plane[5] = {0u, 0u, 0u, 0u, 0u};
     for (int j = 0; j < ns; ++j) {
-      const int q = max(last[(size_t)j * L + p], agg[j * nch + blockIdx.x]);
-      if (q < 0) continue;   // never hit so far: the entry is FLT_MAX in all three tests
-      const int s = src[j];
-      const FusionViewDev S = views[s];
-      const DpeCamera& sc = cams[s];
-      const int qr = q / R.w, qc = q - qr * R.w;
-      const int sp = tat_hit(fz_world(qc, qr, R.depth[q], rc), S, sc, tviews[s].mask);   // the hit k_tat_hit_scan found
-      if (sp < 0) continue;
-      const TatEntry e = tat_entry(R, rc, q, S, sc, sp);
+      int sv;
+      TatEntry e;
+      if (!tat_carried(j, p, L, nch, last, agg, R, rc, cams, views, tviews, src, sv, e)) continue;
       uint32_t use = 0u;
       for (int k = 2; k <= ns; ++k) {
         bool u = e.dist < k * dist_base && e.depth < k * depth_base;
-        if (mode == 1) u = u && (!(e.dot >= -1.0f && e.dot <= 1.0f) || e.dot >= dthr[k]);
+        if (mode == 1) u = u && fz_angle_ok(e.dot, dthr[k]);
         use |= (uint32_t)u << k;
       }
       uint32_t carry = use;
@@ -200,18 +191,11 @@ __global__ void __launch_bounds__(kTatChunk) k_tat_decide(const DpeCamera* __res
     float col[3] = {(float)TR.bgr[3 * (size_t)p], (float)TR.bgr[3 * (size_t)p + 1], (float)TR.bgr[3 * (size_t)p + 2]};
     if (mode == 1) {   // the colours of the views used at `kept`, ascending j (DPE.cpp:1515-1526)
       for (int j = 0; j < ns; ++j) {
-        const int q = max(last[(size_t)j * L + p], agg[j * nch + blockIdx.x]);
-        if (q < 0) continue;
-        const int s = src[j];
-        const FusionViewDev S = views[s];
-        const DpeCamera& sc = cams[s];
-        const int qr = q / R.w, qc = q - qr * R.w;
-        const int sp = tat_hit(fz_world(qc, qr, R.depth[q], rc), S, sc, tviews[s].mask);
-        if (sp < 0) continue;
-        const TatEntry e = tat_entry(R, rc, q, S, sc, sp);
-        if (e.dist < kept * dist_base && e.depth < kept * depth_base &&
-            (!(e.dot >= -1.0f && e.dot <= 1.0f) || e.dot >= dthr[kept])) {
-          const uint8_t* sb = tviews[s].bgr + 3 * (size_t)sp;
+        int sv;
+        TatEntry e;
+        if (!tat_carried(j, p, L, nch, last, agg, R, rc, cams, views, tviews, src, sv, e)) continue;
+        if (e.dist < kept * dist_base && e.depth < kept * depth_base && fz_angle_ok(e.dot, dthr[kept])) {
+          const uint8_t* sb = tviews[sv].bgr + 3 * (size_t)e.sp;
           col[0] += (float)sb[0];
           col[1] += (float)sb[1];
           col[2] += (float)sb[2];
@@ -232,32 +216,6 @@ __global__ void __launch_bounds__(kTatChunk) k_tat_decide(const DpeCamera* __res
   if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = n;
   __syncthreads();
   if (threadIdx.x == 0) cnt[blockIdx.x] = s4[0] + s4[1] + s4[2] + s4[3];
-}
-
-// exclusive scan of the chunk counts (one 256-thread block); the image's point count into *tot
-__global__ void __launch_bounds__(256) k_tat_offsets(int nch, int* __restrict__ cnt, int* __restrict__ tot) {
-  __shared__ int s4[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int acc = 0;
-  for (int k0 = 0; k0 < nch; k0 += 256) {
-    const int k = k0 + (int)threadIdx.x;
-    const int c = k < nch ? cnt[k] : 0;
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s4[wave] = incl;
-    __syncthreads();
-    int before = acc;
-    for (int w = 0; w < wave; ++w) before += s4[w];
-    const int all = s4[0] + s4[1] + s4[2] + s4[3];
-    __syncthreads();
-    if (k < nch) cnt[k] = before + incl - c;
-    acc += all;
-  }
-  if (threadIdx.x == 0) *tot = acc;
 }
 
 // out[off[chunk] + rank of p among the chunk's fused pixels] = rec[p]: raster order

@@ -7,7 +7,7 @@
 //
 //   k_pts_count    one thread per cell: the valid pixels of the cell into cnt[column * nseg + segment],
 //                  which is the order the reference visits the cells in
-//   k_pts_offsets  exclusive sum-scan of cnt in that order (one block), the image's total into *tot
+//   k_offsets_scan (block_scan.h) exclusive sum-scan of cnt in that order (one block), the image's total into *tot
 //   k_pts_fill     one thread per cell again: its pixels top to bottom into out[cnt[cell]...]
 //
 // No atomics, so the order is the reference's whatever the schedule.  A block is kPtsCols adjacent
@@ -19,6 +19,7 @@
 // the test, so with depth_min <= 0 it is emitted at depth 0, as the reference's code would.
 // The test `depth < depth_min || depth > depth_max || isnan(depth)`: NaN on the bit pattern.
 #pragma once
+#include "block_scan.h"      // k_offsets_scan
 #include "fusion_world.h"
 #include "dpe_fusion_types.h"   // TatPoint (= DpeFusedPoint)
 
@@ -49,32 +50,6 @@ __global__ void __launch_bounds__(kPtsCols) k_pts_count(int mode, const float4* 
   for (int j = j0; j < j1; ++j)
     n += pts_valid(pts_depth(mode, planes, weak, (size_t)j * w + c), dmin, dmax) ? 1 : 0;
   cnt[(size_t)c * nseg + seg] = n;
-}
-
-// exclusive scan of the ncell cell counts in place (one 256-thread block); the total into *tot
-__global__ void __launch_bounds__(256) k_pts_offsets(int ncell, int* __restrict__ cnt, int* __restrict__ tot) {
-  __shared__ int s4[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int acc = 0;
-  for (int k0 = 0; k0 < ncell; k0 += 256) {
-    const int k = k0 + (int)threadIdx.x;
-    const int c = k < ncell ? cnt[k] : 0;
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) s4[wave] = incl;
-    __syncthreads();
-    int before = acc;
-    for (int v = 0; v < wave; ++v) before += s4[v];
-    const int all = s4[0] + s4[1] + s4[2] + s4[3];
-    __syncthreads();
-    if (k < ncell) cnt[k] = before + incl - c;
-    acc += all;
-  }
-  if (threadIdx.x == 0) *tot = acc;
 }
 
 // grid as k_pts_count; off = the scanned cnt.  Writes exactly the pixels k_pts_count counted.

@@ -7,7 +7,6 @@
 // RunFusion's dynamic_consistency weight (exp) is not part of it.
 #include "host.h"
 
-#include <cmath>
 #include <string>
 
 namespace dpe_host {
@@ -26,28 +25,17 @@ void consistency_image(const DpeFusionView* views, int ref, const int* src, int 
       int num_consistent = 0;
       if (ref_depth > 0.0f) {
         const float* ref_normal = R.normal + 3 * p;
-        const F3 PointX = world_point(c, r, ref_depth, R.cam);
+        const FP3 PointX = fz_world(c, r, ref_depth, R.cam);
         for (int j = 0; j < ns; ++j) {
           const DpeFusionView& S = views[src[j]];
-          const int src_cols = S.width, src_rows = S.height;
-          float px, py, proj_depth;
-          project_camera(PointX, S.cam, px, py, proj_depth);
-          const float fx = px + 0.5f, fy = py + 0.5f;
-          if (!(fx > -1.0f && fx < (float)src_cols && fy > -1.0f && fy < (float)src_rows)) continue;
-          const int src_r = int(fy), src_c = int(fx);
-          const size_t sp = (size_t)src_r * src_cols + src_c;
+          int src_c, src_r;
+          if (!fz_pixel(PointX, S.cam, S.width, S.height, src_c, src_r)) continue;
+          const size_t sp = (size_t)src_r * S.width + src_c;
           const float src_depth = S.depth[sp];
           if (!(src_depth > 0.0f)) continue;
-          const float* src_normal = S.normal + 3 * sp;
-          const F3 tmp_X = world_point(src_c, src_r, src_depth, S.cam);
-          float tx, ty;
-          project_camera(tmp_X, R.cam, tx, ty, proj_depth);
-          // sqrt(pow(c - x, 2) + pow(r - y, 2)): pow(float, int) promotes to double, rounded to float once
-          const float dx = c - tx, dy = r - ty;
-          const float reproj_error = (float)std::sqrt((double)dx * dx + (double)dy * dy);
-          const float relative_depth_diff = std::fabs(proj_depth - ref_depth) / ref_depth;
-          const float angle =
-              get_angle(ref_normal[0] * src_normal[0] + ref_normal[1] * src_normal[1] + ref_normal[2] * src_normal[2]);
+          const FzPair d = fz_pair(c, r, ref_depth, R.cam, src_c, src_r, src_depth, S.cam);
+          const float reproj_error = d.dist, relative_depth_diff = d.depth;
+          const float angle = get_angle(fz_dot(ref_normal, S.normal + 3 * sp));
           if (reproj_error < 2.0f && relative_depth_diff < 0.01f && angle < kAngleMax) num_consistent++;
         }
       }

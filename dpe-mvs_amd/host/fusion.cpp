@@ -25,15 +25,25 @@
 #include <cstdlib>
 #include <memory>
 #include <thread>
-#include <unordered_map>
 
 namespace dpe_host {
 
-// RunFusion's serial part (DPE.cpp:1286-1367) over the candidates of `fn`.
+FusionPlan fusion_plan(const std::vector<FusionView>& views) {
+  std::vector<FusionPlan::Image> images;
+  for (const FusionView& v : views) images.emplace_back(v.image_id, &v.src_ids);
+  return FusionPlan(images);
+}
+
+namespace {
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// RunFusion's serial part (DPE.cpp:1286-1367) over the candidates of `fn`, one image at a time.
 //
 // Round 6, three changes that keep every result (tests/test_fusion.py: the PLY bit for bit):
 //  * the next image's candidates are fetched on a worker thread while this image is fused (double
-//    buffer; only one `fn` call runs at a time, and the fusion itself makes no `fn` call);
+//    buffer; only one `fn` call runs at a time, and the fusion itself makes no `fn` call) -- so `fn`
+//    is called from two threads in turn, which include/dpe_host.h states at dpe_fusion_fn;
 //  * the candidate buffers are allocated once, uninitialised (`fn` writes every index, and every
 //    value the walk reads);
 //  * what in the reference's loop does not depend on the masks -- the angle test (acos) and the
@@ -41,79 +51,76 @@ namespace dpe_host {
 //    same float expressions, into a per-pixel bit set of the candidates that pass and their weights;
 //    the serial walk then visits only those, in ascending view order, and adds the same weights in
 //    the same order (the masks it tests and sets are exactly the reference's).
-bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
-                std::string& err) {
-  const int n = (int)views.size();
-  std::unordered_map<int, int> index;
-  for (int i = 0; i < n; ++i) index.emplace(views[i].image_id, i);
-  auto idx_of = [&](int id) { auto it = index.find(id); return it == index.end() ? 0 : it->second; };   // operator[]
-  std::vector<DpeFusionView> dv(n);
-  for (int i = 0; i < n; ++i) {
-    dv[i] = views[i].view;
-    views[i].mask.assign((size_t)views[i].view.width * views[i].view.height, 0);
-  }
-  std::vector<std::vector<int>> srcs(n);
-  std::vector<int> refs(n);
-  size_t cap = 1;
-  for (int i = 0; i < n; ++i) {
-    refs[i] = idx_of(views[i].image_id);
-    for (int id : views[i].src_ids) srcs[i].push_back(idx_of(id));
-    if (srcs[i].size() > 32) { err = "fusion: more than 32 source views"; return false; }
-    const DpeFusionView& R = views[refs[i]].view;
-    cap = std::max(cap, (size_t)R.width * R.height * srcs[i].size());
-  }
+struct Fuser {
+  // the candidates of one image as `fn` writes them; page-locked when the runtime allows (the candidate
+  // copies are ~16 B per (pixel, source view))
   struct Cand {
     std::unique_ptr<int32_t[]> idx;
     std::unique_ptr<float[]> val;
+    PinnedRange pin_idx, pin_val;   // after the buffers: unpinned before they are freed
     int rc = 0;
   };
-  Cand buf[2];
-  // page-locked when the runtime allows (the candidate copies are ~16 B per (pixel, source view))
-  struct Pin {
-    void* p = nullptr;
-    void pin(void* q, size_t n) { if (dpe_host_pin(q, n) == DPE_OK) p = q; }
-    ~Pin() { if (p) dpe_host_unpin(p); }
-  } pins[4];
-  // DPE_FUSION_PROFILE=1: seconds pinning, waiting for candidates, in the terms, the walk, the points
-  static const bool prof = [] { const char* e = getenv("DPE_FUSION_PROFILE"); return e && atoi(e) != 0; }();
-  // DPE_FUSION_PIN=0: pageable candidate buffers (A/B of the pinning)
-  static const bool pin = [] { const char* e = getenv("DPE_FUSION_PIN"); return !(e && atoi(e) == 0); }();
-  double t_wait = 0, t_terms = 0, t_walk = 0, t_points = 0, t_pin = 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  {
-    const double tp = now();
-    for (int k = 0; k < 2; ++k) {
-      buf[k].idx.reset(new int32_t[cap]);
-      buf[k].val.reset(new float[cap * 3]);
-      if (pin) {
-        pins[2 * k].pin(buf[k].idx.get(), cap * sizeof(int32_t));
-        pins[2 * k + 1].pin(buf[k].val.get(), cap * 3 * sizeof(float));
-      }
-    }
-    t_pin = now() - tp;
-  }
-  auto fetch = [&](int i, Cand* b) {
-    const int ns = (int)srcs[i].size();
-    b->rc = ns > 0 ? fn(user, dv.data(), n, refs[i], srcs[i].data(), ns, b->idx.get(), b->val.get()) : 0;
-  };
-  const int nt = host_threads();
   // per image: the candidates whose angle test passes (bit j of pass[p]) and their weights
   struct Terms {
     std::vector<uint32_t> pass;
     std::vector<float> wgt;
   };
+  // a fused pixel in walk order: pixel, the candidates it used (bit j), depth
+  struct Fused {
+    uint32_t p, used;
+    float depth;
+  };
+
+  std::vector<FusionView>& views;
+  const FusionPlan& plan;
+  const dpe_fusion_fn fn;
+  void* const user;
+  std::vector<FusedPoint>& cloud;
+  const int nt = host_threads();
+  std::vector<DpeFusionView> dv;
+  Cand buf[2];
   Terms terms[2];
-  auto make_terms = [&](int i, const Cand* b, Terms* tm, int threads) {   // DPE.cpp:1318-1343 without the masks
-    const FusionView& R = views[refs[i]];
-    const int ns = (int)srcs[i].size();
+  std::vector<Fused> fused;
+  // DPE_FUSION_PROFILE=1: seconds pinning, waiting for candidates, in the terms, the walk, the points
+  double t_pin = 0, t_wait = 0, t_terms = 0, t_walk = 0, t_points = 0;
+
+  // `cap`: the largest number of (pixel, source view) pairs of an image
+  Fuser(std::vector<FusionView>& views_, const FusionPlan& plan_, dpe_fusion_fn fn_, void* user_, size_t cap,
+        std::vector<FusedPoint>& cloud_)
+      : views(views_), plan(plan_), fn(fn_), user(user_), cloud(cloud_), dv(views_.size()) {
+    for (size_t i = 0; i < views.size(); ++i) dv[i] = views[i].view;
+    // DPE_FUSION_PIN=0: pageable candidate buffers (A/B of the pinning)
+    static const bool pin = [] { const char* e = getenv("DPE_FUSION_PIN"); return !(e && atoi(e) == 0); }();
+    const double tp = now();
+    for (Cand& b : buf) {
+      b.idx.reset(new int32_t[cap]);
+      b.val.reset(new float[cap * 3]);
+      if (pin) {
+        b.pin_idx.pin(b.idx.get(), cap * sizeof(int32_t));
+        b.pin_val.pin(b.val.get(), cap * 3 * sizeof(float));
+      }
+    }
+    t_pin = now() - tp;
+  }
+
+  void fetch(int i) {
+    Cand& b = buf[i & 1];
+    const int ns = (int)plan.srcs[i].size();
+    b.rc = ns > 0 ? fn(user, dv.data(), (int)dv.size(), plan.refs[i], plan.srcs[i].data(), ns, b.idx.get(), b.val.get()) : 0;
+  }
+
+  void make_terms(int i, int threads) {   // DPE.cpp:1318-1343 without the masks
+    const FusionView& R = views[plan.refs[i]];
+    Terms& tm = terms[i & 1];
+    const int ns = (int)plan.srcs[i].size();
     const size_t L = (size_t)R.view.width * R.view.height;
-    tm->pass.assign(L, 0u);
-    tm->wgt.resize(L * (size_t)std::max(ns, 1));
+    tm.pass.assign(L, 0u);
+    tm.wgt.resize(L * (size_t)std::max(ns, 1));
     if (ns == 0) return;
-    const int32_t* cidx = b->idx.get();
-    const float* cval = b->val.get();
-    uint32_t* pass = tm->pass.data();
-    float* wgt = tm->wgt.data();
+    const int32_t* cidx = buf[i & 1].idx.get();
+    const float* cval = buf[i & 1].val.get();
+    uint32_t* pass = tm.pass.data();
+    float* wgt = tm.wgt.data();
     run_on_threads(threads, [&](int t) {
       const size_t lo = L * t / threads, hi = L * (t + 1) / threads;
       for (size_t p = lo; p < hi; ++p) {
@@ -134,42 +141,23 @@ bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, st
         pass[p] = m;
       }
     });
-  };
-  // the fused pixels of one image in walk order: pixel, depth, the candidates it used (bit j)
-  struct Fused {
-    uint32_t p, used;
-    float depth;
-  };
-  std::vector<Fused> fused;
-  std::thread worker;
-  double t0 = now();
-  fetch(0, &buf[0]);
-  if (buf[0].rc == 0) make_terms(0, &buf[0], &terms[0], nt);
-  t_terms += now() - t0;
-  for (int i = 0; i < n; ++i) {
-    t0 = now();
-    if (worker.joinable()) worker.join();
-    t_wait += now() - t0;
-    const Cand& b = buf[i & 1];
-    if (b.rc != 0) {
-      err = "fusion candidates failed (" + std::to_string(b.rc) + ")";
-      return false;
-    }
-    // the next image's candidates and terms on the worker (its own threads) while this one is walked
-    if (i + 1 < n)
-      worker = std::thread([&, i]() {
-        Cand* nb = &buf[(i + 1) & 1];
-        fetch(i + 1, nb);
-        if (nb->rc == 0) make_terms(i + 1, nb, &terms[(i + 1) & 1], std::max(1, nt - 1));
-      });
-    FusionView& R = views[refs[i]];
+  }
+
+  // the candidates and the terms of image i, as the first image's or on the worker
+  void prepare(int i, int threads) {
+    fetch(i);
+    if (buf[i & 1].rc == 0) make_terms(i, threads);
+  }
+
+  // the serial mask walk of image i into `fused`
+  void walk_image(int i) {
+    FusionView& R = views[plan.refs[i]];
     const int cols = R.view.width, rows = R.view.height;
-    const std::vector<int>& src = srcs[i];
+    const std::vector<int>& src = plan.srcs[i];
     const int ns = (int)src.size();   // <= DPE_MAX_IMAGES - 1: one bit per view
-    const int32_t* cidx = b.idx.get();
+    const int32_t* cidx = buf[i & 1].idx.get();
     const uint32_t* pass = terms[i & 1].pass.data();
     const float* wgt = terms[i & 1].wgt.data();
-    t0 = now();
     uint8_t* smask[32];
     for (int j = 0; j < ns; ++j) smask[j] = views[src[j]].mask.data();
     fused.clear();
@@ -201,55 +189,86 @@ bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, st
           fused.push_back(Fused{(uint32_t)p, used, ref_depth});
         }
       }
-    t_walk += now() - t0;
-    // colours and 3-D points of the fused pixels (DPE.cpp:1345-1366): they read only the images'
-    // colours, which nothing writes, so they run on host threads, each point at its walk position
-    t0 = now();
+  }
+
+  // colours and 3-D points of the fused pixels of image i (DPE.cpp:1345-1366): they read only the images'
+  // colours, which nothing writes, so they run on host threads, each point at its walk position
+  void emit_points(int i) {
+    const FusionView& R = views[plan.refs[i]];
+    const int cols = R.view.width;
+    const std::vector<int>& src = plan.srcs[i];
+    const int ns = (int)src.size();
+    const int32_t* cidx = buf[i & 1].idx.get();
     const size_t base = cloud.size(), nf = fused.size();
     cloud.resize(base + nf);
-    {
-      const int th = (int)std::min<size_t>((size_t)nt, std::max<size_t>(1, nf / 4096));
-      run_on_threads(th, [&](int t) {
-        for (size_t k = nf * t / th; k < nf * (t + 1) / th; ++k) {
-          const Fused& f = fused[k];
-          const size_t p = f.p;
-          float col[3] = {(float)R.bgr[3 * p], (float)R.bgr[3 * p + 1], (float)R.bgr[3 * p + 2]};
-          for (uint32_t m = f.used; m; m &= m - 1) {
-            const int j = __builtin_ctz(m);
-            const size_t sp = (size_t)cidx[p * ns + j];
-            const FusionView& S = views[src[j]];
-            col[0] += S.bgr[3 * sp];
-            col[1] += S.bgr[3 * sp + 1];
-            col[2] += S.bgr[3 * sp + 2];
-          }
-          const int num_consistent = __builtin_popcount(f.used);
-          for (float& x : col) x /= (num_consistent + 1);
-          cloud[base + k] = fusion_point((int)(p % cols), (int)(p / cols), f.depth, R.view.cam, col);
+    const int th = (int)std::min<size_t>((size_t)nt, std::max<size_t>(1, nf / 4096));
+    run_on_threads(th, [&](int t) {
+      for (size_t k = nf * t / th; k < nf * (t + 1) / th; ++k) {
+        const Fused& f = fused[k];
+        const size_t p = f.p;
+        float col[3] = {(float)R.bgr[3 * p], (float)R.bgr[3 * p + 1], (float)R.bgr[3 * p + 2]};
+        for (uint32_t m = f.used; m; m &= m - 1) {
+          const int j = __builtin_ctz(m);
+          const size_t sp = (size_t)cidx[p * ns + j];
+          const FusionView& S = views[src[j]];
+          col[0] += S.bgr[3 * sp];
+          col[1] += S.bgr[3 * sp + 1];
+          col[2] += S.bgr[3 * sp + 2];
         }
-      });
+        const int num_consistent = __builtin_popcount(f.used);
+        for (float& x : col) x /= (num_consistent + 1);
+        cloud[base + k] = fusion_point((int)(p % cols), (int)(p / cols), f.depth, R.view.cam, col);
+      }
+    });
+  }
+
+  void report() const {
+    static const bool prof = [] { const char* e = getenv("DPE_FUSION_PROFILE"); return e && atoi(e) != 0; }();
+    if (prof)
+      fprintf(stderr, "fusion: %d images, buffers + pinning %.3f s, wait for candidates + terms %.3f s, first image "
+              "%.3f s, serial walk %.3f s, points %.3f s, %zu points\n", (int)views.size(), t_pin, t_wait, t_terms, t_walk,
+              t_points, cloud.size());
+  }
+};
+
+}  // namespace
+
+bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
+                std::string& err) {
+  const int n = (int)views.size();
+  const FusionPlan plan = fusion_plan(views);
+  for (FusionView& v : views) v.mask.assign((size_t)v.view.width * v.view.height, 0);
+  size_t cap = 1;
+  for (int i = 0; i < n; ++i) {
+    if (plan.srcs[i].size() > 32) { err = "fusion: more than 32 source views"; return false; }
+    const DpeFusionView& R = views[plan.refs[i]].view;
+    cap = std::max(cap, (size_t)R.width * R.height * plan.srcs[i].size());
+  }
+  Fuser f(views, plan, fn, user, cap, cloud);
+  std::thread worker;
+  double t0 = now();
+  f.prepare(0, f.nt);
+  f.t_terms += now() - t0;
+  for (int i = 0; i < n; ++i) {
+    t0 = now();
+    if (worker.joinable()) worker.join();
+    f.t_wait += now() - t0;
+    if (f.buf[i & 1].rc != 0) {
+      err = "fusion candidates failed (" + std::to_string(f.buf[i & 1].rc) + ")";
+      return false;
     }
-    t_points += now() - t0;
+    // the next image's candidates and terms on the worker (its own threads) while this one is walked
+    if (i + 1 < n) worker = std::thread([&f, i]() { f.prepare(i + 1, std::max(1, f.nt - 1)); });
+    t0 = now();
+    f.walk_image(i);
+    f.t_walk += now() - t0;
+    t0 = now();
+    f.emit_points(i);
+    f.t_points += now() - t0;
   }
   if (worker.joinable()) worker.join();
-  if (prof)
-    fprintf(stderr, "fusion: %d images, buffers + pinning %.3f s, wait for candidates + terms %.3f s, first image "
-            "%.3f s, serial walk %.3f s, points %.3f s, %zu points\n", n, t_pin, t_wait, t_terms, t_walk, t_points,
-            cloud.size());
+  f.report();
   return true;
-}
-
-// Get3DPointonWorld (DPE.cpp:1170-1194), the point a fused pixel contributes
-FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const float* bgr) {
-  float px = depth * (x - cam.K[2]) / cam.K[0];
-  float py = depth * (y - cam.K[5]) / cam.K[4];
-  float pz = depth;
-  const float tx = cam.R[0] * px + cam.R[3] * py + cam.R[6] * pz;
-  const float ty = cam.R[1] * px + cam.R[4] * py + cam.R[7] * pz;
-  const float tz = cam.R[2] * px + cam.R[5] * py + cam.R[8] * pz;
-  const float cx = -(cam.R[0] * cam.t[0] + cam.R[3] * cam.t[1] + cam.R[6] * cam.t[2]);
-  const float cy = -(cam.R[1] * cam.t[0] + cam.R[4] * cam.t[1] + cam.R[7] * cam.t[2]);
-  const float cz = -(cam.R[2] * cam.t[0] + cam.R[5] * cam.t[1] + cam.R[8] * cam.t[2]);
-  return FusedPoint{tx + cx, ty + cy, tz + cz, bgr[0], bgr[1], bgr[2]};
 }
 
 // ExportPointCloud (DPE.cpp:532-572): binary little-endian PLY, xyz float + BGR uchar

@@ -21,7 +21,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <unordered_map>
 
 namespace dpe_host {
 
@@ -32,21 +31,6 @@ float get_angle(float dot_product) {
   return angle;
 }
 
-F3 world_point(int x, int y, float depth, const DpeCamera& cam) {   // Get3DPointonWorld (DPE.cpp:1170-1194)
-  const float zero[3] = {0.0f, 0.0f, 0.0f};
-  const FusedPoint p = fusion_point(x, y, depth, cam, zero);
-  return F3{p.x, p.y, p.z};
-}
-
-void project_camera(const F3& X, const DpeCamera& cam, float& px, float& py, float& depth) {   // DPE.cpp:1196-1206
-  const float tx = cam.R[0] * X.x + cam.R[1] * X.y + cam.R[2] * X.z + cam.t[0];
-  const float ty = cam.R[3] * X.x + cam.R[4] * X.y + cam.R[5] * X.z + cam.t[1];
-  const float tz = cam.R[6] * X.x + cam.R[7] * X.y + cam.R[8] * X.z + cam.t[2];
-  depth = cam.K[6] * tx + cam.K[7] * ty + cam.K[8] * tz;
-  px = (cam.K[0] * tx + cam.K[1] * ty + cam.K[2] * tz) / depth;
-  py = (cam.K[3] * tx + cam.K[4] * ty + cam.K[5] * tz) / depth;
-}
-
 namespace {
 
 const float kAngleBase = 0.06981317007977318f;   // 4 degree (DPE.cpp:1380)
@@ -54,57 +38,25 @@ const float kAngleGrad = 0.05235987755982988f;   // 3 degree (DPE.cpp:1381)
 
 float angle_threshold(int k) { return k * kAngleGrad + kAngleBase; }   // DPE.cpp:1508
 
-// The problems as indices into `views`, with the reference's imageIdToindexMap (emplace keeps the
-// first of equal ids, operator[] gives 0 for an unknown one).
-struct Plan {
-  std::vector<int> refs;
-  std::vector<std::vector<int>> srcs;
-  bool aliased = false;   // a reference among its own sources, or an image id twice
-};
-Plan make_plan(const std::vector<FusionView>& views) {
-  const int n = (int)views.size();
-  std::unordered_map<int, int> index;
-  Plan pl;
-  for (int i = 0; i < n; ++i)
-    if (!index.emplace(views[i].image_id, i).second) pl.aliased = true;
-  auto idx_of = [&](int id) { auto it = index.find(id); return it == index.end() ? 0 : it->second; };
-  pl.refs.resize(n); pl.srcs.resize(n);
-  for (int i = 0; i < n; ++i) {
-    pl.refs[i] = idx_of(views[i].image_id);
-    for (int id : views[i].src_ids) {
-      pl.srcs[i].push_back(idx_of(id));
-      if (pl.srcs[i].back() == pl.refs[i]) pl.aliased = true;
-    }
-  }
-  return pl;
-}
+using Plan = FusionPlan;   // host.h
 
 // What both loops do per (pixel, source view) before the entry is written (DPE.cpp:1481-1496): the
 // source pixel when the rounded projection lies inside the view (the in-range test on the float, as
 // the GPU kernels take it: NaN and huge projections are rejected), is not masked and has a depth.
 struct Hit { bool ok; int src_r, src_c; float reproj_error, relative_depth_diff, angle; };
-Hit project_and_test(const F3& PointX, int r, int c, float ref_depth, const float* ref_normal, const FusionView& R,
+Hit project_and_test(const FP3& PointX, int r, int c, float ref_depth, const float* ref_normal, const FusionView& R,
                      const FusionView& S) {
   Hit h{false, 0, 0, 0.0f, 0.0f, 0.0f};
-  const int src_cols = S.view.width, src_rows = S.view.height;
-  float px, py, proj_depth;
-  project_camera(PointX, S.view.cam, px, py, proj_depth);
-  const float fx = px + 0.5f, fy = py + 0.5f;
-  if (!(fx > -1.0f && fx < (float)src_cols && fy > -1.0f && fy < (float)src_rows)) return h;
-  const int src_r = int(fy), src_c = int(fx);
-  const size_t sp = (size_t)src_r * src_cols + src_c;
+  int src_c, src_r;
+  if (!fz_pixel(PointX, S.view.cam, S.view.width, S.view.height, src_c, src_r)) return h;
+  const size_t sp = (size_t)src_r * S.view.width + src_c;
   if (S.mask[sp] == 1) return h;
   const float src_depth = S.view.depth[sp];
   if (src_depth <= 0.0) return h;
-  const float* src_normal = S.view.normal + 3 * sp;
-  const F3 tmp_X = world_point(src_c, src_r, src_depth, S.view.cam);
-  float tx, ty;
-  project_camera(tmp_X, R.view.cam, tx, ty, proj_depth);
-  // sqrt(pow(c - x, 2) + pow(r - y, 2)): pow(float, int) promotes to double, rounded to float once
-  const float dx = c - tx, dy = r - ty;
-  h.reproj_error = (float)std::sqrt((double)dx * dx + (double)dy * dy);
-  h.relative_depth_diff = std::fabs(proj_depth - ref_depth) / ref_depth;
-  h.angle = get_angle(ref_normal[0] * src_normal[0] + ref_normal[1] * src_normal[1] + ref_normal[2] * src_normal[2]);
+  const FzPair d = fz_pair(c, r, ref_depth, R.view.cam, src_c, src_r, src_depth, S.view.cam);
+  h.reproj_error = d.dist;
+  h.relative_depth_diff = d.depth;
+  h.angle = get_angle(fz_dot(ref_normal, S.view.normal + 3 * sp));
   h.ok = true; h.src_r = src_r; h.src_c = src_c;
   return h;
 }
@@ -133,7 +85,7 @@ void tat_intermediate_serial(std::vector<FusionView>& views, const Plan& pl, std
         const float ref_depth = R.view.depth[p];
         if (ref_depth <= 0.0) continue;
         const float* ref_normal = R.view.normal + 3 * p;
-        const F3 PointX = world_point(c, r, ref_depth, R.view.cam);
+        const FP3 PointX = fz_world(c, r, ref_depth, R.view.cam);
         for (int j = 0; j < num_ngb; ++j) {
           const Hit h = project_and_test(PointX, r, c, ref_depth, ref_normal, R, views[pl.srcs[i][j]]);
           if (!h.ok) continue;
@@ -197,7 +149,7 @@ void tat_advanced_serial(std::vector<FusionView>& views, const Plan& pl, std::ve
         const float ref_depth = R.view.depth[p];
         if (ref_depth <= 0.0) continue;
         const float* ref_normal = R.view.normal + 3 * p;
-        const F3 PointX = world_point(c, r, ref_depth, R.view.cam);
+        const FP3 PointX = fz_world(c, r, ref_depth, R.view.cam);
         const float consistent_Color[3] = {(float)R.bgr[3 * p], (float)R.bgr[3 * p + 1], (float)R.bgr[3 * p + 2]};
         for (int j = 0; j < num_ngb; ++j) {
           const Hit h = project_and_test(PointX, r, c, ref_depth, ref_normal, R, views[pl.srcs[i][j]]);
@@ -243,11 +195,7 @@ bool tat_device(std::vector<FusionView>& views, const Plan& pl, int mode, DpeCon
   if (dpe_fusion_tat_begin(ctx, bgr.data(), block.data()) != DPE_OK) return fail("dpe_fusion_tat_begin");
   // the points of image i land in buf[i & 1] while image i + 1 runs; page-locked when the runtime allows
   std::vector<FusedPoint> buf[2] = {std::vector<FusedPoint>(cap), std::vector<FusedPoint>(cap)};
-  struct Pin {
-    void* p = nullptr;
-    void pin(void* q, size_t bytes) { if (dpe_host_pin(q, bytes) == DPE_OK) p = q; }
-    ~Pin() { if (p) dpe_host_unpin(p); }
-  } pins[2];
+  PinnedRange pins[2];
   for (int k = 0; k < 2; ++k) pins[k].pin(buf[k].data(), cap * sizeof(FusedPoint));
   size_t before = 0;   // points of the image before, whose copy the next call completes
   bool ok = true;
@@ -312,7 +260,7 @@ bool tat_thresholds(float* D, int n, std::string& err) {
 bool run_fusion_tat(std::vector<FusionView>& views, int mode, DpeContext* ctx, std::vector<FusedPoint>& cloud,
                     std::string& err) {
   if (mode != DPE_FUSION_TAT_INTERMEDIATE && mode != DPE_FUSION_TAT_ADVANCED) { err = "fusion: bad mode"; return false; }
-  const Plan pl = make_plan(views);
+  const Plan pl = fusion_plan(views);
   for (const auto& s : pl.srcs)
     if (s.size() > 31) { err = "fusion: more than 31 source views"; return false; }
   for (FusionView& v : views) v.mask.assign((size_t)v.view.width * v.view.height, 0);

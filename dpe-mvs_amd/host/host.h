@@ -5,9 +5,12 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/dpe_host.h"
+#include "../csrc/fusion_world.h"   // FP3, fz_world, fz_pixel, fz_pair, fz_dot: the arithmetic shared with the kernels
 
 namespace dpe_host {
 
@@ -103,7 +106,48 @@ struct FusionView {
 using FusedPoint = DpeFusedPoint;   // x, y, z, b, g, r
 bool run_fusion(std::vector<FusionView>& views, dpe_fusion_fn fn, void* user, std::vector<FusedPoint>& cloud,
                 std::string& err);
-FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const float* bgr);
+// fz_world with the colour packed in: the point a fused pixel contributes
+inline FusedPoint fusion_point(int x, int y, float depth, const DpeCamera& cam, const float* bgr) {
+  const dpe::FP3 X = dpe::fz_world(x, y, depth, cam);
+  return FusedPoint{X.x, X.y, X.z, bgr[0], bgr[1], bgr[2]};
+}
+// The problems as indices into the views, by the reference's imageIdToindexMap: emplace keeps the first of equal
+// ids, operator[] gives 0 for an unknown one.  `images`: (image id, source ids) of every view, in view order; the
+// plan covers the problems `mine` (indices into `images`), or all of them.  The limits on the number of sources
+// stay with the callers.
+struct FusionPlan {
+  std::vector<int> refs;
+  std::vector<std::vector<int>> srcs;
+  bool aliased = false;   // a reference among its own sources, or an image id twice
+  using Image = std::pair<int, const std::vector<int>*>;
+  explicit FusionPlan(const std::vector<Image>& images, const std::vector<int>* mine = nullptr) {
+    std::unordered_map<int, int> index;
+    for (size_t i = 0; i < images.size(); ++i)
+      if (!index.emplace(images[i].first, (int)i).second) aliased = true;
+    auto idx_of = [&](int id) { auto it = index.find(id); return it == index.end() ? 0 : it->second; };
+    const size_t n = mine ? mine->size() : images.size();
+    refs.resize(n); srcs.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      const Image& im = images[mine ? (size_t)(*mine)[k] : k];
+      refs[k] = idx_of(im.first);
+      for (int id : *im.second) {
+        srcs[k].push_back(idx_of(id));
+        if (srcs[k].back() == refs[k]) aliased = true;
+      }
+    }
+  }
+};
+FusionPlan fusion_plan(const std::vector<FusionView>& views);   // fusion.cpp: the plan of every view
+// a host range page-locked for its lifetime when the runtime allows (dpe_host_pin); a refusal is silent: the range
+// stays pageable and everything still works
+struct PinnedRange {
+  void* p = nullptr;
+  void pin(void* q, size_t bytes) { if (dpe_host_pin(q, bytes) == DPE_OK) p = q; }
+  PinnedRange() = default;
+  ~PinnedRange() { if (p) dpe_host_unpin(p); }
+  PinnedRange(const PinnedRange&) = delete;
+  PinnedRange& operator=(const PinnedRange&) = delete;
+};
 bool export_point_cloud(const std::string& path, const FusedPoint* cloud, size_t n, std::string& err);
 bool export_point_cloud(const std::string& path, const std::vector<FusedPoint>& cloud, std::string& err);
 // points.cpp: RescaleImageAndCamera (DPE.cpp:1123-1144) and ExportDepthImagePointCloud (DPE.cpp:1691-1724)
@@ -120,12 +164,11 @@ bool run_fusion_tat(std::vector<FusionView>& views, int mode, DpeContext* ctx, s
                     std::string& err);
 // D[k], k = 2..n-1: smallest dot product in [-1, 1] that passes the Intermediate angle test at k
 bool tat_thresholds(float* D, int n, std::string& err);
-// what every fusion loop is written with (fusion_tat.cpp): Get3DPointonWorld, ProjectCamera and GetAngle
-// from the dot product (DPE.cpp:1170-1217), and the smallest float D in [-1, 1] with get_angle(D) < T
-// (bisection on the float's bits, verified at D and at its predecessor)
-struct F3 { float x, y, z; };
-F3 world_point(int x, int y, float depth, const DpeCamera& cam);
-void project_camera(const F3& X, const DpeCamera& cam, float& px, float& py, float& depth);
+// what every fusion loop is written with: Get3DPointonWorld, ProjectCamera, the source pixel of a projection and the
+// pair arithmetic are csrc/fusion_world.h's (fz_*); GetAngle from the dot product (DPE.cpp:1208-1217) and the
+// smallest float D in [-1, 1] with get_angle(D) < T (bisection on the float's bits, verified at D and at its
+// predecessor) are fusion_tat.cpp's, the only callers of acos
+using dpe::FP3; using dpe::FzPair; using dpe::fz_world; using dpe::fz_pixel; using dpe::fz_pair; using dpe::fz_dot;
 float get_angle(float dot_product);
 enum class DotThreshold { kOk, kNonePasses, kUnverified };
 DotThreshold angle_dot_threshold(float T, float& D);

@@ -908,26 +908,23 @@ struct PipelineRun {
   }
 
   // consistency.npy / depth_filtered.npy of this rank's images against the gathered final states.  The
-  // problems as indices into the views with RunFusion's imageIdToindexMap (the first of equal ids, 0 for an
-  // unknown one).  fusion_runner == NULL: every image on the device, the views staged once (and left for
+  // problems as indices into the views by FusionPlan (host.h).  fusion_runner == NULL: every image on the device, the views staged once (and left for
   // ETH3D fusion); else dpe_host_consistency's loop on host threads, one image each.
   bool write_consistency_maps() {
     const int n = (int)problems.size();
     std::vector<DpeFusionView> cv(n);
-    std::map<int, int> index;
+    std::vector<FusionPlan::Image> images;
     for (int i = 0; i < n; ++i) {
       const Problem& p = problems[i];
       if (!map_view(p, fusion_states.at(p.ref_image_id), w0, h0, cv[i], err)) return false;
-      index.emplace(p.ref_image_id, i);
+      images.emplace_back(p.ref_image_id, &p.src_image_ids);
     }
-    auto idx_of = [&](int id) { auto it = index.find(id); return it == index.end() ? 0 : it->second; };
     const std::vector<int>& mine = ranks.mine();
-    std::vector<int> refs(mine.size());
-    std::vector<std::vector<int>> srcs(mine.size());
+    const FusionPlan plan(images, &mine);
+    const std::vector<int>& refs = plan.refs;
+    const std::vector<std::vector<int>>& srcs = plan.srcs;
     for (size_t k = 0; k < mine.size(); ++k) {
       const Problem& p = problems[mine[k]];
-      refs[k] = idx_of(p.ref_image_id);
-      for (int id : p.src_image_ids) srcs[k].push_back(idx_of(id));
       std::string aerr;
       if (!consistency_args_ok(n, refs[k], srcs[k].data(), (int)srcs[k].size(), opt.consistency, aerr)) {
         err = aerr + " (image " + std::to_string(p.ref_image_id) + ")";

@@ -69,7 +69,10 @@ typedef int (*dpe_abort_fn)(void* user);
  * (include/dpe_mvs.h) over the given views (the default runs the HIP kernel on gpu_index).
  * Threading: the callback may be invoked from a thread other than the caller of dpe_run_pipeline
  * (the pipeline fetches the next image's candidates on a worker thread while it fuses the current
- * one), and never concurrently with itself: one call returns before the next begins. */
+ * one), and never concurrently with itself: one call returns before the next begins.  So the
+ * callee must not rely on per-thread state set up by an earlier call or by the pipeline's caller --
+ * the current device of the HIP runtime and a per-thread last-error slot are such state: select
+ * the device in every call and return errors through the return value (the default runner does). */
 typedef int (*dpe_fusion_fn)(void* user, const DpeFusionView* views, int n_views, int ref, const int* src, int ns,
                              int32_t* idx, float* val);
 

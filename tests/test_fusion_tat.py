@@ -306,6 +306,42 @@ def test_gpu_tat_image_matches_yardstick_on_hand_built_scenes(mode, size, hole):
         assert np.array_equal(a, b)
 
 
+def ragged_block(W, H):
+    """A block mask that drops the pixels with (x * 7 + y * 13) % 5 == 0 and the whole of rows 60 to 139."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    keep = (xx * 7 + yy * 13) % 5 != 0
+    keep[60:140] = False
+    return np.where(keep, 255, 0).astype(np.uint8)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("size", [(331, 199), (7, 5)])
+def test_gpu_tat_image_matches_yardstick_with_unequal_chunk_counts(mode, size):
+    """The chunk counts and their offsets where they differ from chunk to chunk: every view carries ragged_block, so
+    image 0 fuses exactly the pixels it keeps and a chunk holds anything from 0 to 206 points.  331x199 = 65,869
+    pixels = 258 chunks, the last with 77 pixels: unequal counts on both sides of the 256-chunk tile of the offsets
+    scan (chunks 256 and 257 hold 205 and 62 points) and a run of 103 empty chunks (rows 60 to 139).
+    7x5 = 35 pixels: one chunk with less than one wave."""
+    from DPE_MVS import native
+    lib = native.load_library()
+    W, H = size
+    views = plane_scene(W, H)
+    for v in views:
+        v["block"] = ragged_block(W, H)
+    ref, ref_masks = pipeline.fusion_tat_serial(views, mode)
+    assert 0 < len(ref) < W * H                      # the comparison below is not over nothing, nor over every pixel
+    assert np.array_equal(ref_masks[0] == 1, views[0]["block"] >= 128)
+    ctx = lib.dpe_create(0)
+    try:
+        pts, masks = _device_fuse(lib, ctx, views, mode)
+    finally:
+        lib.dpe_destroy(ctx)
+    assert pts.shape == ref.shape and np.array_equal(pts.view(np.uint32), ref.view(np.uint32))   # points, colours, order
+    for a, b in zip(masks, ref_masks):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 def test_gpu_carry_crosses_more_chunks_than_one_scan_tile(mode):
