@@ -26,6 +26,7 @@
 
 #include "pass_tables.h"
 #include "pass_kernels.h"
+#include "pass_neighbours.h"
 #include "pass_refine.h"
 #include "pass_sweep.h"
 #include "tap_launch.h"
@@ -849,9 +850,9 @@ static int gen_neighbours(PassRun& X, const DevBufs& Bc) {
   const hipStream_t a = X.a;
   const int* weak_list = X.list(X.lay.all_weak());
   const int* cnt = X.total(PassLists::kTotAllWeak);
-  if (X.gn_skip) {
-  } else if (X.pc.P.rotate_time <= 4) {
-    // the scratch-free kernel; pixels with more support points than its LDS slots (none at the
+  if (!X.gn_skip) {
+    // rotate_time is in [1,4] (stage_check_args): both kernels' point stores rely on it.
+    // The scratch-free kernel; pixels with more support points than its LDS slots (none at the
     // BASELINE workloads) or a NaN go to the scratch kernel, a small persistent grid that loops over
     // that overflow list (its count: the GenNeighbours-overflow total, dpe_pm_last_stat)
     int* ovf = X.total(PassLists::kTotGnOverflow);
@@ -865,8 +866,6 @@ static int gen_neighbours(PassRun& X, const DevBufs& Bc) {
     else
       k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
     k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, c->pass.gn_ovf.p, ovf);
-  } else {
-    k_gen_neighbours<<<kGnOvfBlocks, 256, 0, a>>>(X.dpc, Bc, weak_list, cnt);
   }
 #if DPE_GN_ONCE
   if (!X.gn_skip) {   // kept for the next executes of this staged state (see dpe_pm_execute)

@@ -93,7 +93,8 @@ def test_gpu_matches_oracle(ctx, W, H, N, kind):
     assert_same(ctx.run(inp, st), oracle.run_pass(inp, st), f"{W}x{H}x{N} {kind}")
 
 
-@pytest.mark.parametrize("W,H,N,kind", [(128, 96, 6, "refine_iter"), (96, 72, 4, "refine_init"), (88, 66, 4, "no_limit")])
+@pytest.mark.parametrize("W,H,N,kind", [(128, 96, 6, "refine_iter"), (96, 72, 4, "refine_init"), (88, 66, 4, "no_limit"),
+                                        (72, 54, 5, "refine_iter_lowres")])   # the fit's 125 tries and 0.005 branch
 def test_gpu_gen_neighbours_overflow_path(W, H, N, kind):
     # GenNeighbours' deferral path (DPE.cu:2281-2307 point collection, :2367-2449 sorts): with 8
     # support-point slots (DPE_OPT_GN_SLOTS) the scratch-free kernel hands every pixel with more points

@@ -66,7 +66,7 @@ for path in libs:
     d["wall_rounds_ms"] = [round(w, 2) for w in wall[path]]
     d["wall_spread_ms"] = round(max(wall[path]) - min(wall[path]), 2)
     d["total_rounds_ms"] = [round(t[0], 2) for t in res[path]]
-    # the two sweep classes round by round too: a mean and a spread of their own
-    for k in ("strong", "weak"):
+    # the sweep, setup and fit classes round by round too: a mean and a spread of their own
+    for k in ("strong", "weak", "setup", "ransac"):
         d[k + "_rounds_ms"] = [round(t[names.index(k)], 2) for t in res[path]]
     print(os.path.basename(path), json.dumps(d), flush=True)
