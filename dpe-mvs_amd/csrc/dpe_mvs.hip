@@ -861,7 +861,9 @@ static int gen_neighbours(PassRun& X, const DevBufs& Bc) {
     const unsigned gg = (unsigned)((X.L + kGnBT - 1) / kGnBT);
     if (c->pass.gn_slots == 8)   // test setting: most pixels overflow into the scratch kernel
       k_gen_neighbours_lds<8><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
-    else if (X.pc.P.rotate_time <= 2 && c->pass.gn_slots != 64)   // at most 16 x rotate_time support points
+    // at most 16 x rotate_time support points; 32 slots asked for above rotate_time 2 is a test setting
+    // too: the pixels with more than 32 points overflow
+    else if (c->pass.gn_slots == 32 || (X.pc.P.rotate_time <= 2 && c->pass.gn_slots != 64))
       k_gen_neighbours_lds<32><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);
     else
       k_gen_neighbours_lds<64><<<gg, kGnBT, 0, a>>>(X.dpc, Bc, weak_list, cnt, c->pass.gn_tab.p, c->pass.gn_ovf.p, ovf);

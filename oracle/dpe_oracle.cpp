@@ -130,13 +130,96 @@ static void tap_stats_reset() {
   for (int k = 0; k < kTapStats; ++k) { t_tap_stats[k] = 0; g_tap_stats[k].store(0, std::memory_order_relaxed); }
 }
 
+// Decision-path counts of the last pass (TEST INFRASTRUCTURE, oracle_last_path_stats; they change no
+// output): how often the pass took each branch that an input can take or miss, so that a test can say
+// which decisions its inputs reach (tests/test_pass_paths.py, DESIGN.md §4 "pass paths").  One name per
+// counter, in the order of oracle.PATH_STATS; fns_max_radius is a maximum, every other one a count.
+// Summed per thread and added to the totals with the tap counts.
+#define ORACLE_PATH_STATS(X)                                                                              \
+  /* GenEdgeInform: (2r+1)^2 windows with bound_pix / tot_pix == 1; label rays stopped by -1, with an    \
+     own-label pixel beyond a foreign (> 0, other) label, longer than 8 / 16 in-image pixels */          \
+  X(gei_window_all_label0) X(gei_ray_stop_minus1) X(gei_ray_past_foreign) X(gei_ray_len_gt8)             \
+  X(gei_ray_len_gt16)                                                                                    \
+  /* FindNearestStrongPoint, per WEAK pixel: none within 100; largest ring radius found (a maximum);     \
+     found at r == 100; the found ring holds more than one STRONG pixel (the ring order decides) */      \
+  X(fns_none) X(fns_max_radius) X(fns_found_r100) X(fns_ring_multi)                                      \
+  /* BresenhamLine (GenNeighbours and RANSACToGetFitPlane): calls past the end-point test, blocked,      \
+     low-resolution indices out of range (restatement choice 5) */                                       \
+  X(walk_called) X(walk_blocked) X(walk_lowres_oob)                                                      \
+  /* GenNeighbours, per WEAK pixel unless a probe, an extension step or a RANSAC draw is named */         \
+  X(gn_weak) X(gn_edge_limit_on) X(gn_edge_limit_off) X(gn_probe_nearest) X(gn_probe_none)               \
+  X(gn_ext_none) X(gn_ext_push) X(gn_ext_foreign_drop) X(gn_pts_le3) X(gn_pts_gt8) X(gn_pts_gt32)        \
+  X(gn_pts_eq64)                                                                                         \
+  X(gn_triangle_optional) X(gn_pair_block) X(gn_normal_skip) X(gn_degenerate) X(gn_inliers_lt6)          \
+  X(gn_tie_won) X(gn_thr_tightened) X(gn_thr_kept) X(gn_no_plane)                                        \
+  /* RANSACToGetFitPlane, per WEAK pixel: no triple accepted, a fit written */                           \
+  X(fit_none) X(fit_found)                                                                               \
+  /* CheckerboardPropagationStrong, edge scheme, per first scan (8 a pixel): centre on an edge; ray none \
+     or beyond max_edge_dist; ray used; ray used with >= 64 pixel steps to the edge; step_num 11..22;    \
+     step_len after the parity rule in bins 2 / 3 / >= 4 for d < 4 (c) and d >= 4 (d); odd decrements */ \
+  X(ps_scans) X(ps_centre_on_edge) X(ps_ray_clipped) X(ps_ray_used) X(ps_ray_used_ge64)                  \
+  X(ps_step_num_11) X(ps_step_num_12) X(ps_step_num_13) X(ps_step_num_14) X(ps_step_num_15)              \
+  X(ps_step_num_16) X(ps_step_num_17) X(ps_step_num_18) X(ps_step_num_19) X(ps_step_num_20)              \
+  X(ps_step_num_21) X(ps_step_num_22)                                                                    \
+  X(ps_len2_c) X(ps_len3_c) X(ps_len4_c) X(ps_len2_d) X(ps_len3_d) X(ps_len4_d) X(ps_odd_decrement)      \
+  /* step_len > 2 after the parity rule on a scan whose edge ray was used, d < 4 / d >= 4 */             \
+  X(ps_lengt2_used_c) X(ps_lengt2_used_d)                                                                \
+  /* the second (11 x 2) scan replaces the first: no first result, more good views, as many good and     \
+     fewer bad; then per pixel: best candidate accepted, rejected by depth range, by cost; REFINE_INIT's \
+     0.1 rule keeps the old plane or replaces it */                                                      \
+  X(ps_second_no_first) X(ps_second_more_good) X(ps_second_fewer_bad)                                    \
+  X(ps_cand_accepted) X(ps_cand_rej_range) X(ps_cand_rej_cost) X(ps_init_kept) X(ps_init_replaced)       \
+  /* ACMH scheme: candidate slot absent (image border), per slot index */                                \
+  X(ps_acmh_absent_0) X(ps_acmh_absent_1) X(ps_acmh_absent_2) X(ps_acmh_absent_3) X(ps_acmh_absent_4)    \
+  X(ps_acmh_absent_5) X(ps_acmh_absent_6) X(ps_acmh_absent_7)                                            \
+  /* CheckerboardPropagationWeak: neighbour slots none / not STRONG / used; RefinementWeak: fit plane    \
+     zero, fit plane taken, each of the five hypotheses taken */                                         \
+  X(pw_slot_none) X(pw_slot_not_strong) X(pw_slot_used) X(rw_fit_zero) X(rw_fit_taken)                   \
+  X(rw_hyp0_taken) X(rw_hyp1_taken) X(rw_hyp2_taken) X(rw_hyp3_taken) X(rw_hyp4_taken)                   \
+  /* DepthToWeak, per pixel but d2w_sample_oor (per depth sample) */                                      \
+  X(d2w_border) X(d2w_od_zero) X(d2w_no_view) X(d2w_sample_oor) X(d2w_no_peak) X(d2w_far_or_costly)      \
+  X(d2w_single_strong) X(d2w_single_weak) X(d2w_var_strong) X(d2w_var_weak)                              \
+  /* LocalRefine, per pixel */                                                                           \
+  X(lr_early) X(lr_taken) X(lr_not_taken)
+enum PathStat {
+#define X(n) PS_##n,
+  ORACLE_PATH_STATS(X)
+#undef X
+  kPathStats
+};
+static const char* const kPathStatNames[kPathStats] = {
+#define X(n) #n,
+  ORACLE_PATH_STATS(X)
+#undef X
+};
+static std::atomic<uint64_t> g_path_stats[kPathStats];
+static thread_local uint64_t t_path_stats[kPathStats];
+#define PS(n) (++t_path_stats[PS_##n])
+#define PS_IF(c, n) do { if (c) PS(n); } while (0)
+static void path_stats_flush() {
+  for (int k = 0; k < kPathStats; ++k) {
+    const uint64_t v = t_path_stats[k];
+    t_path_stats[k] = 0;
+    if (!v) continue;
+    if (k == PS_fns_max_radius) {
+      uint64_t cur = g_path_stats[k].load(std::memory_order_relaxed);
+      while (cur < v && !g_path_stats[k].compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
+    } else {
+      g_path_stats[k].fetch_add(v, std::memory_order_relaxed);
+    }
+  }
+}
+static void path_stats_reset() {
+  for (int k = 0; k < kPathStats; ++k) { t_path_stats[k] = 0; g_path_stats[k].store(0, std::memory_order_relaxed); }
+}
+
 template <class F>
 static void parallel_rows(int H, int nthreads, F f) {
   if (nthreads <= 1) { for (int y = 0; y < H; ++y) f(y); return; }
   std::atomic<int> next(0);
   std::vector<std::thread> th;
   for (int t = 0; t < nthreads; ++t)
-    th.emplace_back([&]() { for (int y; (y = next.fetch_add(1)) < H;) f(y); tap_stats_flush(); });
+    th.emplace_back([&]() { for (int y; (y = next.fetch_add(1)) < H;) f(y); tap_stats_flush(); path_stats_flush(); });
   for (auto& t : th) t.join();
 }
 
@@ -614,12 +697,13 @@ static float GeomCost(const Pass& S, int px, int py, int v, const float4_& pl) {
 
 // ------------------------------------------------------------------ BresenhamLine (DPE.cu:158-244)
 static inline uint8_t LowEdgeAt(const Pass& S, int idx) {
-  if (idx < 0 || idx >= S.LW * S.LH) return 0;   // restatement choice 5
+  if (idx < 0 || idx >= S.LW * S.LH) { PS(walk_lowres_oob); return 0; }   // restatement choice 5
   return S.edge_low[idx];
 }
 static bool BresenhamLine(const Pass& S, int Ax, int Ay, int Bx, int By) {
   const int W = S.W;
   if (S.edge[Ax + Ay * W] || S.edge[Bx + By * W]) return false;
+  PS(walk_called);
   const float scale_x = 1.0f * S.LW / (float)S.W;
   const float scale_y = 1.0f * S.LH / (float)S.H;
   const int height = S.LH, width = S.LW;
@@ -642,7 +726,7 @@ static bool BresenhamLine(const Pass& S, int Ax, int Ay, int Bx, int By) {
       int e2 = erro;
       if (e2 > -dx) { erro -= dy; x0 += sx; }
       if (e2 < dy) { erro += dx; y0 += sy; }
-      if (LowEdgeAt(S, x0 + y0 * width)) return true;
+      if (LowEdgeAt(S, x0 + y0 * width)) { PS(walk_blocked); return true; }
       step += 1;
       if (step >= max_step) break;
     }
@@ -707,6 +791,7 @@ static void GenEdgeInform(Pass& S, int x, int y) {
           if (S.label[ny * W + nx] == 0) bound_pix++;
         }
       density = MAXo(density, (float)(bound_pix / tot_pix));   // integer division (:2551)
+      PS_IF(bound_pix / tot_pix == 1, gei_window_all_label0);
     }
     S.complex_[center] = (float)(1.0f / (1.0f + o_exp_d(-25.0 * ((double)density - 0.35))));
   }
@@ -718,13 +803,20 @@ static void GenEdgeInform(Pass& S, int x, int y) {
         int dx = kDir[i][0], dy = kDir[i][1];
         int nx = x + dx, ny = y + dy;
         int lx = -1, ly = -1;
+        int ray_len = 0;                               // path counts only
+        bool seen_foreign = false, past_foreign = false;
         while (true) {
           if (nx < 0 || nx >= W || ny < 0 || ny >= H) break;
           int nl = S.label[nx + ny * W];
-          if (nl == cl) { lx = nx; ly = ny; }
-          else if (nl == -1) break;
+          ray_len++;
+          if (nl == cl) { lx = nx; ly = ny; past_foreign = seen_foreign; }
+          else if (nl == -1) { PS(gei_ray_stop_minus1); break; }
+          else if (nl > 0) seen_foreign = true;
           nx += dx; ny += dy;
         }
+        PS_IF(past_foreign, gei_ray_past_foreign);
+        PS_IF(ray_len > 8, gei_ray_len_gt8);
+        PS_IF(ray_len > 16, gei_ray_len_gt16);
         lb[i] = mk_s2((short)lx, (short)ly);
       }
     }
@@ -743,8 +835,25 @@ static void FindNearestStrongPoint(Pass& S, int x, int y) {
         if (abs(dx) != r && abs(dy) != r) continue;
         int nx = x + dx, ny = y + dy;
         if (nx < 0 || ny < 0 || nx >= W || ny >= H) continue;
-        if (S.weak[nx + ny * W] == DPE_STRONG) { S.nearest_strong[center] = mk_s2((short)nx, (short)ny); return; }
+        if (S.weak[nx + ny * W] == DPE_STRONG) {
+          S.nearest_strong[center] = mk_s2((short)nx, (short)ny);
+          {   // path counts only
+            if ((uint64_t)r > t_path_stats[PS_fns_max_radius]) t_path_stats[PS_fns_max_radius] = (uint64_t)r;
+            PS_IF(r == 100, fns_found_r100);
+            int in_ring = 0;
+            for (int ex = -r; ex <= r; ++ex)
+              for (int ey = -r; ey <= r; ++ey) {
+                if (abs(ex) != r && abs(ey) != r) continue;
+                const int mx = x + ex, my = y + ey;
+                if (mx < 0 || my < 0 || mx >= W || my >= H) continue;
+                if (S.weak[mx + my * W] == DPE_STRONG) in_ring++;
+              }
+            PS_IF(in_ring > 1, fns_ring_multi);
+          }
+          return;
+        }
       }
+  PS(fns_none);
 }
 
 // GenNeighbours (DPE.cu:2103-2463)
@@ -780,6 +889,8 @@ static void GenNeighbours(Pass& S, int x, int y) {
       else S.complex_[center] = MAXo(0.99f, cv);
     }
   }
+  PS(gn_weak);
+  if (edge_limit) PS(gn_edge_limit_on); else PS(gn_edge_limit_off);
 
   for (int odx = -1; odx <= 1; ++odx) {
     for (int ody = -1; ody <= 1; ++ody) {
@@ -804,7 +915,8 @@ static void GenNeighbours(Pass& S, int x, int y) {
             int npc = np.x + np.y * W;
             if (S.weak[npc] != DPE_STRONG) {
               np = S.nearest_strong[npc];
-              if (np.x == -1 || np.y == -1) continue;
+              PS(gn_probe_nearest);
+              if (np.x == -1 || np.y == -1) { PS(gn_probe_none); continue; }
               npc = np.x + np.y * W;
             }
             float2_ td = {(float)(np.x - x), (float)(np.y - y)};
@@ -862,10 +974,11 @@ static void GenNeighbours(Pass& S, int x, int y) {
         int npc = np.x + np.y * W;
         if (S.weak[npc] != DPE_STRONG) {
           np = S.nearest_strong[npc];
-          if (np.x == -1 || np.y == -1) continue;
+          if (np.x == -1 || np.y == -1) { PS(gn_ext_none); continue; }
           npc = np.x + np.y * W;
         }
-        if (S.label[npc] != 0 && S.label[npc] != S.label[center]) continue;
+        if (S.label[npc] != 0 && S.label[npc] != S.label[center]) { PS(gn_ext_foreign_drop); continue; }
+        PS(gn_ext_push);
         extend_index++;
         strong_points[extend_index] = np;
         dir_valid[extend_index] = true;
@@ -874,7 +987,10 @@ static void GenNeighbours(Pass& S, int x, int y) {
     }
   }
 
-  if (strong_point_size <= 3) { S.weak_reliable[center] = 0; return; }
+  PS_IF(strong_point_size > 8, gn_pts_gt8);
+  PS_IF(strong_point_size > 32, gn_pts_gt32);
+  PS_IF(strong_point_size == 64, gn_pts_eq64);
+  if (strong_point_size <= 3) { PS(gn_pts_le3); S.weak_reliable[center] = 0; return; }
 
   float4_ best_plane = {0, 0, 0, 0};
   bool has_valid_plane = false;
@@ -907,6 +1023,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
     std::memset(edge_test, 0, sizeof(edge_test));
     bool has_consist_normal_plane = false;
     bool must_in_triangle = (S.P.use_label && S.label[center] > 0 && edge_limit) ? false : true;
+    PS_IF(!must_in_triangle, gn_triangle_optional);
     while (iteration > 0 && max_iter > 0) {
       max_iter--;
       int a = (int)(rng_u32(&rs) % (uint32_t)valid_count);
@@ -918,7 +1035,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
         if (edge_test[a][b] == 0) edge_test[a][b] = edge_test[b][a] = (BresenhamLine(S, spv[a].x, spv[a].y, spv[b].x, spv[b].y) ? 1 : 2);
         if (edge_test[b][c] == 0) edge_test[b][c] = edge_test[c][b] = (BresenhamLine(S, spv[b].x, spv[b].y, spv[c].x, spv[c].y) ? 1 : 2);
         if (edge_test[c][a] == 0) edge_test[c][a] = edge_test[a][c] = (BresenhamLine(S, spv[c].x, spv[c].y, spv[a].x, spv[a].y) ? 1 : 2);
-        if (edge_test[a][b] == 1 || edge_test[b][c] == 1 || edge_test[c][a] == 1) continue;
+        if (edge_test[a][b] == 1 || edge_test[b][c] == 1 || edge_test[c][a] == 1) { PS(gn_pair_block); continue; }
       }
       bool normal_consistency = false;
       if (S.P.geom_consistency && edge_limit) {
@@ -928,7 +1045,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
             (double)(AN.x * CN.x + AN.y * CN.y + AN.z * CN.z) < 0.8660254 ||
             (double)(BN.x * CN.x + BN.y * CN.y + BN.z * CN.z) < 0.8660254)
           normal_consistency = false;
-        if (has_consist_normal_plane && !normal_consistency) continue;
+        if (has_consist_normal_plane && !normal_consistency) { PS(gn_normal_skip); continue; }
       }
       iteration--;
       const float3_ &A = spv3[a], &B = spv3[b], &C = spv3[c];
@@ -938,7 +1055,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
       cv.x = A_C.y * B_C.z - B_C.y * A_C.z;
       cv.y = -(A_C.x * B_C.z - B_C.x * A_C.z);
       cv.z = A_C.x * B_C.y - B_C.x * A_C.y;
-      if ((cv.x == 0 && cv.y == 0 && cv.z == 0) || std::isnan(cv.x) || std::isnan(cv.y) || std::isnan(cv.z)) continue;
+      if ((cv.x == 0 && cv.y == 0 && cv.z == 0) || std::isnan(cv.x) || std::isnan(cv.y) || std::isnan(cv.z)) { PS(gn_degenerate); continue; }
       NormalizeVec3(&cv);
       cv.w = -(cv.x * A.x + cv.y * A.y + cv.z * A.z);
       int temp_count = 0;
@@ -953,7 +1070,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
         residuals[si] = dist;
         if (dist < temp_thr) { temp_count++; strong_dist += dist; }
       }
-      if (temp_count < 6) continue;
+      if (temp_count < 6) { PS(gn_inliers_lt6); continue; }
       if (temp_count > max_count) {
         if (!must_in_triangle && PointinTriangle(spv[a], spv[b], spv[c], x, y)) must_in_triangle = true;
         if (!has_consist_normal_plane && normal_consistency) has_consist_normal_plane = true;
@@ -968,7 +1085,8 @@ static void GenNeighbours(Pass& S, int x, int y) {
         has_valid_plane = true;
         if ((double)temp_thr > (S.P.high_res_img ? 0.05 : 0.005)) {
           sort_small(residuals, valid_count);
-          if (temp_thr < residuals[DPE_NEIGHBOUR_NUM]) continue;
+          if (temp_thr < residuals[DPE_NEIGHBOUR_NUM]) { PS(gn_thr_kept); continue; }
+          PS(gn_thr_tightened);
           temp_thr = (float)((double)residuals[DPE_NEIGHBOUR_NUM] - 1e-6);
           temp_count = 0;
           for (int i = 0; i < valid_count; ++i) {
@@ -984,6 +1102,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
         float fd = -cv.w / (cv.x * fx + cv.y * fy + cv.z);
         const float cd = fabsf(fd - cpw.z);
         if (cd < min_cost) {
+          PS(gn_tie_won);
           best_plane = cv;
           max_count = temp_count;
           strong_dist /= temp_count;
@@ -993,7 +1112,7 @@ static void GenNeighbours(Pass& S, int x, int y) {
     }
   }
   float weight[64];
-  if (!has_valid_plane) { S.weak_reliable[center] = 0; return; }
+  if (!has_valid_plane) { PS(gn_no_plane); S.weak_reliable[center] = 0; return; }
   for (int i = 0; i < valid_count; ++i) {
     const float3_& tp = spv3[i];
     const short2_& pos = spv[i];
@@ -1189,14 +1308,24 @@ static void PropagationStrong(Pass& S, int x, int y, int iter) {
       double ex = (double)(ep.x - x), ey = (double)(ep.y - y);
       float dist = (float)std::sqrt(ex * ex + ey * ey);
       if (d >= 4) dist = (float)((double)dist / std::sqrt(2.0));
-      if (S.edge[center]) dist = 11 * min_step_len;
+      PS(ps_scans);
+      bool ray_used = false;   // path counts only
+      if (S.edge[center]) { PS(ps_centre_on_edge); dist = 11 * min_step_len; }
       else if (ep.x == -1 || ep.y == -1 || dist > max_edge_dist) {
+        PS(ps_ray_clipped);
         dist = max_edge_dist;
         if (d >= 4) dist = (float)((double)dist / std::sqrt(2.0));
+      } else {
+        PS(ps_ray_used);
+        ray_used = true;
+        PS_IF(MAXo(abs(ep.x - x), abs(ep.y - y)) >= 64, ps_ray_used_ge64);
       }
       int step_num = MINo(MAXo(11, o_f2i(1.0f * dist / min_step_len)), 22);
       int step_len = MAXo(o_f2i(1.0f * dist / step_num), min_step_len);
-      if (d < 4 && step_len % 2 == 1) step_len -= 1;
+      if (d < 4 && step_len % 2 == 1) { PS(ps_odd_decrement); step_len -= 1; }
+      ++t_path_stats[PS_ps_step_num_11 + (step_num - 11)];
+      ++t_path_stats[(d < 4 ? PS_ps_len2_c : PS_ps_len2_d) + (MINo(step_len, 4) - 2)];
+      if (ray_used && step_len > 2) ++t_path_stats[d < 4 ? PS_ps_lengt2_used_c : PS_ps_lengt2_used_d];
       int mx = 0, my = 0; float mc = FLT_MAX;
       for (int step = 0; step < step_num; ++step) {
         int fx = 0, fy = 0;
@@ -1243,6 +1372,9 @@ static void PropagationStrong(Pass& S, int x, int y, int iter) {
               if (val > bad_threshold) bad[i]++;
             }
           if (!hasResBefore || good[1] > good[0] || (good[1] == good[0] && bad[1] < bad[0])) {
+            if (!hasResBefore) PS(ps_second_no_first);
+            else if (good[1] > good[0]) PS(ps_second_more_good);
+            else PS(ps_second_fewer_bad);
             positions[d] = tpos;
             for (int j = 0; j < nv; j++) cost_array[d][j] = tca[j];
           }
@@ -1305,6 +1437,7 @@ static void PropagationStrong(Pass& S, int x, int y, int iter) {
       }
       right_near = costMinPoint; costvec(planes[right_near], cost_array[6]);
     }
+    for (int i = 0; i < 8; ++i) if (!flag[i]) ++t_path_stats[PS_ps_acmh_absent_0 + i];
     positions[0] = up_near; positions[1] = up_far; positions[2] = down_near; positions[3] = down_far;
     positions[4] = left_near; positions[5] = left_far; positions[6] = right_near; positions[7] = right_far;
   }
@@ -1343,15 +1476,18 @@ static void PropagationStrong(Pass& S, int x, int y, int iter) {
   if (flag[mi]) {
     float db = ComputeDepthfromPlaneHypothesis(c0, planes[positions[mi]], x, y);
     if (db >= S.P.depth_min && db <= S.P.depth_max && final_costs[mi] < cost_now) {
+      PS(ps_cand_accepted);
       depth_now = db;
       pnow = planes[positions[mi]];
       cost_now = final_costs[mi];
       S.sel[center] = tsv;
-    }
+    } else if (!(db >= S.P.depth_min && db <= S.P.depth_max)) PS(ps_cand_rej_range);
+    else PS(ps_cand_rej_cost);
   }
   RefinementStrong(S, &pnow, &depth_now, &cost_now, &rs, vw, wnorm, x, y);
   if (S.P.state == DPE_REFINE_INIT) {
-    if ((double)cost_now < (double)cost_written - 0.1) { S.costs[center] = cost_now; S.planes[center] = pnow; }
+    if ((double)cost_now < (double)cost_written - 0.1) { PS(ps_init_replaced); S.costs[center] = cost_now; S.planes[center] = pnow; }
+    else PS(ps_init_kept);
   } else {
     S.costs[center] = cost_now;
     S.planes[center] = pnow;
@@ -1379,10 +1515,10 @@ static void RefinementWeak(Pass& S, float4_* plane, float* depth, float* cost, P
   };
   if (S.weak[center] == DPE_WEAK) {
     float4_ fp = S.fit_plane[center];
-    if (fp.x == 0 && fp.y == 0 && fp.z == 0) return;
+    if (fp.x == 0 && fp.y == 0 && fp.z == 0) { PS(rw_fit_zero); return; }
     float tc = hyp_cost(fp);
     float db = ComputeDepthfromPlaneHypothesis(c0, fp, x, y);
-    if (db >= dmin && db <= dmax && tc < *cost) { *depth = db; *plane = fp; *cost = tc; }
+    if (db >= dmin && db <= dmax && tc < *cost) { PS(rw_fit_taken); *depth = db; *plane = fp; *cost = tc; }
   }
   float depth_rand = rng_uniform(rs) * (dmax - dmin) + dmin;
   float4_ prand = GenerateRandomNormal(c0, x, y, rs, *depth);
@@ -1398,7 +1534,7 @@ static void RefinementWeak(Pass& S, float4_* plane, float* depth, float* cost, P
     tp.w = GetDistance2Origin(c0, x, y, depths[i], tp);
     float tc = hyp_cost(tp);
     float db = ComputeDepthfromPlaneHypothesis(c0, tp, x, y);
-    if (db >= dmin && db <= dmax && tc < *cost) { *depth = db; *plane = tp; *cost = tc; }
+    if (db >= dmin && db <= dmax && tc < *cost) { ++t_path_stats[PS_rw_hyp0_taken + i]; *depth = db; *plane = tp; *cost = tc; }
   }
 }
 
@@ -1416,7 +1552,11 @@ static void PropagationWeak(Pass& S, int x, int y, int iter) {
   float4_ nph[8];
   for (int i = 0; i < 8; ++i) {
     const short2_ np = Neighbour(S, center, i + 1);
-    if (np.x == -1 || np.y == -1 || S.weak[np.x + np.y * W] != DPE_STRONG) { flag[i] = false; continue; }
+    if (np.x == -1 || np.y == -1 || S.weak[np.x + np.y * W] != DPE_STRONG) {
+      if (np.x == -1 || np.y == -1) PS(pw_slot_none); else PS(pw_slot_not_strong);
+      flag[i] = false; continue;
+    }
+    PS(pw_slot_used);
     positions[i] = np.x + np.y * W;
     flag[i] = true;
     const float4_ pl = S.planes[positions[i]];
@@ -1574,6 +1714,7 @@ static void RANSACFitPlane(Pass& S, int x, int y, int iter) {
       min_cost = tcost; best = cv; has_best = true; ua = a; ub = b; uc = c;
     }
   }
+  if (has_best) PS(fit_found); else PS(fit_none);
   if (has_best) {
     float depth = ComputeDepthfromPlaneHypothesis(camera, S.planes[center], x, y);
     float4_ vd = GetViewDirection(camera, x, y, depth);
@@ -1719,12 +1860,17 @@ static uint8_t ClassifyCostCurve(const float* pc, int weak_peak_radius) {
       if (pc[i] < min_cost) { min_peak = i; min_cost = pc[i]; }
     }
   }
-  if (abs(min_peak - radius) > weak_peak_radius || pc[min_peak] > 0.5f) return DPE_WEAK;
-  if (peak_count == 1) return pc[min_peak] <= 0.15f ? DPE_STRONG : DPE_WEAK;
+  PS_IF(peak_count == 0, d2w_no_peak);
+  if (abs(min_peak - radius) > weak_peak_radius || pc[min_peak] > 0.5f) { PS_IF(peak_count > 0, d2w_far_or_costly); return DPE_WEAK; }
+  if (peak_count == 1) {
+    if (pc[min_peak] <= 0.15f) PS(d2w_single_strong); else PS(d2w_single_weak);
+    return pc[min_peak] <= 0.15f ? DPE_STRONG : DPE_WEAK;
+  }
   float var = 0.0f;
   for (int i = 2; i < n - 2; ++i) if (is_peak[i] && i != min_peak) { float d = pc[i] - min_cost; var += d * d; }
   var = sqrtf(var);
   var /= (peak_count - 1);
+  if (var > 0.2f) PS(d2w_var_strong); else PS(d2w_var_weak);
   return var > 0.2f ? DPE_STRONG : DPE_WEAK;
 }
 
@@ -1733,14 +1879,14 @@ static void DepthToWeak(Pass& S, int x, int y) {
   const int W = S.W, H = S.H;
   const int min_margin = 6;
   const int center = x + y * W;
-  if (x < min_margin || y < min_margin || x >= W - min_margin || y >= H - min_margin) { S.weak[center] = DPE_UNKNOWN; return; }
+  if (x < min_margin || y < min_margin || x >= W - min_margin || y >= H - min_margin) { PS(d2w_border); S.weak[center] = DPE_UNKNOWN; return; }
   const DpeCamera& c0 = S.cams[0];
   const uint8_t* vw = &S.view_weight[(size_t)DPE_MAX_IMAGES * center];
   float4_ op = TransformNormal2RefCam(c0, S.planes[center]);
   float od = op.w;
-  if (od == 0) { S.weak[center] = DPE_UNKNOWN; return; }
+  if (od == 0) { PS(d2w_od_zero); S.weak[center] = DPE_UNKNOWN; return; }
   CostNow cn = CostAndBaseline(S, x, y, op, od);
-  if (cn.valid == 0) { S.weak[center] = DPE_UNKNOWN; return; }
+  if (cn.valid == 0) { PS(d2w_no_view); S.weak[center] = DPE_UNKNOWN; return; }
   cn.cost_now /= cn.weight_normal;
   cn.base_line /= cn.valid;
   float disp = c0.K[0] * cn.base_line / od;
@@ -1748,7 +1894,7 @@ static void DepthToWeak(Pass& S, int x, int y) {
   float pc[61];
   for (int pd = -radius; pd <= radius; pd += 1) {
     float p_depth = c0.K[0] * cn.base_line / (disp + (float)pd);
-    if (p_depth < S.P.depth_min || p_depth > S.P.depth_max) { pc[pd + radius] = 2.0f; continue; }
+    if (p_depth < S.P.depth_min || p_depth > S.P.depth_max) { PS(d2w_sample_oor); pc[pd + radius] = 2.0f; continue; }
     float4_ tp = op;
     tp.w = GetDistance2Origin(c0, x, y, p_depth, tp);
     float p_cost = 0.0f;
@@ -1787,9 +1933,9 @@ static void LocalRefine(Pass& S, int x, int y) {
   const uint8_t* vw = &S.view_weight[(size_t)DPE_MAX_IMAGES * center];
   float4_ op = TransformNormal2RefCam(c0, S.planes[center]);
   float od = op.w;
-  if (od == 0) return;
+  if (od == 0) { PS(lr_early); return; }
   CostNow cn = CostAndBaseline(S, x, y, op, od);
-  if (cn.weight_normal == 0 || cn.valid == 0) return;
+  if (cn.weight_normal == 0 || cn.valid == 0) { PS(lr_early); return; }
   cn.cost_now /= cn.weight_normal;
   cn.base_line /= cn.valid;
   float disp = c0.K[0] * cn.base_line / od;
@@ -1816,7 +1962,8 @@ static void LocalRefine(Pass& S, int x, int y) {
     tcs[pd + radius] = tc;
   }
   float best_depth;
-  if (LocalRefineSelect(tcs, ok, depths, cn.cost_now, od, &best_depth)) S.planes[center].w = best_depth;
+  if (LocalRefineSelect(tcs, ok, depths, cn.cost_now, od, &best_depth)) { PS(lr_taken); S.planes[center].w = best_depth; }
+  else PS(lr_not_taken);
 }
 
 // half-sweep geometry (DPE.cu:1864-1938): Black = (x+y) even, Red = (x+y) odd.
@@ -1903,10 +2050,19 @@ void oracle_last_tap_stats(uint64_t out[6]) {
   for (int k = 0; k < kTapStats; ++k) out[k] = g_tap_stats[k].load(std::memory_order_relaxed);
 }
 
+// The decision-path counts of the last oracle_pm_run (path_stats above): test infrastructure.
+// out holds oracle_path_stats_count() values, named by oracle_path_stat_name(k).
+void oracle_last_path_stats(uint64_t* out) {
+  for (int k = 0; k < kPathStats; ++k) out[k] = g_path_stats[k].load(std::memory_order_relaxed);
+}
+int oracle_path_stats_count(void) { return kPathStats; }
+const char* oracle_path_stat_name(int k) { return k >= 0 && k < kPathStats ? kPathStatNames[k] : ""; }
+
 // Runs one pass on the CPU.  Same structs and in/out semantics as dpe_pm_run (include/dpe_mvs.h).
 int oracle_pm_run(const DpePassInput* in, const DpePassState* st, int nthreads) {
   g_err[0] = 0;
   tap_stats_reset();
+  path_stats_reset();
   if (!in || !st || !st->planes || !st->weak_info || !st->selected_views) { snprintf(g_err, sizeof g_err, "null arg"); return DPE_ERR_ARG; }
   if (in->num_images > DPE_MAX_IMAGES) { snprintf(g_err, sizeof g_err, "too many images"); return DPE_ERR_TOO_MANY; }
   if (in->num_images < 2 || in->width <= 0 || in->height <= 0) { snprintf(g_err, sizeof g_err, "bad shape"); return DPE_ERR_ARG; }
@@ -1955,6 +2111,7 @@ int oracle_pm_run(const DpePassInput* in, const DpePassState* st, int nthreads) 
   S.radius.assign(L, 0);
   RunPass(S);
   tap_stats_flush();   // rows run on the calling thread (nthreads 1)
+  path_stats_flush();
   std::memcpy(st->planes, S.planes.data(), L * sizeof(float4_));
   std::memcpy(st->weak_info, S.weak.data(), L);
   std::memcpy(st->selected_views, S.sel.data(), L * sizeof(uint32_t));

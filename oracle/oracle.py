@@ -41,6 +41,11 @@ def _load(path: str = LIB):
     lib.oracle_rcp_tap.restype = None
     lib.oracle_last_tap_stats.argtypes = [C.POINTER(C.c_uint64)]
     lib.oracle_last_tap_stats.restype = None
+    lib.oracle_last_path_stats.argtypes = [C.POINTER(C.c_uint64)]
+    lib.oracle_last_path_stats.restype = None
+    lib.oracle_path_stats_count.restype = C.c_int
+    lib.oracle_path_stat_name.argtypes = [C.c_int]
+    lib.oracle_path_stat_name.restype = C.c_char_p
     lib.oracle_expf.argtypes = [C.c_float]
     lib.oracle_expf.restype = C.c_float
     lib.oracle_sinf.argtypes = [C.c_float]
@@ -152,6 +157,48 @@ def last_tap_stats(library=None) -> dict:
     out = (C.c_uint64 * len(TAP_STATS))()
     (library or lib()).oracle_last_tap_stats(out)
     return dict(zip(TAP_STATS, (int(v) for v in out)))
+
+
+# Decision-path counts (dpe_oracle.cpp ORACLE_PATH_STATS, where each name is explained), in the library's
+# order; tests/test_pass_paths.py checks this tuple against oracle_path_stat_name().
+PATH_STATS = (
+    "gei_window_all_label0", "gei_ray_stop_minus1", "gei_ray_past_foreign", "gei_ray_len_gt8", "gei_ray_len_gt16",
+    "fns_none", "fns_max_radius", "fns_found_r100", "fns_ring_multi",
+    "walk_called", "walk_blocked", "walk_lowres_oob",
+    "gn_weak", "gn_edge_limit_on", "gn_edge_limit_off", "gn_probe_nearest", "gn_probe_none",
+    "gn_ext_none", "gn_ext_push", "gn_ext_foreign_drop", "gn_pts_le3", "gn_pts_gt8", "gn_pts_gt32", "gn_pts_eq64",
+    "gn_triangle_optional", "gn_pair_block", "gn_normal_skip", "gn_degenerate", "gn_inliers_lt6",
+    "gn_tie_won", "gn_thr_tightened", "gn_thr_kept", "gn_no_plane",
+    "fit_none", "fit_found",
+    "ps_scans", "ps_centre_on_edge", "ps_ray_clipped", "ps_ray_used", "ps_ray_used_ge64",
+    *[f"ps_step_num_{n}" for n in range(11, 23)],
+    "ps_len2_c", "ps_len3_c", "ps_len4_c", "ps_len2_d", "ps_len3_d", "ps_len4_d", "ps_odd_decrement",
+    "ps_lengt2_used_c", "ps_lengt2_used_d",
+    "ps_second_no_first", "ps_second_more_good", "ps_second_fewer_bad",
+    "ps_cand_accepted", "ps_cand_rej_range", "ps_cand_rej_cost", "ps_init_kept", "ps_init_replaced",
+    *[f"ps_acmh_absent_{k}" for k in range(8)],
+    "pw_slot_none", "pw_slot_not_strong", "pw_slot_used", "rw_fit_zero", "rw_fit_taken",
+    *[f"rw_hyp{k}_taken" for k in range(5)],
+    "d2w_border", "d2w_od_zero", "d2w_no_view", "d2w_sample_oor", "d2w_no_peak", "d2w_far_or_costly",
+    "d2w_single_strong", "d2w_single_weak", "d2w_var_strong", "d2w_var_weak",
+    "lr_early", "lr_taken", "lr_not_taken",
+)
+PATH_STATS_MAXIMA = ("fns_max_radius",)   # maxima over the pass; every other entry is a count
+
+
+def path_stat_names(library=None) -> tuple:
+    """The counter names as the library holds them (PATH_STATS must equal this)."""
+    L = library or lib()
+    return tuple(L.oracle_path_stat_name(k).decode() for k in range(L.oracle_path_stats_count()))
+
+
+def last_path_stats(library=None) -> dict:
+    """Decision-path counts of the last run_pass, by PATH_STATS name."""
+    L = library or lib()
+    assert L.oracle_path_stats_count() == len(PATH_STATS)
+    out = (C.c_uint64 * len(PATH_STATS))()
+    L.oracle_last_path_stats(out)
+    return dict(zip(PATH_STATS, (int(v) for v in out)))
 
 
 def ncc_old(pass_input: dict, x: int, y: int, view: int, plane) -> float:
